@@ -25,6 +25,18 @@ synthetic feature buffer that is already resident in HBM.
 Run without torch.distributed.run and --gpus N > 1, the script starts the N ranks itself (a child torch.distributed.run,
 before this process touches a GPU) and passes rank 0's line through.
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, the kernel time and roofline
+figures read off the timed steps).  --full adds everything else the benchmark measures or checks, each leg after the
+timed steps: the CPU baseline (the oracle on a sample of the same buffer) and the parity probes, the opt-in fp32
+pair-weight figure, neighbourhood-size percentiles, and with cfg2 the 3840x2160x32 strong-scaling leg and the one-process
+multi-GPU leg (the --no-* options switch single legs off).
+--dump-outputs DIR writes what the last timed step computed, as the caller of rpf_filter_device receives it, before any
+--full leg runs: DIR/colour_sample.npy (float64 [3, n, S], the filtered sample colours of n owned pixels drawn with a fixed
+seed, n bounded so that the files stay under 48 MB in all), DIR/nbhd_sample.npy (float32 [n], those pixels' neighbourhood
+sizes, rpf_query_nbhd) and DIR/counters.npy (float64 [sum_nbhd, max_nbhd, nonfinite_pixels] of the last pass).  With
+several ranks each rank writes its own slab's files, suffixed _rank<r> for r > 0.  The inputs are seeded: the same
+arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -69,8 +81,13 @@ def parse():
     ap.add_argument("--rows-per-gpu", type=int, default=None)
     ap.add_argument("--spp", type=int, default=None)
     ap.add_argument("--box", type=int, default=7)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-scaling-4k32", action="store_true", help="skip the strong-scaling 3840x2160x32 object")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs beyond the headline: CPU baseline, parity probes, fp32 "
+                         "pair weights, neighbourhood percentiles, strong scaling 3840x2160x32, one-process multi-GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 48 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity probes")
+    ap.add_argument("--no-scaling-4k32", action="store_true", help="with --full: skip the strong-scaling 3840x2160x32 object")
     ap.add_argument("--fast-weights", action="store_true", help="opt-in fp32 pair weights (RPF_FLAG_FAST_WEIGHTS)")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="rpf_set_option override (diagnostics: stage_mask, binning, waves_per_pixel, table_in_lds, lds_pad, screen)")
@@ -79,7 +96,8 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL, one GPU per rank) is the measured path; gloo lets several ranks share one GPU to "
                          "rehearse the multi-rank code path (halo rows staged through the host)")
-    ap.add_argument("--no-multi-inprocess", action="store_true", help="skip the rpf_multi_filter (one process, all visible GPUs) object")
+    ap.add_argument("--no-multi-inprocess", action="store_true",
+                    help="with --full: skip the rpf_multi_filter (one process, all visible GPUs) object")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="ranks meet over gloo, all-reduce one number and rank 0 prints {n_gpus, rendezvous}: exercises the "
                          "self-spawn / launcher path without a GPU (tests/test_slabs_gloo.py)")
@@ -191,6 +209,31 @@ def nbhd_statistics(ctx, W, H_buf, rb, re, S):
     q = np.percentile(n, [50, 90, 99])
     return {"mean": float(n.mean()), "p50": float(q[0]), "p90": float(q[1]), "p99": float(q[2]), "max": int(n.max()),
             "frac_N_eq_S": float((n == S).mean())}
+
+
+DUMP_BYTES = 48 << 20    # --dump-outputs: all files of all ranks together
+DUMP_SEED = 20240611
+
+
+def dump_outputs(torch, ctx, job, out_dir, rank, world):
+    """--dump-outputs: the filtered sample colours and neighbourhood sizes of a seeded sample of this rank's owned pixels,
+    and the last pass's counters, as the last timed step left them"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    S, W, n_own = job.S, job.W, job.n_own
+    rb, re = job.desc.row_begin, job.desc.row_end
+    n_pix = n_own * W
+    n = min(n_pix, DUMP_BYTES // world // (3 * S * 8 + 4))
+    idx = np.sort(np.random.default_rng(DUMP_SEED + rank).choice(n_pix, size=n, replace=False))
+    torch.cuda.synchronize()
+    own = job.colour[:, rb:re].reshape(3, n_pix, S)
+    colour = own.index_select(1, torch.from_numpy(idx).to(own.device)).cpu().numpy().astype(np.float64)
+    nbhd = ctx.nbhd(W, job.H_buf)[rb:re].reshape(-1)[idx].astype(np.float32)
+    c = ctx.counters()
+    counters = np.array([c.sum_nbhd, c.max_nbhd, c.nonfinite_pixels], np.float64)
+    sfx = "_rank%d" % rank if rank else ""
+    for name, a in (("colour_sample", colour), ("nbhd_sample", nbhd), ("counters", counters)):
+        np.save(os.path.join(out_dir, name + sfx + ".npy"), a)
 
 
 def multi_inprocess(torch, hip, fb, dev, box):
@@ -340,6 +383,8 @@ def main():
     job = Job(torch, dist, hip, fb, slabs, args, dev, rank, world, W, rows_per_gpu * world, S, box, layout, ctx,
               gen_kw=wl["gen"], boxes=boxes, policy=policy)
     elapsed = job.timed(args.steps, args.warmup, dev, args.dist_backend)
+    if args.dump_outputs:
+        dump_outputs(torch, ctx, job, args.dump_outputs, rank, world)
     cnt = ctx.counters()
     n_own = job.n_own
     n_pass = len(boxes)
@@ -360,7 +405,6 @@ def main():
         "config": {"workload": workload, "image": "%dx%d" % (W, H_total), "rows_per_gpu": rows_per_gpu,
                    "passes_per_step": n_pass,
                    "mean_nbhd": cnt.sum_nbhd / float(n_own * W), "max_nbhd": cnt.max_nbhd,
-                   "nbhd": nbhd_statistics(ctx, W, job.H_buf, job.desc.row_begin, job.desc.row_end, S),
                    "beta_map": "REF_GCC11_O3", "degenerate_policy": policy,
                    "nonfinite_pixels": cnt.nonfinite_pixels, "redo_pixels": cnt.redo_pixels,
                    "library": os.path.relpath(hip.LIB_PATH, ROOT) + (" (RPF_HIP_LIB override)" if os.environ.get("RPF_HIP_LIB") else ""),
@@ -388,8 +432,10 @@ def main():
                                         "own_microbenchmark_rate": lds_peak / 1e12, "unit": "T increments/s",
                                         "ratio": (incr / (k_ms * 1e-3)) / lds_peak if k_ms > 0 else 0.0,
                                         "note": "whole-kernel time in the denominator; the MI stage alone is ~35% of it (scripts/ablate_mi.sh)"}
+    if args.full:   # before any other filter call replaces what rpf_query_nbhd reports
+        out["config"]["nbhd"] = nbhd_statistics(ctx, W, job.H_buf, job.desc.row_begin, job.desc.row_end, S)
     single = rank == 0 and world == 1
-    if single and not args.no_cpu_baseline:
+    if args.full and single and not args.no_cpu_baseline:
         if n_pass > 1:   # the oracle sample is one pass: compare it with the colours after the first pass alone
             d1 = hip.make_desc(W, job.H_buf, S, boxes=(box,), row_begin=job.desc.row_begin, row_end=job.desc.row_end,
                                policy=job.desc.degenerate_policy)
@@ -414,7 +460,7 @@ def main():
             out["fast_weights_f32"] = {"kernel_ms": min(ms), "Msamples_per_s_kernel": n_own * W * S / (min(ms) * 1e-3) / 1e6,
                                        "rel_l2_vs_f64_path": rel}
 
-    if single and not args.no_cpu_baseline and args.workload == "cfg2":
+    if args.full and single and not args.no_cpu_baseline and args.workload == "cfg2":
         # the headline buffer is close to the identity regime (most cross weights underflow), so its GPU-vs-oracle
         # figure says little about stage 4: the same comparison on a small filter-ACTIVE buffer (clustered generator)
         import numpy as np
@@ -439,7 +485,7 @@ def main():
                                      "gpu_vs_oracle_rel_l2": float(np.linalg.norm(r["colour"] - want) / np.linalg.norm(want))}
 
     # ---- strong scaling of BASELINE configs[3]: 3840x2160x32 spp row-tiled over the N ranks ---------------------------
-    if args.workload == "cfg2" and not args.no_scaling_4k32 and not args.option:
+    if args.full and args.workload == "cfg2" and not args.no_scaling_4k32 and not args.option:
         del job
         torch.cuda.empty_cache()
         W4, H4, S4 = 3840, 2160, 32

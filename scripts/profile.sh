@@ -7,7 +7,7 @@ OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 export RPF_BENCH_WATCHDOG=100
-CMD="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-multi-inprocess $BENCH_FLAGS"
+CMD="python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-multi-inprocess $BENCH_FLAGS"
 # every pass runs under its own limit; a pass that is killed at the limit ends the script (no further GPU step after a hang)
 LIM=${PASS_LIMIT:-160}
 pass() {  # pass <name> <rocprofv3 args...>

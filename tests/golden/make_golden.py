@@ -16,6 +16,8 @@
 
   clustered_10x8x8.rpfb (+ _expected.npz)   an on-disk feature buffer in the .rpfb wire format and the oracle's
                  two-pass result on it.
+  ref_checks.npz known answers of the REAL reference code on the inputs of test_oracle.py's randomised and
+                 stage-3 / stage-4a checks (python tests/golden/make_golden.py refchecks).
 
 Fixtures are data only: inputs and expected outputs.
 """
@@ -66,10 +68,92 @@ def rpfb_fixture():
         os.path.getsize(os.path.join(HERE, "clustered_10x8x8.rpfb")) / 1024, np.linalg.norm(c - cin) / np.linalg.norm(cin)))
 
 
+def ref_checks_fixture():
+    """ref_checks.npz: the compiled reference's answers on the inputs of tests/test_oracle.py's randomised MI / mean-std
+    check, its stage-3 pixels (neighbourhood size, mean, stddev, 96 MI values from the reference's own 3-sigma test,
+    getMean / getStdDev, normalisation and MutualInformation) and its stage-4a weighted distances.  Inputs stored verbatim,
+    so those tests run without the compiled reference."""
+    out = {}
+    # ---- randomised MI and mean / stddev ------------------------------------------------------------
+    rng = np.random.default_rng(5)
+    xs, ys, lens, mis = [], [], [], []
+    for n in (1, 2, 5, 8, 49, 64, 200, 392, 784):
+        for t in range(12):
+            x = rng.normal(size=n)
+            y = rng.normal(size=n) + (t % 3) * 0.5 * x
+            if t % 4 == 0:
+                x = np.round(x * 3) / 3
+            if t % 6 == 0:
+                y = np.full(n, 0.25)
+            xs.append(x); ys.append(y); lens.append(n); mis.append(O.ref_mi(x, y))
+    out.update(mi_x=np.concatenate(xs), mi_y=np.concatenate(ys), mi_n=np.array(lens, np.int32), mi=np.array(mis))
+    for nc in (12, 19):
+        r = np.float32(rng.normal(size=(300, nc)) * 0.02 + 500).astype(float)
+        out["ms%d_rows" % nc] = r
+        out["ms%d_mean" % nc], out["ms%d_std" % nc] = O.ref_mean_std(r)
+
+    # ---- stage 3 of three pixels --------------------------------------------------------------------
+    W, H, S, box = 9, 8, 8, 7
+    planes = fb.synth_planes(W, H, S, seed=13, sigma_f=1e-3, sigma_c=0.01, mode="clustered")
+    pa, pb = O.pair_table()
+    b = (box - 1) // 2
+    mean12, sd12 = O.pixel_stats(planes, O.make_desc(W, H, S))
+    pixels = ((4, 4), (0, 0), (7, 3))
+    cnt, ms, ss, mi3 = [], [], [], []
+    for (y, x) in pixels:
+        rows = [planes[:, y, x, s].astype(float) for s in range(S)]
+        for xn in range(x - b, x + b + 1):
+            for yn in range(y - b, y + b + 1):
+                if (xn, yn) == (x, y) or not (0 <= xn < W and 0 <= yn < H):
+                    continue
+                for s in range(S):
+                    v = planes[:, yn, xn, s].astype(float)
+                    if O.ref_within_3std(v[7:], mean12[y, x], sd12[y, x]):
+                        rows.append(v)
+        rows = np.array(rows)
+        m, s = O.ref_mean_std(rows)
+        z = np.stack([O.ref_normalize(v, m, s) for v in rows])
+        cnt.append(len(rows)); ms.append(m); ss.append(s)
+        mi3.append([O.ref_mi(z[:, a], z[:, bb]) for a, bb in zip(pa, pb)])
+    out.update(s3_planes=planes, s3_pixels=np.array(pixels, np.int32), s3_nbhd=np.array(cnt, np.int32),
+               s3_mean=np.array(ms), s3_std=np.array(ss), s3_mi=np.array(mi3))
+
+    # ---- stage 4a weighted squared distances --------------------------------------------------------
+    planes = planes.copy()
+    planes[10:13] += 700.0
+    r = O.filter_pass(planes, O.make_desc(W, H, S, box=box, n_threads=1))
+    rng = np.random.default_rng(9)
+    own, oth, al, be, d = [], [], [], [], []
+    for (y, x) in ((4, 4), (0, 0), (7, 3), (2, 8)):
+        m, s = r["mean"][y, x], r["stddev"][y, x]
+        zo = np.stack([O.ref_normalize(planes[:, y, x, i].astype(float), m, s) for i in range(S)])
+        zn = np.stack([O.ref_normalize(planes[:, (y + dy) % H, (x + dx) % W, i].astype(float), m, s)
+                       for dy, dx, i in rng.integers(0, 4, size=(24, 3))])
+        a, bt = r["alpha"][y, x], r["beta"][y, x]
+        own.append(zo); oth.append(zn); al.append(a); be.append(bt)
+        d.append([[O.ref_weighted_sqdist(zi, zj, a, bt) for zj in np.concatenate([zo, zn])] for zi in zo])
+    out.update(s4_own=np.array(own), s4_other=np.array(oth), s4_alpha=np.array(al), s4_beta=np.array(be), s4_d=np.array(d))
+    z = rng.normal(size=(2, 19))
+    nf_a, nf_b, nf_d = [], [], []
+    for a in (np.array([np.nan, 1.0, 2.0]), np.array([np.inf, 0.0, -1.0])):
+        bt = np.concatenate([a, rng.normal(size=9)])
+        nf_a.append(a); nf_b.append(bt); nf_d.append(O.ref_weighted_sqdist(z[0], z[1], a, bt))
+    out.update(s4nf_z=z, s4nf_alpha=np.array(nf_a), s4nf_beta=np.array(nf_b), s4nf_d=np.array(nf_d))
+    np.savez_compressed(os.path.join(HERE, "ref_checks.npz"), **out,
+                        source="MutualInformation() of mi.cpp and the ops.h templates of the reference, "
+                               "g++ 11.4 -O3 -std=gnu++11; inputs stored verbatim")
+    print("ref_checks.npz  %.1f KB" % (os.path.getsize(os.path.join(HERE, "ref_checks.npz")) / 1024))
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "rpfb":
         O.build(force=False)
         return rpfb_fixture()
+    if len(sys.argv) > 1 and sys.argv[1] == "refchecks":
+        O.build(force=False)
+        if not O.ref_available():
+            sys.exit("oracle/_ref/libref_mi.so missing: build it from the reference sources first (oracle/Makefile)")
+        return ref_checks_fixture()
     O.build(force=False)
     if not O.ref_available():
         sys.exit("oracle/_ref/libref_mi.so missing: this script must run where /root/reference exists")

@@ -1,6 +1,6 @@
 """CPU tests (-m "not gpu"): the oracle against (1) golden vectors produced by the REAL reference code
-(mi.cpp, ops.h), (2) the compiled reference itself when oracle/_ref/libref_mi.so is present, (3) its own
-committed end-to-end fixtures.  These pin the checker; nothing here touches the product path."""
+(mi.cpp, ops.h), (2) the compiled reference's answers on randomised inputs and on real pixels' stage-3 / stage-4a
+operands (ref_checks.npz), (3) its own committed end-to-end fixtures.  These pin the checker; nothing here touches the product path."""
 import os
 
 import numpy as np
@@ -51,88 +51,55 @@ def test_three_sigma_rule_matches_reference_known_answers(oracle):
     assert not g["w3_pass"][:20].any() and not g["w3_pass"][40:60].any()
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(GOLD), "..", "oracle", "_ref", "libref_mi.so")),
-                    reason="oracle/_ref/libref_mi.so not built (needs /root/reference)")
 def test_oracle_against_compiled_reference_randomised(oracle):
-    rng = np.random.default_rng(5)
-    for n in (1, 2, 5, 8, 49, 64, 200, 392, 784):
-        for t in range(12):
-            x = rng.normal(size=n)
-            y = rng.normal(size=n) + (t % 3) * 0.5 * x
-            if t % 4 == 0:
-                x = np.round(x * 3) / 3
-            if t % 6 == 0:
-                y = np.full(n, 0.25)
-            assert same(oracle.mi(x, y), oracle.ref_mi(x, y))
+    """the compiled reference's MutualInformation and getMean / getStdDev on seeded random inputs (ref_checks.npz)"""
+    g = load("ref_checks.npz")
+    off = 0
+    for n, want in zip(g["mi_n"], g["mi"]):
+        x, y = g["mi_x"][off:off + n], g["mi_y"][off:off + n]
+        off += n
+        assert same(oracle.mi(x, y), want), (n, oracle.mi(x, y), want)
+    assert off == len(g["mi_x"]) and len(g["mi_n"]) == 9 * 12
     for nc in (12, 19):
-        r = np.float32(rng.normal(size=(300, nc)) * 0.02 + 500).astype(float)
-        m, s = oracle.mean_std(r)
-        m2, s2 = oracle.ref_mean_std(r)
-        assert np.array_equal(m, m2) and np.array_equal(s, s2, equal_nan=True)
+        m, s = oracle.mean_std(g["ms%d_rows" % nc])
+        assert np.array_equal(m, g["ms%d_mean" % nc]) and np.array_equal(s, g["ms%d_std" % nc], equal_nan=True)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(GOLD), "..", "oracle", "_ref", "libref_mi.so")),
-                    reason="oracle/_ref/libref_mi.so not built (needs /root/reference)")
 def test_oracle_stage3_inputs_and_mi_equal_the_compiled_reference(oracle):
-    """Rebuild one pixel's neighbourhood statistics, normalisation and all 96 MI values with the compiled
-    reference functions (getMean/getStdDev, divideArrays(subtractArrays), MutualInformation) from the oracle's
-    own member list, and require bit-identity with what the oracle's filter pass reports."""
-    from raytracer_rpf_amd import feature_buffer as fb
+    """One pixel's neighbourhood statistics, normalisation and all 96 MI values as the compiled reference functions
+    (the 3-sigma test, getMean/getStdDev, divideArrays(subtractArrays), MutualInformation) compute them from the
+    reference's own member list (ref_checks.npz), against what the oracle's filter pass reports, bit for bit."""
+    g = load("ref_checks.npz")
+    planes = g["s3_planes"]
     W, H, S, box = 9, 8, 8, 7
-    planes = fb.synth_planes(W, H, S, seed=13, sigma_f=1e-3, sigma_c=0.01, mode="clustered")
+    assert planes.shape == (19, H, W, S)
     r = oracle.filter_pass(planes, oracle.make_desc(W, H, S, box=box, n_threads=1))
-    pa, pb = oracle.pair_table()
-    b = (box - 1) // 2
-    mean12, sd12 = oracle.pixel_stats(planes, oracle.make_desc(W, H, S))
-    for (y, x) in ((4, 4), (0, 0), (7, 3)):
-        rows = [planes[:, y, x, s].astype(float) for s in range(S)]
-        for xn in range(x - b, x + b + 1):
-            for yn in range(y - b, y + b + 1):
-                if (xn, yn) == (x, y) or not (0 <= xn < W and 0 <= yn < H):
-                    continue
-                for s in range(S):
-                    v = planes[:, yn, xn, s].astype(float)
-                    if oracle.ref_within_3std(v[7:], mean12[y, x], sd12[y, x]):
-                        rows.append(v)
-        rows = np.array(rows)
-        assert len(rows) == r["nbhd_size"][y, x]
-        m, s = oracle.ref_mean_std(rows)
-        assert np.array_equal(m, r["mean"][y, x]) and np.array_equal(s, r["stddev"][y, x])
-        z = np.stack([oracle.ref_normalize(v, m, s) for v in rows])
-        mi = np.array([oracle.ref_mi(z[:, a], z[:, bb]) for a, bb in zip(pa, pb)])
-        assert np.array_equal(mi, r["mi"][y, x])
+    for k, (y, x) in enumerate(g["s3_pixels"]):
+        assert g["s3_nbhd"][k] == r["nbhd_size"][y, x]
+        assert np.array_equal(g["s3_mean"][k], r["mean"][y, x]) and np.array_equal(g["s3_std"][k], r["stddev"][y, x])
+        assert np.array_equal(g["s3_mi"][k], r["mi"][y, x])
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(os.path.dirname(GOLD), "..", "oracle", "_ref", "libref_mi.so")),
-                    reason="oracle/_ref/libref_mi.so not built (needs /root/reference)")
 def test_oracle_stage4a_distances_equal_the_compiled_reference(oracle):
     """stage 4a (rpf.cpp:646-670): the oracle's three weighted squared distances of normalised sample pairs against
     sumArray(multiplyArrays(squareArray(subtractArrays(.,.)), w)) composed from the compiled ops.h, bit for bit, on the
-    normalised rows and the alpha / beta of real pixels (incl. large-magnitude rows and NaN / inf weights)"""
-    from raytracer_rpf_amd import feature_buffer as fb
-    W, H, S, box = 9, 8, 8, 7
-    planes = fb.synth_planes(W, H, S, seed=13, sigma_f=1e-3, sigma_c=0.01, mode="clustered")
-    planes[10:13] += 700.0
-    r = oracle.filter_pass(planes, oracle.make_desc(W, H, S, box=box, n_threads=1))
-    rng = np.random.default_rng(9)
+    normalised rows and the alpha / beta of real pixels (incl. large-magnitude rows and NaN / inf weights); the rows,
+    weights and the reference's sums are stored in ref_checks.npz"""
+    g = load("ref_checks.npz")
     checked = 0
-    for (y, x) in ((4, 4), (0, 0), (7, 3), (2, 8)):
-        m, s = r["mean"][y, x], r["stddev"][y, x]
-        own = np.stack([oracle.ref_normalize(planes[:, y, x, i].astype(float), m, s) for i in range(S)])
-        others = np.stack([oracle.ref_normalize(planes[:, (y + dy) % H, (x + dx) % W, i].astype(float), m, s)
-                           for dy, dx, i in rng.integers(0, 4, size=(24, 3))])
-        for zi in own:
-            for zj in np.concatenate([own, others]):
-                got = oracle.weighted_sqdist(zi, zj, r["alpha"][y, x], r["beta"][y, x])
-                want = oracle.ref_weighted_sqdist(zi, zj, r["alpha"][y, x], r["beta"][y, x])
-                assert np.array_equal(got, want, equal_nan=True), (y, x, got, want)
+    for p in range(len(g["s4_own"])):
+        own, a, b = g["s4_own"][p], g["s4_alpha"][p], g["s4_beta"][p]
+        for i, zi in enumerate(own):
+            for j, zj in enumerate(np.concatenate([own, g["s4_other"][p]])):
+                got = oracle.weighted_sqdist(zi, zj, a, b)
+                want = g["s4_d"][p, i, j]
+                assert np.array_equal(got, want, equal_nan=True), (p, i, j, got, want)
                 checked += 1
     # non-finite weights propagate identically
-    z = rng.normal(size=(2, 19))
-    for a in (np.array([np.nan, 1.0, 2.0]), np.array([np.inf, 0.0, -1.0])):
-        b = np.concatenate([a, rng.normal(size=9)])
-        assert np.array_equal(oracle.weighted_sqdist(z[0], z[1], a, b), oracle.ref_weighted_sqdist(z[0], z[1], a, b),
-                              equal_nan=True)
+    z = g["s4nf_z"]
+    for a, b, want in zip(g["s4nf_alpha"], g["s4nf_beta"], g["s4nf_d"]):
+        assert not np.isfinite(a).all()
+        assert np.array_equal(oracle.weighted_sqdist(z[0], z[1], a, b), want, equal_nan=True)
     assert checked >= 1000
 
 
