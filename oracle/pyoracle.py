@@ -77,6 +77,8 @@ def lib():
         L.rpf_oracle_pair_table_ex.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         L.rpf_oracle_feature_images.argtypes = [C.POINTER(Desc), C.c_void_p, C.c_void_p]
         L.rpf_oracle_weighted_sqdist.argtypes = [C.c_void_p] * 5
+        L.rpf_oracle_within_3std.restype = C.c_int32
+        L.rpf_oracle_within_3std.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
         _lib = L
     return _lib
 
@@ -156,6 +158,13 @@ def mean_std(rows):
     m, s = np.empty(nc), np.empty(nc)
     lib().rpf_oracle_mean_std(_p(rows), n, nc, _p(m), _p(s))
     return m, s
+
+
+def within_3std(f, mean, sd):
+    """stage 1b's 3-sigma test of one candidate's features against a pixel's means / stds, as the filter pass applies it"""
+    f, mean, sd = _f64(f), _f64(mean), _f64(sd)
+    assert f.shape == mean.shape == sd.shape and f.ndim == 1
+    return bool(lib().rpf_oracle_within_3std(_p(f), _p(mean), _p(sd), len(f)))
 
 
 def weighted_sqdist(zi, zj, alpha, beta):

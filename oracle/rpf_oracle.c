@@ -156,6 +156,19 @@ void rpf_oracle_mean_std(const double *rows, int32_t n, int32_t ncols, double *m
     for (int c = 0; c < ncols; ++c) stddev[c] = sqrt(stddev[c] / (double)n - mean[c] * mean[c]); /* ops.h:141 */
 }
 
+/* rpf.cpp:577-580, ops.h:99-107: a feature rejects the candidate iff |f - m| >= 3 sd (NaN on either side never rejects) */
+static inline int fails_3std(double f, double m, double sd) {
+    const double a = fabs(f - m);
+    const double lim = sd * 3; /* rpf.cpp:579 */
+    return a >= lim;
+}
+
+int32_t rpf_oracle_within_3std(const double *f, const double *mean, const double *sd, int32_t nf) {
+    for (int k = 0; k < nf; ++k)
+        if (fails_3std(f[k], mean[k], sd[k])) return 0;
+    return 1;
+}
+
 static size_t plane_stride(const rpf_oracle_desc *d) { return (size_t)d->H * d->W * d->S; }
 static size_t sample_off(const rpf_oracle_desc *d, int y, int x, int s) {
     return ((size_t)y * d->W + x) * d->S + s;
@@ -389,11 +402,8 @@ void rpf_oracle_filter_pass(const rpf_oracle_desc *d, const float *planes, const
                         for (int s = 0; s < S; ++s) {
                             size_t o = sample_off(d, yn, xn, s);
                             int within = 1;
-                            for (int k = 0; k < NF; ++k) { /* ops.h:99-107 : fail iff a >= b */
-                                double a = fabs((double)planes[(F0 + k) * ps + o] - m12[k]);
-                                double lim = s12[k] * 3; /* rpf.cpp:579 */
-                                if (a >= lim) { within = 0; break; }
-                            }
+                            for (int k = 0; k < NF; ++k)
+                                if (fails_3std((double)planes[(F0 + k) * ps + o], m12[k], s12[k])) { within = 0; break; }
                             if (!within) continue;
                             for (int c = 0; c < ND; ++c) nb[(size_t)n * ND + c] = planes[c * ps + o];
                             if (colour_in)

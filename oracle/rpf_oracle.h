@@ -106,6 +106,10 @@ double rpf_oracle_mi(const double *x, const double *y, int32_t n);
 /* ops.h:111-144 on an n x ncols row-major matrix: sequential sums, population std = sqrt(E[x^2]-m^2). */
 void rpf_oracle_mean_std(const double *rows, int32_t n, int32_t ncols, double *mean, double *stddev);
 
+/* stage 1b's 3-sigma test of one candidate against a pixel's nf feature means / stds (rpf.cpp:577-580): 1 = accepted.
+ * The very predicate rpf_oracle_filter_pass applies; pinned against the compiled ops.h composition in tests/test_oracle.py. */
+int32_t rpf_oracle_within_3std(const double *f, const double *mean, const double *sd, int32_t nf);
+
 /* A1: per-pixel mean/std of the 12 features over the pixel's own S samples. Output [H*W*12] each. */
 void rpf_oracle_pixel_stats(const rpf_oracle_desc *d, const float *planes, double *mean, double *stddev);
 

@@ -304,7 +304,9 @@ int32_t launch_filter_binned(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s
         bool run_main = true;
         int count_first = packed ? ctx->tun.count_first : 0;
         uint32_t n_general = npix;
-        const bool prelisted = packed && ctx->flat_fresh;
+        // (the packed kernels are what filters the pixels the prelist leaves out: above 64 spp their N = S fits no packed class,
+        // so every pixel goes to the fused kernel, which proves a flat pixel's N = S itself -- flat_quad_shortcut)
+        const bool prelisted = packed && ctx->flat_fresh && p.S <= class_capacity(kNumPacked - 1);
         if (packed && (count_first < 0 || prelisted)) {
             // pixels that stage 1a proved flat (a zero-variance feature, no NaN mean in the buffer: N = S) never reach the fused
             // kernel or the count pass: the others are listed in slab order (the list of the streaming class is free on this

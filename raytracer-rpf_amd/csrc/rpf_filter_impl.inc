@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256) void pixel_stats_kernel(PassParams p, uint64_t
         ((double *)p.pmean)[(uint64_t)k * HW + pix] = mean;
         ((double *)p.pstd)[(uint64_t)k * HW + pix] = sd;
         any_nan = any_nan || isnan(mean);
-        flat = flat || (sd * 3.0 == 0.0 && !isnan(mean)); // multiplyArray(std, 3) == 0: rejects every finite candidate
+        flat = flat || (sd * 3.0 == 0.0 && isfinite(mean)); // multiplyArray(std, 3) == 0: rejects every finite candidate
     }
     if (p.flat != nullptr) {
         p.flat[pix] = flat ? 1 : 0;
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(256) void pixel_stats_tile_kernel(PassParams p, uin
             ((double *)p.pmean)[(uint64_t)k * HW + base + tid] = mean;
             ((double *)p.pstd)[(uint64_t)k * HW + base + tid] = sd;
             any_nan = any_nan || isnan(mean);
-            flat = flat || (sd * 3.0 == 0.0 && !isnan(mean));
+            flat = flat || (sd * 3.0 == 0.0 && isfinite(mean));
         }
         __syncthreads();
     }
@@ -886,14 +886,15 @@ __device__ __forceinline__ void wave_minmax(const float (&fmn)[kNX], const float
 // would still pass that feature is a NaN one (NaN >= 0 is false), and a NaN sample makes its own pixel's stage-1a mean NaN:
 // so if no pixel of the window has a NaN mean in that feature, N = S is proven with one load per window PIXEL instead of
 // twelve gathers per window SAMPLE.  Returns true when proven (wave-uniform); false = run the general test.
-// (The pixel's own mean must be a number: under the EPS policy stage 1a clamps a NaN sigma to 0, and |f - NaN| >= 0 is false
-// for every candidate -- that feature then rejects nobody.)
+// (The pixel's own mean must be finite: under the EPS policy stage 1a clamps a NaN sigma to 0, and |f - NaN| >= 0 is false
+// for every candidate -- that feature then rejects nobody; a mean of +-inf (a sample at +-inf: sigma = sqrt(inf - inf) = NaN,
+// clamped to 0) is passed by every candidate at the same infinity, |inf - inf| = NaN, whose own pixel's mean is not NaN.)
 __device__ __forceinline__ bool flat_quad_shortcut(const PassParams &p, const double (&m12)[kNFeat], const double (&lim12)[kNFeat],
                                                    int lane, uint64_t HW, int x0, int y0, int nyv, int ncells, int centre_rank) {
     int k0 = -1;
 #pragma unroll
     for (int k = 0; k < kNFeat; ++k)
-        if (lim12[k] == 0.0 && !isnan(m12[k])) k0 = k;
+        if (lim12[k] == 0.0 && isfinite(m12[k])) k0 = k;
     if (k0 < 0) return false; // wave-uniform
     const double *pm = p.pmean + (uint64_t)k0 * HW;
     bool nan_seen = false;
@@ -1722,11 +1723,13 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
             sCoef[lane] = wkk * (lane < 2 ? inv2sp : inv2sc); // cz_k (overwrites the raw-space coefficient slot)
         }
         bsync();
+        // (SD == 0 gives z = 0 by a select, not by (x - M) * 0: a column whose samples hold +-inf has M = +-inf or NaN and SD =
+        // NaN, which EPS clamps to 0 -- there x - M is inf or NaN, and the reference's z is still 0, ops.h:48)
         if constexpr (FAST) {
             for (int t = tid; t < S * kFZ; t += kThreads) {
                 const int i = t / kFZ, k = t - i * kFZ;
                 float z = 0.f;
-                if (k < kNWt) z = (float)((sOwn[i * kNDim + wcol(k)] - sFastM[k]) * sFastI[k]);
+                if (k < kNWt && sFastI[k] != 0.0) z = (float)((sOwn[i * kNDim + wcol(k)] - sFastM[k]) * sFastI[k]);
                 sFastZ[t] = z;
             }
         } else {
@@ -1734,7 +1737,7 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
                 double A = 0.0;
 #pragma unroll
                 for (int k = 0; k < kNWt; ++k) {
-                    const double z = (sOwn[i * kNDim + wcol(k)] - sFastM[k]) * sFastI[k];
+                    const double z = sFastI[k] == 0.0 ? 0.0 : (sOwn[i * kNDim + wcol(k)] - sFastM[k]) * sFastI[k];
                     const double t = sCoef[k] * z;
                     A = fma(t, z, A);
                     sOwnU[i * kOR + k] = -2.0 * t;
@@ -1897,7 +1900,7 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
                         const int k = k0 + g;
                         if (k < kNWt) {
                             const double xv = k < 2 ? (double)pf[k] : (k < 5 ? pc[k < 5 && k >= 2 ? k - 2 : 0] : (double)pf[k >= 5 ? k - 3 : 0]);
-                            const double z = (xv - cm[g]) * ci[g];
+                            const double z = ci[g] == 0.0 ? 0.0 : (xv - cm[g]) * ci[g];
                             zj[k] = z;
                             Bj = fma(cc[g] * z, z, Bj);
                         }
@@ -1907,7 +1910,7 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
 #pragma unroll
                 for (int k = 0; k < kNWt; ++k) {
                     const double xv = k < 2 ? (double)pf[k] : (k < 5 ? pc[k < 5 && k >= 2 ? k - 2 : 0] : (double)pf[k >= 5 ? k - 3 : 0]);
-                    const double z = (xv - sFastM[k]) * sFastI[k];
+                    const double z = sFastI[k] == 0.0 ? 0.0 : (xv - sFastM[k]) * sFastI[k];
                     zj[k] = z;
                     Bj = fma(sCoef[k] * z, z, Bj);
                 }
@@ -2042,6 +2045,9 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
                 for (int k = 0; k < 3; ++k) { cj[k] = pc[k]; zj[2 + k] = (float)((pc[k] - sFastM[2 + k]) * sFastI[2 + k]); }
 #pragma unroll
                 for (int k = 0; k < kNFeat; ++k) zj[5 + k] = (float)(((double)pf[2 + k] - sFastM[5 + k]) * sFastI[5 + k]);
+#pragma unroll
+                for (int k = 0; k < kNWt; ++k)
+                    if (sFastI[k] == 0.0) zj[k] = 0.f;
                 if constexpr (kAhead) fetch17(j + kWave);
 #pragma unroll
                 for (int ii = 0; ii < kOwnBlock; ++ii) {

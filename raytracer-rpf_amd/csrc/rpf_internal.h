@@ -56,9 +56,12 @@ struct PassParams {
     // the packed kernels -- it writes its acceptance masks and N and exits; classify_kernel then deals those pixels into the
     // lane-class lists (one atomic per wave and class: a per-pixel append on one counter cost 11 ns per pixel, 22 ms a frame)
     uint64_t *reroute_masks;   // [H*W][mask_stride], or null = no re-routing
-    // stage 1a's by-product: flat[pix] = 1 when some feature of the pixel has sigma == 0 (and a finite mean) -- the strict 3-sigma
-    // test then rejects every finite candidate (flat_quad_shortcut) -- and *nan_flag != 0 when any feature mean of the buffer is
-    // NaN (the one kind of candidate that would still pass).  flat && !*nan_flag proves N = S without touching a sample.
+    // stage 1a's by-product: flat[pix] = 1 when some feature of the pixel has sigma == 0 and a FINITE mean -- the strict 3-sigma
+    // test then rejects every finite candidate (|f - m| >= 0) and every infinite one (|+-inf - m| = inf >= 0), see
+    // flat_quad_shortcut -- and *nan_flag != 0 when any feature mean of the buffer is NaN (a NaN sample makes its pixel's mean
+    // NaN, and a NaN candidate is the one kind that would still pass).  flat && !*nan_flag proves N = S without touching a
+    // sample.  (A mean of +-inf is not enough: EPS clamps its NaN sigma to 0, and a candidate at the same infinity gives
+    // |inf - inf| = NaN, which never rejects, while its own pixel's mean is +-inf, not NaN.)
     uint8_t *flat;         // [H*W], or null
     int32_t *nan_flag;     // [1]
     uint32_t *redo_list;   // REF_ABORT: pixels whose MI stage met a table inside the rounding band at a non-power-of-two N are

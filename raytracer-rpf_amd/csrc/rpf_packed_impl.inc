@@ -506,7 +506,7 @@ __global__ __launch_bounds__(64 * kPkWaves, kRef19 ? 2 : 1) void filter_packed_k
         const int col = k < 5 ? k : k + kNR;
         const double2 ms = *reinterpret_cast<const double2 *>(sStat + (gbase + col) * 4);
         const double2 ic = *reinterpret_cast<const double2 *>(sStat + (gbase + col) * 4 + 2);
-        const double z = (xval(col) - ms.x) * ic.x;
+        const double z = ic.x == 0.0 ? 0.0 : (xval(col) - ms.x) * ic.x; // SD == 0: z = 0 (ops.h:48), also where x - M is not finite
         zj[k] = z;
         Bj = fma(ic.y * z, z, Bj);
         if ((k & 3) == 3) __builtin_amdgcn_sched_barrier(0);

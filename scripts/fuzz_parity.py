@@ -5,7 +5,8 @@ order / bins / statistics, MI 1e-11, alpha/beta/W 1e-9 under both policies, RGB 
 layouts (19-dim fp32, 27-dim fp16), boxes up to 21 (neighbourhoods beyond 3136 samples run the streaming kernel).  Round 3:
 flat-quad pixels (zero-variance normals: the stage-1a shortcut, the prelist, the packed kernels at N = S), and every case also
 on the one-wave route (option packed = 0) with bit-identical stage outputs demanded between the two routes; the packed run
-takes the probe's route, the fused route and the count-first route in turn (option count_first).
+takes the probe's route, the fused route and the count-first route in turn (option count_first).  72 spp (flat pixels whose
+N = S fits no packed class), and one case in three with a NaN or +-inf sample, a +-inf pixel or +inf and -inf in one pixel.
 usage: fuzz_parity.py [cases] [seed]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,7 +28,7 @@ for i in range(cases):
     wide = bool(rng.integers(0, 4) == 0)   # one case in four: the 27-dim fp16 layout
     L = dict(n_random=4, n_feat=18) if wide else {}
     smax = max(1, 65535 // (box * box))
-    S = int(rng.choice([s for s in (1, 2, 3, 4, 5, 8, 8, 12, 16, 24, 32, 48, 64) if s <= smax]))
+    S = int(rng.choice([s for s in (1, 2, 3, 4, 5, 8, 8, 12, 16, 24, 32, 48, 64, 72) if s <= smax]))
     W, H = int(rng.integers(3, 26)), int(rng.integers(2, 18))
     while W * H * S > (30000 if box > 11 or wide else 60000):  # keep the oracle in seconds
         W, H = max(3, W - 2), max(2, H - 1)
@@ -37,9 +38,21 @@ for i in range(cases):
     beta = int(rng.integers(0, 3))
     seed = int(rng.integers(0, 1 << 30))
     flat = float(rng.choice([0.0, 0.0, 0.5, 0.94]))
+    inject = int(rng.integers(1, 5)) if i % 3 == 0 else 0   # NaN sample, +inf pixel, +inf sample, +inf and -inf in one pixel
+    iy, ix, isamp, ik = int(rng.integers(0, H)), int(rng.integers(0, W)), int(rng.integers(0, S)), int(rng.integers(0, 12))
     if os.environ.get("FUZZ_ONLY") and int(os.environ["FUZZ_ONLY"]) != i:
         continue
     planes = fb.synth_planes(W, H, S, seed=seed, sigma_f=sf, sigma_c=0.01, mode=mode, dtype="f16" if wide else "f32", flat_frac=flat, **L)
+    f0 = 9 if wide else 7
+    if inject == 1:
+        planes[f0 + ik, iy, ix, isamp] = np.nan
+    elif inject == 2:
+        planes[f0 + ik, iy, ix, :] = np.inf
+        planes[f0:, iy, (ix + 1) % W, isamp] = planes[f0:, iy, ix, isamp]
+    elif inject == 3:
+        planes[f0 + ik, iy, ix, isamp] = np.inf
+    elif inject == 4:
+        planes[f0 + ik, iy, ix, isamp], planes[f0 + ik, iy, ix, (isamp + 1) % S] = np.inf, -np.inf
     desc = hip.make_desc(W, H, S, policy=policy, beta_map=beta, plane_dtype=hip.PLANES_F16 if wide else hip.PLANES_F32, **L)
     ctx.set_option("count_first", (-1, 0, 1)[i % 3])   # the probe's choice, the fused route, the count-first route (box*box*S <= 512)
     got = ctx.filter_pass_debug(planes, desc, box=box, allow_nonfinite=True)

@@ -18,6 +18,9 @@
                  two-pass result on it.
   ref_checks.npz known answers of the REAL reference code on the inputs of test_oracle.py's randomised and
                  stage-3 / stage-4a checks (python tests/golden/make_golden.py refchecks).
+  ref_nonfinite.npz  known answers of the REAL ops.h templates on infinite values: getMean / getStdDev of columns
+                 holding +inf, -inf and both, and the 3-sigma test with infinite features and means
+                 (python tests/golden/make_golden.py nonfinite).
 
 Fixtures are data only: inputs and expected outputs.
 """
@@ -145,10 +148,69 @@ def ref_checks_fixture():
     print("ref_checks.npz  %.1f KB" % (os.path.getsize(os.path.join(HERE, "ref_checks.npz")) / 1024))
 
 
+def ref_nonfinite_fixture():
+    """ref_nonfinite.npz: the compiled reference's getMean / getStdDev and 3-sigma test where a value is infinite (a miss
+    ray's depth or position; an fp16 feature above 65504).  Inputs stored verbatim."""
+    out = {}
+    rng = np.random.default_rng(31)
+    inf = np.inf
+    for nc, n in ((12, 8), (19, 24)):
+        r = np.float32(rng.normal(size=(n, nc)) * 0.1 + 0.5).astype(float)
+        r[3, 0] = inf                          # one +inf sample
+        r[5, 1] = -inf                         # one -inf sample
+        r[2, 2], r[6, 2] = inf, -inf           # both: the mean is NaN
+        r[:, 3] = inf                          # every sample +inf
+        r[:, 4] = -inf                         # every sample -inf
+        r[1, 5], r[4, 5] = inf, inf            # two +inf samples
+        r[0, 6] = np.nan                       # a NaN next to them
+        out["ms%d_rows" % nc] = r
+        out["ms%d_mean" % nc], out["ms%d_std" % nc] = O.ref_mean_std(r)
+    # the 3-sigma test (rpf.cpp:577-580): feature 0 of each row is the case, features 1..11 sit inside 3 sigma
+    cases = [  # (f, m, sd)
+        (inf, inf, 0.0),        # a candidate at +inf against a pixel whose mean is +inf (EPS: NaN sigma clamped to 0)
+        (inf, inf, np.nan),     # ... REF_ABORT keeps that sigma NaN
+        (-inf, -inf, 0.0),
+        (-inf, inf, 0.0),
+        (inf, -inf, 0.0),
+        (inf, 0.5, 0.0),        # +inf against a finite mean, sigma 0
+        (-inf, 0.5, 0.0),
+        (inf, 0.5, 0.2),        # ... and a finite sigma
+        (inf, 0.5, inf),
+        (inf, 0.5, np.nan),
+        (0.5, inf, 0.0),        # a finite candidate against a mean of +inf
+        (0.5, inf, np.nan),
+        (0.5, -inf, 0.0),
+        (0.5, inf, inf),
+        (inf, inf, inf),
+        (np.nan, inf, 0.0),
+        (inf, np.nan, 0.0),
+        (0.5, 0.5, 0.0),        # the finite zero-sigma case the flat proof rests on
+        (0.5, 0.5, inf),
+        (1e308, -1e308, 0.0),   # |f - m| overflows to inf
+    ]
+    f = np.float32(rng.normal(size=(len(cases), 12)) * 0.01).astype(float)
+    mean = np.zeros((len(cases), 12))
+    sd = np.full((len(cases), 12), 0.6)
+    for i, (fv, mv, sv) in enumerate(cases):
+        f[i, 0], mean[i, 0], sd[i, 0] = fv, mv, sv
+    out["w3_f"], out["w3_mean"], out["w3_sd"] = f, mean, sd
+    out["w3_pass"] = np.array([O.ref_within_3std(f[i], mean[i], sd[i]) for i in range(len(cases))])
+    path = os.path.join(HERE, "ref_nonfinite.npz")
+    with np.errstate(invalid="ignore", over="ignore"):
+        np.savez_compressed(path, **out, source="getMean / getStdDev / allLessThan of the reference's ops.h, "
+                                                "g++ 11.4 -O3 -std=gnu++11; inputs stored verbatim")
+    print("ref_nonfinite.npz  %.1f KB" % (os.path.getsize(path) / 1024))
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "rpfb":
         O.build(force=False)
         return rpfb_fixture()
+    if len(sys.argv) > 1 and sys.argv[1] == "nonfinite":
+        O.build(force=False)
+        if not O.ref_available():
+            sys.exit("oracle/_ref/libref_mi.so missing: build it from the reference sources first (oracle/Makefile)")
+        return ref_nonfinite_fixture()
     if len(sys.argv) > 1 and sys.argv[1] == "refchecks":
         O.build(force=False)
         if not O.ref_available():

@@ -1066,3 +1066,251 @@ def test_randomised_parity_sweep(ctx, hipmod, oracle):
             for k in ("nbhd_size", "member_hash", "bin_hash"):
                 assert (got[k] == want[k]).all(), (k, tag)
             assert (np.isfinite(got["colour"]) == np.isfinite(want["colour"])).all(), tag
+
+
+# ---- route options, non-finite features, the headline regime at full width ------------------------------------------
+STAGE_KEYS = ("nbhd_size", "member_hash", "bin_hash", "mean", "stddev", "mi", "alpha", "beta", "wrc")
+# options documented as giving the same colour BITS (include/rpf_hip.h rpf_set_option); the others change which kernel, and
+# so which order of the weight sums, filters a pixel: their colours agree to rounding
+SAME_BITS = ("screen", "split_weights", "split_chunk", "count_first")
+
+
+def _run_opts(hipmod, planes, desc, box, opts=()):
+    """one pass on a fresh context (no option outlives its run), every debug plane"""
+    with hipmod.Context(0) as c:
+        for name, value in opts:
+            c.set_option(name, value)
+        got = c.filter_pass_debug(planes, desc, box=box, allow_nonfinite=True)
+        got["route"] = c.route()
+        got["options_active"] = c.counters().options_active
+    return got
+
+
+def _assert_oracle_parity(got, want, hipmod):
+    """check_pass where the oracle's colours are finite; otherwise (REF_ABORT) the oracle's NaN pattern and status"""
+    assert (got["status"] == hipmod.E_NONFINITE) == (want["status"] == 1)
+    assert got["nonfinite_pixels"] == want["nonfinite_pixels"] and got["first_bad_pixel"] == want["first_bad_pixel"]
+    assert np.array_equal(np.isnan(got["colour"]), np.isnan(want["colour"]))
+    if np.isfinite(want["colour"]).all():
+        check_pass(got, want)
+    else:
+        for k in ("nbhd_size", "member_hash", "bin_hash"):
+            assert (got[k] == want[k]).all(), k
+        fin = np.isfinite(want["colour"])
+        assert rel_l2(got["colour"][fin], want["colour"][fin]) <= REL_L2_BAR
+
+
+# name: (W, H, S, box, mode, sigma_f, sigma_c, flat_frac, policy, layout)
+ROUTE_BUFFERS = {
+    "8spp-b7-flat0": (40, 24, 8, 7, "smooth", 3e-3, 0.01, 0.0, 1, 19),      # unbinned; N = 8 ... 97: count first by the probe
+    "8spp-b7-flat94": (40, 24, 8, 7, "smooth", 0.05, 0.01, 0.94, 0, 19),    # unbinned, 94 % flat pixels, REF_ABORT: the oracle's NaNs
+    "16spp-b7": (30, 14, 16, 7, "smooth", 3e-3, 0.01, 0.0, 1, 19),          # binned; N = 23 ... 130: packed and one-wave classes
+    "32spp-b7-smooth": (11, 9, 32, 7, "smooth", 0.05, 1e-4, 0.0, 1, 19),    # split route, K = 25
+    "64spp-b7-smooth": (11, 8, 64, 7, "smooth", 0.05, 1e-4, 0.0, 1, 19),    # split route, K = 49
+    "72spp-b5-flat60": (10, 8, 72, 5, "clustered", 1e-3, 0.01, 0.6, 1, 19),  # flat pixels whose N = S = 72 fits no packed class
+    "27dim-8spp-b7": (16, 10, 8, 7, "smooth", 3e-3, 0.01, 0.3, 1, 27),      # fp16 planes
+    "16spp-b17": (20, 18, 16, 17, "smooth", 0.05, 1e-4, 0.0, 1, 19),        # N up to 4142: the streaming kernel
+}
+ROUTE_OPTIONS = [("binning", 0), ("binning", 1), ("table_in_lds", 0), ("table_in_lds", 1), ("strip_w", 8), ("strip_w", 128),
+                 ("waves_per_pixel", 1), ("waves_per_pixel", 4), ("count_first", 0), ("count_first", 1), ("packed", 0),
+                 ("split_weights", 0), ("split_chunk", 17), ("screen", 0)]
+# table_in_lds = 1 at 64 spp: the K = 49 kernel's 147 KiB plus the 25 KiB table exceed the 160 KiB of LDS a workgroup may
+# have, and the launch is refused (rpf_lds_bytes_required(64, 7) = 150784 without the table)
+ROUTE_SKIP = {("64spp-b7-smooth", "table_in_lds", 1)}
+
+
+_ROUTE_CACHE = {}  # name -> (planes, desc, box, oracle result, default-options run): each buffer is filtered once per session
+
+
+def _route_buffer(hipmod, oracle, name):
+    _cache = _ROUTE_CACHE
+    if name not in _cache:
+        W, H, S, box, mode, sf, sc, flat, policy, layout = ROUTE_BUFFERS[name]
+        kw = dict(L27, dtype="f16") if layout == 27 else {}
+        planes = fb.synth_planes(W, H, S, seed=21, sigma_f=sf, sigma_c=sc, mode=mode, flat_frac=flat, **kw)
+        lay = dict(L27, plane_dtype=hipmod.PLANES_F16) if layout == 27 else {}
+        olay = L27 if layout == 27 else {}
+        desc = hipmod.make_desc(W, H, S, policy=policy, **lay)
+        want = oracle.filter_pass(planes.astype(np.float32), oracle.make_desc(W, H, S, box=box, policy=policy, **olay))
+        _cache[name] = (planes, desc, box, want, _run_opts(hipmod, planes, desc, box))
+    return _cache[name]
+
+
+@pytest.mark.parametrize("name,option,value", [(b, o, v) for b in ROUTE_BUFFERS for o, v in ROUTE_OPTIONS
+                                               if (b, o, v) not in ROUTE_SKIP])
+def test_route_options_change_nothing(hipmod, oracle, name, option, value):
+    """Every route option documented as changing nothing (rpf_set_option), on buffers that reach every kernel route: the run
+    with the option against the oracle AND against the default run -- every stage output the same bits, colours the same bits
+    where the option promises it, to rounding otherwise."""
+    planes, desc, box, want, base = _route_buffer(hipmod, oracle, name)
+    got = _run_opts(hipmod, planes, desc, box, [(option, value)])
+    assert got["options_active"] == 1
+    _assert_oracle_parity(got, want, hipmod)
+    _assert_oracle_parity(base, want, hipmod)
+    for k in STAGE_KEYS:
+        assert np.array_equal(got[k], base[k], equal_nan=True), k
+    assert got["status"] == base["status"] and got["nonfinite_pixels"] == base["nonfinite_pixels"]
+    assert got["first_bad_pixel"] == base["first_bad_pixel"]
+    assert np.array_equal(np.isnan(got["colour"]), np.isnan(base["colour"]))
+    if option in SAME_BITS:
+        assert np.array_equal(got["colour"], base["colour"], equal_nan=True)
+    else:
+        # another kernel (or the same kernel with another LDS layout / pixel walk) sums the weights of a pixel: same terms,
+        # possibly in another order
+        m = np.isfinite(base["colour"])
+        np.testing.assert_allclose(got["colour"][m], base["colour"][m], rtol=1e-12, atol=1e-300)
+    if name == "72spp-b5-flat60":
+        # not vacuous: the oracle moves the colours of the flat pixels (N = S), so a pixel left unfiltered fails above
+        flat = want["nbhd_size"] == ROUTE_BUFFERS[name][2]
+        cin = planes[2:5].astype(np.float64)
+        assert flat.sum() > 10 and np.abs(want["colour"][:, flat] - cin[:, flat]).max() > 1e-3
+    if option == "binning" and name in ("8spp-b7-flat0", "8spp-b7-flat94", "27dim-8spp-b7"):
+        assert got["route"] == (2 if value else base["route"])
+
+
+INF_INJECTIONS = ("pixel_inf", "sample_inf", "mixed_inf", "random_inf", "colour_inf")
+
+
+def _nonflat_pixel(planes, f0, y, x):
+    """the first pixel at or right of (y, x) none of whose features is constant over its samples"""
+    while (planes[f0:, y, x].astype(np.float64).std(axis=-1) == 0).any():
+        x += 1
+    return y, x
+
+
+def _inject_inf(planes, layout, kind):
+    """non-finite values where path tracers put them (a miss ray's depth / position): returns the injected pixels"""
+    f0 = 5 + (4 if layout == 27 else 2)
+    k = f0 + 9                                  # second-hit position x (p1x)
+    if kind == "pixel_inf":
+        # a whole pixel at +inf in one feature, and two neighbour samples equal to two of its own samples in every feature
+        # (the infinite one included): they pass its 3-sigma test, |inf - inf| = NaN never rejects
+        y, x = _nonflat_pixel(planes, f0, 5, 6)
+        planes[k, y, x, :] = np.inf
+        planes[f0:, y, x + 1, 1] = planes[f0:, y, x, 1]
+        planes[f0:, y + 1, x, 2] = planes[f0:, y, x, 2]
+        return [(y, x), (y, x + 1), (y + 1, x)]
+    if kind == "sample_inf":
+        planes[k, 4, 7, 3] = np.inf
+        return [(4, 7)]
+    if kind == "mixed_inf":                     # +inf and -inf in one feature of one pixel: a NaN mean (the nan_flag path)
+        planes[k, 6, 8, 0], planes[k, 6, 8, 5] = np.inf, -np.inf
+        return [(6, 8)]
+    if kind == "random_inf":
+        planes[5, 5, 9, 2] = np.inf
+        return [(5, 9)]
+    planes[3, 6, 5, 4] = np.inf                 # colour_inf: green
+    return [(6, 5)]
+
+
+@pytest.mark.parametrize("kind", INF_INJECTIONS)
+@pytest.mark.parametrize("mode,flat", [("smooth", 0.0), ("smooth", 0.5), ("clustered", 0.0), ("clustered", 0.5)])
+@pytest.mark.parametrize("layout", [19, 27])
+def test_infinite_features_vs_oracle(hipmod, oracle, layout, mode, flat, kind):
+    """+-inf in the feature, random-parameter and colour planes, under both policies, on the default route and the count-first
+    route: membership (size, order) the oracle's bits everywhere, the oracle's NaN pattern, status and first bad pixel, and
+    every stage output where the oracle's colours are finite.  A pixel whose samples hold +inf in a feature has mean +inf and
+    (EPS) sigma 0: it is NOT flat -- neighbour samples at +inf in that feature pass its test."""
+    W, H, S = 16, 12, 8
+    sf, sc = (0.05, 1e-4) if mode == "smooth" else (1e-3, 0.01)
+    kw = dict(L27, dtype="f16") if layout == 27 else {}
+    planes = fb.synth_planes(W, H, S, seed=61, sigma_f=sf, sigma_c=sc, mode=mode, flat_frac=flat, **kw)
+    pix = _inject_inf(planes, layout, kind)
+    lay = dict(L27, plane_dtype=hipmod.PLANES_F16) if layout == 27 else {}
+    olay = L27 if layout == 27 else {}
+    for policy in (hipmod.DEGEN_EPS, hipmod.DEGEN_REF_ABORT):
+        want = oracle.filter_pass(planes.astype(np.float32), oracle.make_desc(W, H, S, box=7, policy=policy, **olay))
+        if kind == "pixel_inf" and policy == hipmod.DEGEN_EPS:
+            assert want["nbhd_size"][pix[0]] > S      # the samples a flat proof resting on "mean is not NaN" drops
+        for cf in (-1, 1):
+            got = _run_opts(hipmod, planes, hipmod.make_desc(W, H, S, policy=policy, **lay), 7, [("count_first", cf)])
+            tag = (policy, cf)
+            assert np.array_equal(got["nbhd_size"], want["nbhd_size"]), tag
+            assert np.array_equal(got["member_hash"], want["member_hash"]), tag
+            assert (got["status"] == hipmod.E_NONFINITE) == (want["status"] == 1), tag
+            assert got["nonfinite_pixels"] == want["nonfinite_pixels"], tag
+            assert got["first_bad_pixel"] == want["first_bad_pixel"], tag
+            assert np.array_equal(np.isnan(got["colour"]), np.isnan(want["colour"])), tag
+            if np.isfinite(want["colour"]).all():
+                check_pass(got, want)
+            else:
+                fin = np.isfinite(want["colour"])
+                assert rel_l2(got["colour"][fin], want["colour"][fin]) <= REL_L2_BAR, tag
+
+
+@pytest.mark.parametrize("W,S,R,kclass", [(1920, 8, 2, "K7"), (3840, 32, 1, "K25"), (1920, 64, 1, "K49")])
+def test_headline_regime_full_width_stages(ctx, hipmod, oracle, W, S, R, kclass):
+    """The bench's buffer (bench.py: mode "smooth", sigma_f 0.05, sigma_c 1e-4), R full-width rows at the frame centre with
+    their halo: every stage output against the oracle, not only the colours -- on this buffer the filter barely moves a
+    colour, so membership, bins, MI, alpha, beta and W_r_c are what a wrong kernel would change."""
+    b = 3
+    H = 2 * b + R
+    planes = fb.synth_planes(W, H, S, row0=540 - b, mode="smooth", sigma_f=0.05, sigma_c=1e-4)
+    rows = (b, b + R)
+    got = ctx.filter_pass_debug(planes, hipmod.make_desc(W, H, S, row_begin=b, row_end=b + R, policy=hipmod.DEGEN_EPS), box=7)
+    route = ctx.route()
+    want = oracle.filter_pass(planes, oracle.make_desc(W, H, S, box=7, row_begin=b, row_end=b + R, policy=oracle.DEGEN_EPS))
+    check_pass(got, want, rows=rows)
+    assert rel_l2(got["colour"][:, b:b + R], want["colour"][:, b:b + R]) <= REL_L2_BAR
+    assert got["nonfinite_pixels"] == want["nonfinite_pixels"] == 0
+    mean_n = want["sum_nbhd"] / (W * R)
+    assert got["sum_nbhd"] == want["sum_nbhd"] and got["max_nbhd"] == want["max_nbhd"]
+    if kclass == "K7":       # the bench's 1080p x 8 regime: mean N ~ 295 on the fused route's one-wave K = 7 kernel
+        assert 64 < got["max_nbhd"] <= 7 * 64 and mean_n > 250 and route == 0
+    else:                    # the four-wave classes of the split route: K = 25 (832 < N <= 1600), K = 49 (N > 1600)
+        assert mean_n > 832 and route == 2
+        if kclass == "K49":
+            assert mean_n > 1600
+
+
+def test_randomised_parity_sweep_flat_wide_nonfinite(hipmod, oracle):
+    """A second seeded sweep over what test_randomised_parity_sweep never draws: flat pixels, the 27-dim fp16 layout, 72 spp
+    at box 5, one route option per case (each on a fresh context), +-inf / NaN samples.  Same assertions."""
+    rng = np.random.default_rng(515151)
+    opts = [o for o in ROUTE_OPTIONS]
+    for i in range(30):
+        box = int(rng.choice([3, 5, 5, 7, 7, 9]))
+        smax = max(1, 3136 // (box * box))
+        S = int(rng.choice([s for s in (1, 3, 4, 8, 8, 12, 16, 24, 32, 48, 64, 72) if s <= smax]))
+        W, H = int(rng.integers(3, 22)), int(rng.integers(2, 15))
+        while W * H * S > 30000:
+            W, H = max(3, W - 2), max(2, H - 1)
+        layout = 27 if i % 4 == 1 else 19
+        mode = str(rng.choice(["smooth", "clustered"]))
+        sf = float(rng.choice([1e-5, 1e-3, 0.02, 0.05]))
+        flat = float(rng.choice([0.0, 0.5, 0.94]))
+        policy = int(rng.choice([hipmod.DEGEN_EPS, hipmod.DEGEN_EPS, hipmod.DEGEN_REF_ABORT]))
+        beta = int(rng.integers(0, 3))
+        opt = opts[int(rng.integers(0, len(opts)))]
+        if opt == ("table_in_lds", 1) and box * box * S > 832:
+            opt = ("table_in_lds", 0)      # a forced LDS table beside the K = 25 / 49 kernels' LDS can exceed 160 KiB: refused
+        if opt == ("waves_per_pixel", 4) and layout == 27:
+            opt = ("waves_per_pixel", 1)   # (forced four-wave runs are drawn for the reference layout only)
+        kw = dict(L27, dtype="f16") if layout == 27 else {}
+        planes = fb.synth_planes(W, H, S, seed=int(rng.integers(0, 1 << 30)), sigma_f=sf, sigma_c=0.01, mode=mode,
+                                 flat_frac=flat, **kw)
+        f0 = 9 if layout == 27 else 7
+        inject = ("none", "nan", "inf_pixel", "inf_sample", "inf_mixed")[int(rng.integers(1, 5))] if i % 3 == 0 else "none"
+        y, x, s = int(rng.integers(0, H)), int(rng.integers(0, W)), int(rng.integers(0, S))
+        k = f0 + int(rng.integers(0, 12))
+        if inject == "nan":
+            planes[k, y, x, s] = np.nan
+        elif inject == "inf_pixel":
+            planes[k, y, x, :] = np.inf
+            planes[f0:, y, (x + 1) % W, s] = planes[f0:, y, x, s]
+        elif inject == "inf_sample":
+            planes[k, y, x, s] = np.inf
+        elif inject == "inf_mixed":
+            planes[k, y, x, s], planes[k, y, x, (s + 1) % S] = np.inf, -np.inf
+        lay = dict(L27, plane_dtype=hipmod.PLANES_F16) if layout == 27 else {}
+        olay = L27 if layout == 27 else {}
+        got = _run_opts(hipmod, planes, hipmod.make_desc(W, H, S, policy=policy, beta_map=beta, **lay), box, [opt])
+        want = oracle.filter_pass(planes.astype(np.float32), oracle.make_desc(W, H, S, box=box, policy=policy, beta_map=beta, **olay))
+        tag = (i, W, H, S, box, layout, mode, sf, flat, policy, beta, opt, inject)
+        assert got["nonfinite_pixels"] == want["nonfinite_pixels"], tag
+        if np.isfinite(want["colour"]).all():
+            check_pass(got, want)
+        else:
+            for k in ("nbhd_size", "member_hash", "bin_hash"):
+                assert (got[k] == want[k]).all(), (k, tag)
+            assert (np.isfinite(got["colour"]) == np.isfinite(want["colour"])).all(), tag

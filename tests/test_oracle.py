@@ -65,6 +65,28 @@ def test_oracle_against_compiled_reference_randomised(oracle):
         assert np.array_equal(m, g["ms%d_mean" % nc]) and np.array_equal(s, g["ms%d_std" % nc], equal_nan=True)
 
 
+def test_oracle_nonfinite_mean_std_and_three_sigma_equal_the_compiled_reference(oracle):
+    """+-inf in the features (ref_nonfinite.npz): getMean / getStdDev of columns holding +inf, -inf, both, and the 3-sigma
+    test with infinite candidates, means and sigmas -- the oracle's own functions (the ones its filter pass calls) against
+    the compiled reference, bit for bit.  The flat-pixel proof of stage 1b rests on these answers."""
+    g = load("ref_nonfinite.npz")
+    for nc in (12, 19):
+        m, s = oracle.mean_std(g["ms%d_rows" % nc])
+        assert np.array_equal(m, g["ms%d_mean" % nc], equal_nan=True)
+        assert np.array_equal(s, g["ms%d_std" % nc], equal_nan=True)
+        # a column holding +inf has mean +inf and sigma sqrt(inf - inf) = NaN; one holding both infinities a NaN mean
+        assert m[0] == np.inf and m[1] == -np.inf and np.isnan(m[2]) and np.isnan(s[:3]).all()
+    f, mean, sd, want = g["w3_f"], g["w3_mean"], g["w3_sd"], g["w3_pass"]
+    got = np.array([oracle.within_3std(f[i], mean[i], sd[i]) for i in range(len(f))])
+    assert np.array_equal(got, want)
+    # the cases the stage-1b flat proof needs: sigma 0 and a FINITE mean reject finite and infinite candidates alike, a mean
+    # of +inf with sigma 0 accepts a candidate at +inf (|inf - inf| = NaN never rejects)
+    i_inf_inf = int(np.flatnonzero((f[:, 0] == np.inf) & (mean[:, 0] == np.inf) & (sd[:, 0] == 0))[0])
+    assert want[i_inf_inf]
+    fin0 = np.isfinite(mean[:, 0]) & (sd[:, 0] == 0) & ~np.isnan(f[:, 0])
+    assert fin0.sum() >= 3 and not want[fin0].any()
+
+
 def test_oracle_stage3_inputs_and_mi_equal_the_compiled_reference(oracle):
     """One pixel's neighbourhood statistics, normalisation and all 96 MI values as the compiled reference functions
     (the 3-sigma test, getMean/getStdDev, divideArrays(subtractArrays), MutualInformation) compute them from the
