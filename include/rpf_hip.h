@@ -265,6 +265,51 @@ int32_t rpf_multi_query_counters(rpf_multi *m, rpf_counters *out);
 /* LDS bytes per workgroup the fused kernel needs for (S, box); > device limit => RPF_E_UNSUPPORTED */
 int64_t rpf_lds_bytes_required(int32_t S, int32_t box);
 
+/* ---- the film step: pbrt's reconstruction filter and crop window on the filtered samples -----------------------------
+ * RPFIntegrator::Render ends by feeding every sample through FilmTile::AddSample (rpf.cpp:779-794, film.h:121-161), x outer,
+ * y inner, then s, and then MergeFilmTile + WriteImage (film.cpp:117-130, 169-203).  rpf_filter()'s pixel_rgb_out covers
+ * only pbrt's default box filter of radius 0.5 with no crop window, and not in pbrt's arithmetic; these entry points
+ * compute the film's values for any of pbrt's five PixelFilters and any crop window, bit-identical to a serial fp32
+ * evaluation in the reference's order.  The buffer [H][W][S] is the sample film: its pixel (0,0) is raster pixel
+ * (sample_x0, sample_y0) = Film::GetSampleBounds().pMin, which lies left of / above the image when the filter is wider
+ * than half a pixel (e.g. (-2,-2) for gaussian r = 2 on a full frame).
+ * Preconditions (RPF_E_BADARG otherwise, the message names the first offending sample in the reference's order):
+ * every sample's pFilm lies in [q, q+1] on each axis, q = the raster coordinate of its pixel (what pbrt's
+ * pPixel + Get2D() gives, fp32 rounding up to q+1 included; NaN fails); radii finite, > 0; non-empty pixel bounds; raster
+ * coordinates (sample film and pixel bounds) and radii within +-2^22; the whole buffer is one slab (row_begin == 0,
+ * row_end == H).  fp16 planes (the 27-dim layout) are RPF_E_UNSUPPORTED: fp16 cannot place pFilm in its pixel
+ * beyond 2048. */
+enum { RPF_PIXFILTER_BOX = 0, RPF_PIXFILTER_TRIANGLE, RPF_PIXFILTER_GAUSSIAN, RPF_PIXFILTER_MITCHELL, RPF_PIXFILTER_SINC };
+#define RPF_FILTER_TABLE_WIDTH 16 /* Film::filterTableWidth, film.h:91 */
+
+typedef struct rpf_film {
+    int32_t sample_x0, sample_y0;   /* raster coords of buffer pixel (0,0) = Film::GetSampleBounds().pMin              */
+    int32_t px0, py0, px1, py1;     /* Film::croppedPixelBounds [p0, p1): the output pixels                            */
+    float radius_x, radius_y;       /* Filter::radius                                                                 */
+    float max_sample_luminance;     /* Film "maxsampleluminance" (film.cpp:248); INFINITY = off                       */
+    float scale;                    /* Film "scale" (film.cpp:246); used by image_rgb_out only                        */
+    float table[RPF_FILTER_TABLE_WIDTH * RPF_FILTER_TABLE_WIDTH]; /* Film::filterTable, [y][x], as film.cpp:66-76 fills it */
+} rpf_film;
+
+/* pbrt's filter table for the five filters (film.cpp:66-76 with each filter's Evaluate), host only, works without a GPU.
+ * p0 / p1: gaussian alpha | mitchell B, C | sinc tau; a NaN parameter takes pbrt's default (gaussian alpha 2, mitchell
+ * B = C = 1/3, sinc tau 3).  A pbrt binding passes pbrt's own table instead. */
+int32_t rpf_film_filter_table(int32_t kind, float radius_x, float radius_y, float p0, float p1, float *table_out);
+
+/* rpf_filter()'s passes over the W x H x S buffer (the sample film), then the film step.  Any output may be NULL.
+ *   sample_rgb_out   [3][H][W][S]           filtered sample colours, as rpf_filter
+ *   tile_rgb_out     [py1-py0][px1-px0][3]  FilmTilePixel::contribSum
+ *   tile_weight_out  [py1-py0][px1-px0]     FilmTilePixel::filterWeightSum
+ *   image_rgb_out    [py1-py0][px1-px0][3]  Film::WriteImage's value of the pixel (no splats), scale applied */
+int32_t rpf_filter_film(rpf_ctx *ctx, const rpf_desc *desc, const rpf_film *film, const void *planes, const float *ray_weight,
+                        float *sample_rgb_out, float *tile_rgb_out, float *tile_weight_out, float *image_rgb_out);
+/* the film step alone on device buffers: d_planes' pFilm planes (0, 1), d_colour 3 fp64 planes [3][H][W][S] (what
+ * rpf_filter_device leaves), d_ray_weight [H][W][S] or NULL (= 1); outputs as above, device pointers, any may be NULL.
+ * Stream-ordered on `stream` like rpf_reduce_device; returns after the stream has drained (the pFilm check is read back). */
+int32_t rpf_film_splat_device(rpf_ctx *ctx, const rpf_desc *desc, const rpf_film *film, const void *d_planes,
+                              const double *d_colour, const float *d_ray_weight, float *d_tile_rgb, float *d_tile_weight,
+                              float *d_image_rgb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

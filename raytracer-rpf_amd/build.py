@@ -12,6 +12,7 @@ LIB = os.path.join(_HERE, "lib", "librpf_hip.so")
 # the fused per-pixel kernels compile as one translation unit per sample layout and size-class part (rpf_filter_impl.inc
 # with RPF_IMPL_PART = 1 / 2 / 3), in parallel: the single kernel TU of rounds 1-2 took 3.2 minutes
 KERNEL_TUS = ["rpf_impl_%s_%s.hip" % (lay, part) for lay in ("d19", "d27") for part in ("small", "mid", "large")] + ["rpf_kernels.hip"]
+KERNEL_TUS += ["rpf_film.hip"]  # the film step (pbrt's reconstruction filter): rpf_filter_film / rpf_film_splat_device
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in KERNEL_TUS + ["rpf_api.hip"]]
 HEADERS = [os.path.join(_HERE, "csrc", "rpf_internal.h"), os.path.join(_HERE, "csrc", "rpf_xlane.h"),
            os.path.join(_HERE, "csrc", "rpf_filter_impl.inc"), os.path.join(_HERE, "csrc", "rpf_packed_impl.inc"),

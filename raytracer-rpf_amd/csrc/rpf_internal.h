@@ -142,6 +142,25 @@ hipError_t launch_prelist(const PassParams &p, uint32_t *list, uint32_t *count /
 hipError_t launch_nbhd_reduce(const int32_t *nbhd, int W, int row_begin, int row_end, unsigned long long *out2,
                               hipStream_t s);
 hipError_t launch_feature_images(const float *planes, int W, int H, int S, double *out, unsigned long long *maxbits, hipStream_t s);
+// the film step (rpf_film.hip): pbrt's FilmTile::AddSample for every sample, gathered per output pixel
+struct FilmParams {
+    int32_t W, H, S;
+    int32_t sx0, sy0;          // raster coords of buffer pixel (0,0)
+    int32_t px0, py0, px1, py1;
+    int32_t hx, hy;            // window half-widths in pixels (rpf_api.hip film_window)
+    float rx, ry, inv_rx, inv_ry; // Filter::radius, FilmTile::invFilterRadius (1 / r, formed on the host)
+    float max_lum, scale;
+    uint64_t plane_stride;     // H*W*S
+};
+// pFilm outside [q, q+1] (or NaN): *first_bad = min over such samples of ((x*H + y)*S + s), the reference's order
+hipError_t launch_film_check(const FilmParams &f, const float *planes, unsigned long long *first_bad, hipStream_t s);
+// per sample: d = pFilm - 0.5 (float2, [y][s][x]) and the clamped L * sampleWeight (3 planes [y][s][x])
+hipError_t launch_film_stage(const FilmParams &f, const float *planes, const double *colour, const float *ray_weight,
+                             float2 *d_stage, float *lw_stage, hipStream_t s);
+// every output pixel: contribSum, filterWeightSum and WriteImage's value; any output may be null
+hipError_t launch_film_splat(const FilmParams &f, const float *table, const float2 *d_stage, const float *lw_stage,
+                             float *tile_rgb, float *tile_w, float *image_rgb, hipStream_t s);
+
 int max_lds_per_block();
 hipError_t launch_udiv_selftest(uint64_t n, uint64_t seed, int mode, unsigned long long *d_mismatch, hipStream_t s);
 

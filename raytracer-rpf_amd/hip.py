@@ -29,7 +29,14 @@ EXPORTS = ["rpf_version", "rpf_status_string", "rpf_create", "rpf_destroy", "rpf
            "rpf_filter_pass_debug", "rpf_query_counters", "rpf_lds_bytes_required", "rpf_selftest_udiv", "rpf_feature_images",
            "rpf_host_alloc", "rpf_host_free", "rpf_filter_ex", "rpf_set_option", "rpf_multi_create", "rpf_multi_destroy",
            "rpf_multi_last_error", "rpf_multi_device_count", "rpf_multi_set_option", "rpf_multi_filter",
-           "rpf_multi_query_counters", "rpf_query_nbhd", "rpf_query_route"]
+           "rpf_multi_query_counters", "rpf_query_nbhd", "rpf_query_route", "rpf_film_filter_table", "rpf_filter_film",
+           "rpf_film_splat_device"]
+
+# the film step: pbrt's PixelFilters (include/rpf_hip.h, rpf_film)
+PIXFILTER_BOX, PIXFILTER_TRIANGLE, PIXFILTER_GAUSSIAN, PIXFILTER_MITCHELL, PIXFILTER_SINC = range(5)
+FILTER_TABLE_WIDTH = 16
+# pbrt's default radius per filter (box.cpp:44-45, triangle.cpp:46-47, gaussian.cpp:44-45, mitchell.cpp:57-58, sinc.cpp:54-55)
+DEFAULT_RADIUS = {PIXFILTER_BOX: 0.5, PIXFILTER_TRIANGLE: 2.0, PIXFILTER_GAUSSIAN: 2.0, PIXFILTER_MITCHELL: 2.0, PIXFILTER_SINC: 4.0}
 
 
 class Desc(C.Structure):
@@ -58,6 +65,49 @@ class Counters(C.Structure):
                 ("stats_kernel_ms", C.c_float), ("device_total_ms", C.c_float), ("h2d_ms", C.c_float),
                 ("d2h_ms", C.c_float), ("filter_kernel_launches", C.c_int32), ("options_active", C.c_int32),
                 ("redo_pixels", C.c_int32)]
+
+
+class Film(C.Structure):
+    _fields_ = [("sample_x0", C.c_int32), ("sample_y0", C.c_int32), ("px0", C.c_int32), ("py0", C.c_int32),
+                ("px1", C.c_int32), ("py1", C.c_int32), ("radius_x", C.c_float), ("radius_y", C.c_float),
+                ("max_sample_luminance", C.c_float), ("scale", C.c_float),
+                ("table", C.c_float * (FILTER_TABLE_WIDTH * FILTER_TABLE_WIDTH))]
+
+
+def film_table(kind, radius=None, p0=None, p1=None):
+    """pbrt's filter table (rpf_film_filter_table): float32 [16][16], [y][x].  radius: float or (rx, ry), None = pbrt's
+    default for the filter; p0 / p1: gaussian alpha | mitchell B, C | sinc tau, None = pbrt's default"""
+    rx, ry = _radii(kind, radius)
+    out = np.empty((FILTER_TABLE_WIDTH, FILTER_TABLE_WIDTH), np.float32)
+    nan = float("nan")
+    st = load().rpf_film_filter_table(int(kind), rx, ry, nan if p0 is None else p0, nan if p1 is None else p1, _p(out))
+    if st != OK:
+        raise RpfError(st, "rpf_film_filter_table(kind=%r, radius=(%r, %r))" % (kind, rx, ry))
+    return out
+
+
+def _radii(kind, radius):
+    if radius is None:
+        radius = DEFAULT_RADIUS.get(int(kind), 1.0)
+    rx, ry = (radius, radius) if np.isscalar(radius) else radius
+    return float(rx), float(ry)
+
+
+def make_film(pixel_bounds, radius, table, sample_origin=None, max_sample_luminance=float("inf"), scale=1.0):
+    """rpf_film for croppedPixelBounds ((px0, py0), (px1, py1)) and a filter of `radius` (float or (rx, ry)) with its 16x16
+    `table`.  sample_origin None = Film::GetSampleBounds().pMin: floor(p0 + 0.5 - r) per axis (film.cpp:80-86)."""
+    (px0, py0), (px1, py1) = pixel_bounds
+    rx, ry = _radii(None, radius)
+    if sample_origin is None:
+        sample_origin = (int(np.floor(np.float32(px0) + np.float32(0.5) - np.float32(rx))),
+                         int(np.floor(np.float32(py0) + np.float32(0.5) - np.float32(ry))))
+    f = Film()
+    f.sample_x0, f.sample_y0 = sample_origin
+    f.px0, f.py0, f.px1, f.py1 = px0, py0, px1, py1
+    f.radius_x, f.radius_y = rx, ry
+    f.max_sample_luminance, f.scale = max_sample_luminance, scale
+    C.memmove(f.table, np.ascontiguousarray(table, np.float32).ctypes.data, C.sizeof(f.table))
+    return f
 
 
 class RpfError(RuntimeError):
@@ -117,6 +167,9 @@ def load():
         L.rpf_multi_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
         L.rpf_multi_filter.argtypes = [C.c_void_p, C.POINTER(Desc)] + [C.c_void_p] * 4
         L.rpf_multi_query_counters.argtypes = [C.c_void_p, C.POINTER(Counters)]
+        L.rpf_film_filter_table.argtypes = [C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]
+        L.rpf_filter_film.argtypes = [C.c_void_p, C.POINTER(Desc), C.POINTER(Film)] + [C.c_void_p] * 6
+        L.rpf_film_splat_device.argtypes = [C.c_void_p, C.POINTER(Desc), C.POINTER(Film)] + [C.c_void_p] * 7
         L.rpf_host_alloc.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
         L.rpf_host_free.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
@@ -229,6 +282,22 @@ class Context:
         self._check(st, allow=(E_NONFINITE,) if allow_nonfinite else ())
         return srgb, prgb, st
 
+    def filter_film(self, planes, desc, film, ray_weight=None, allow_nonfinite=False):
+        """rpf_filter_film: the passes of desc, then pbrt's film step with `film` (make_film).  Returns (sample_rgb
+        [3,H,W,S], tile_rgb [ny,nx,3] = contribSum, tile_weight [ny,nx] = filterWeightSum, image_rgb [ny,nx,3] =
+        WriteImage's pixel values), nx, ny = the extent of film's pixel bounds."""
+        nd, _, _, pdt = dims(desc)
+        planes = np.ascontiguousarray(planes, pdt)
+        assert planes.shape == (nd, desc.H, desc.W, desc.S), planes.shape
+        rw = None if ray_weight is None else np.ascontiguousarray(ray_weight, np.float32)
+        nx, ny = max(film.px1 - film.px0, 0), max(film.py1 - film.py0, 0)
+        srgb = np.empty((3, desc.H, desc.W, desc.S), np.float32)
+        tile, w, img = np.empty((ny, nx, 3), np.float32), np.empty((ny, nx), np.float32), np.empty((ny, nx, 3), np.float32)
+        st = self._L.rpf_filter_film(self._h, C.byref(desc), C.byref(film), _p(planes), _p(rw), _p(srgb), _p(tile), _p(w),
+                                     _p(img))
+        self._check(st, allow=(E_NONFINITE,) if allow_nonfinite else ())
+        return srgb, tile, w, img
+
     def pixel_stats(self, planes, desc):
         _, nf, _, pdt = dims(desc)
         planes = np.ascontiguousarray(planes, pdt)
@@ -281,6 +350,12 @@ class Context:
     def reduce_device(self, desc, d_colour, d_ray_weight, d_sample_rgb, d_pixel_rgb, stream=None):
         self._check(self._L.rpf_reduce_device(self._h, C.byref(desc), d_colour, d_ray_weight, d_sample_rgb,
                                               d_pixel_rgb, stream))
+
+    def film_splat_device(self, desc, film, d_planes, d_colour, d_ray_weight, d_tile_rgb, d_tile_weight, d_image_rgb,
+                          stream=None):
+        """rpf_film_splat_device: the film step alone on device buffers (raw pointers; any output may be None)"""
+        self._check(self._L.rpf_film_splat_device(self._h, C.byref(desc), C.byref(film), d_planes, d_colour, d_ray_weight,
+                                                  d_tile_rgb, d_tile_weight, d_image_rgb, stream))
 
 
 class MultiContext:

@@ -51,12 +51,12 @@ bool PlaneFilm::complete() const {
     return !count_.empty();
 }
 
-int RPFFilter::FilterAndReduce(PlaneFilm &film, const std::vector<int> &boxes, std::vector<float> *pixel_rgb) {
+int RPFFilter::plane_desc(const PlaneFilm &film, const std::vector<int> &boxes, rpf_desc *out) {
     if (!ctx_) return RPF_E_NODEVICE;
     if (!film.ok()) { err_ = "PlaneFilm allocation failed"; return RPF_E_NOMEM; }
     if (!film.complete()) { err_ = "PlaneFilm: some pixel holds fewer than S samples"; return RPF_E_BADARG; }
     if (boxes.empty() || boxes.size() > RPF_MAX_BOXES) { err_ = "1..8 box sizes"; return RPF_E_BADARG; }
-    rpf_desc d;
+    rpf_desc &d = *out;
     std::memset(&d, 0, sizeof(d));
     d.W = film.W_; d.H = film.H_; d.S = film.S_;
     d.row_begin = 0; d.row_end = film.H_;
@@ -64,6 +64,32 @@ int RPFFilter::FilterAndReduce(PlaneFilm &film, const std::vector<int> &boxes, s
     for (size_t i = 0; i < boxes.size(); ++i) d.box_sizes[i] = boxes[i];
     d.beta_map = beta_map; d.degenerate_policy = degenerate_policy;
     d.eps = eps; d.sigma_seed = sigma_seed;
+    return RPF_OK;
+}
+
+int RPFFilter::FilterAndSplat(PlaneFilm &film, const std::vector<int> &boxes, const rpf_film &film_params,
+                              std::vector<float> *tile_rgb, std::vector<float> *tile_weight, std::vector<float> *image_rgb) {
+    rpf_desc d;
+    int32_t st = plane_desc(film, boxes, &d);
+    if (st != RPF_OK) return st;
+    rpf_film f = film_params;
+    f.sample_x0 = film.x0_; f.sample_y0 = film.y0_;
+    const size_t npix = (size_t)std::max(0, f.px1 - f.px0) * (size_t)std::max(0, f.py1 - f.py0);
+    if (tile_rgb) tile_rgb->resize(3 * npix);
+    if (tile_weight) tile_weight->resize(npix);
+    if (image_rgb) image_rgb->resize(3 * npix);
+    st = rpf_filter_film(ctx_, &d, &f, film.planes_.data(), film.rayw_.data(), film.srgb_.data(),
+                         tile_rgb ? tile_rgb->data() : nullptr, tile_weight ? tile_weight->data() : nullptr,
+                         image_rgb ? image_rgb->data() : nullptr);
+    rpf_query_counters(ctx_, &counters_);
+    if (st != RPF_OK) err_ = std::string(rpf_status_string(st)) + ": " + rpf_last_error(ctx_);
+    return st;
+}
+
+int RPFFilter::FilterAndReduce(PlaneFilm &film, const std::vector<int> &boxes, std::vector<float> *pixel_rgb) {
+    rpf_desc d;
+    const int32_t dst = plane_desc(film, boxes, &d);
+    if (dst != RPF_OK) return dst;
     if (pixel_rgb) pixel_rgb->resize((size_t)film.W_ * film.H_ * 3);
     const int32_t st = rpf_filter(ctx_, &d, film.planes_.data(), film.rayw_.data(), film.srgb_.data(),
                                   pixel_rgb ? pixel_rgb->data() : nullptr);
@@ -254,6 +280,46 @@ extern "C" int32_t rpf_host_planefilm_filter(const double *aos, const float *ray
         if (st == RPF_OK || st == RPF_E_NONFINITE) {
             if (sample_rgb_out) std::memcpy(sample_rgb_out, film.filtered(), (size_t)3 * W * H * S * sizeof(float));
             if (pixel_rgb_out) std::memcpy(pixel_rgb_out, pix.data(), pix.size() * sizeof(float));
+        }
+    }
+    if (err && err_len > 0) std::snprintf(err, err_len, "%s", f.last_error().c_str());
+    return st;
+}
+
+extern "C" int32_t rpf_host_planefilm_film(const double *aos, const float *ray_weight, int32_t W, int32_t H, int32_t S,
+                                           int32_t x0, int32_t y0, const int32_t *box_sizes, int32_t n_box, int32_t beta_map,
+                                           int32_t policy, int32_t device, const rpf_film *film, float *sample_rgb_out,
+                                           float *tile_rgb_out, float *tile_weight_out, float *image_rgb_out, char *err,
+                                           int32_t err_len) {
+    using namespace rpf_host;
+    if (!aos || !box_sizes || !film || W <= 0 || H <= 0 || S <= 0 || n_box <= 0) return RPF_E_BADARG;
+    RPFFilter f(device);
+    f.beta_map = beta_map;
+    f.degenerate_policy = policy;
+    PlaneFilm pf(f, W, H, S, x0, y0);
+    int st = RPF_OK;
+    if (!pf.ok()) {
+        st = f.context() ? RPF_E_NOMEM : RPF_E_NODEVICE;
+    } else {
+        bool all = true;
+        for (int x = 0; x < W; ++x)
+            for (int y = 0; y < H; ++y)
+                for (int s = 0; s < S; ++s) {
+                    const size_t o = (((size_t)x * H + y) * S + s);
+                    SampleData sd;
+                    std::memcpy(sd.data, aos + o * RPF_NDIM, sizeof(double) * RPF_NDIM);
+                    sd.rayWeight = ray_weight ? ray_weight[o] : 1.0f;
+                    all = pf.AddSample(x0 + x, y0 + y, sd) && all; // raster coordinates
+                }
+        std::vector<float> tile, w, img;
+        st = all ? f.FilterAndSplat(pf, std::vector<int>(box_sizes, box_sizes + n_box), *film, tile_rgb_out ? &tile : nullptr,
+                                    tile_weight_out ? &w : nullptr, image_rgb_out ? &img : nullptr)
+                 : (int)RPF_E_BADARG;
+        if (st == RPF_OK || st == RPF_E_NONFINITE) {
+            if (sample_rgb_out) std::memcpy(sample_rgb_out, pf.filtered(), (size_t)3 * W * H * S * sizeof(float));
+            if (tile_rgb_out) std::memcpy(tile_rgb_out, tile.data(), tile.size() * sizeof(float));
+            if (tile_weight_out) std::memcpy(tile_weight_out, w.data(), w.size() * sizeof(float));
+            if (image_rgb_out) std::memcpy(image_rgb_out, img.data(), img.size() * sizeof(float));
         }
     }
     if (err && err_len > 0) std::snprintf(err, err_len, "%s", f.last_error().c_str());

@@ -137,6 +137,13 @@ class RPFFilter {
     // Same on a PlaneFilm: no marshalling at all, the pinned planes go straight to rpf_filter()'s band pipeline;
     // filtered sample colours land in film.filtered().
     int FilterAndReduce(PlaneFilm &film, const std::vector<int> &box_sizes, std::vector<float> *pixel_rgb);
+    // The same passes, then the rest of Render() for any pbrt PixelFilter and crop window: every sample through
+    // FilmTile::AddSample (rpf.cpp:779-794) on the device (rpf_filter_film).  The PlaneFilm's x0, y0 are the sample origin,
+    // Film::GetSampleBounds().pMin (they replace film_params.sample_x0 / y0); film_params carries croppedPixelBounds, the
+    // filter's radius and table, maxSampleLuminance and scale.  Outputs, each [ny][nx](x3) over croppedPixelBounds and
+    // may be NULL: FilmTilePixel::contribSum, ::filterWeightSum, and WriteImage's pixel values.
+    int FilterAndSplat(PlaneFilm &film, const std::vector<int> &box_sizes, const rpf_film &film_params,
+                       std::vector<float> *tile_rgb, std::vector<float> *tile_weight, std::vector<float> *image_rgb);
     rpf_ctx *context() { return ctx_; }
 
     const std::string &last_error() const { return err_; }
@@ -144,6 +151,7 @@ class RPFFilter {
 
   private:
     int run(SamplingFilm &film, const std::vector<int> &boxes, std::vector<float> *pixel_rgb);
+    int plane_desc(const PlaneFilm &film, const std::vector<int> &boxes, rpf_desc *d); // checks film and boxes
     rpf_ctx *ctx_ = nullptr;
     std::string err_;
     rpf_counters counters_{};
@@ -168,6 +176,12 @@ int32_t rpf_host_apply_filter_aos(double *aos, const float *ray_weight, int32_t 
 // RPFParams::Parse through a C doorway: boxes_out[RPF_MAX_BOXES]; returns 0 or -1 with the message in err
 int32_t rpf_host_parse_params(const int32_t *boxsizes, int32_t n_boxsizes, const char *backend, int32_t *boxes_out,
                               int32_t *n_out, int32_t *backend_out, char *err, int32_t err_len);
+// PlaneFilm(x0, y0) filled as above (sample (x, y) of aos lands in raster pixel (x0 + x, y0 + y)), then
+// RPFFilter::FilterAndSplat with `film` (its sample origin is replaced by (x0, y0)); outputs as rpf_filter_film's.
+int32_t rpf_host_planefilm_film(const double *aos, const float *ray_weight, int32_t W, int32_t H, int32_t S, int32_t x0,
+                                int32_t y0, const int32_t *box_sizes, int32_t n_box, int32_t beta_map, int32_t policy,
+                                int32_t device, const rpf_film *film, float *sample_rgb_out, float *tile_rgb_out,
+                                float *tile_weight_out, float *image_rgb_out, char *err, int32_t err_len);
 int32_t rpf_host_planefilm_filter(const double *aos, const float *ray_weight, int32_t W, int32_t H, int32_t S,
                                   const int32_t *box_sizes, int32_t n_box, int32_t beta_map, int32_t policy,
                                   int32_t device, float *sample_rgb_out, float *pixel_rgb_out, char *err, int32_t err_len);
