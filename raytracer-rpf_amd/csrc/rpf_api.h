@@ -1,0 +1,160 @@
+// rpf_api.h -- host only: what the three TUs of the C ABI share.  rpf_api.hip holds the context, validation, pass set-up,
+// the routes and the two pass loops; rpf_api_film.hip the film step's host half; rpf_api_multi.hip the one-process
+// multi-GPU driver.
+#pragma once
+#include <dlfcn.h>
+
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "rpf_internal.h"
+
+struct rpf_ctx;
+
+namespace rpf {
+
+int32_t fail(rpf_ctx *c, int32_t st, const std::string &msg); // records the message in the context, returns st
+
+// A grow-only device allocation, pointer + capacity: the one place that allocates and frees HBM.  It frees itself with the
+// context that holds it.
+template <class T>
+struct DevBuf {
+    T *ptr = nullptr;
+    size_t cap = 0; // the bytes last asked for
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    operator T *() const { return ptr; }
+    void release() {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        cap = 0;
+    }
+    void swap(DevBuf &o) { std::swap(ptr, o.ptr); std::swap(cap, o.cap); }
+    // keeps an allocation that is large enough; otherwise frees it and allocates anew (the contents are not carried over)
+    int32_t ensure(rpf_ctx *ctx, size_t bytes) {
+        if (bytes <= cap && ptr) return RPF_OK;
+        release();
+        hipError_t e = hipMalloc((void **)&ptr, bytes ? bytes : 16);
+        if (e != hipSuccess) return fail(ctx, e == hipErrorOutOfMemory ? RPF_E_NOMEM : RPF_E_HIP,
+                                         std::string("hipMalloc: ") + hipGetErrorString(e));
+        cap = bytes;
+        return RPF_OK;
+    }
+};
+
+} // namespace rpf
+
+struct rpf_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    // grow-only HBM workspace
+    rpf::DevBuf<char> d_planes;                 // ndim planes of fp32 (or fp16)
+    rpf::DevBuf<float> d_rayw;
+    rpf::DevBuf<double> d_colA, d_colB;         // 3 planes fp64
+    rpf::DevBuf<double> d_pmean, d_pstd;        // [12][H*W]
+    rpf::DevBuf<int32_t> d_nbhd;
+    rpf::DevBuf<uint64_t> d_tfix; int tfix_n = 0; // round(k ln k * 2^44), k = 0..n
+    rpf::DevBuf<uint64_t> d_dfix;               // first differences
+    rpf::DevBuf<float> d_srgb, d_prgb;
+    rpf::DevBuf<double> d_carry;                // split route of the 32- / 64-spp classes: statistics / weights between its three kernels
+    rpf::DevBuf<int32_t> d_status;              // [0] bad count [1] first bad
+    rpf::DevBuf<unsigned long long> d_nred;     // [0] sum N [1] max N
+    rpf::DevBuf<uint32_t> d_lists;              // size binning: [kNumClasses][H*W] pixel lists
+    int last_route = -1;                        // last pass: 1 = count first, 0 = fused, 2 = size-binned (rpf_query_route)
+    rpf::DevBuf<uint32_t> d_class_counts;       // [kNumClasses] list sizes + [2] the route probe's counts
+    rpf::DevBuf<uint64_t> d_masks;              // size binning: stage-1b acceptance masks [H*W][stride]
+    rpf::DevBuf<char> d_big_list;               // streaming kernel: member lists [slots][nmax] u32
+    rpf::DevBuf<char> d_big_bins;               //                   bin ids [slots][ndim][nmax] u8
+    rpf::DevBuf<uint8_t> d_flat;                // stage 1a by-product: pixels with a zero-variance feature [H*W]
+    rpf::DevBuf<int32_t> d_nan_flag;            // ... and whether any feature mean of the buffer is NaN
+    rpf::DevBuf<uint32_t> d_redo_list;          // REF_ABORT: pixels handed to the reference-expression kernel [H*W]
+    rpf::DevBuf<uint32_t> d_redo_count;
+    // membership depends on the features only, so within one call a pass with the same box and rows re-uses the
+    // previous pass's masks and lists (reset at every API entry: the planes may change between calls)
+    bool flat_fresh = false;                    // d_flat / d_nan_flag describe the planes of the call in progress (stage 1a ran in it)
+    bool bin_valid = false;
+    int bin_box = 0, bin_r0 = 0, bin_r1 = 0;
+    uint32_t bin_counts[rpf::kNumClasses] = {};
+    rpf::DevBuf<void> d_dbg[9];                 // debug planes
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    // host-buffer entry (rpf_filter): row-band pipeline, uploads / downloads on their own streams
+    hipStream_t s_up = nullptr, s_down = nullptr;
+    std::vector<hipEvent_t> band_ev; // no-timing events, two per band
+    rpf_counters counters{};
+    rpf::Tuning tun;                      // rpf_set_option
+    // the film step (rpf_filter_film / rpf_film_splat_device)
+    rpf::DevBuf<float2> d_film_d;               // [H][S][W] pFilm - 0.5
+    rpf::DevBuf<float> d_film_lw;               // 3 planes [H][S][W] clamped L * sampleWeight
+    rpf::DevBuf<float> d_film_out;              // host entry: tile rgb | tile weight | image rgb
+    rpf::DevBuf<float> d_film_table;            // [16*16]
+    rpf::DevBuf<unsigned long long> d_film_bad; // first sample whose pFilm lies outside its pixel
+};
+
+namespace rpf {
+
+// Per-stage tracing hooks (the reference brackets its phases with ProfilePhase, core/stats.h:254): roctx ranges around the
+// host-side enqueue of upload / stage 1a / count + classify / each size-class launch / redo / reduce / download, visible in
+// `rocprofv3 --marker-trace --kernel-trace`.  The marker library is looked up at run time (the profiler preloads it; without
+// it, or without the library on the machine, the hooks are two null checks): librpf_hip.so has no link-time dependency on it.
+struct Roctx {
+    int (*push)(const char *) = nullptr;
+    int (*pop)() = nullptr;
+    Roctx() {
+        for (const char *lib : {"librocprofiler-sdk-roctx.so.1", "librocprofiler-sdk-roctx.so", "libroctx64.so.4", "libroctx64.so"}) {
+            void *h = dlopen(lib, RTLD_LAZY | RTLD_GLOBAL);
+            if (!h) continue;
+            push = reinterpret_cast<int (*)(const char *)>(dlsym(h, "roctxRangePushA"));
+            pop = reinterpret_cast<int (*)()>(dlsym(h, "roctxRangePop"));
+            if (push && pop) return;
+            push = nullptr; pop = nullptr;
+        }
+    }
+};
+inline const Roctx &roctx() { static const Roctx r; return r; }
+struct Range {
+    bool on;
+    explicit Range(const char *name) : on(roctx().push != nullptr) { if (on) roctx().push(name); }
+    ~Range() { if (on) roctx().pop(); }
+    Range(const Range &) = delete;
+    Range &operator=(const Range &) = delete;
+};
+
+// needs `ctx` in scope
+#define HIP_TRY(expr)                                                                            \
+    do {                                                                                         \
+        hipError_t _e = (expr);                                                                  \
+        if (_e != hipSuccess)                                                                    \
+            return rpf::fail(ctx, RPF_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
+    } while (0)
+
+// defined in rpf_api.hip, where each is described
+SampleLayout layout_of(const rpf_desc *d);
+int32_t validate(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes);
+int32_t enter(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes); // validate, then make the context's device current
+
+struct PassSetup {
+    PassParams p;
+    uint32_t lds = 0;
+};
+int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_planes, const double *col_in,
+                   double *col_out, const rpf_debug *dbg_dev, PassSetup &out);
+int32_t launch_filter_binned(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches);
+
+int32_t begin_call(rpf_ctx *ctx, hipStream_t s);
+std::string nonfinite_message(int x, int y, long long count);
+int32_t finish_counters(rpf_ctx *ctx, const rpf_desc *d, int n_pass, hipStream_t s);
+int32_t pass_through(rpf_ctx *ctx, const rpf_desc *d, const double *cin, double *cout, int r0, int r1, hipStream_t s);
+int32_t ensure_frame(rpf_ctx *ctx, const rpf_desc *d, bool ray_weight, bool colour);
+int32_t ensure_outputs(rpf_ctx *ctx, const rpf_desc *d, bool sample_rgb, bool pixel_rgb);
+int32_t upload_frame(rpf_ctx *ctx, const rpf_desc *d, const void *planes, const float *ray_weight, bool colour,
+                     const double *colour64, hipStream_t s);
+int32_t download_rows(rpf_ctx *ctx, const rpf_desc *d, const double *colour, const float *d_ray_weight, int r0, int r1,
+                      float *sample_rgb_out, float *pixel_rgb_out, size_t out_plane, int out_row, hipStream_t s,
+                      hipStream_t to, hipEvent_t ready);
+int32_t run_passes(rpf_ctx *ctx, const rpf_desc *d, const void *d_planes, double *d_colour, hipStream_t s);
+
+} // namespace rpf

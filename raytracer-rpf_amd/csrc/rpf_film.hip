@@ -11,7 +11,7 @@
 //   film_splat_kernel  a GATHER: one lane per output pixel walks the sample pixels that can reach it, qx ascending, qy
 //                      ascending, s ascending -- the order in which pbrt's serial loop adds to that pixel -- runs pbrt's own
 //                      p0 <= x < p1 test and table lookup, and accumulates in fp32 registers.  No float atomics, so the bits
-//                      do not depend on scheduling.  The window half-width (hx, hy) is proven on the host (rpf_api.hip
+//                      do not depend on scheduling.  The window half-width (hx, hy) is proven on the host (rpf_api_film.hip
 //                      film_window); the candidate test itself is pbrt's, so a wider window changes
 //                      nothing but time.
 #include "rpf_internal.h"

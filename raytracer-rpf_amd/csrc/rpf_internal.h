@@ -1,4 +1,4 @@
-// rpf_internal.h -- shared between the kernel TU (rpf_kernels.hip) and the C-ABI TU (rpf_api.hip).
+// rpf_internal.h -- shared between the kernel TUs (rpf_kernels.hip, rpf_film.hip, rpf_impl_*.hip) and the C-ABI TUs (rpf_api*.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -147,7 +147,7 @@ struct FilmParams {
     int32_t W, H, S;
     int32_t sx0, sy0;          // raster coords of buffer pixel (0,0)
     int32_t px0, py0, px1, py1;
-    int32_t hx, hy;            // window half-widths in pixels (rpf_api.hip film_window)
+    int32_t hx, hy;            // window half-widths in pixels (rpf_api_film.hip film_window)
     float rx, ry, inv_rx, inv_ry; // Filter::radius, FilmTile::invFilterRadius (1 / r, formed on the host)
     float max_lum, scale;
     uint64_t plane_stride;     // H*W*S
