@@ -265,6 +265,12 @@ int32_t rpf_multi_query_counters(rpf_multi *m, rpf_counters *out);
 /* LDS bytes per workgroup the fused kernel needs for (S, box); > device limit => RPF_E_UNSUPPORTED */
 int64_t rpf_lds_bytes_required(int32_t S, int32_t box);
 
+/* The fused kernels gather a pixel's window through 32-bit byte offsets from the window's first sample, so the span of
+ * box rows of the slab in bytes of an fp64 plane, box*W*S*8, must fit 32 bits.  RPF_OK if it does, RPF_E_UNSUPPORTED if
+ * not (every filter entry point refuses such a call the same way), RPF_E_BADARG for non-positive arguments.  Needs no
+ * device.  With box*box*S <= 65535 this only binds for slabs hundreds of thousands of pixels wide. */
+int32_t rpf_check_window_span(int32_t W, int32_t S, int32_t box);
+
 /* ---- the film step: pbrt's reconstruction filter and crop window on the filtered samples -----------------------------
  * RPFIntegrator::Render ends by feeding every sample through FilmTile::AddSample (rpf.cpp:779-794, film.h:121-161), x outer,
  * y inner, then s, and then MergeFilmTile + WriteImage (film.cpp:117-130, 169-203).  rpf_filter()'s pixel_rgb_out covers

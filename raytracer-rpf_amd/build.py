@@ -90,9 +90,9 @@ def _build(LIB, OBJ_DIR, defs, shipped, force, verbose):
                 o = os.path.join(OBJ_DIR, os.path.basename(a).split("-hip-amdgcn")[0] + ".hip.o")
                 if os.path.exists(o):
                     os.remove(o)
-            raise RuntimeError("miscompiled spill placement in a kernel TU (see scripts/check_spills.py):\n" + chk.stdout)
+            raise RuntimeError("spill code in front of an EXEC restore, or a DPP read hazard, in a kernel TU (see scripts/check_spills.py):\n" + chk.stdout)
         with open(SCAN_OK, "w") as f:
-            f.write("check_spills.py: no spill code in front of an EXEC restore\n" + chk.stdout)
+            f.write("check_spills.py: no spill code in front of an EXEC restore, no DPP read hazard\n" + chk.stdout)
         if verbose:
             print(chk.stdout)
     for f in glob.glob(os.path.join(OBJ_DIR, "*")):  # the -save-temps intermediates (~100 MB) have served their purpose

@@ -115,6 +115,9 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     const int64_t nmax64 = (int64_t)box * box * d->S;
     if (nmax64 > kMaxNbhd) return fail(ctx, RPF_E_UNSUPPORTED, "box*box*S > 65535: neighbourhood too large (16-bit histogram cells, one-byte bin ids)");
     p.nmax = (int)nmax64;
+    // the fused kernels address a window's samples by 32-bit byte offsets from its first sample (Window, rpf_filter_impl.inc)
+    if (rpf_check_window_span(d->W, d->S, box) != RPF_OK)
+        return fail(ctx, RPF_E_UNSUPPORTED, "box*W*S*8 >= 2^32: a window's span in bytes of an fp64 plane must fit 32 bits (narrower slabs or a smaller box)");
     {   // XCD strip width: box rows x (strip + halo) px x S samples x ~88 B against a budget of L2 bytes.  Measured
         // (scripts/strip_sweep.sh, profiles/r02_strip_width.txt): the kernel time does not depend on it, the fetched bytes
         // do -- at 8 spp wide strips win (a quarter of the 4 MiB L2: 128 px), from 16 spp up narrow ones (the size-binned
@@ -716,6 +719,12 @@ void rpf_destroy(rpf_ctx *ctx) {
 }
 
 const char *rpf_last_error(const rpf_ctx *ctx) { return ctx ? ctx->err.c_str() : "ctx is NULL"; }
+
+int32_t rpf_check_window_span(int32_t W, int32_t S, int32_t box) {
+    if (W <= 0 || S <= 0 || box <= 0) return RPF_E_BADARG;
+    // box rows of W pixels of S samples, 8 bytes each in the widest plane type (the fp64 colours)
+    return (uint64_t)box * (uint64_t)W * (uint64_t)S * 8ull < (1ull << 32) ? RPF_OK : RPF_E_UNSUPPORTED;
+}
 
 int64_t rpf_lds_bytes_required(int32_t S, int32_t box) {
     if (S <= 0 || box <= 0) return -1;

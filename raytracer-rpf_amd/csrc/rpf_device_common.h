@@ -53,6 +53,23 @@ __device__ __forceinline__ void lds_store_u64_if(bool pred, uint64_t *p, uint64_
                  : "=&s"(saved) : "s"(mask), "v"(addr), "v"(v) : "memory", "scc");
 }
 
+// ---- gathers from a wave-uniform base with a 32-bit per-lane byte offset -----------------------------------------
+// `global_load_* v, v_off32, s[base:base+1]` adds a 32-bit per-lane byte offset to a 64-bit base held in SGPRs: a gather
+// whose base is the same for every lane needs no per-lane 64-bit address (formerly one v_lshl_add_u64 per load).  hipcc
+// picks that form when the base is a global-address-space pointer it cannot fold the per-lane part into -- sbase() pins
+// it in an SGPR pair and hides its value from reassociation (the empty statement executes nothing) -- and the per-lane
+// operand is a uint32_t added to a char pointer.
+typedef __attribute__((address_space(1))) const char gchar;
+__device__ __forceinline__ gchar *sbase(gchar *q) {
+    asm volatile("" : "+s"(q));
+    return q;
+}
+__device__ __forceinline__ gchar *gptr(const void *q) { return (gchar *)reinterpret_cast<const char *>(q); }
+template <class T>
+__device__ __forceinline__ T ldg_rel(gchar *base, uint32_t byte_off) {
+    return *reinterpret_cast<__attribute__((address_space(1))) const T *>(base + byte_off);
+}
+
 __device__ __forceinline__ uint32_t fnv1a_u32(uint32_t h, uint32_t v) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) { h ^= (v >> (8 * i)) & 0xffu; h *= 16777619u; }

@@ -16,6 +16,12 @@ constexpr int kNAnc = kNR + 2;                 // r.. and p.. anchors: every fea
 constexpr int kNPairF = kNFeat * kNAnc;        // pairs (f_i, r_l | p_l)                       rpf.cpp:416-427
 constexpr int kNPairC = kNAnc + kNFeat;        // pairs of one colour channel                  rpf.cpp:429-442
 constexpr int kNPair = kNPairF + 3 * kNPairC;  // 96 in the reference
+#ifndef RPF_CHAIN_BOTH
+#define RPF_CHAIN_BOTH 1 // stage 2, one-wave kernels: 1 = lanes 0..18 carry the sum(x) and the sum(x*x) chain of their column; 0 = lanes 32..50 carry the second (a select per element)
+#endif
+#ifndef RPF_Z_HOIST
+#define RPF_Z_HOIST 1 // stage 4, one-wave kernels: 1 = a sweep loop without the SD == 0 select for pixels whose weighted columns all have SD != 0
+#endif
 #ifndef RPF_ROWS_EARLY
 #define RPF_ROWS_EARLY 1 // stage 4: own rows read in front of the own-sample loop (0: where the compiler sinks them; 1080p x 8: 65.1 vs 62.9 ms)
 #endif
@@ -55,6 +61,78 @@ __device__ __forceinline__ int anchor_col(int a) { return a < kNR ? kColR + a : 
 __device__ __forceinline__ double load_col(const PassParams &p, int c, uint32_t off) {
     if (c >= kColC && c < kColC + 3) return p.col_in[(uint64_t)(c - kColC) * p.plane_stride + off];
     return (double)ldp(p, c, off);
+}
+
+// ---- the planes as the fused per-pixel kernel gathers from them ----------------------------------------------------
+// The member list of a pixel (sOff) holds each sample's element offset RELATIVE to the first sample of the pixel's window,
+// ((y0 * W + x0) * S: the smallest plane offset of the window, so a relative offset is >= 0 and < box * W * S), and the
+// window origin is folded into the wave-uniform base of each plane.  A gather is then `global_load v, v_off32, s[base]`
+// with a 32-bit per-lane byte offset (sbase / ldg_rel, rpf_device_common.h) and no per-lane address arithmetic beyond the
+// shift that turns the element offset into bytes; stepping the base from one column's plane to the next is two scalar
+// adds.  setup_pass refuses a call whose window span box * W * S * 8 bytes does not fit 32 bits (rpf_check_window_span).
+struct Window {
+    gchar *pl, *co;  // feature plane 0 / colour plane 0 at the window origin
+    uint64_t pb, cb; // bytes per feature plane / per colour plane
+    __device__ __forceinline__ Window(const PassParams &p, uint64_t origin)
+        : pl(gptr(p.planes) + origin * sizeof(plane_t)), co(gptr(p.col_in) + origin * 8u),
+          pb(p.plane_stride * sizeof(plane_t)), cb(p.plane_stride * 8u) {}
+    __device__ __forceinline__ gchar *plane(int c) const { return sbase(pl + (uint64_t)c * pb); }
+    __device__ __forceinline__ gchar *colour(int c) const { return sbase(co + (uint64_t)c * cb); }
+    __device__ __forceinline__ gchar *next_plane(gchar *q, int n = 1) const { return sbase(q + (uint64_t)n * pb); }
+    __device__ __forceinline__ gchar *next_colour(gchar *q) const { return sbase(q + cb); }
+};
+// feature-plane value at relative element offset `rel` of the plane based at q, as the fp32 it stands for
+__device__ __forceinline__ float ldw(gchar *q, uint32_t rel) {
+    if constexpr (sizeof(plane_t) == 2) return (float)__ushort_as_half(ldg_rel<unsigned short>(q, rel << 1));
+    else return ldg_rel<float>(q, rel << 2);
+}
+// fp64 colour at relative element offset `rel` of the colour plane based at q
+__device__ __forceinline__ double ldwc(gchar *q, uint32_t rel) { return ldg_rel<double>(q, rel << 3); }
+// ... and both from the offset already in bytes of a feature plane (rel * sizeof(plane_t): formed once where it is reused)
+constexpr int kPlaneShift = sizeof(plane_t) == 2 ? 1 : 2;
+__device__ __forceinline__ float ldw_b(gchar *q, uint32_t pb) {
+    if constexpr (sizeof(plane_t) == 2) return (float)__ushort_as_half(ldg_rel<unsigned short>(q, pb));
+    else return ldg_rel<float>(q, pb);
+}
+__device__ __forceinline__ double ldwc_b(gchar *q, uint32_t pb) { return ldg_rel<double>(q, pb << (3 - kPlaneShift)); }
+// the kNX plane columns (xcol order) and the three colours of one sample
+__device__ __forceinline__ void gather_sample(const Window &w, uint32_t rel, float (&vf)[kNX], double (&vd)[3]) {
+    gchar *q = w.plane(0);
+#pragma unroll
+    for (int i = 0; i < kNX; ++i) {
+        vf[i] = ldw(q, rel);
+        if (i + 1 < kNX) q = w.next_plane(q, xcol(i + 1) - xcol(i));
+    }
+    gchar *c = w.colour(0);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        vd[i] = ldwc(c, rel);
+        if (i < 2) c = w.next_colour(c);
+    }
+}
+// the kNFeat feature columns of one sample (stage 1b)
+__device__ __forceinline__ void gather_features(const Window &w, uint32_t rel, float (&f)[kNFeat]) {
+    gchar *q = w.plane(kColF);
+#pragma unroll
+    for (int k = 0; k < kNFeat; ++k) {
+        f[k] = ldw(q, rel);
+        if (k + 1 < kNFeat) q = w.next_plane(q);
+    }
+}
+// stage 4's columns of one sample: pFilm and the features (pf), the colours (pc)
+__device__ __forceinline__ void gather_weighted(const Window &w, uint32_t rel, float (&pf)[2 + kNFeat], double (&pc)[3]) {
+    gchar *q = w.plane(0);
+#pragma unroll
+    for (int k = 0; k < 2 + kNFeat; ++k) {
+        pf[k] = ldw(q, rel);
+        if (k + 1 < 2 + kNFeat) q = w.next_plane(q, k == 1 ? kColF - 1 : 1);
+    }
+    gchar *c = w.colour(0);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        pc[i] = ldwc(c, rel);
+        if (i < 2) c = w.next_colour(c);
+    }
 }
 
 #if RPF_IMPL_PART == 1
@@ -211,13 +289,13 @@ __device__ __forceinline__ void column_constants(const double *sStat, double *sC
 }
 
 template <int KD, int KW, int PACK5, int NW = 1>
-__device__ __forceinline__ void bins_stage(const PassParams &p, const double *sStat, const uint32_t *sOff, uint32_t *sBinW,
+__device__ __forceinline__ void bins_stage(const PassParams &p, const Window &win, const double *sStat, const uint32_t *sOff, uint32_t *sBinW,
                                            int lane, int n, int B, const double *sCK, int wv = 0) {
     const double dB = (double)B;
     {
         uint32_t offk[KD];
 #pragma unroll
-        for (int kk = 0; kk < KD; ++kk) offk[kk] = (lane + kWave * kk < n) ? sOff[lane + kWave * kk] : 0u;
+        for (int kk = 0; kk < KD; ++kk) offk[kk] = (lane + kWave * kk < n) ? sOff[lane + kWave * kk] << kPlaneShift : 0u; // in bytes of a feature plane
         // one column: z, t, bin for the lane's K samples, packed into KW words
         auto do_column = [&](int c, const double (&xv)[KD]) {
             const double Mc = sStat[c], SDc = sStat[kNDim + c];
@@ -272,9 +350,12 @@ __device__ __forceinline__ void bins_stage(const PassParams &p, const double *sS
                 auto colidx = [](int i) { return xcol(i); };
                 float xb[KD];
                 auto issue3 = [&](int i) {
-                    const plane_t *fplane = reinterpret_cast<const plane_t *>(p.planes) + (uint64_t)colidx(i) * p.plane_stride;
+                    gchar *fplane = win.plane(colidx(i));
 #pragma unroll
-                    for (int kk = 0; kk < KD; ++kk) xb[kk] = (float)fplane[offk[kk]];
+                    for (int kk = 0; kk < KD; ++kk) {
+                        asm volatile("" : "+v"(offk[kk])); // (see the one-wave form below)
+                        xb[kk] = ldw_b(fplane, offk[kk]);
+                    }
                 };
                 issue3(wv); // NW <= kNX
 #pragma unroll 1
@@ -288,9 +369,9 @@ __device__ __forceinline__ void bins_stage(const PassParams &p, const double *sS
 #pragma unroll 1
                 for (int c = wv; c < 3; c += NW) {
                     double xc[KD];
-                    const double *dplane = p.col_in + (uint64_t)c * p.plane_stride;
+                    gchar *dplane = win.colour(c);
 #pragma unroll
-                    for (int kk = 0; kk < KD; ++kk) xc[kk] = dplane[offk[kk]];
+                    for (int kk = 0; kk < KD; ++kk) xc[kk] = ldwc_b(dplane, offk[kk]);
                     do_column(kColC + c, xc);
                 }
             }
@@ -301,9 +382,14 @@ __device__ __forceinline__ void bins_stage(const PassParams &p, const double *sS
             float xb[kPF3][KD];
             auto colidx = [](int i) { return xcol(i); };
             auto issue3 = [&](int i, float (&dst)[KD]) {
-                const plane_t *fplane = reinterpret_cast<const plane_t *>(p.planes) + (uint64_t)colidx(i) * p.plane_stride;
+                gchar *fplane = win.plane(colidx(i));
 #pragma unroll
-                for (int kk = 0; kk < KD; ++kk) dst[kk] = (float)fplane[offk[kk]];
+                for (int kk = 0; kk < KD; ++kk) {
+                    // the offsets are loop invariants: left visible, their 64-bit extensions are hoisted out of the column loop
+                    // and every load gets a per-lane v_lshl_add_u64 again (the scalar-base form is matched per basic block)
+                    asm volatile("" : "+v"(offk[kk]));
+                    dst[kk] = ldw_b(fplane, offk[kk]);
+                }
             };
 #pragma unroll
             for (int u = 0; u < kPF3; ++u) issue3(u, xb[u]);
@@ -322,9 +408,9 @@ __device__ __forceinline__ void bins_stage(const PassParams &p, const double *sS
             double xc[3][KD];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const double *dplane = p.col_in + (uint64_t)c * p.plane_stride;
+                gchar *dplane = win.colour(c);
 #pragma unroll
-                for (int kk = 0; kk < KD; ++kk) xc[c][kk] = dplane[offk[kk]];
+                for (int kk = 0; kk < KD; ++kk) xc[c][kk] = ldwc_b(dplane, offk[kk]);
             }
 #pragma unroll
             for (int c = 0; c < 3; ++c) do_column(kColC + c, xc[c]);
@@ -998,7 +1084,11 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
     const int ncand = (ncells - 1) * S;
     const uint32_t magic_S = div_magic((uint32_t)S), magic_ny = div_magic((uint32_t)nyv); // qq < 4096, S, nyv <= 64
 
-    for (int s = tid; s < S; s += kThreads) sOff[s] = (uint32_t)(pix * S + s); // own samples first
+    // the member list holds offsets relative to the window's first sample (see Window)
+    const Window win(p, ((uint64_t)y0 * W + x0) * S);
+    const uint32_t own_rel = (uint32_t)((y - y0) * W + (x - x0)) * (uint32_t)S;
+    [[maybe_unused]] const uint32_t win_par = ((uint32_t)(y0 * W + x0) * (uint32_t)S) & 1u; // parity of the origin's element index (fp16 planes)
+    for (int s = tid; s < S; s += kThreads) sOff[s] = own_rel + (uint32_t)s; // own samples first
 
     int n = S;
     if constexpr (NW > 1) {
@@ -1021,16 +1111,14 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
             if (cell >= centre_rank) ++cell;          // rpf.cpp:565: skip the centre pixel
             const int ix = (int)div_small((uint32_t)cell, magic_ny); // xn outer ascending (rpf.cpp:562)
             const int iy = cell - ix * nyv;            // yn inner ascending (rpf.cpp:563)
-            return (uint32_t)(((uint64_t)(y0 + iy) * W + (x0 + ix)) * S + s);
+            return (uint32_t)(iy * W + ix) * (uint32_t)S + (uint32_t)s;
         };
         constexpr int kPF1 = kNFeat <= 12 ? 3 : 2;
         float fb[kPF1][kNFeat];
         auto issue1 = [&](int blk, float (&f)[kNFeat]) {
             const int qq = blk * kWave + lane;
             if (blk < nblk && qq < ncand) {
-                const uint32_t off = cand_off(qq);
-#pragma unroll
-                for (int k = 0; k < kNFeat; ++k) f[k] = ldp(p, kColF + k, off);
+                gather_features(win, cand_off(qq), f);
             }
         };
 #pragma unroll
@@ -1086,7 +1174,7 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
                 if (cell >= centre_rank) ++cell;          // rpf.cpp:565: skip the centre pixel
                 const int ix = (int)div_small((uint32_t)cell, magic_ny); // xn outer ascending (rpf.cpp:562)
                 const int iy = cell - ix * nyv;            // yn inner ascending (rpf.cpp:563)
-                sOff[at] = (uint32_t)(((uint64_t)(y0 + iy) * W + (x0 + ix)) * S + s);
+                sOff[at] = (uint32_t)(iy * W + ix) * (uint32_t)S + (uint32_t)s;
             }
             n += __popcll(mask);
         }
@@ -1104,7 +1192,7 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
             if (cell >= centre_rank) ++cell;          // rpf.cpp:565: skip the centre pixel
             const int ix = (int)div_small((uint32_t)cell, magic_ny); // xn outer ascending (rpf.cpp:562)
             const int iy = cell - ix * nyv;            // yn inner ascending (rpf.cpp:563)
-            return (uint32_t)(((uint64_t)(y0 + iy) * W + (x0 + ix)) * S + s);
+            return (uint32_t)(iy * W + ix) * (uint32_t)S + (uint32_t)s;
         };
         // rotating register buffers: the 12 feature gathers of the next kPF1 64-candidate steps are in flight while
         // a step is tested and appended (an L2/MALL round trip is ~1-2k cycles under load, a step ~0.5k)
@@ -1114,8 +1202,7 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
         auto issue1 = [&](int qq, float (&f)[kNFeat], uint32_t &off) {
             if (qq < ncand) {
                 off = cand_off(qq);
-#pragma unroll
-                for (int k = 0; k < kNFeat; ++k) f[k] = ldp(p, kColF + k, off);
+                gather_features(win, off, f);
             }
         };
         // (the shortcut needs the masks only where somebody reads them: a re-routed pixel with N = S reads none)
@@ -1156,10 +1243,10 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
     if (p.dbg.member_hash != nullptr && tid == 0) {
         uint32_t h = 2166136261u;
         for (int j = 0; j < n; ++j) {
-            const uint32_t o = sOff[j];
+            const uint32_t o = sOff[j];                 // relative to the window origin (x0, y0): pp = iy * W + ix, ix < W
             const uint32_t s = o % (uint32_t)S;
             const uint32_t pp = o / (uint32_t)S;
-            const int yn = (int)(pp / (uint32_t)W), xn = (int)(pp % (uint32_t)W);
+            const int yn = y0 + (int)(pp / (uint32_t)W), xn = x0 + (int)(pp % (uint32_t)W);
             h = fnv1a_u32(h, (uint32_t)(((xn - x + b) * p.box + (yn - y + b)) * S) + s);
         }
         p.dbg.member_hash[pix] = h;
@@ -1270,11 +1357,7 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
             double vd[3];
             auto fetch = [&](int j) {
                 if (j < nrun) {
-                    const uint32_t off = sOff[j];
-#pragma unroll
-                    for (int i = 0; i < kNX; ++i) vf[i] = ldp(p, xcol(i), off);
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) vd[i] = p.col_in[(uint64_t)i * p.plane_stride + off];
+                    gather_sample(win, sOff[j], vf, vd);
                 }
             };
             fetch((wv - NCH) * kStageChunk + lane);
@@ -1341,20 +1424,21 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
 #pragma unroll
         for (int i = 0; i < 3; ++i) { cmn[i] = INFINITY; cmx[i] = -INFINITY; }
         {
+            // RPF_CHAIN_BOTH: lane c < 19 runs both in-order chains of column c -- sum(x) and sum(x*x): a multiply and two
+            // adds per sample on two independent dependency chains; the other lanes idle.  (The earlier form gave the
+            // squares to lanes 32..50 and paid for it with a multiply and a 64-bit select per element in every lane:
+            // four instructions per sample.  Same additions, same operands, same order: the same bits.)
             double acc = 0.0;
-            const int myc = lane & 31;
+            [[maybe_unused]] double accq = 0.0;
+            const int myc = RPF_CHAIN_BOTH ? lane : (lane & 31);
             const bool chain = myc < kNDim;
-            const bool is_sq = lane >= 32;
+            [[maybe_unused]] const bool is_sq = lane >= 32;
             const int nrun = (p.stage_mask & 1) ? n : 0;
             float vf[kNX];
             double vd[3];
             auto fetch = [&](int j) {
                 if (j < nrun) {
-                    const uint32_t off = sOff[j];
-#pragma unroll
-                    for (int i = 0; i < kNX; ++i) vf[i] = ldp(p, xcol(i), off);
-#pragma unroll
-                    for (int i = 0; i < 3; ++i) vd[i] = p.col_in[(uint64_t)i * p.plane_stride + off];
+                    gather_sample(win, sOff[j], vf, vd);
                 }
             };
             fetch(lane);
@@ -1399,21 +1483,39 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
                                 double v[16];
 #pragma unroll
                                 for (int q = 0; q < 16; ++q) v[q] = src[h + q];
+#if RPF_CHAIN_BOTH
+#pragma unroll
+                                for (int q = 0; q < 16; ++q) {
+                                    acc = acc + v[q];                                   // ops.h:121 sumArrays
+                                    accq = accq + v[q] * v[q];                          // ops.h:138 multiplyArrays, sumArrays
+                                }
+#else
 #pragma unroll
                                 for (int q = 0; q < 16; ++q) v[q] = is_sq ? v[q] * v[q] : v[q]; // ops.h:138 multiplyArrays (branch-free)
 #pragma unroll
                                 for (int q = 0; q < 16; ++q) acc = acc + v[q];          // ops.h:121 / 138 sumArrays
+#endif
                             }
+#if RPF_CHAIN_BOTH
+                        } else {
+                            for (int q = 0; q < cnth; ++q) { const double v = src[q]; acc = acc + v; accq = accq + v * v; }
+                        }
+#else
                         } else if (!is_sq) {
                             for (int q = 0; q < cnth; ++q) acc = acc + src[q];
                         } else {
                             for (int q = 0; q < cnth; ++q) { const double v = src[q]; acc = acc + v * v; }
                         }
+#endif
                     }
                     wsync();
                 }
             }
+#if RPF_CHAIN_BOTH
+            const double sq = accq;
+#else
             const double sq = __shfl(acc, (lane & 31) + 32, 64);
+#endif
             const double dn = (double)n;
             const double mean = acc / dn;                      // ops.h:123
             double sd = sqrt(sq / dn - mean * mean);           // ops.h:141
@@ -1458,17 +1560,17 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
     bsync();
     if constexpr (K <= 8) {
         switch (kdyn) {
-        case 1: bins_stage<1, KW, PACK5>(p, sStat, sOff, sBinW, lane, n, B, sCK); break;
-        case 2: if constexpr (K >= 2) bins_stage<2, KW, PACK5>(p, sStat, sOff, sBinW, lane, n, B, sCK); break;
-        case 3: if constexpr (K >= 3) bins_stage<3, KW, PACK5>(p, sStat, sOff, sBinW, lane, n, B, sCK); break;
-        case 4: if constexpr (K >= 4) bins_stage<4, KW, PACK5>(p, sStat, sOff, sBinW, lane, n, B, sCK); break;
-        case 5: if constexpr (K >= 5) bins_stage<5, KW, PACK5>(p, sStat, sOff, sBinW, lane, n, B, sCK); break;
-        case 6: if constexpr (K >= 6) bins_stage<6, KW, PACK5>(p, sStat, sOff, sBinW, lane, n, B, sCK); break;
-        case 7: if constexpr (K >= 7) bins_stage<7, KW, PACK5>(p, sStat, sOff, sBinW, lane, n, B, sCK); break;
-        default: if constexpr (K >= 8) bins_stage<8, KW, PACK5>(p, sStat, sOff, sBinW, lane, n, B, sCK); break;
+        case 1: bins_stage<1, KW, PACK5>(p, win, sStat, sOff, sBinW, lane, n, B, sCK); break;
+        case 2: if constexpr (K >= 2) bins_stage<2, KW, PACK5>(p, win, sStat, sOff, sBinW, lane, n, B, sCK); break;
+        case 3: if constexpr (K >= 3) bins_stage<3, KW, PACK5>(p, win, sStat, sOff, sBinW, lane, n, B, sCK); break;
+        case 4: if constexpr (K >= 4) bins_stage<4, KW, PACK5>(p, win, sStat, sOff, sBinW, lane, n, B, sCK); break;
+        case 5: if constexpr (K >= 5) bins_stage<5, KW, PACK5>(p, win, sStat, sOff, sBinW, lane, n, B, sCK); break;
+        case 6: if constexpr (K >= 6) bins_stage<6, KW, PACK5>(p, win, sStat, sOff, sBinW, lane, n, B, sCK); break;
+        case 7: if constexpr (K >= 7) bins_stage<7, KW, PACK5>(p, win, sStat, sOff, sBinW, lane, n, B, sCK); break;
+        default: if constexpr (K >= 8) bins_stage<8, KW, PACK5>(p, win, sStat, sOff, sBinW, lane, n, B, sCK); break;
         }
     } else {
-        bins_stage<K, KW, PACK5, NW>(p, sStat, sOff, sBinW, lane, n, B, sCK, wv);
+        bins_stage<K, KW, PACK5, NW>(p, win, sStat, sOff, sBinW, lane, n, B, sCK, wv);
     }
     bsync();
     if (p.dbg.bin_hash != nullptr && tid < kNDim) { // debug only: hash in sample order j = lane + 64*slot
@@ -1620,11 +1722,13 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
         // stage 2 left there -- gathered again (entries 0 .. S-1 of the member list)
         if (L.off_own >= L.off_hist) { // (wave-uniform)
             for (int j = lane; j < S; j += kWave) {
-                const uint32_t off = sOff[j];
+                float vf[kNX];
+                double vd[3];
+                gather_sample(win, sOff[j], vf, vd);
 #pragma unroll
-                for (int i = 0; i < kNX; ++i) sOwn[j * kNDim + xcol(i)] = (double)ldp(p, xcol(i), off);
+                for (int i = 0; i < kNX; ++i) sOwn[j * kNDim + xcol(i)] = (double)vf[i];
 #pragma unroll
-                for (int i = 0; i < 3; ++i) sOwn[j * kNDim + kColC + i] = p.col_in[(uint64_t)i * p.plane_stride + off];
+                for (int i = 0; i < 3; ++i) sOwn[j * kNDim + kColC + i] = vd[i];
             }
             wsync();
         }
@@ -1634,11 +1738,13 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
         // weights the two earlier kernels left for this pixel
         bsync();
         for (int j = tid; j < S; j += kThreads) {
-            const uint32_t off = sOff[j];
+            float vf[kNX];
+            double vd[3];
+            gather_sample(win, sOff[j], vf, vd);
 #pragma unroll
-            for (int i = 0; i < kNX; ++i) sOwn[j * kNDim + xcol(i)] = (double)ldp(p, xcol(i), off);
+            for (int i = 0; i < kNX; ++i) sOwn[j * kNDim + xcol(i)] = (double)vf[i];
 #pragma unroll
-            for (int i = 0; i < 3; ++i) sOwn[j * kNDim + kColC + i] = p.col_in[(uint64_t)i * p.plane_stride + off];
+            for (int i = 0; i < 3; ++i) sOwn[j * kNDim + kColC + i] = vd[i];
         }
         const double *cr = p.carry + pix * kCarry;
         if (cr[4 * kNDim + 3 + kNFeat + 1] != 0.0) return; // handed to the reference-expression kernel by PHASE 4 (uniform)
@@ -1758,6 +1864,9 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
         }
         bsync();
     }
+    // (one-wave kernels) no weighted column of this pixel has SD == 0: the sweeps form z without the select.  Wave-uniform.
+    [[maybe_unused]] bool z_plain = false;
+    if constexpr (NW == 1 && RPF_Z_HOIST && !FAST) z_plain = !__any(lane < kNWt && sFastI[min(lane, kNWt - 1)] == 0.0);
     bool bad = false;
     // own samples weighted per sweep over the neighbourhood (register budget: 4 at 3 waves/SIMD; the multi-wave kernels
     // run 1-2 waves/SIMD and take 8, halving the per-sample set-up, and gather one sample slot ahead)
@@ -1773,11 +1882,7 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
         float pf[2 + kNFeat];  // pFilm and the features
         double pc[3];  // colours
         auto fetch17 = [&](int j) { // lanes past the end re-load the last sample (no branch, never an invalid address)
-            const uint32_t off = sOff[min(j, n - 1)];
-#pragma unroll
-            for (int k = 0; k < 2 + kNFeat; ++k) pf[k] = ldp(p, k < 2 ? k : kColF + (k - 2), off);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) pc[k] = p.col_in[(uint64_t)k * p.plane_stride + off];
+            gather_weighted(win, sOff[min(j, n - 1)], pf, pc);
         };
         // gathers one sample slot ahead (a second register set) in the four-wave kernels.  Not in the weight kernel of the
         // split route: with 16 own samples per sweep the second set spilled 6-7 registers per sweep step INSIDE the loop --
@@ -1809,21 +1914,21 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
         auto pre_row = [&](int r) -> unsigned char * { return r < kPreMain ? sPre + r * kPreRowF : sPre2 + (r - kPreMain) * kPreRowF; };
         uint32_t off_cur = 0u, off_nxt = 0u; // fp16 planes: the staged slot's plane offset (parity of the element index)
         auto prefetch17 = [&](int j) { // lanes past the end re-load their last sample: never an invalid address
-            const uint32_t off = sOff[min(j, n - 1)];
+            const uint32_t off = sOff[min(j, n - 1)]; // relative to the window origin
             off_nxt = off;
 #pragma unroll
             for (int k = 0; k < 2 + kNFeat; ++k) {
-                const uint64_t e = (uint64_t)(k < 2 ? k : kColF + (k - 2)) * p.plane_stride + off; // element index
-                const char *src = reinterpret_cast<const char *>(p.planes) + (kHalfPlanes ? (e & ~1ull) * 2ull : e * 4ull);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
+                // byte address of the value; fp16 planes: of the aligned dword that holds it
+                const uint64_t a = (uint64_t)(uintptr_t)(win.pl + (uint64_t)(k < 2 ? k : kColF + (k - 2)) * win.pb) + ((uint64_t)off << (kHalfPlanes ? 1 : 2));
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(uintptr_t)(kHalfPlanes ? (a & ~3ull) : a),
                                                  (__attribute__((address_space(3))) void *)pre_row(k), 4, 0, 0);
             }
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
-                const uint32_t *src = reinterpret_cast<const uint32_t *>(p.col_in + (uint64_t)k * p.plane_stride + off);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
+                const uint64_t a = (uint64_t)(uintptr_t)(win.co + (uint64_t)k * win.cb) + ((uint64_t)off << 3);
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(uintptr_t)a,
                                                  (__attribute__((address_space(3))) void *)pre_row(2 + kNFeat + 2 * k), 4, 0, 0);
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + 1),
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(uintptr_t)(a + 4),
                                                  (__attribute__((address_space(3))) void *)pre_row(2 + kNFeat + 2 * k + 1), 4, 0, 0);
             }
         };
@@ -1834,7 +1939,8 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
             for (int k = 0; k < 2 + kNFeat; ++k) {
                 const uint32_t wd = reinterpret_cast<const uint32_t *>(pre_row(k))[lane];
                 if constexpr (kHalfPlanes) {
-                    const uint32_t par = (((uint32_t)(k < 2 ? k : kColF + (k - 2)) & (uint32_t)p.plane_stride) + off_cur) & 1u;
+                    // which half of the dword: the parity of the value's element index in the plane buffer (4-byte aligned)
+                    const uint32_t par = (((uint32_t)(k < 2 ? k : kColF + (k - 2)) & (uint32_t)p.plane_stride) + win_par + off_cur) & 1u;
                     pf[k] = (float)__ushort_as_half((unsigned short)(wd >> (16u * par)));
                 } else {
                     pf[k] = __uint_as_float(wd);
@@ -1868,6 +1974,12 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
             constexpr int kNQ = (kOwnBlock + kOwnsPerQ - 1) / kOwnsPerQ;
             int l16 = lane & 15;
             const int nu = __builtin_amdgcn_readfirstlane(n);
+            // The sweep loop exists twice in the one-wave kernels (RPF_Z_HOIST): whether a weighted column has SD == 0 is a
+            // property of the pixel, so the select that forces its z to 0 (a compare and two v_cndmask per column and sweep
+            // step, on a wave-uniform condition) is left out of the copy that runs when no such column exists.  Both copies
+            // compute (x - M) * (1 / SD) there: the same bits.  One scalar branch per sweep, no EXEC region.
+            auto sweep = [&](auto plain_tag) {
+            constexpr bool kPlainZ = decltype(plain_tag)::value;
 #pragma unroll 1
             for (int kk = 0; kk < K; ++kk) {
                 const int j = lane + kWave * kk;
@@ -1900,7 +2012,8 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
                         const int k = k0 + g;
                         if (k < kNWt) {
                             const double xv = k < 2 ? (double)pf[k] : (k < 5 ? pc[k < 5 && k >= 2 ? k - 2 : 0] : (double)pf[k >= 5 ? k - 3 : 0]);
-                            const double z = ci[g] == 0.0 ? 0.0 : (xv - cm[g]) * ci[g];
+                            double z = (xv - cm[g]) * ci[g];
+                            if constexpr (!kPlainZ) z = ci[g] == 0.0 ? 0.0 : z;
                             zj[k] = z;
                             Bj = fma(cc[g] * z, z, Bj);
                         }
@@ -2027,6 +2140,13 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
                         weigh(iic, exponent(iic));
                     });
                 }
+            }
+            };
+            if constexpr (NW == 1 && RPF_Z_HOIST) {
+                if (z_plain) sweep(std::true_type{});
+                else sweep(std::false_type{});
+            } else {
+                sweep(std::false_type{});
             }
         } else {
             // opt-in RPF_FLAG_FAST_WEIGHTS: per-pair arithmetic in fp32 on z-space values (x-M)/SD that are formed in

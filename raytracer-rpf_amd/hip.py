@@ -26,7 +26,7 @@ PLANES_F32, PLANES_F16 = 0, 1
 
 EXPORTS = ["rpf_version", "rpf_status_string", "rpf_create", "rpf_destroy", "rpf_last_error", "rpf_filter",
            "rpf_filter_device", "rpf_colour_from_planes_device", "rpf_reduce_device", "rpf_stage_pixel_stats",
-           "rpf_filter_pass_debug", "rpf_query_counters", "rpf_lds_bytes_required", "rpf_selftest_udiv", "rpf_feature_images",
+           "rpf_filter_pass_debug", "rpf_query_counters", "rpf_lds_bytes_required", "rpf_check_window_span", "rpf_selftest_udiv", "rpf_feature_images",
            "rpf_host_alloc", "rpf_host_free", "rpf_filter_ex", "rpf_set_option", "rpf_multi_create", "rpf_multi_destroy",
            "rpf_multi_last_error", "rpf_multi_device_count", "rpf_multi_set_option", "rpf_multi_filter",
            "rpf_multi_query_counters", "rpf_query_nbhd", "rpf_query_route", "rpf_film_filter_table", "rpf_filter_film",
@@ -158,6 +158,8 @@ def load():
         L.rpf_feature_images.argtypes = [C.c_void_p, C.POINTER(Desc), C.c_void_p, C.c_void_p]
         L.rpf_lds_bytes_required.restype = C.c_int64
         L.rpf_lds_bytes_required.argtypes = [C.c_int32, C.c_int32]
+        if hasattr(L, "rpf_check_window_span"):  # (a build from before the symbol, loaded through RPF_HIP_LIB to be measured side by side)
+            L.rpf_check_window_span.argtypes = [C.c_int32, C.c_int32, C.c_int32]
         L.rpf_multi_create.argtypes = [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_int32]
         L.rpf_multi_destroy.argtypes = [C.c_void_p]
         L.rpf_multi_destroy.restype = None

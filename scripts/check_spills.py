@@ -13,9 +13,18 @@ the first instruction doing real work (a value parked or fetched after that is t
 that reads a parked operand and ends in its own s_or), at a branch, at the next label, or at an instruction that only
 narrows EXEC (s_and / s_andn2 forms, or s_mov from a pair and-ed in the block: the head of an inner `if`).
 
-Usage: check_spills.py [--report FILE] file.s [...]; exit status 1 if the placement is found.  --report writes, per
+Second rule: DPP read hazards.  The `row_newbcast` instructions of rpf_xlane.h sit in inline assembly, which neither the
+compiler's hazard recogniser nor the assembler looks into; only the first read of a block carries its own `s_nop 1`.  The
+hardware wants two wait states between a VALU write of a VGPR and a DPP read of it, and five between a VALU write of EXEC
+and a DPP instruction.  For every `v_*_dpp ... row_newbcast` the scan walks back over the preceding instructions (one wait
+state each, `s_nop N` counts N + 1; through labels and conditional branches along the fall-through path, up to an
+unconditional branch or the head of the kernel) and flags a VALU instruction -- v_accvgpr_read included -- that writes a
+register of the DPP source operand within two wait states, or EXEC within five.
+
+Usage: check_spills.py [--report FILE] file.s [...]; exit status 1 if either is found.  --report writes, per
 kernel, VGPR / AGPR / SGPR counts, LDS and scratch bytes, the compiler's spill counts (from the .amdgpu_metadata block of
-the same assembly) and the number of scratch spill instructions: the resource usage of the build that ships."""
+the same assembly), the number of scratch spill instructions, and the static VALU / LDS / vector-memory / s_nop instruction
+totals of the kernel's text: the resource usage of the build that ships."""
 import re
 import sys
 
@@ -69,6 +78,104 @@ def scan(path):
     return bad, spills
 
 
+DPP_BCAST = re.compile(r"^v_\w+_dpp\s+(.*?)\s+row_newbcast")
+VREG = re.compile(r"^v(\d+)$|^v\[(\d+):(\d+)\]$")
+HARD_END = re.compile(r"^(s_branch|s_endpgm|s_setpc)")
+TWO_DEST = re.compile(r"^(v_swap_b32|v_permlane\d+_swap)")  # both operands are written
+DPP_VGPR_WAIT, DPP_EXEC_WAIT = 2, 5
+
+
+def _vregs(op):
+    m = VREG.match(op.strip())
+    if not m:
+        return set()
+    if m.group(1) is not None:
+        return {int(m.group(1))}
+    return set(range(int(m.group(2)), int(m.group(3)) + 1))
+
+
+def _instr(line):
+    """the instruction of an assembly line ('' for labels, directives, comments and blank lines)"""
+    t = line.split(";")[0].strip()
+    if not t or t.startswith(".") or t.endswith(":"):
+        return ""
+    return t
+
+
+def _operands(t):
+    parts = t.split(None, 1)
+    return [o.strip() for o in parts[1].split(",")] if len(parts) > 1 else []
+
+
+def scan_dpp(path):
+    """{kernel: [(line number, what)]}: VALU writes too close in front of a row_newbcast DPP read (see the module docstring)"""
+    lines = open(path, errors="replace").read().split("\n")
+    cur, bad = None, {}
+    for i, l in enumerate(lines):
+        m = re.match(r"^(_Z\S+):", l)
+        if m:
+            cur = m.group(1)
+        t = _instr(l)
+        d = DPP_BCAST.match(t) if t else None
+        if not d:
+            continue
+        ops = _operands(t.split("row_newbcast")[0])
+        src = _vregs(ops[1]) if len(ops) > 1 else set()
+        ws, j = 0, i - 1
+        while j >= 0 and ws < DPP_EXEC_WAIT:
+            if re.match(r"^_Z\S+:", lines[j]):
+                break  # the head of the kernel
+            p = _instr(lines[j])
+            j -= 1
+            if not p:
+                continue
+            if HARD_END.match(p):
+                break  # nothing falls through into the DPP from here
+            n = re.match(r"^s_nop\s+(\d+)", p)
+            if n:
+                ws += int(n.group(1)) + 1
+                continue
+            if p.startswith("v_"):
+                po = _operands(p)
+                dst = _vregs(po[0]) if po else set()
+                if TWO_DEST.match(p) and len(po) > 1:
+                    dst |= _vregs(po[1])
+                if ws < DPP_VGPR_WAIT and dst & src:
+                    bad.setdefault(cur or "?", []).append((i + 1, "VALU write of the DPP source %d wait state(s) ahead (line %d)" % (ws, j + 2)))
+                if p.startswith("v_cmpx") or (po and po[0] == "exec"):
+                    bad.setdefault(cur or "?", []).append((i + 1, "VALU write of EXEC %d wait state(s) ahead (line %d)" % (ws, j + 2)))
+            ws += 1
+    return bad
+
+
+def instruction_totals(path):
+    """{kernel: (VALU, LDS, vector memory, s_nop)}: static instruction counts of each kernel's text"""
+    out, cur = {}, None
+    for l in open(path, errors="replace"):
+        m = re.match(r"^(_Z\S+):", l)
+        if m:
+            cur = m.group(1)
+            out[cur] = [0, 0, 0, 0]
+            continue
+        if cur is None:
+            continue
+        if l.startswith(".Lfunc_end"):
+            cur = None
+            continue
+        t = _instr(l)
+        if not t:
+            continue
+        if t.startswith("v_"):
+            out[cur][0] += 1
+        elif t.startswith("ds_"):
+            out[cur][1] += 1
+        elif t.startswith(("global_", "flat_", "buffer_", "scratch_")):
+            out[cur][2] += 1
+        elif t.startswith("s_nop"):
+            out[cur][3] += 1
+    return out
+
+
 def metadata(path):
     """per-kernel resource figures from the .amdgpu_metadata block"""
     text = open(path, errors="replace").read()
@@ -109,19 +216,26 @@ def main():
     for path in args:
         bad, spills = scan(path)
         meta = metadata(path)
+        dpp = scan_dpp(path)
+        tot = instruction_totals(path)
+        for k, v in dpp.items():
+            rc = 1
+            for ln, what in v:
+                print("%s: DPP READ HAZARD in %s at line %d: %s" % (path, k[:110], ln, what))
         for k, v in sorted(spills.items()):
             print("%s: %d scratch spill instructions in %s" % (path, v, k[:110]))
         for k, v in bad.items():
             rc = 1
             print("%s: SPILL CODE BEFORE EXEC RESTORE in %s at lines %s" % (path, k, v))
         for k, m in sorted(meta.items()):
-            rows.append("%-58s VGPR %3s AGPR %3s SGPR %3s  LDS(static) %6s B  scratch %5s B/lane  spilled VGPR %3s SGPR %3s  spill-store instrs %3d  %s"
+            rows.append("%-58s VGPR %3s AGPR %3s SGPR %3s  LDS(static) %6s B  scratch %5s B/lane  spilled VGPR %3s SGPR %3s  spill-store instrs %3d  VALU %5d LDS %4d VMEM %4d s_nop %4d  %s"
                         % (demangle_short(k), m["vgpr"], m["agpr"], m["sgpr"], m["lds"], m["scratch"], m["vspill"], m["sspill"],
-                           spills.get(k, 0), "HAZARD" if k in bad else "ok"))
+                           spills.get(k, 0), *tot.get(k, (0, 0, 0, 0)), "HAZARD" if (k in bad or k in dpp) else "ok"))
     if report:
         with open(report, "w") as f:
             f.write("# resource usage of the shipped build, per kernel (scripts/check_spills.py --report, written by build.py)\n"
-                    "# LDS is dynamic for the fused kernels (see DESIGN.md section 4); 'HAZARD' = spill code in front of an EXEC restore\n")
+                    "# LDS is dynamic for the fused kernels (see DESIGN.md section 4); 'HAZARD' = spill code in front of an EXEC restore, or a\n"
+                    "# VALU write too close in front of a row_newbcast DPP read; VALU / LDS / VMEM / s_nop = static instruction totals\n")
             f.write("\n".join(rows) + "\n")
     return rc
 
