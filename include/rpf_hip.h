@@ -262,6 +262,17 @@ int32_t rpf_multi_filter(rpf_multi *m, const rpf_desc *desc, const void *planes,
  * slowest slab's kernel time */
 int32_t rpf_multi_query_counters(rpf_multi *m, rpf_counters *out);
 
+/* The slab / halo planner every slab path uses (rpf_multi_filter, rpf_multi_filter_film; raytracer-rpf_amd/slabs.py holds the
+ * same slabs).  Needs no device.  n_slabs row slabs of an image of H rows, each holding `depth` halo rows of its neighbours:
+ *   slabs_out   [n_slabs][4] = {a, b, ht, hb}: owned image rows [a, b) = [g*H/n_slabs, (g+1)*H/n_slabs), halo rows held above
+ *               and below (min(depth, rows that exist)); buffer row 0 of slab g is image row a - ht
+ *   copies_out  [*n_copies_out][5] = {source slab, source buffer row, destination slab, destination buffer row, rows}: a
+ *               refresh of every halo row from the neighbour's OWNED boundary rows; room for 2 * (n_slabs - 1) entries
+ * Any output may be NULL.  RPF_E_BADARG for H <= 0, n_slabs <= 0, depth < 0, or when n_slabs > 1 and a slab owns fewer than
+ * `depth` rows (it would have to forward rows it does not own). */
+int32_t rpf_multi_halo_plan(int32_t H, int32_t n_slabs, int32_t depth, int32_t *slabs_out, int32_t *copies_out,
+                            int32_t *n_copies_out);
+
 /* LDS bytes per workgroup the fused kernel needs for (S, box); > device limit => RPF_E_UNSUPPORTED */
 int64_t rpf_lds_bytes_required(int32_t S, int32_t box);
 
@@ -283,7 +294,7 @@ int32_t rpf_check_window_span(int32_t W, int32_t S, int32_t box);
  * every sample's pFilm lies in [q, q+1] on each axis, q = the raster coordinate of its pixel (what pbrt's
  * pPixel + Get2D() gives, fp32 rounding up to q+1 included; NaN fails); radii finite, > 0; non-empty pixel bounds; raster
  * coordinates (sample film and pixel bounds) and radii within +-2^22; the whole buffer is one slab (row_begin == 0,
- * row_end == H).  fp16 planes (the 27-dim layout) are RPF_E_UNSUPPORTED: fp16 cannot place pFilm in its pixel
+ * row_end == H; row slabs over several contexts: rpf_multi_filter_film below).  fp16 planes (the 27-dim layout) are RPF_E_UNSUPPORTED: fp16 cannot place pFilm in its pixel
  * beyond 2048. */
 enum { RPF_PIXFILTER_BOX = 0, RPF_PIXFILTER_TRIANGLE, RPF_PIXFILTER_GAUSSIAN, RPF_PIXFILTER_MITCHELL, RPF_PIXFILTER_SINC };
 #define RPF_FILTER_TABLE_WIDTH 16 /* Film::filterTableWidth, film.h:91 */
@@ -315,6 +326,32 @@ int32_t rpf_filter_film(rpf_ctx *ctx, const rpf_desc *desc, const rpf_film *film
 int32_t rpf_film_splat_device(rpf_ctx *ctx, const rpf_desc *desc, const rpf_film *film, const void *d_planes,
                               const double *d_colour, const float *d_ray_weight, float *d_tile_rgb, float *d_tile_weight,
                               float *d_image_rgb, void *stream);
+
+/* The gather half-widths of the film step for the buffer of desc as the sample film: a sample of buffer pixel q can reach
+ * output pixel x only if |q - x| <= half (floor(r + 0.5), or one more where fp32 rounding can close the gap; DESIGN.md
+ * section 10).  half_y is the number of rows of each neighbour a row slab must hold for the film step.  Needs no context and
+ * no device; refuses what rpf_filter_film refuses about desc and film, with the same status (radii, empty bounds,
+ * coordinates beyond +-2^22, a sub-slab: RPF_E_BADARG; fp16 planes: RPF_E_UNSUPPORTED).  Either output may be NULL. */
+int32_t rpf_film_window(const rpf_desc *desc, const rpf_film *film, int32_t *half_x, int32_t *half_y);
+
+/* rpf_filter_film() for the whole image on every slab context of a rpf_multi: arguments, output shapes and meaning as
+ * rpf_filter_film, any output may be NULL; results (samples, contribSum, filterWeightSum, image, status, merged counters)
+ * are bit-identical to rpf_filter_film on one device -- VERIFIED with one, two and three slab contexts on ONE device; like
+ * rpf_multi_filter, the peer-copy branch (two different ordinals) has still only run between slab contexts on one device.
+ *   - refuses what rpf_multi_filter refuses (whole image only, ...) and what rpf_filter_film refuses for the whole frame,
+ *     before anything is uploaded;
+ *   - every slab holds depth = max(max over boxes of (box-1)/2, half_y of rpf_film_window for the whole image) rows of each
+ *     neighbour, planes and ray weights; a slab that owns fewer rows is RPF_E_BADARG;
+ *   - the pFilm check runs on every slab before any pass and is merged: the refusal names the first offender of the whole
+ *     image in the reference's order, in whole-buffer coordinates, with rpf_filter_film's text;
+ *   - after the last pass the colour halo is refreshed once more, then every slab runs the film step on its own buffer
+ *     (origin moved to the buffer's first image row, output rows clipped to the rows it owns; the first / last slab also
+ *     takes output rows above / below the sample film) and its rows go straight into the caller's arrays.  A slab whose rows
+ *     meet no output row (a crop window elsewhere) does no film work;
+ *   - RPF_E_NONFINITE as rpf_multi_filter: the film step still runs and every output is written. */
+int32_t rpf_multi_filter_film(rpf_multi *m, const rpf_desc *desc, const rpf_film *film, const void *planes,
+                              const float *ray_weight, float *sample_rgb_out, float *tile_rgb_out, float *tile_weight_out,
+                              float *image_rgb_out);
 
 #ifdef __cplusplus
 }

@@ -157,4 +157,13 @@ int32_t download_rows(rpf_ctx *ctx, const rpf_desc *d, const double *colour, con
                       hipStream_t to, hipEvent_t ready);
 int32_t run_passes(rpf_ctx *ctx, const rpf_desc *d, const void *d_planes, double *d_colour, hipStream_t s);
 
+// defined in rpf_api_film.hip, where each is described; the multi-GPU driver runs the same film step on every slab
+int32_t film_geometry(const rpf_desc *d, const rpf_film *film, FilmParams &f, std::string &why);
+int32_t film_ensure(rpf_ctx *ctx, const FilmParams &f);
+constexpr unsigned long long kFilmNoOffender = ~0ull;
+int32_t film_first_offender(rpf_ctx *ctx, const FilmParams &f, const float *d_planes, hipStream_t s, unsigned long long *key);
+std::string film_offender_message(const FilmParams &f, int x, int y, int smp, float pfilm_x, float pfilm_y);
+int32_t film_splat(rpf_ctx *ctx, const FilmParams &f, const rpf_film *film, const float *d_planes, const double *d_colour,
+                   const float *d_ray_weight, float *d_tile_rgb, float *d_tile_w, float *d_image, hipStream_t s);
+
 } // namespace rpf

@@ -1,6 +1,7 @@
 // rpf_api_film.hip -- the host half of the film step (kernels: rpf_film.hip): the gather window, set-up and refusals,
-// pbrt's filter tables (pure fp32 host arithmetic), and the entry points rpf_film_filter_table, rpf_filter_film,
-// rpf_film_splat_device.
+// pbrt's filter tables (pure fp32 host arithmetic), and the entry points rpf_film_filter_table, rpf_film_window,
+// rpf_filter_film, rpf_film_splat_device.  rpf_api_multi.hip runs the same step slab by slab (rpf_multi_filter_film) through
+// the helpers rpf_api.h declares.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -30,25 +31,32 @@ int film_window(float r, double M) {
 
 constexpr int32_t kFilmCoordMax = 1 << 22; // raster coordinates and radii: fp32 resolves half pixels (and q + 1) exactly
 
-int32_t film_setup(rpf_ctx *ctx, const rpf_desc *d, const rpf_film *film, FilmParams &f) {
-    if (!film) return fail(ctx, RPF_E_BADARG, "film is NULL");
+} // namespace
+
+namespace rpf {
+
+// The geometry of the film step for the buffer of d as the sample film: the refusals and the gather window, pure host
+// arithmetic (no context, no device).  A refusal's text goes to `why`.
+int32_t film_geometry(const rpf_desc *d, const rpf_film *film, FilmParams &f, std::string &why) {
+    auto refuse = [&](int32_t st, const char *msg) { why = msg; return st; };
+    if (!film) return refuse(RPF_E_BADARG, "film is NULL");
     if (d->row_begin != 0 || d->row_end != d->H)
-        return fail(ctx, RPF_E_BADARG, "the film step needs the whole buffer (row_begin == 0, row_end == H): a sample reaches "
-                                       "pixels of the rows around it");
+        return refuse(RPF_E_BADARG, "the film step needs the whole buffer (row_begin == 0, row_end == H): a sample reaches "
+                                    "pixels of the rows around it");
     if (layout_of(d).f16)
-        return fail(ctx, RPF_E_UNSUPPORTED, "the film step needs fp32 planes: an fp16 pFilm cannot place a sample inside its "
-                                            "pixel beyond 2048");
+        return refuse(RPF_E_UNSUPPORTED, "the film step needs fp32 planes: an fp16 pFilm cannot place a sample inside its "
+                                         "pixel beyond 2048");
     for (float r : {film->radius_x, film->radius_y})
         if (!(r > 0.f) || !std::isfinite(r) || r > (float)kFilmCoordMax)
-            return fail(ctx, RPF_E_BADARG, "filter radius must be finite, > 0 and <= 2^22");
-    if (film->px1 <= film->px0 || film->py1 <= film->py0) return fail(ctx, RPF_E_BADARG, "empty pixel bounds");
+            return refuse(RPF_E_BADARG, "filter radius must be finite, > 0 and <= 2^22");
+    if (film->px1 <= film->px0 || film->py1 <= film->py0) return refuse(RPF_E_BADARG, "empty pixel bounds");
     const int64_t coords[] = {film->sample_x0, (int64_t)film->sample_x0 + d->W, film->sample_y0, (int64_t)film->sample_y0 + d->H,
                               film->px0, film->px1, film->py0, film->py1};
     int64_t m = 0;
     for (int64_t c : coords) m = std::max<int64_t>(m, c < 0 ? -c : c);
-    if (m > kFilmCoordMax) return fail(ctx, RPF_E_BADARG, "raster coordinates (sample film, pixel bounds) must lie within +-2^22");
+    if (m > kFilmCoordMax) return refuse(RPF_E_BADARG, "raster coordinates (sample film, pixel bounds) must lie within +-2^22");
     if ((int64_t)(film->px1 - film->px0) * (film->py1 - film->py0) >= (1ll << 31))
-        return fail(ctx, RPF_E_BADARG, "more than 2^31 output pixels");
+        return refuse(RPF_E_BADARG, "more than 2^31 output pixels");
     std::memset(&f, 0, sizeof(f));
     f.W = d->W; f.H = d->H; f.S = d->S;
     f.sx0 = film->sample_x0; f.sy0 = film->sample_y0;
@@ -60,35 +68,38 @@ int32_t film_setup(rpf_ctx *ctx, const rpf_desc *d, const rpf_film *film, FilmPa
     f.max_lum = film->max_sample_luminance;
     f.scale = film->scale;
     f.plane_stride = (uint64_t)d->W * d->H * d->S;
+    return RPF_OK;
+}
+
+// the context's workspace of the film step for a buffer of f.plane_stride samples
+int32_t film_ensure(rpf_ctx *ctx, const FilmParams &f) {
     int32_t st;
     if ((st = ctx->d_film_d.ensure(ctx, f.plane_stride * sizeof(float2)))) return st;
     if ((st = ctx->d_film_lw.ensure(ctx, 3 * f.plane_stride * sizeof(float)))) return st;
-    if ((st = ctx->d_film_table.ensure(ctx, sizeof(film->table)))) return st;
+    if ((st = ctx->d_film_table.ensure(ctx, sizeof(rpf_film::table)))) return st;
     return ctx->d_film_bad.ensure(ctx, sizeof(unsigned long long));
 }
 
-// pFilm inside its pixel, for every sample (read back: the refusal names the first offender in the reference's order)
-int32_t film_check(rpf_ctx *ctx, const FilmParams &f, const float *d_planes, hipStream_t s) {
-    const unsigned long long none = ~0ull;
-    unsigned long long bad = none;
-    HIP_TRY(hipMemsetAsync(ctx->d_film_bad, 0xff, sizeof(bad), s)); // = none
+// pFilm inside its pixel, for every sample of the buffer: *key = the first offender in the reference's order,
+// (x * f.H + y) * f.S + s in buffer coordinates, or kFilmNoOffender.  Synchronises s.
+int32_t film_first_offender(rpf_ctx *ctx, const FilmParams &f, const float *d_planes, hipStream_t s, unsigned long long *key) {
+    HIP_TRY(hipMemsetAsync(ctx->d_film_bad, 0xff, sizeof(*key), s)); // = kFilmNoOffender
     HIP_TRY(launch_film_check(f, d_planes, ctx->d_film_bad, s));
-    HIP_TRY(hipMemcpyAsync(&bad, ctx->d_film_bad, sizeof(bad), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(key, ctx->d_film_bad, sizeof(*key), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    if (bad == none) return RPF_OK;
-    const int smp = (int)(bad % (uint64_t)f.S), y = (int)(bad / f.S % (uint64_t)f.H), x = (int)(bad / f.S / f.H);
-    const uint64_t i = ((uint64_t)y * f.W + x) * f.S + smp;
-    float p[2] = {0.f, 0.f};
-    HIP_TRY(hipMemcpy(&p[0], d_planes + i, sizeof(float), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&p[1], d_planes + f.plane_stride + i, sizeof(float), hipMemcpyDeviceToHost));
-    char buf[256];
-    std::snprintf(buf, sizeof(buf), "pFilm (%.9g, %.9g) of sample %d of buffer pixel (x=%d, y=%d) lies outside its raster pixel "
-                  "[%d, %d] x [%d, %d] (pPixel + Get2D() stays inside it)", p[0], p[1], smp, x, y, f.sx0 + x, f.sx0 + x + 1,
-                  f.sy0 + y, f.sy0 + y + 1);
-    return fail(ctx, RPF_E_BADARG, buf);
+    return RPF_OK;
 }
 
-// stage + gather; the caller has run film_check on the same planes
+// the refusal's text: sample smp of buffer pixel (x, y) of the sample film of f, with its pFilm
+std::string film_offender_message(const FilmParams &f, int x, int y, int smp, float pfilm_x, float pfilm_y) {
+    char buf[256];
+    std::snprintf(buf, sizeof(buf), "pFilm (%.9g, %.9g) of sample %d of buffer pixel (x=%d, y=%d) lies outside its raster pixel "
+                  "[%d, %d] x [%d, %d] (pPixel + Get2D() stays inside it)", pfilm_x, pfilm_y, smp, x, y, f.sx0 + x, f.sx0 + x + 1,
+                  f.sy0 + y, f.sy0 + y + 1);
+    return buf;
+}
+
+// stage + gather; the caller has run the pFilm check on the same planes
 int32_t film_splat(rpf_ctx *ctx, const FilmParams &f, const rpf_film *film, const float *d_planes, const double *d_colour,
                    const float *d_ray_weight, float *d_tile_rgb, float *d_tile_w, float *d_image, hipStream_t s) {
     Range rg("rpf:film step");
@@ -96,6 +107,31 @@ int32_t film_splat(rpf_ctx *ctx, const FilmParams &f, const rpf_film *film, cons
     HIP_TRY(launch_film_stage(f, d_planes, d_colour, d_ray_weight, ctx->d_film_d, ctx->d_film_lw, s));
     HIP_TRY(launch_film_splat(f, ctx->d_film_table, ctx->d_film_d, ctx->d_film_lw, d_tile_rgb, d_tile_w, d_image, s));
     return RPF_OK;
+}
+
+} // namespace rpf
+
+namespace {
+
+int32_t film_setup(rpf_ctx *ctx, const rpf_desc *d, const rpf_film *film, FilmParams &f) {
+    std::string why;
+    const int32_t st = film_geometry(d, film, f, why);
+    if (st) return fail(ctx, st, why);
+    return film_ensure(ctx, f);
+}
+
+// pFilm inside its pixel, for every sample (read back: the refusal names the first offender in the reference's order)
+int32_t film_check(rpf_ctx *ctx, const FilmParams &f, const float *d_planes, hipStream_t s) {
+    unsigned long long bad = kFilmNoOffender;
+    int32_t st;
+    if ((st = film_first_offender(ctx, f, d_planes, s, &bad))) return st;
+    if (bad == kFilmNoOffender) return RPF_OK;
+    const int smp = (int)(bad % (uint64_t)f.S), y = (int)(bad / f.S % (uint64_t)f.H), x = (int)(bad / f.S / f.H);
+    const uint64_t i = ((uint64_t)y * f.W + x) * f.S + smp;
+    float p[2] = {0.f, 0.f};
+    HIP_TRY(hipMemcpy(&p[0], d_planes + i, sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&p[1], d_planes + f.plane_stride + i, sizeof(float), hipMemcpyDeviceToHost));
+    return fail(ctx, RPF_E_BADARG, film_offender_message(f, x, y, smp, p[0], p[1]));
 }
 
 // ---- pbrt's filter table (film.cpp:66-76 and the five Evaluate()s), host fp32 -----------------------------------------
@@ -157,6 +193,17 @@ int32_t rpf_film_filter_table(int32_t kind, float radius_x, float radius_y, floa
             table_out[offset] = v;
         }
     }
+    return RPF_OK;
+}
+
+int32_t rpf_film_window(const rpf_desc *d, const rpf_film *film, int32_t *half_x, int32_t *half_y) {
+    if (!d || d->W <= 0 || d->H <= 0 || d->S <= 0) return RPF_E_BADARG;
+    FilmParams f;
+    std::string why;
+    const int32_t st = film_geometry(d, film, f, why);
+    if (st) return st;
+    if (half_x) *half_x = f.hx;
+    if (half_y) *half_y = f.hy;
     return RPF_OK;
 }
 

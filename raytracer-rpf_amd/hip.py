@@ -30,7 +30,7 @@ EXPORTS = ["rpf_version", "rpf_status_string", "rpf_create", "rpf_destroy", "rpf
            "rpf_host_alloc", "rpf_host_free", "rpf_filter_ex", "rpf_set_option", "rpf_multi_create", "rpf_multi_destroy",
            "rpf_multi_last_error", "rpf_multi_device_count", "rpf_multi_set_option", "rpf_multi_filter",
            "rpf_multi_query_counters", "rpf_query_nbhd", "rpf_query_route", "rpf_film_filter_table", "rpf_filter_film",
-           "rpf_film_splat_device"]
+           "rpf_film_splat_device", "rpf_film_window", "rpf_multi_halo_plan", "rpf_multi_filter_film"]
 
 # the film step: pbrt's PixelFilters (include/rpf_hip.h, rpf_film)
 PIXFILTER_BOX, PIXFILTER_TRIANGLE, PIXFILTER_GAUSSIAN, PIXFILTER_MITCHELL, PIXFILTER_SINC = range(5)
@@ -91,6 +91,29 @@ def _radii(kind, radius):
         radius = DEFAULT_RADIUS.get(int(kind), 1.0)
     rx, ry = (radius, radius) if np.isscalar(radius) else radius
     return float(rx), float(ry)
+
+
+def film_window(desc, film):
+    """(half_x, half_y) of the film step's gather for the buffer of `desc` as the sample film (rpf_film_window; no GPU
+    needed): half_y is the number of rows of each neighbour a row slab must hold for the film step"""
+    hx, hy = C.c_int32(0), C.c_int32(0)
+    st = load().rpf_film_window(C.byref(desc), C.byref(film), C.byref(hx), C.byref(hy))
+    if st != OK:
+        raise RpfError(st, "rpf_film_window: the film step refuses this descriptor / film (see rpf_filter_film)")
+    return hx.value, hy.value
+
+
+def halo_plan(H, n_slabs, depth):
+    """rpf_multi_halo_plan (no GPU needed): (slabs, copies).  slabs[g] = (a, b, ht, hb): owned image rows [a, b) and the
+    halo rows held, what slabs.slab_for gives; copies = [(source slab, source buffer row, destination slab, destination
+    buffer row, rows)]: a refresh of every halo row from the neighbour's owned boundary rows"""
+    n = max(int(n_slabs), 1)
+    sl, cp, nc = (C.c_int32 * (4 * n))(), (C.c_int32 * (10 * n))(), C.c_int32(0)
+    st = load().rpf_multi_halo_plan(H, n_slabs, depth, sl, cp, C.byref(nc))
+    if st != OK:
+        raise RpfError(st, "rpf_multi_halo_plan(H=%r, n_slabs=%r, depth=%r): bad argument, or a slab owns fewer rows than "
+                           "the depth" % (H, n_slabs, depth))
+    return ([tuple(sl[4 * g:4 * g + 4]) for g in range(n_slabs)], [tuple(cp[5 * i:5 * i + 5]) for i in range(nc.value)])
 
 
 def make_film(pixel_bounds, radius, table, sample_origin=None, max_sample_luminance=float("inf"), scale=1.0):
@@ -172,6 +195,10 @@ def load():
         L.rpf_film_filter_table.argtypes = [C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]
         L.rpf_filter_film.argtypes = [C.c_void_p, C.POINTER(Desc), C.POINTER(Film)] + [C.c_void_p] * 6
         L.rpf_film_splat_device.argtypes = [C.c_void_p, C.POINTER(Desc), C.POINTER(Film)] + [C.c_void_p] * 7
+        if hasattr(L, "rpf_multi_filter_film"):  # (absent from a build of before the film step on slabs, loaded through RPF_HIP_LIB)
+            L.rpf_film_window.argtypes = [C.POINTER(Desc), C.POINTER(Film), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+            L.rpf_multi_halo_plan.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 3
+            L.rpf_multi_filter_film.argtypes = [C.c_void_p, C.POINTER(Desc), C.POINTER(Film)] + [C.c_void_p] * 6
         L.rpf_host_alloc.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
         L.rpf_host_free.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
@@ -409,6 +436,22 @@ class MultiContext:
         if st != OK and not (allow_nonfinite and st == E_NONFINITE):
             raise RpfError(st, self._L.rpf_multi_last_error(self._h).decode())
         return srgb, prgb, st
+
+    def filter_film(self, planes, desc, film, ray_weight=None, allow_nonfinite=False):
+        """rpf_multi_filter_film: Context.filter_film for the whole image on every slab context; returns the same
+        (sample_rgb, tile_rgb, tile_weight, image_rgb)"""
+        nd, _, _, pdt = dims(desc)
+        planes = np.ascontiguousarray(planes, pdt)
+        assert planes.shape == (nd, desc.H, desc.W, desc.S), planes.shape
+        rw = None if ray_weight is None else np.ascontiguousarray(ray_weight, np.float32)
+        nx, ny = max(film.px1 - film.px0, 0), max(film.py1 - film.py0, 0)
+        srgb = np.empty((3, desc.H, desc.W, desc.S), np.float32)
+        tile, w, img = np.empty((ny, nx, 3), np.float32), np.empty((ny, nx), np.float32), np.empty((ny, nx, 3), np.float32)
+        st = self._L.rpf_multi_filter_film(self._h, C.byref(desc), C.byref(film), _p(planes), _p(rw), _p(srgb), _p(tile),
+                                           _p(w), _p(img))
+        if st != OK and not (allow_nonfinite and st == E_NONFINITE):
+            raise RpfError(st, self._L.rpf_multi_last_error(self._h).decode())
+        return srgb, tile, w, img
 
 
 def lds_bytes_required(S, box):

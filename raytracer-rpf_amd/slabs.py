@@ -6,6 +6,10 @@ data-path communication is a send/recv of b boundary rows with the rank above an
 (`torch.distributed` P2P: RCCL over xGMI on the GPUs, gloo in the CPU tests).  Feature planes never change
 between passes, so their halo is exchanged once; colours change every pass and are re-exchanged before
 each pass.  Planes are laid out [plane][row][x][s], so a halo is one contiguous span per plane.
+
+pbrt's film step (rpf_film_splat_device) also runs slab by slab: ``film_halo_rows`` is the halo it needs (the slab takes the
+larger of that and b), and after one more colour exchange behind the last pass ``film_for_slab`` describes the rank's buffer
+as a sample film of its own whose output rows are the rows the rank owns.  Both are pure geometry: no torch, no GPU.
 """
 from collections import namedtuple
 
@@ -31,6 +35,34 @@ def buffer_rows(slab):
     """rows present in the rank's buffers, and the [row_begin,row_end) range the rank filters"""
     n = slab.row1 - slab.row0
     return slab.halo_top + n + slab.halo_bottom, slab.halo_top, slab.halo_top + n
+
+
+def film_halo_rows(desc, film):
+    """rows of each neighbour a slab must hold for the film step: the gather's row half-width for the WHOLE image
+    (rpf_film_window; desc and film describe the whole sample film).  ``slab_for`` is called with the larger of this and
+    the box halo."""
+    from . import hip
+    return hip.film_window(desc, film)[1]
+
+
+def film_for_slab(film, slab, H):
+    """The film step of one rank.  Returns (a copy of ``film`` that describes the rank's buffer as a sample film of its
+    own, (r0, r1)): ``sample_y0`` is moved to the buffer's first image row and the output rows [py0, py1) are clipped to
+    the rows the rank owns (the first / last rank also takes the output rows above / below the sample film); r0, r1 are
+    the rows of the whole-image outputs [py1 - py0][px1 - px0] that the rank's outputs fill.  None when the rank owns no
+    output row (a crop window elsewhere).  H = rows of the whole sample film.  Every output pixel then gathers the same
+    samples in the same order as in the whole frame, provided the slab holds ``film_halo_rows`` rows of each neighbour
+    and their colours were exchanged after the last pass."""
+    y_own0 = film.sample_y0 + slab.row0
+    y_own1 = film.sample_y0 + slab.row1
+    oy0 = film.py0 if slab.row0 == 0 else max(film.py0, y_own0)
+    oy1 = film.py1 if slab.row1 == H else min(film.py1, y_own1)
+    if oy1 <= oy0:
+        return None
+    f = type(film).from_buffer_copy(film)
+    f.sample_y0 = film.sample_y0 + slab.row0 - slab.halo_top
+    f.py0, f.py1 = oy0, oy1
+    return f, (oy0 - film.py0, oy1 - film.py0)
 
 
 def exchange_halo(t, slab, rank, world, group=None):
