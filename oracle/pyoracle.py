@@ -1,5 +1,6 @@
 """ctypes doorway onto oracle/librpf_oracle.so (fp64 C restatement) and oracle/_ref/libref_mi.so (the
-real reference mi.cpp + ops.h built from /root/reference).
+real reference mi.cpp + ops.h built from /root/reference), and the two programs oracle/_ref/ref_filter_harness and
+oracle/_ref/ref_film_harness (the real ApplyRPFFilter and the real pbrt Film, built from the same tree).
 
 TEST INFRASTRUCTURE ONLY -- imported by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg,
 never by the product package (raytracer-rpf_amd).
@@ -7,6 +8,8 @@ never by the product package (raytracer-rpf_amd).
 import ctypes as C
 import os
 import subprocess
+import sys
+import tempfile
 
 import numpy as np
 
@@ -51,6 +54,13 @@ def build(force=False):
     ref = os.path.join(_HERE, "_ref", "libref_mi.so")
     if os.path.isdir("/root/reference/src/custom") and (force or not os.path.exists(ref)):
         subprocess.check_call(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL)
+    if os.path.isdir("/root/reference/src/custom") and (force or not ref_full_available()):
+        # about half a minute, once.  A tree in which this cannot be built (no g++, a read-only checkout) still has every
+        # fixture test; only the live comparisons skip, so a failure here is reported and not raised.
+        r = subprocess.run(["make", "-C", _HERE, "ref_full"], stdout=subprocess.DEVNULL, stderr=subprocess.PIPE)
+        if r.returncode != 0:
+            sys.stderr.write("pyoracle: oracle/_ref/ref_*_harness not built (make ref_full: status %d)\n%s\n" % (
+                r.returncode, r.stderr.decode(errors="replace")[-2000:]))
 
 
 _lib = None
@@ -85,6 +95,15 @@ def lib():
 
 def ref_available():
     return os.path.exists(os.path.join(_HERE, "_ref", "libref_mi.so"))
+
+
+REF_FILTER_EXE = os.path.join(_HERE, "_ref", "ref_filter_harness")
+REF_FILM_EXE = os.path.join(_HERE, "_ref", "ref_film_harness")
+
+
+def ref_full_available():
+    """the two programs of `make ref_full` (the reference's whole filter and whole film step) are there"""
+    return os.path.exists(REF_FILTER_EXE) and os.path.exists(REF_FILM_EXE)
 
 
 def ref():
@@ -144,6 +163,85 @@ def ref_normalize(x, mean, sd):
     out = np.empty(19)
     ref().ref_normalize_19(_p(x), _p(mean), _p(sd), _p(out))
     return out
+
+
+# ---- reference, whole (child processes: the real ApplyRPFFilter exits where a colour is NaN) ---------------
+def ref_filter(planes, boxes, n_threads=1):
+    """The real RPFIntegrator::ApplyRPFFilter once per box of `boxes` on float32 planes [19,H,W,S].  Returns (colour
+    [3,H,W,S] float64 or None, status): status is the reference's own exit status, 1 where it stopped on a NaN colour
+    ("PRIME ERROR"), in which case colour is None.  Keep n_threads = 1 where the reference may stop: its exit() from a
+    worker thread does not return while the other workers wait."""
+    planes = np.ascontiguousarray(planes, np.float32)
+    nd, H, W, S = planes.shape
+    assert nd == NDIM, planes.shape
+    with tempfile.TemporaryDirectory() as d:
+        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
+        with open(fin, "wb") as f:
+            f.write(np.array([W, H, S, n_threads, len(boxes)] + [int(b) for b in boxes], np.int32).tobytes())
+            f.write(planes.tobytes())
+        r = subprocess.run([REF_FILTER_EXE, fin, fout], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        if r.returncode == 1 and b"PRIME ERROR" in r.stdout:
+            return None, 1
+        if r.returncode != 0:
+            raise RuntimeError("ref_filter_harness: status %d\n%s" % (r.returncode, r.stderr.decode(errors="replace")[-2000:]))
+        return np.fromfile(fout, np.float64).reshape(3, H, W, S), 0
+
+
+def _crop_fractions(bounds, res):
+    """crop-window fractions from which Film's constructor (ceil(res * fraction)) arrives at integer pixel bounds"""
+    (x0, y0), (x1, y1) = bounds
+    return [(x0 - 0.5) / res[0], (x1 - 0.5) / res[0], (y0 - 0.5) / res[1], (y1 - 0.5) / res[1]]
+
+
+def ref_film(kind, radius, params, resolution, pixel_bounds, pfilm, colour, ray_weight=None,
+             max_sample_luminance=np.inf, scale=1.0):
+    """The real pbrt Film: `kind` 0..4 (box, triangle, gaussian, mitchell, windowed sinc) of radius (rx, ry) and params
+    (p0, p1); image `resolution` (xres, yres) cropped to `pixel_bounds` ((x0, y0), (x1, y1)); every sample of pfilm float32
+    [2,H,W,S] / colour float64 [3,H,W,S] / ray_weight float32 [H,W,S] through GetFilmTile / AddSample in the order x, y, s,
+    then MergeFilmTile and WriteImage.  Returns a dict: table [16,16], tile_rgb [ny,nx,3], tile_weight [ny,nx], image
+    [ny,nx,3] (float32) and sample_bounds ((x0, y0), (x1, y1))."""
+    pfilm = np.ascontiguousarray(pfilm, np.float32)
+    colour = np.ascontiguousarray(colour, np.float64)
+    _, H, W, S = pfilm.shape
+    rw = np.ones((H, W, S), np.float32) if ray_weight is None else np.ascontiguousarray(ray_weight, np.float32)
+    assert colour.shape == (3, H, W, S) and rw.shape == (H, W, S)
+    with tempfile.TemporaryDirectory() as d:
+        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
+        with open(fin, "wb") as f:
+            f.write(np.array([kind, W, H, S, resolution[0], resolution[1]], np.int32).tobytes())
+            f.write(np.array([radius[0], radius[1], params[0], params[1]] + _crop_fractions(pixel_bounds, resolution)
+                             + [max_sample_luminance, scale], np.float32).tobytes())
+            f.write(pfilm.tobytes() + colour.tobytes() + rw.tobytes())
+        r = subprocess.run([REF_FILM_EXE, "film", fin, fout], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        if r.returncode != 0:
+            raise RuntimeError("ref_film_harness: status %d\n%s" % (r.returncode, r.stderr.decode(errors="replace")[-2000:]))
+        raw = open(fout, "rb").read()
+    b = np.frombuffer(raw, np.int32, 12)
+    (x0, y0), (x1, y1) = pixel_bounds
+    assert tuple(b[0:4]) == (x0, y0, x1, y1), ("croppedPixelBounds", b[0:4], pixel_bounds)
+    assert tuple(b[8:12]) == (x0, y0, x1, y1), ("tile pixel bounds", b[8:12], pixel_bounds)
+    nx, ny = x1 - x0, y1 - y0
+    v = np.frombuffer(raw, np.float32, offset=48)
+    assert v.size == 256 + 7 * nx * ny, (v.size, nx, ny)
+    o = 256
+    return dict(table=v[:o].reshape(16, 16).copy(), tile_rgb=v[o:o + 3 * nx * ny].reshape(ny, nx, 3).copy(),
+                tile_weight=v[o + 3 * nx * ny:o + 4 * nx * ny].reshape(ny, nx).copy(),
+                image=v[o + 4 * nx * ny:].reshape(ny, nx, 3).copy(),
+                sample_bounds=((int(b[4]), int(b[5])), (int(b[6]), int(b[7]))))
+
+
+def ref_film_tables(requests):
+    """Film::filterTable of the real Film for each (kind, rx, ry, p0, p1) of `requests`: float32 [n,16,16]"""
+    with tempfile.TemporaryDirectory() as d:
+        fin, fout = os.path.join(d, "in.bin"), os.path.join(d, "out.bin")
+        with open(fin, "wb") as f:
+            f.write(np.int32(len(requests)).tobytes())
+            for kind, rx, ry, p0, p1 in requests:
+                f.write(np.int32(kind).tobytes() + np.array([rx, ry, p0, p1], np.float32).tobytes())
+        r = subprocess.run([REF_FILM_EXE, "tables", fin, fout], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+        if r.returncode != 0:
+            raise RuntimeError("ref_film_harness tables: status %d" % r.returncode)
+        return np.fromfile(fout, np.float32).reshape(len(requests), 16, 16)
 
 
 # ---- oracle (C restatement) --------------------------------------------------------------------------

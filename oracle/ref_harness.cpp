@@ -9,7 +9,8 @@
  *
  * The rest of the path (rpf.cpp, sd.h, sample_film.cpp) includes pbrt.h -> <glog/logging.h> and
  * visualization/vis.h -> <ImfRgbaFile.h>; both third-party trees are absent (empty submodule dirs), so
- * those files are unbuildable here without stand-ins and are NOT part of this build.
+ * those files need stand-ins and are NOT part of this build: ref_filter_harness.cpp and ref_film_harness.cpp
+ * build them with the stand-ins of ref_stub/ (Makefile target `ref_full`).
  */
 #include <array>
 #include <vector>

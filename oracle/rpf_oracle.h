@@ -19,10 +19,10 @@
  *   - rpf_oracle_mi / rpf_oracle_mean_std are checked bit-for-bit against the REAL reference code
  *     (mi.cpp + ops.h compiled from /root/reference into oracle/_ref/libref_mi.so) in this container,
  *     and against golden vectors generated from that build (tests/golden/).
- *   - the glue around them (gather order, ComputeCFWeights algebra, weights, blend) lives in rpf.cpp,
- *     which cannot be compiled here without stand-ins for glog/OpenEXR (absent submodules), and the
- *     reference holds no test or fixture for it: that part is "parity unpinned" and follows the cited
- *     lines statement by statement.
+ *   - the glue around them (gather order, ComputeCFWeights algebra, weights, blend, NaN exit, colour carry)
+ *     lives in rpf.cpp and follows the cited lines statement by statement; rpf_oracle_filter_pass under
+ *     REF_ABORT is checked bit-for-bit against the real ApplyRPFFilter (rpf.cpp compiled with the glog /
+ *     OpenEXR stand-ins of oracle/ref_stub/: ref_filter_harness.cpp, tests/golden/ref_filter.npz).
  *
  * Data layout (identical to the device layout): SoA planes, plane d at base + d*H*W*S,
  * element (y, x, s) at ((y*W)+x)*S + s.  The 19 dims are those of SampleData (sd.h:62-94):
