@@ -35,6 +35,7 @@ extern "C" {
 #define RPF_NFEAT 12
 #define RPF_NPAIR 96
 #define RPF_MAX_BOXES 8
+#define RPF_MAX_NDIM 40 /* widest sample vector of the layout-generic kernels (RPF_FLAG_GENERIC): 5 + n_random + n_feat */
 /* general layout: columns [0,2) pFilm | [2,5) colour | [5,5+nR) random parameters | [5+nR,5+nR+nF) features */
 #define RPF_NDIM_OF(nR, nF) (5 + (nR) + (nF))
 #define RPF_NPAIR_OF(nR, nF) ((nF) * ((nR) + 2) + 3 * ((nR) + 2 + (nF))) /* MI pairs, rpf.cpp:416-442 generalised */
@@ -49,7 +50,8 @@ typedef enum rpf_status {
     RPF_E_HIP = 2,         /* a HIP runtime call failed; text in rpf_last_error()                  */
     RPF_E_NONFINITE = 3,   /* REF_ABORT policy: a filtered colour came out NaN (reference aborts)  */
     RPF_E_NOMEM = 4,
-    RPF_E_UNSUPPORTED = 5, /* neighbourhood too large for the LDS-resident kernel  */
+    RPF_E_UNSUPPORTED = 5, /* neighbourhood too large (box*box*S > 65535, or its LDS working set); a sample layout
+                              without compiled kernels and without RPF_FLAG_GENERIC, or outside that flag's bounds */
     RPF_E_NODEVICE = 6
 } rpf_status;
 
@@ -74,8 +76,16 @@ enum {
                                   fp64-formed normalised values, with the hardware exp; everything that decides
                                   discrete outcomes (membership, bins, MI) is unchanged.  Colours move by ~1e-6
                                   relative (bar 1e-4).  Default off: fp64 throughout, like the reference. */
-    RPF_FLAG_NO_OVERLAP = 4    /* rpf_filter(): upload, filter and download one after the other instead of the
+    RPF_FLAG_NO_OVERLAP = 4,   /* rpf_filter(): upload, filter and download one after the other instead of the
                                   row-band pipeline (same results; for A/B timing).  RPF_FLAG_TIMING implies it. */
+    RPF_FLAG_GENERIC = 8       /* opt-in: run this call on the layout-generic kernels, which take n_random / n_feat as run-time
+                                  values: n_random >= 1, n_feat >= 1, 5 + n_random + n_feat <= RPF_MAX_NDIM, fp32 or fp16
+                                  planes, neighbourhoods up to 65535 samples.  REQUIRED for a layout without compiled kernels
+                                  (without it such a descriptor stays RPF_E_UNSUPPORTED: the refusal also tells a caller that
+                                  a layout was mis-declared, and this route is several times slower than the fused kernels);
+                                  ALLOWED for the two compiled layouts, where it selects the generic kernels instead of the
+                                  fused routes (A/B timing, parity).  fp64 throughout: together with RPF_FLAG_FAST_WEIGHTS
+                                  it is RPF_E_UNSUPPORTED.  One filter launch per pass; rpf_query_route says 3. */
 };
 
 typedef struct rpf_desc {
@@ -92,8 +102,10 @@ typedef struct rpf_desc {
     double eps;                        /* RPF_DEGEN_EPS epsilon (1e-10)                             */
     double sigma_seed;                 /* rpf.cpp:533: 0.002                                        */
     /* Sample-vector layout.  All three 0 = the reference's: 2 random parameters (pLens), 12 features, fp32 planes.
-     * Kernels also exist for n_random = 4, n_feat = 18 with RPF_PLANES_F16 (27 dims, fp16 feature storage: BASELINE
-     * configs[4]); anything else returns RPF_E_UNSUPPORTED.  With fp16 planes every `planes` pointer of this header
+     * Compiled kernels also exist for n_random = 4, n_feat = 18 with RPF_PLANES_F16 (27 dims, fp16 feature storage: BASELINE
+     * configs[4]).  Any other layout -- a pbrt fork that records time, or the light-sample coordinates of each bounce, as
+     * further random parameters, or more features -- needs RPF_FLAG_GENERIC in `flags` (bounds there; a field of 0 still means
+     * the reference's value) and returns RPF_E_UNSUPPORTED without it; rpf_layout_kernels() tells which.  With fp16 planes every `planes` pointer of this header
      * addresses 16-bit IEEE halves instead of floats; colours are still carried as fp64, outputs stay fp32.
      * Per-pixel debug planes are then sized by RPF_NDIM_OF / RPF_NPAIR_OF / n_feat. */
     int32_t n_random;
@@ -180,6 +192,8 @@ int32_t rpf_filter_ex(rpf_ctx *ctx, const rpf_desc *desc, const void *planes, co
  *                      decides per pass), 0 fused, 1 count first.  Same results bit for bit; rpf_query_route tells.
  *   "screen"           far-pair screen of the weight stage (four-wave kernels): 1 on (default), 0 off.  Both settings
  *                      give the same filtered colours bit for bit.
+ * These names steer the fused routes only: a call with RPF_FLAG_GENERIC runs one kernel per pass whatever they say (they
+ * are accepted and have no effect there; options_active still reports them).
  * rpf_counters.options_active tells whether a result was produced under any override. */
 int32_t rpf_set_option(rpf_ctx *ctx, const char *name, int64_t value);
 
@@ -214,6 +228,8 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *desc, int32_t box, c
                               const double *colour_in, double *colour_out, const rpf_debug *dbg);
 
 /* counters of the most recent rpf_filter / rpf_filter_device / rpf_filter_pass_debug call */
+/* On the generic route (RPF_FLAG_GENERIC) filter_kernel_launches counts one launch per pass and redo_pixels is 0: that
+ * kernel evaluates the reference's floating-point MI expression in place. */
 int32_t rpf_query_counters(rpf_ctx *ctx, rpf_counters *out);
 
 /* neighbourhood size N of every pixel (rpf.cpp:586: the neighbourhood vector's size) as the last pass of the most recent
@@ -224,7 +240,8 @@ int32_t rpf_query_nbhd(rpf_ctx *ctx, int32_t *nbhd_out, int64_t count);
 /* which kernel route the last pass of the most recent call took (a performance decision, the results are the same bits):
  * 0 = fused (filter_pixel_kernel runs stage 1b itself), 1 = count first (stage 1b as its own launch, then the packed
  * small-neighbourhood kernels take most pixels: the route of path-traced buffers), 2 = size-binned
- * (box*box*S > 512), -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1. */
+ * (box*box*S > 512), 3 = the layout-generic kernels (RPF_FLAG_GENERIC; several times slower, same membership, bins and
+ * statistics), -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1. */
 int32_t rpf_query_route(rpf_ctx *ctx, int32_t *route_out);
 
 /* visualizeSF (rpf.cpp:37-101, visualization/vis.cpp:34-51): the reference's six debug images, without the EXR
@@ -272,6 +289,12 @@ int32_t rpf_multi_query_counters(rpf_multi *m, rpf_counters *out);
  * `depth` rows (it would have to forward rows it does not own). */
 int32_t rpf_multi_halo_plan(int32_t H, int32_t n_slabs, int32_t depth, int32_t *slabs_out, int32_t *copies_out,
                             int32_t *n_copies_out);
+
+/* Which kernels the filter entry points will run for the layout and flags of desc, and whether they take it at all: RPF_OK
+ * with *generic_out = 0 (the compiled, fused kernels) or 1 (the layout-generic kernels); RPF_E_UNSUPPORTED where every filter
+ * entry point refuses the layout / flag combination (same function, so the two cannot drift); RPF_E_BADARG for a NULL desc.
+ * Only n_random, n_feat, plane_dtype and flags are read.  Needs no context and no device.  generic_out may be NULL. */
+int32_t rpf_layout_kernels(const rpf_desc *desc, int32_t *generic_out);
 
 /* LDS bytes per workgroup the fused kernel needs for (S, box); > device limit => RPF_E_UNSUPPORTED */
 int64_t rpf_lds_bytes_required(int32_t S, int32_t box);

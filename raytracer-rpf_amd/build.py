@@ -13,6 +13,7 @@ LIB = os.path.join(_HERE, "lib", "librpf_hip.so")
 # with RPF_IMPL_PART = 1 / 2 / 3), in parallel: the single kernel TU of rounds 1-2 took 3.2 minutes
 KERNEL_TUS = ["rpf_impl_%s_%s.hip" % (lay, part) for lay in ("d19", "d27") for part in ("small", "mid", "large")] + ["rpf_kernels.hip"]
 KERNEL_TUS += ["rpf_film.hip"]  # the film step (pbrt's reconstruction filter): rpf_filter_film / rpf_film_splat_device
+KERNEL_TUS += ["rpf_generic.hip"]  # the layout-generic kernel pair (RPF_FLAG_GENERIC): n_random / n_feat at run time
 # the C ABI (host code only; rpf_api.h is what they share): context, validation, routes and pass loops | film step | multi-GPU
 API_TUS = ["rpf_api.hip", "rpf_api_film.hip", "rpf_api_multi.hip"]
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in KERNEL_TUS + API_TUS]

@@ -36,6 +36,33 @@ SampleLayout layout_of(const rpf_desc *d) {
     return l;
 }
 
+// Which kernels the filter entry points run for the layout and flags of d (rpf_layout_kernels; needs no device): RPF_OK with
+// *generic_out = 0 (the compiled, fused kernels) or 1 (the layout-generic kernels, RPF_FLAG_GENERIC), else the refusal and
+// its text in *why.
+int32_t layout_kernels(const rpf_desc *d, int32_t *generic_out, std::string *why) {
+    if (!d) return RPF_E_BADARG;
+    const SampleLayout lay = layout_of(d);
+    int32_t generic = 0;
+    const char *msg = nullptr;
+    if (d->flags & RPF_FLAG_GENERIC) {
+        generic = 1;
+        if (d->flags & RPF_FLAG_FAST_WEIGHTS)
+            msg = "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_GENERIC: the layout-generic kernels are fp64 throughout";
+        else if (!lay.generic_ok())
+            msg = "sample layout: the layout-generic kernels take n_random >= 1, n_feat >= 1, 5 + n_random + n_feat <= "
+                  "RPF_MAX_NDIM (40), fp32 or fp16 planes";
+    } else if (!lay.supported()) {
+        msg = "sample layout: kernels exist for n_random=2, n_feat=12, fp32 planes (the reference's 19 dims) and n_random=4, "
+              "n_feat=18, fp16 planes (27 dims); any other layout needs RPF_FLAG_GENERIC (the layout-generic kernels)";
+    }
+    if (msg) {
+        if (why) *why = msg;
+        return RPF_E_UNSUPPORTED;
+    }
+    if (generic_out) *generic_out = generic;
+    return RPF_OK;
+}
+
 int32_t validate(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes) {
     if (!ctx) return RPF_E_BADARG;
     if (!d) return fail(ctx, RPF_E_BADARG, "desc is NULL");
@@ -45,9 +72,11 @@ int32_t validate(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes) {
     if ((uint64_t)d->W * d->H * d->S >= (1ull << 32))
         return fail(ctx, RPF_E_BADARG, "W*H*S must be < 2^32 per slab (split the image into row slabs)");
     if (d->beta_map < 0 || d->beta_map > RPF_BETA_PAPER) return fail(ctx, RPF_E_BADARG, "unknown beta_map");
-    if (!layout_of(d).supported())
-        return fail(ctx, RPF_E_UNSUPPORTED, "sample layout: kernels exist for n_random=2, n_feat=12, fp32 planes (the reference's "
-                                            "19 dims) and n_random=4, n_feat=18, fp16 planes (27 dims)");
+    {
+        std::string why;
+        const int32_t st = layout_kernels(d, nullptr, &why);
+        if (st) return fail(ctx, st, why);
+    }
     if (d->degenerate_policy < 0 || d->degenerate_policy > RPF_DEGEN_EPS)
         return fail(ctx, RPF_E_BADARG, "unknown degenerate_policy");
     if (need_boxes) {
@@ -110,6 +139,7 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     p.box = box; p.b = (box - 1) / 2;
     p.beta_map = d->beta_map; p.policy = d->degenerate_policy;
     p.fast_weights = (d->flags & RPF_FLAG_FAST_WEIGHTS) ? 1 : 0;
+    p.generic = (d->flags & RPF_FLAG_GENERIC) ? 1 : 0;
     p.stage_mask = ctx->tun.stage_mask; // timing ablation knob (rpf_set_option); results are wrong unless -1
     p.screen = ctx->tun.screen;
     const int64_t nmax64 = (int64_t)box * box * d->S;
@@ -145,7 +175,9 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     if ((st = ctx->d_flat.ensure(ctx, HW))) return st;
     p.flat = ctx->d_flat; p.nan_flag = ctx->d_nan_flag;
     if (dbg_dev) p.dbg = *dbg_dev;
-    {   // LDS of the largest resident kernel this pass can launch (larger neighbourhoods stream: filter_pixel_big_kernel)
+    if (p.generic) { // the generic kernel's own carve-up (one kernel for every neighbourhood size of the pass)
+        out.lds = generic_carve(p.lay, p.nmax).total;
+    } else { // LDS of the largest resident kernel this pass can launch (larger neighbourhoods stream: filter_pixel_big_kernel)
         const int nres = std::min(p.nmax, kMaxResident), bres = bmax_of(nres);
         out.lds = lds_layout(p.S, nres, bres, table_in_lds(p.S, nres, bres, ctx->tun, p.lay), ctx->tun, p.lay).total;
     }
@@ -354,6 +386,28 @@ int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream_t
     return launch_redo(ctx, pc, s, launches);
 }
 
+// The layout-generic route (RPF_FLAG_GENERIC): one launch per pass, every neighbourhood size on the same kernel; member
+// lists and bin ids in LDS, or -- when generic_carve says they do not fit -- in the streaming kernel's HBM slots.  No redo
+// list: the kernel evaluates the reference's MI expression in place.  None of the rpf_set_option names applies here.
+int32_t route_generic(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *launches) {
+    Range rg("rpf:generic filter kernel");
+    ctx->last_route = 3;
+    if (p.policy == RPF_DEGEN_REF_ABORT) HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
+    if (p.row_end <= p.row_begin) return RPF_OK;
+    const GenericCarve cv = generic_carve(p.lay, p.nmax);
+    const uint64_t npix = (uint64_t)(p.row_end - p.row_begin) * p.W;
+    uint32_t slots = (uint32_t)std::min<uint64_t>(npix, 2048); // resident: eight workgroups on each of 256 CUs
+    if (!cv.resident) {
+        const size_t per_slot = (size_t)p.nmax * (4 + (size_t)p.lay.ndim());
+        slots = (uint32_t)std::min<uint64_t>(npix, std::max<size_t>(64, std::min<size_t>(1024, ((size_t)1 << 30) / per_slot)));
+        int32_t st;
+        if ((st = ensure_big_scratch(ctx, p, slots))) return st;
+    }
+    HIP_TRY(generic::launch_filter(p, ctx->d_big_list, ctx->d_big_bins, slots, s));
+    if (launches) ++*launches;
+    return RPF_OK;
+}
+
 } // namespace
 
 // One fused-filter pass over rows [p.row_begin, p.row_end).  When box*box*S is above what the one-wave kernels hold
@@ -361,6 +415,7 @@ int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream_t
 // LDS sized for its capacity (rpf_kernels.hip, "neighbourhood-size binning"); option "binning" = 0/1 overrides.
 // Needs stage 1a's planes (pmean / pstd) for those rows.  Synchronises the stream when it bins (list sizes).
 int32_t launch_filter_binned(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
+    if (p_in.generic) return route_generic(ctx, p_in, s, launches);
     PassParams p = p_in;
     p.redo_list = nullptr; p.redo_count = nullptr;
     if (p.policy == RPF_DEGEN_REF_ABORT && !p.fast_weights && ctx->tun.stage_mask == -1) {
@@ -726,6 +781,8 @@ int32_t rpf_check_window_span(int32_t W, int32_t S, int32_t box) {
     return (uint64_t)box * (uint64_t)W * (uint64_t)S * 8ull < (1ull << 32) ? RPF_OK : RPF_E_UNSUPPORTED;
 }
 
+int32_t rpf_layout_kernels(const rpf_desc *d, int32_t *generic_out) { return layout_kernels(d, generic_out, nullptr); }
+
 int64_t rpf_lds_bytes_required(int32_t S, int32_t box) {
     if (S <= 0 || box <= 0) return -1;
     const int64_t nmax = (int64_t)box * box * S;
@@ -870,6 +927,7 @@ int32_t rpf_stage_pixel_stats(rpf_ctx *ctx, const rpf_desc *d, const void *plane
     if ((st = upload_frame(ctx, d, planes, nullptr, false, nullptr, s))) return st;
     PassParams p{};
     p.lay = lay;
+    p.generic = (d->flags & RPF_FLAG_GENERIC) ? 1 : 0;
     p.W = d->W; p.H = d->H; p.S = d->S; p.policy = d->degenerate_policy;
     p.plane_stride = ps; p.planes = ctx->d_planes; p.pmean = ctx->d_pmean; p.pstd = ctx->d_pstd;
     HIP_TRY(launch_pixel_stats(p, s));

@@ -10,8 +10,9 @@ namespace rpf {
 constexpr int kWave = 64;
 
 // Which sample-vector layout a call uses (rpf_desc n_random / n_feat / plane_dtype).  Columns: [0,2) pFilm | [2,5) colour
-// | [5,5+nR) random parameters | [5+nR, 5+nR+nF) features (sd.h:62-94 is nR = 2, nF = 12).  The kernels exist for the
-// reference layout with fp32 planes and for BASELINE configs[4]'s 27 dims (nR = 4, nF = 18) with fp16 planes.
+// | [5,5+nR) random parameters | [5+nR, 5+nR+nF) features (sd.h:62-94 is nR = 2, nF = 12).  Compiled (fused) kernels exist
+// for the reference layout with fp32 planes and for BASELINE configs[4]'s 27 dims (nR = 4, nF = 18) with fp16 planes; the
+// layout-generic kernels (rpf_generic.hip, RPF_FLAG_GENERIC) take any layout within generic_ok().
 struct SampleLayout {
     int32_t nR = 2, nF = 12, f16 = 0;
     int ndim() const { return 5 + nR + nF; }
@@ -20,6 +21,7 @@ struct SampleLayout {
     size_t plane_bytes() const { return f16 ? 2 : 4; }
     bool is_ref19() const { return nR == 2 && nF == 12 && !f16; }
     bool supported() const { return is_ref19() || (nR == 4 && nF == 18 && f16 == 1); }
+    bool generic_ok() const { return nR >= 1 && nF >= 1 && ndim() <= RPF_MAX_NDIM && (f16 == 0 || f16 == 1); }
 };
 constexpr int kStageChunk = 64; // samples gathered per step of the in-order (reference-order) sums
 constexpr int kStageHalf = 32;  // ... and staged through LDS this many at a time
@@ -31,6 +33,7 @@ struct PassParams {
     int32_t box, b;        // b = (box-1)/2, rpf.cpp:561
     int32_t beta_map, policy;
     int32_t fast_weights;  // RPF_FLAG_FAST_WEIGHTS: fp32 pair arithmetic in stage 4
+    int32_t generic;       // RPF_FLAG_GENERIC: stage 1a and the filter pass run on the layout-generic kernels (rpf_generic.hip)
     int32_t stage_mask;    // diagnostics only (rpf_set_option "stage_mask"): bit0 stats chain, bit1 bins, bit2 MI, bit3 weights; -1 = all
     int32_t screen;        // far-pair screen of the four-wave kernels: 0 off, 1 on
     int32_t strip_w;       // pixels per XCD strip of the pixel walk (slab_pixel)
@@ -160,6 +163,21 @@ hipError_t launch_film_stage(const FilmParams &f, const float *planes, const dou
 // every output pixel: contribSum, filterWeightSum and WriteImage's value; any output may be null
 hipError_t launch_film_splat(const FilmParams &f, const float *table, const float2 *d_stage, const float *lw_stage,
                              float *tile_rgb, float *tile_w, float *image_rgb, hipStream_t s);
+
+// ---- the layout-generic route (rpf_generic.hip): nR / nF are run-time values of p.lay --------------------------------
+// LDS carve-up of its filter kernel, a host-side function of the layout and the neighbourhood capacity only (byte offsets
+// into the dynamic LDS block); resident: member list and bin ids live in LDS (off_list / off_bins), else in HBM slots
+struct GenericCarve {
+    uint32_t off_chunk, off_hist, off_red4, off_list, off_bins, total, resident;
+    uint32_t hist_par, hist_words; // histograms in the hist region (4: one per wave, 1) and the 32-bit words of one
+};
+GenericCarve generic_carve(const SampleLayout &lay, int nmax);
+namespace generic {
+hipError_t launch_pixel_stats(const PassParams &p, uint64_t pix0, uint64_t pix1, hipStream_t s);
+// one launch filters rows [p.row_begin, p.row_end); list / bins: the streaming kernel's scratch layout with `slots` slots
+// (needed when the carve-up is not resident); the grid is min(pixels, slots)
+hipError_t launch_filter(const PassParams &p, void *list, void *bins, uint32_t slots, hipStream_t s);
+} // namespace generic
 
 int max_lds_per_block();
 hipError_t launch_udiv_selftest(uint64_t n, uint64_t seed, int mode, unsigned long long *d_mismatch, hipStream_t s);

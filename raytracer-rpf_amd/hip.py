@@ -22,6 +22,8 @@ DEGEN_REF_ABORT, DEGEN_EPS = 0, 1
 FLAG_TIMING = 1
 FLAG_FAST_WEIGHTS = 2
 FLAG_NO_OVERLAP = 4
+FLAG_GENERIC = 8  # the layout-generic kernels: required for a layout without compiled kernels, allowed for the two compiled ones
+MAX_NDIM = 40     # ... which take 5 + n_random + n_feat up to this
 PLANES_F32, PLANES_F16 = 0, 1
 
 EXPORTS = ["rpf_version", "rpf_status_string", "rpf_create", "rpf_destroy", "rpf_last_error", "rpf_filter",
@@ -30,7 +32,7 @@ EXPORTS = ["rpf_version", "rpf_status_string", "rpf_create", "rpf_destroy", "rpf
            "rpf_host_alloc", "rpf_host_free", "rpf_filter_ex", "rpf_set_option", "rpf_multi_create", "rpf_multi_destroy",
            "rpf_multi_last_error", "rpf_multi_device_count", "rpf_multi_set_option", "rpf_multi_filter",
            "rpf_multi_query_counters", "rpf_query_nbhd", "rpf_query_route", "rpf_film_filter_table", "rpf_filter_film",
-           "rpf_film_splat_device", "rpf_film_window", "rpf_multi_halo_plan", "rpf_multi_filter_film"]
+           "rpf_film_splat_device", "rpf_film_window", "rpf_multi_halo_plan", "rpf_multi_filter_film", "rpf_layout_kernels"]
 
 # the film step: pbrt's PixelFilters (include/rpf_hip.h, rpf_film)
 PIXFILTER_BOX, PIXFILTER_TRIANGLE, PIXFILTER_GAUSSIAN, PIXFILTER_MITCHELL, PIXFILTER_SINC = range(5)
@@ -101,6 +103,15 @@ def film_window(desc, film):
     if st != OK:
         raise RpfError(st, "rpf_film_window: the film step refuses this descriptor / film (see rpf_filter_film)")
     return hx.value, hy.value
+
+
+def layout_kernels(desc):
+    """rpf_layout_kernels (no GPU needed): (status, generic) for the layout and flags of `desc` -- (OK, 0) the compiled fused
+    kernels, (OK, 1) the layout-generic kernels (FLAG_GENERIC), (E_UNSUPPORTED, None) where the filter entry points refuse
+    it; desc None: (E_BADARG, None)"""
+    g = C.c_int32(-1)
+    st = load().rpf_layout_kernels(None if desc is None else C.byref(desc), C.byref(g))
+    return st, (g.value if st == OK else None)
 
 
 def halo_plan(H, n_slabs, depth):
@@ -199,6 +210,8 @@ def load():
             L.rpf_film_window.argtypes = [C.POINTER(Desc), C.POINTER(Film), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
             L.rpf_multi_halo_plan.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_int32)] * 3
             L.rpf_multi_filter_film.argtypes = [C.c_void_p, C.POINTER(Desc), C.POINTER(Film)] + [C.c_void_p] * 6
+        if hasattr(L, "rpf_layout_kernels"):  # (absent from a build of before the generic route, loaded through RPF_HIP_LIB)
+            L.rpf_layout_kernels.argtypes = [C.POINTER(Desc), C.POINTER(C.c_int32)]
         L.rpf_host_alloc.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
         L.rpf_host_free.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
@@ -276,7 +289,8 @@ class Context:
         return out
 
     def route(self):
-        """kernel route of the last pass: 0 fused, 1 count first, 2 size-binned (rpf_query_route)"""
+        """kernel route of the last pass: 0 fused, 1 count first, 2 size-binned, 3 the layout-generic kernels
+        (FLAG_GENERIC); -1 before any pass (rpf_query_route)"""
         r = C.c_int32(-1)
         self._check(self._L.rpf_query_route(self._h, C.byref(r)))
         return r.value

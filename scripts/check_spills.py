@@ -194,12 +194,15 @@ def metadata(path):
 
 def demangle_short(name):
     m = re.search(r"(d19|d27)(\d+)(\w+?)(I.*)?E?v?NS_", name)
-    ns = re.search(r"3rpf3(d19|d27)", name)
+    ns = re.search(r"3rpf\d+(d19|d27|generic)", name)
     k = re.search(r"kernelILi(\d+)ELb(\d)ELb(\d)ELi(\d)ELi(\d)E", name)
     base = re.search(r"\d+([a-z_]+kernel)", name)
     s = (ns.group(1) + "::" if ns else "") + (base.group(1) if base else name[:60])
     if k:
         s += "<K=%s,TL=%s,FAST=%s,NW=%s,PHASE=%s>" % k.groups()
+    t = re.search(r"3rpf7generic.*kernelI(f|6__half)E", name)  # the layout-generic kernels: the plane type is the only parameter
+    if t:
+        s += "<%s>" % ("float" if t.group(1) == "f" else "__half")
     g = re.search(r"packed_kernelILi(\d+)E", name)
     if g:
         s += "<G=%s>" % g.group(1)

@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Time the filter pass of the layout-generic route (RPF_FLAG_GENERIC) next to the fused routes: seeded buffers generated on
+the device, rpf_filter_device with RPF_FLAG_TIMING (filter_kernel_ms: events around the pass's filter launches, stage 1a
+excluded), one warm-up call, then --steps calls; one JSON line per case with the min and max over the calls, the route,
+the launches and the mean neighbourhood size.  Cases (--case to pick by name):
+  smooth8      1920x270x8 smooth sigma_f = 0.05, box 7 (mean N ~ 296): 19-dim layout without and with the flag
+  flat8        the same slab with flat_frac = 0.94 under EPS (the captured-like small-N regime): without and with the flag
+  lay3_12      the smooth slab as (3, 12, fp32) with the flag
+  lay4_18      the smooth slab as (4, 18, fp32) with the flag
+  box17        256x64x16 smooth, box 17 (N > 3136 for most pixels): 19-dim layout without the flag (the streaming kernel)
+               and with it
+A library loaded through RPF_HIP_LIB (a build variant) is measured by the same script."""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import rpf_pkg  # noqa: E402
+
+rpf_pkg.load()
+from raytracer_rpf_amd import feature_buffer as fb  # noqa: E402
+from raytracer_rpf_amd import hip  # noqa: E402
+
+# name: (W, H, S, box, flat_frac, [(n_random, n_feat, generic), ...])
+CASES = {
+    "smooth8": (1920, 270, 8, 7, 0.0, [(2, 12, 0), (2, 12, 1)]),
+    "flat8": (1920, 270, 8, 7, 0.94, [(2, 12, 0), (2, 12, 1)]),
+    "lay3_12": (1920, 270, 8, 7, 0.0, [(3, 12, 1)]),
+    "lay4_18": (1920, 270, 8, 7, 0.0, [(4, 18, 1)]),
+    "box17": (256, 64, 16, 17, 0.0, [(2, 12, 0), (2, 12, 1)]),
+}
+
+
+def run(ctx, name, steps):
+    W, H, S, box, flat, legs = CASES[name]
+    dev = torch.device("cuda", 0)
+    stream = torch.cuda.current_stream().cuda_stream
+    out = {}
+    for nr, nf, generic in legs:
+        planes = fb.synth_planes_chunked(W, H, S, xp=fb.torch_backend(dev), seed=20261017, sigma_f=0.05, sigma_c=1e-4,
+                                         mode="smooth", flat_frac=flat, n_random=nr, n_feat=nf)
+        colour = torch.empty((3, H, W, S), dtype=torch.float64, device=dev)
+        flags = hip.FLAG_TIMING | (hip.FLAG_GENERIC if generic else 0)
+        desc = hip.make_desc(W, H, S, boxes=(box,), policy=hip.DEGEN_EPS, flags=flags, n_random=nr, n_feat=nf)
+        ms = []
+        for it in range(steps + 1):
+            ctx.colour_from_planes_device(desc, planes.data_ptr(), colour.data_ptr(), stream)
+            ctx.filter_device(desc, planes.data_ptr(), colour.data_ptr(), stream)
+            if it:  # the first call warms up (allocations, tables)
+                ms.append(ctx.counters().filter_kernel_ms)
+        c = ctx.counters()
+        rec = {"case": name, "shape": "%dx%dx%d box %d" % (W, H, S, box), "flat_frac": flat, "layout": [nr, nf, "f32"],
+               "generic": generic, "route": ctx.route(), "launches": c.filter_kernel_launches,
+               "mean_nbhd": round(c.sum_nbhd / (W * H), 1), "max_nbhd": c.max_nbhd,
+               "filter_ms_min": round(min(ms), 3), "filter_ms_max": round(max(ms), 3), "stats_ms": round(c.stats_kernel_ms, 3),
+               "colour_mean": float(colour.mean())}
+        out[(nr, nf, generic)] = rec
+        base = out.get((nr, nf, 0))
+        if generic and base:
+            rec["ratio_to_fused"] = round(rec["filter_ms_min"] / base["filter_ms_min"], 2)
+        print(json.dumps(rec), flush=True)
+        del planes, colour
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--case", nargs="*", default=list(CASES))
+    a = ap.parse_args()
+    print(json.dumps({"library": hip.LIB_PATH, "version": hip.load().rpf_version().decode()}), flush=True)
+    with hip.Context(0) as ctx:
+        for name in a.case:
+            run(ctx, name, a.steps)
+
+
+if __name__ == "__main__":
+    main()
