@@ -177,7 +177,7 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     if (dbg_dev) p.dbg = *dbg_dev;
     if (p.generic) { // the generic kernel's own carve-up (one kernel for every neighbourhood size of the pass)
         out.lds = generic_carve(p.lay, p.nmax).total;
-    } else { // LDS of the largest resident kernel this pass can launch (larger neighbourhoods stream: filter_pixel_big_kernel)
+    } else { // LDS of the largest resident kernel this pass can launch (larger neighbourhoods stream: generic::filter_pixel_kernel)
         const int nres = std::min(p.nmax, kMaxResident), bres = bmax_of(nres);
         out.lds = lds_layout(p.S, nres, bres, table_in_lds(p.S, nres, bres, ctx->tun, p.lay), ctx->tun, p.lay).total;
     }
@@ -188,8 +188,10 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
 
 namespace {
 
-// the streaming kernel's scratch in HBM: member lists [slots][nmax] u32 and bin ids [slots][ndim][nmax] u8
+// the streaming kernel's scratch in HBM: member lists [slots][nmax] u32 and bin ids [slots][ndim][nmax] u8; none when its
+// carve-up holds them in LDS
 int32_t ensure_big_scratch(rpf_ctx *ctx, const PassParams &p, uint32_t slots) {
+    if (generic_carve(p.lay, p.nmax).resident) return RPF_OK;
     int32_t st;
     if ((st = ctx->d_big_list.ensure(ctx, (size_t)slots * p.nmax * 4))) return st;
     return ctx->d_big_bins.ensure(ctx, (size_t)slots * p.nmax * p.lay.ndim());
@@ -209,7 +211,7 @@ int32_t launch_redo(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *launc
     const uint32_t slots = (uint32_t)std::max<size_t>(8, std::min<size_t>(128, (64u << 20) / per_slot));
     int32_t st;
     if ((st = ensure_big_scratch(ctx, q, slots))) return st;
-    HIP_TRY(launch_filter_big(q, ctx->d_big_list, ctx->d_big_bins, slots, p.redo_count, s));
+    HIP_TRY(generic::launch_filter(q, ctx->d_big_list, ctx->d_big_bins, slots, p.redo_count, s));
     if (launches) ++*launches;
     return RPF_OK;
 }
@@ -375,7 +377,7 @@ int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream_t
         if (c == kNumClasses - 1) { // neighbourhoods beyond the LDS-resident kernels: stream through global scratch
             const uint32_t slots = std::min<uint32_t>(counts[c], 1024u);
             if ((st = ensure_big_scratch(ctx, q, slots))) return st;
-            HIP_TRY(launch_filter_big(q, ctx->d_big_list, ctx->d_big_bins, slots, nullptr, s));
+            HIP_TRY(generic::launch_filter(q, ctx->d_big_list, ctx->d_big_bins, slots, nullptr, s));
         } else if (c < kNumPacked && packed) {
             HIP_TRY(launch_filter_packed(q, class_capacity(c), nullptr, s));
         } else {
@@ -403,7 +405,7 @@ int32_t route_generic(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *lau
         int32_t st;
         if ((st = ensure_big_scratch(ctx, p, slots))) return st;
     }
-    HIP_TRY(generic::launch_filter(p, ctx->d_big_list, ctx->d_big_bins, slots, s));
+    HIP_TRY(generic::launch_filter(p, ctx->d_big_list, ctx->d_big_bins, slots, nullptr, s));
     if (launches) ++*launches;
     return RPF_OK;
 }

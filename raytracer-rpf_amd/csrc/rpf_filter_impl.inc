@@ -57,12 +57,6 @@ __device__ __forceinline__ int pair_index_of(int a, int i) {
 // column of anchor a
 __device__ __forceinline__ int anchor_col(int a) { return a < kNR ? kColR + a : (a < kNAnc ? kColP + (a - kNR) : kColC + (a - kNAnc)); }
 
-// value of column c of the sample at plane offset `off`: colours come from the fp64 colour planes
-__device__ __forceinline__ double load_col(const PassParams &p, int c, uint32_t off) {
-    if (c >= kColC && c < kColC + 3) return p.col_in[(uint64_t)(c - kColC) * p.plane_stride + off];
-    return (double)ldp(p, c, off);
-}
-
 // ---- the planes as the fused per-pixel kernel gathers from them ----------------------------------------------------
 // The member list of a pixel (sOff) holds each sample's element offset RELATIVE to the first sample of the pixel's window,
 // ((y0 * W + x0) * S: the smallest plane offset of the window, so a relative offset is >= 0 and < box * W * S), and the
@@ -1643,7 +1637,7 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
     // REF_ABORT promises the reference's own value.  When N is not a power of two and both columns of a pair occupy more
     // than one bin, mi.cpp:79-86 returns rounding RESIDUE for a table inside the band (its quotients are 1 +- a few ulp),
     // not 0, and rpf.cpp:465/470 divide those residues by each other.  Such a pixel (rare: it needs an exactly independent
-    // table) is appended to the redo list and filtered again, whole, by filter_pixel_big_kernel, which evaluates the
+    // table) is appended to the redo list and filtered again, whole, by generic::filter_pixel_kernel, which evaluates the
     // reference's floating-point expression for these tables.  A one-bin column makes the integer sum an exact 0 and the
     // reference's terms exact zeros: nothing to redo.  (A second walk over the pairs, only taken at non-power-of-two N: the
     // test inside the loop above cost the K = 7 kernel a spilled register.)
@@ -2219,7 +2213,7 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
             }
         }
     }
-    // a pixel on the redo list (stage 3b) reports nothing here: filter_pixel_big_kernel filters it again and owns its status
+    // a pixel on the redo list (stage 3b) reports nothing here: generic::filter_pixel_kernel filters it again and owns its status
     if constexpr (NW > 1) {
         if (__any(bad) && lane == 0) sBadFlag[0] = 1;
         __syncthreads();
@@ -2385,433 +2379,6 @@ __global__ __launch_bounds__(256) void nbhd_count_kernel(PassParams p, int step,
         if (flat) atomicAdd(probe + 1, 1u);
         else if (n <= 64) atomicAdd(probe, 1u);
     }
-}
-
-// ------------------------------------------------------------------------------------------------------------------
-// Neighbourhoods beyond the LDS-resident kernels (N > 3136: boxes 17 / 35 / 55 of the reference's commented list,
-// rpf.cpp:767, at 8+ spp).  A neighbourhood of tens of thousands of samples does not fit a CU's LDS (member list +
-// bin ids alone are ~0.5 MiB at box 55), so this kernel STREAMS: the member list and the per-column bin ids (one byte
-// each: N < 65536 => B <= 255) live in a global scratch slot of the workgroup, and LDS holds one joint histogram at a
-// time (16-bit cells: counts <= N), the staging chunk of the in-order sums and the per-pixel statistics.  Counts are
-// integers and the in-order chains walk the list front to back, so chunking changes no result: membership, order,
-// statistics and bins are bit-identical to the oracle, MI comes from the same 2^-44 fixed-point table (same snap rule),
-// weights follow rpf.cpp:646-670 term by term.  256 threads per pixel, workgroups loop over the pixel list of the "big"
-// size class (the acceptance masks of nbhd_count_kernel are required).  Built for correctness: it is the tail of the
-// size distribution (a pixel with N <= 3136 of the same pass runs the LDS-resident kernels).
-struct BigScratch {
-    uint32_t *list;     // [slots][nmax]        member list (plane offsets), reference order
-    uint8_t *bins;      // [slots][kNDim][nmax] bin ids
-    uint32_t slots;
-    uint32_t lds_hist;  // byte offset of the histogram inside the dynamic LDS block
-    const uint32_t *count_dev; // redo mode: the size of the pixel list lives in device memory (no host read-back), else null
-};
-constexpr int kBigThreads = 256, kBigChunk = 64;
-
-template <class T, class Op>
-__device__ __forceinline__ T big_block_reduce(T v, T *sRed, Op op) { // all 256 threads; result in every thread
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sRed[tid] = v;
-    __syncthreads();
-    for (int s = kBigThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) sRed[tid] = op(sRed[tid], sRed[tid + s]);
-        __syncthreads();
-    }
-    return sRed[0];
-}
-
-__global__ __launch_bounds__(256) void filter_pixel_big_kernel(PassParams p, BigScratch bs) {
-    extern __shared__ __align__(16) unsigned char smem[];
-    double *sStat = reinterpret_cast<double *>(smem);                 // M | SD | xmin | xmax
-    double *sZ = sStat + 4 * kNDim;                                   // lo | range | flags(sd0 | flat << 1) per column
-    uint64_t *sHX = reinterpret_cast<uint64_t *>(sZ + 3 * kNDim);     // sum_i T[hx_i] per column
-    uint64_t *sPair = sHX + kNDim;                                    // sum_ij T[J_ij] per pair, then the MI values
-    double *sMI = reinterpret_cast<double *>(sPair);
-    double *sW = sMI + kNPair;                                        // Drf[NF] | D9[12] | alpha[4] | beta[NF] | wrc[4]
-    double *sRedD = sW + 2 * kNFeat + 20;                             // [256] reduction scratch (also u64 / int views)
-    double *sChunk = sRedD + kBigThreads;                             // [kNDim][kBigChunk + 1]
-    uint32_t *sHist = reinterpret_cast<uint32_t *>(smem + bs.lds_hist);
-    int *sCnt = reinterpret_cast<int *>(sChunk);                      // stage 1b: per-wave counts (the chunk is not live yet)
-
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int W = p.W, H = p.H, S = p.S, b = p.b;
-    const uint64_t HW = (uint64_t)H * W;
-    uint32_t *list = bs.list + (uint64_t)blockIdx.x * p.nmax;
-    uint8_t *bins = bs.bins + (uint64_t)blockIdx.x * kNDim * p.nmax;
-    const double e_eps = (p.policy == RPF_DEGEN_EPS) ? p.eps : 0.0;
-
-    const uint32_t list_count = bs.count_dev ? *bs.count_dev : p.list_count;
-    for (uint32_t e = blockIdx.x; e < list_count; e += gridDim.x) {
-        const uint32_t pp = p.pix_list[e];
-        const int y = (int)(pp / (uint32_t)W), x = (int)(pp - (uint32_t)y * (uint32_t)W);
-        const uint64_t pix = (uint64_t)y * W + x;
-        __syncthreads(); // the previous pixel's LDS is dead
-
-        // ---- stage 1b: member list from the acceptance masks, reference order (rpf.cpp:556-586) -----------------
-        const int x0 = max(x - b, 0), x1 = min(x + b, W - 1), y0 = max(y - b, 0), y1 = min(y + b, H - 1);
-        const int nyv = y1 - y0 + 1;
-        const int centre_rank = (x - x0) * nyv + (y - y0);
-        const int ncand = ((x1 - x0 + 1) * nyv - 1) * S;
-        for (int s = tid; s < S; s += kBigThreads) list[s] = (uint32_t)(pix * S + s); // own samples first
-        int n = S;
-        // acceptance masks: the count pass left them (size-binned launch), or -- redo mode on the unbinned route -- the
-        // 3-sigma test runs here (rpf.cpp:577-580 / ops.h:99-107, same statements as stage 1b of filter_pixel_kernel)
-        const bool have_masks = p.masks != nullptr;
-        const uint64_t *pm = have_masks ? p.masks + pix * p.mask_stride : nullptr;
-        double *sM12 = sChunk + 8, *sL12 = sM12 + kNFeat;
-        if (!have_masks) {
-            if (tid < kNFeat) {
-                sM12[tid] = p.pmean[(uint64_t)tid * HW + pix];
-                sL12[tid] = p.pstd[(uint64_t)tid * HW + pix] * 3.0; // multiplyArray(std, 3), rpf.cpp:579
-            }
-            __syncthreads();
-        }
-        for (int q0 = 0; q0 < ncand; q0 += kBigThreads) {
-            const int qb = q0 + wv * 64;                       // this wave's 64-candidate block
-            unsigned long long mask = 0ull;
-            if (qb < ncand) { // wave-uniform
-                if (have_masks) {
-                    mask = pm[qb >> 6];
-                } else {
-                    const int qq = qb + lane;
-                    bool pass = qq < ncand;
-                    if (pass) {
-                        int cell = qq / S;
-                        const int s = qq - cell * S;
-                        if (cell >= centre_rank) ++cell;
-                        const int ix = cell / nyv, iy = cell - ix * nyv;
-                        const uint32_t off = (uint32_t)(((uint64_t)(y0 + iy) * W + (x0 + ix)) * S + s);
-                        for (int k = 0; k < kNFeat; ++k) {
-                            const double a = fabs((double)ldp(p, kColF + k, off) - sM12[k]);
-                            if (a >= sL12[k]) pass = false;     // allLessThan: fails iff a >= b (ops.h:101-104)
-                        }
-                    }
-                    mask = __ballot(pass);
-                }
-            }
-            if (lane == 0) sCnt[wv] = __popcll(mask);
-            __syncthreads();
-            int base = n;
-            for (int w = 0; w < wv; ++w) base += sCnt[w];
-            const int tot = sCnt[0] + sCnt[1] + sCnt[2] + sCnt[3];
-            if ((mask >> lane) & 1ull) {
-                const int qq = qb + lane;
-                int cell = qq / S;
-                const int s = qq - cell * S;
-                if (cell >= centre_rank) ++cell;              // rpf.cpp:565: skip the centre pixel
-                const int ix = cell / nyv, iy = cell - ix * nyv; // xn outer, yn inner ascending (rpf.cpp:562-563)
-                const int at = base + __popcll(mask & ((1ull << lane) - 1ull));
-                if (at < p.nmax) list[at] = (uint32_t)(((uint64_t)(y0 + iy) * W + (x0 + ix)) * S + s);
-            }
-            n += tot;
-            __syncthreads();
-        }
-        if (tid == 0) p.nbhd[pix] = n;
-        __threadfence_block();
-        __syncthreads();
-        const int B = max(1, (int)sqrt((double)n));                // mi.cpp:54
-        const double dn = (double)n;
-
-        // ---- stage 2: in-order sums over the neighbourhood (rpf.cpp:596-601), chunks of 64 staged through LDS ------
-        {
-            double acc = 0.0;
-            const int myc = lane & 31;
-            const bool chain = wv == 0 && myc < kNDim, is_sq = lane >= 32;
-            for (int j0 = 0; j0 < n; j0 += kBigChunk) {
-                const int cnt = min(kBigChunk, n - j0);
-                for (int t = tid; t < cnt * kNDim; t += kBigThreads) {
-                    const int c = t / cnt, q = t - c * cnt;
-                    sChunk[c * (kBigChunk + 1) + q] = load_col(p, c, list[j0 + q]);
-                }
-                __syncthreads();
-                if (chain) {
-                    const double *src = sChunk + myc * (kBigChunk + 1);
-                    for (int q = 0; q < cnt; ++q) { const double v = src[q]; acc = acc + (is_sq ? v * v : v); } // ops.h:121, 138
-                }
-                __syncthreads();
-            }
-            if (wv == 0) {
-                const double sq = __shfl(acc, (lane & 31) + 32, 64);
-                const double mean = acc / dn;                                  // ops.h:123
-                double sd = sqrt(sq / dn - mean * mean);                       // ops.h:141
-                if (p.policy == RPF_DEGEN_EPS && isnan(sd)) sd = 0.0;
-                if (lane < kNDim) {
-                    sStat[lane] = mean; sStat[kNDim + lane] = sd;
-                    if (p.dbg.mean) p.dbg.mean[pix * kNDim + lane] = mean;
-                    if (p.dbg.stddev) p.dbg.stddev[pix * kNDim + lane] = sd;
-                }
-            }
-        }
-        // column minima / maxima (order-free), then the per-column constants of the binning (sd.h:229-232, mi.cpp:47-50)
-        for (int c = 0; c < kNDim; ++c) {
-            double mn = INFINITY, mx = -INFINITY;
-            for (int j = tid; j < n; j += kBigThreads) { const double v = load_col(p, c, list[j]); mn = fmin(mn, v); mx = fmax(mx, v); }
-            mn = big_block_reduce(mn, sRedD, [](double a, double b2) { return fmin(a, b2); });
-            mx = big_block_reduce(mx, sRedD, [](double a, double b2) { return fmax(a, b2); });
-            if (tid == 0) { sStat[2 * kNDim + c] = mn; sStat[3 * kNDim + c] = mx; }
-        }
-        __syncthreads();
-        if (tid < kNDim) {
-            const double Mc = sStat[tid], SDc = sStat[kNDim + tid];
-            const bool sd0 = (SDc == 0.0);
-            const double lo = sd0 ? 0.0 : (sStat[2 * kNDim + tid] - Mc) / SDc, hi = sd0 ? 0.0 : (sStat[3 * kNDim + tid] - Mc) / SDc;
-            sZ[tid] = lo; sZ[kNDim + tid] = hi - lo;
-            sZ[2 * kNDim + tid] = (double)((sd0 ? 1 : 0) | (!(hi != lo) ? 2 : 0)); // mi.cpp:7 / 28 / 34
-        }
-        __syncthreads();
-
-        // ---- stage 3a: normalise, bin ids -> global scratch (one byte per sample and column) --------------------------
-        for (int c = 0; c < kNDim; ++c) {
-            const double Mc = sStat[c], SDc = sStat[kNDim + c], lo = sZ[c], range = sZ[kNDim + c];
-            const int flags = (int)sZ[2 * kNDim + c];
-            const bool sd0 = flags & 1, flat = flags & 2;
-            uint8_t *bc = bins + (uint64_t)c * p.nmax;
-            for (int j = tid; j < n; j += kBigThreads) {
-                int bin = 0;
-                if (!flat) {
-                    const double a = load_col(p, c, list[j]) - Mc;          // subtractArrays
-                    const double z = sd0 ? 0.0 : a / SDc;                      // divideArrays, ops.h:48
-                    const double t = (z - lo) / range * (double)B;             // mi.cpp:14
-                    bin = max(min((int)t, B - 1), 0);
-                }
-                bc[j] = (uint8_t)bin;
-            }
-        }
-        __threadfence_block();
-        __syncthreads();
-        if (p.dbg.member_hash != nullptr && tid == 0) {
-            uint32_t h = 2166136261u;
-            for (int j = 0; j < n; ++j) {
-                const uint32_t o = list[j], s = o % (uint32_t)S, q = o / (uint32_t)S;
-                const int yn = (int)(q / (uint32_t)W), xn = (int)(q % (uint32_t)W);
-                h = fnv1a_u32(h, (uint32_t)(((xn - x + b) * p.box + (yn - y + b)) * S) + s);
-            }
-            p.dbg.member_hash[pix] = h;
-        }
-        if (p.dbg.bin_hash != nullptr && tid < kNDim) {
-            uint32_t h = 2166136261u;
-            const uint8_t *bc = bins + (uint64_t)tid * p.nmax;
-            for (int j = 0; j < n; ++j) h = fnv1a_u16(h, bc[j]);
-            p.dbg.bin_hash[pix * kNDim + tid] = h;
-        }
-
-        // ---- stage 3b: histograms, 16-bit cells packed two per word (counts <= N < 65536) ------------------------------
-        auto hist_T = [&](const uint8_t *ba, const uint8_t *bb, int cells) -> uint64_t { // sum over cells of T[count]
-            for (int t = tid; t < (cells + 1) / 2; t += kBigThreads) sHist[t] = 0u;
-            __syncthreads();
-            for (int j = tid; j < n; j += kBigThreads) {
-                const uint32_t cell = ba ? (uint32_t)ba[j] * (uint32_t)B + bb[j] : bb[j];     // mi.cpp:39
-                atomicAdd(&sHist[cell >> 1], 1u << (16u * (cell & 1u)));
-            }
-            __syncthreads();
-            uint64_t acc = 0ull;
-            for (int t = tid; t < cells; t += kBigThreads) acc += p.tfix[(sHist[t >> 1] >> (16u * (t & 1u))) & 0xffffu];
-            return big_block_reduce(acc, reinterpret_cast<uint64_t *>(sRedD), [](uint64_t a, uint64_t b2) { return a + b2; });
-        };
-        for (int c = 0; c < kNDim; ++c) {
-            const uint64_t t = hist_T(nullptr, bins + (uint64_t)c * p.nmax, B);
-            if (tid == 0) sHX[c] = t;
-        }
-        for (int pr = 0; pr < kNPair; ++pr) {
-            int ca, cb;
-            pair_cols(pr, ca, cb);
-            const uint64_t t = hist_T(bins + (uint64_t)ca * p.nmax, bins + (uint64_t)cb * p.nmax, B * B);
-            if (tid == 0) sPair[pr] = t;
-        }
-        __syncthreads();
-        uint32_t *sMargX = reinterpret_cast<uint32_t *>(sChunk), *sMargY = sMargX + 256; // (the staging chunk is not live here)
-        int *sNeed = reinterpret_cast<int *>(sMargY + 256);                               // [kNPair]
-        {
-            const int64_t TNf = (int64_t)p.tfix[n];
-            const int64_t zero_band = ((int64_t)B * B + 2 * B + 1) / 2 + 1;   // see filter_pixel_kernel
-            for (int pr = tid; pr < kNPair; pr += kBigThreads) {
-                int ca, cb;
-                pair_cols(pr, ca, cb);
-                int64_t f = TNf + (int64_t)sPair[pr] - (int64_t)sHX[ca] - (int64_t)sHX[cb];
-                int need = 0;
-                if (f <= zero_band && f >= -zero_band) {
-                    // REF_ABORT: the reference's own value for such a table is rounding residue unless its quotients are
-                    // exact (N a power of two, or a one-bin column): evaluated below, term by term
-                    need = p.policy == RPF_DEGEN_REF_ABORT && (n & (n - 1)) != 0 && (int64_t)sHX[ca] != TNf && (int64_t)sHX[cb] != TNf;
-                    f = 0;
-                }
-                sNeed[pr] = need;
-                const double mi = ldexp((double)f, -kTFixBits) / dn;
-                sMI[pr] = mi; // (same slot as sPair[pr]: each thread overwrites only what it has just read)
-                if (p.dbg.mi) p.dbg.mi[pix * kNPair + pr] = mi;
-            }
-        }
-        __syncthreads();
-        // ---- the reference expression for tables inside the rounding band (REF_ABORT): mi.cpp:66-86 on the integer counts,
-        // same operations in the same cell order -- pX = hx/N, pY = hy/N, pXY = J/N, mi += pXY * log(pXY / (pX * pY)) for
-        // i outer, j inner -- with log(1 +- k ulp) as the host's libm returns it (rpf_reflog.h).  A skipped cell adds
-        // nothing in the reference and +0.0 here (mi is never -0.0), so the running sum is the same double.
-        if (p.policy == RPF_DEGEN_REF_ABORT) {
-            for (int pr = 0; pr < kNPair; ++pr) {
-                if (!sNeed[pr]) continue; // workgroup-uniform
-                int ca, cb;
-                pair_cols(pr, ca, cb);
-                const uint8_t *ba = bins + (uint64_t)ca * p.nmax, *bb = bins + (uint64_t)cb * p.nmax;
-                const int cells = B * B;
-                __syncthreads();
-                for (int t = tid; t < (cells + 1) / 2; t += kBigThreads) sHist[t] = 0u;
-                for (int t = tid; t < 512; t += kBigThreads) sMargX[t] = 0u; // both marginals
-                __syncthreads();
-                for (int j = tid; j < n; j += kBigThreads) {
-                    const uint32_t bx = ba[j], by = bb[j], cell = bx * (uint32_t)B + by;       // mi.cpp:39
-                    atomicAdd(&sHist[cell >> 1], 1u << (16u * (cell & 1u)));
-                    atomicAdd(&sMargX[bx], 1u);                                                 // mi.cpp:17
-                    atomicAdd(&sMargY[by], 1u);
-                }
-                __syncthreads();
-                double mi = 0.0; // thread 0's running sum
-                for (int t0 = 0; t0 < cells; t0 += kBigThreads) {
-                    const int t = t0 + tid;
-                    double term = 0.0;
-                    if (t < cells) {
-                        const int i = t / B, j = t - i * B;
-                        const double pX = (double)sMargX[i] / dn, pY = (double)sMargY[j] / dn;  // mi.cpp:70-75
-                        const double pXY = (double)((sHist[t >> 1] >> (16u * (t & 1u))) & 0xffffu) / dn; // mi.cpp:81
-                        const double pp = pX * pY;                                              // mi.cpp:82
-                        if (pXY > 0 && pp != 0) {
-                            const double q = pXY / pp;
-                            term = pXY * (reflog_in_range(q) ? reflog_near_one(q) : log(q));    // mi.cpp:84
-                        }
-                    }
-                    sRedD[tid] = term;
-                    __syncthreads();
-                    if (tid == 0) {
-                        const int cnt = min(kBigThreads, cells - t0);
-                        for (int q = 0; q < cnt; ++q) mi += sRedD[q];
-                    }
-                    __syncthreads();
-                }
-                if (tid == 0) {
-                    sMI[pr] = mi;
-                    if (p.dbg.mi) p.dbg.mi[pix * kNPair + pr] = mi;
-                }
-            }
-            __syncthreads();
-        }
-
-        // ---- stage 3c: alpha, beta, W_r_c (rpf.cpp:444-487) ----------------------------------------------------------
-        double *sDrf = sW, *sD9 = sDrf + kNFeat, *sAlpha = sD9 + 12, *sBeta = sAlpha + 4, *sWrc = sBeta + kNFeat;
-        {
-            const int k = min(tid, kNFeat - 1), c = min(tid, 2);
-            double Drf = 0.0, Dpf = 0.0, Dcf = 0.0, Drc = 0.0, Dpc = 0.0, Dfc = 0.0;
-            const int base = kNPairF + c * kNPairC;
-            for (int l = 0; l < kNR; ++l) { Drf += sMI[k * kNAnc + l]; Drc += sMI[base + l]; }                 // rpf.cpp:421, 432
-            for (int l = 0; l < 2; ++l) { Dpf += sMI[k * kNAnc + kNR + l]; Dpc += sMI[base + kNR + l]; }       // rpf.cpp:425, 436
-            for (int cc = 0; cc < 3; ++cc) Dcf += sMI[kNPairF + cc * kNPairC + kNAnc + k];
-            for (int j = 0; j < kNFeat; ++j) Dfc += sMI[base + kNAnc + j];                                      // rpf.cpp:440
-            if (tid < kNFeat) sDrf[tid] = Drf;
-            if (tid < 3) { sD9[tid] = Drc; sD9[3 + tid] = Dpc; sD9[6 + tid] = Dfc; }
-            __syncthreads();
-            double D_f_c = 0.0, D_r_c = 0.0, D_p_c = 0.0;                                                      // rpf.cpp:449-456
-            for (int i = 0; i < 3; ++i) { D_f_c += sD9[6 + i]; D_r_c += sD9[i]; D_p_c += sD9[3 + i]; }
-            const double den = D_f_c + D_r_c + D_p_c + e_eps;
-            double wsum = 0.0;
-            for (int i = 0; i < 3; ++i) wsum += sD9[i] / (sD9[i] + sD9[3 + i] + e_eps);                        // rpf.cpp:470, 485
-            const double wrc = wsum / 3;                                                                       // rpf.cpp:487
-            const double alpha_c = 1 - Drc / (Drc + Dpc + e_eps);                                              // rpf.cpp:470, 475
-            double num;
-            if (p.beta_map == RPF_BETA_PAPER) num = Dcf;
-            else if (p.beta_map == RPF_BETA_REF_GCC11_O2) num = k < 3 ? sD9[6 + c] : (k < 8 ? 0.0 : sDrf[max(k - 8, 0)]);
-            else num = k < 3 ? sD9[6 + c] : (k < 4 ? 0.0 : sDrf[max(k - 4, 0)]);
-            const double beta_k = (1 - Drf / (Drf + Dpf + e_eps)) * (num / den);                               // rpf.cpp:464-465, 479
-            if (tid < kNFeat) { sBeta[tid] = beta_k; if (p.dbg.beta) p.dbg.beta[pix * kNFeat + tid] = beta_k; }
-            if (tid < 3) { sAlpha[tid] = alpha_c; if (p.dbg.alpha) p.dbg.alpha[pix * 3 + tid] = alpha_c; }
-            if (tid == 0) { sWrc[0] = wrc; if (p.dbg.wrc) p.dbg.wrc[pix] = wrc; }
-            __syncthreads();
-        }
-
-        // ---- stage 4: weights and blend, term by term as rpf.cpp:646-717; eight own samples per sweep ------------------
-        {
-            const double wrc = sWrc[0];
-            const double sigma_c2 = p.seed * p.seed / (1 - wrc) / (1 - wrc);                                    // rpf.cpp:662
-            const double sigma_p2 = p.sigma_p * p.sigma_p;
-            auto znorm = [&](int c, double xv) { const double sd = sStat[kNDim + c]; return sd == 0.0 ? 0.0 : (xv - sStat[c]) / sd; };
-            double *sOwnZ = sChunk; // [8][kNWt] normalised own samples of the sweep (the staging chunk is dead)
-            bool bad = false;
-            for (int i0 = 0; i0 < S; i0 += 8) {
-                __syncthreads();
-                for (int t = tid; t < 8 * kNWt; t += kBigThreads) {
-                    const int ii = t / kNWt, k = t - ii * kNWt, i = min(i0 + ii, S - 1);
-                    const int col = k < 5 ? k : k + kNR;
-                    sOwnZ[t] = znorm(col, load_col(p, col, (uint32_t)(pix * S + i)));
-                }
-                __syncthreads();
-                double sw[8], s0[8], s1[8], s2[8];
-                for (int ii = 0; ii < 8; ++ii) { sw[ii] = 0.0; s0[ii] = 0.0; s1[ii] = 0.0; s2[ii] = 0.0; }
-                for (int j = tid; j < n; j += kBigThreads) {
-                    const uint32_t off = list[j];
-                    double zj[kNWt], cj[3];
-                    for (int k = 0; k < kNWt; ++k) {
-                        const int col = k < 5 ? k : k + kNR;
-                        const double xv = load_col(p, col, off);
-                        if (k >= 2 && k < 5) cj[k - 2] = xv;
-                        zj[k] = znorm(col, xv);
-                    }
-                    for (int ii = 0; ii < 8; ++ii) {
-                        const double *zi = sOwnZ + ii * kNWt;
-                        double sp = 0.0, sc = 0.0, sf = 0.0;
-                        for (int k = 0; k < 2; ++k) { const double t = zi[k] - zj[k]; sp += t * t; }
-                        for (int k = 0; k < 3; ++k) { const double t = zi[2 + k] - zj[2 + k]; sc += (t * t) * sAlpha[k]; }
-                        for (int k = 0; k < kNFeat; ++k) { const double t = zi[5 + k] - zj[5 + k]; sf += (t * t) * sBeta[k]; }
-                        double w = exp(-sp / (2 * sigma_p2)) * exp(-sc / (2 * sigma_c2)) * exp(-sf / (2 * sigma_c2)); // rpf.cpp:667-670
-                        w = (i0 + ii < S) ? w : 0.0;
-                        sw[ii] += w; s0[ii] += w * cj[0]; s1[ii] += w * cj[1]; s2[ii] += w * cj[2];   // rpf.cpp:691-692
-                    }
-                }
-                for (int ii = 0; ii < 8; ++ii) {
-                    auto add = [](double a, double b2) { return a + b2; };
-                    const double tw = big_block_reduce(sw[ii], sRedD, add);
-                    const double t0 = big_block_reduce(s0[ii], sRedD, add);
-                    const double t1 = big_block_reduce(s1[ii], sRedD, add);
-                    const double t2 = big_block_reduce(s2[ii], sRedD, add);
-                    const int i = i0 + ii;
-                    if (tid < 3 && i < S) {
-                        double prime = (tid == 0 ? t0 : (tid == 1 ? t1 : t2)) / tw;                           // rpf.cpp:700
-                        if (isnan(prime)) {                                                                    // rpf.cpp:702
-                            bad = true;
-                            if (p.policy == RPF_DEGEN_EPS) prime = p.col_in[(uint64_t)tid * p.plane_stride + pix * S + i];
-                        }
-                        p.col_out[(uint64_t)tid * p.plane_stride + pix * S + i] = prime;
-                    }
-                }
-            }
-            const int anybad = big_block_reduce(bad ? 1 : 0, reinterpret_cast<int *>(sRedD), [](int a, int b2) { return a | b2; });
-            if (tid == 0 && anybad) {
-                atomicAdd(&p.status[0], 1);
-                atomicMin(&p.status[1], (int)pix);
-            }
-        }
-    }
-}
-
-// LDS bytes of the big kernel for a neighbourhood capacity nmax and S samples per pixel; hist offset via *off_hist
-uint32_t big_lds_bytes(int nmax, uint32_t *off_hist) {
-    const uint32_t bmax = (uint32_t)sqrt((double)nmax);
-    uint32_t o = (uint32_t)((4 * kNDim + 3 * kNDim + kNDim + kNPair + 2 * kNFeat + 20 + kBigThreads) * 8);
-    const uint32_t chunk = (uint32_t)kNDim * (kBigChunk + 1) * 8u, ownz = 8u * kNWt * 8u;
-    o += chunk > ownz ? chunk : ownz;
-    o = (o + 15u) & ~15u;
-    if (off_hist) *off_hist = o;
-    return o + ((((bmax * bmax + 1u) / 2u) * 4u + 15u) & ~15u);
-}
-
-hipError_t impl_filter_big(const PassParams &p, void *list, void *bins, uint32_t slots, const uint32_t *count_dev, hipStream_t s) {
-    BigScratch bs;
-    bs.list = (uint32_t *)list; bs.bins = (uint8_t *)bins; bs.slots = slots;
-    const uint32_t total = big_lds_bytes(p.nmax, &bs.lds_hist);
-    if (total > 160u * 1024u) return hipErrorInvalidValue;
-    hipError_t e = hipFuncSetAttribute((const void *)filter_pixel_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)total);
-    if (e != hipSuccess) return e;
-    bs.count_dev = count_dev;
-    const unsigned grid = count_dev ? slots : (p.list_count < slots ? p.list_count : slots);
-    if (grid == 0) return hipSuccess;
-    hipLaunchKernelGGL(filter_pixel_big_kernel, dim3(grid), dim3(kBigThreads), total, s, p, bs);
-    return hipGetLastError();
 }
 
 #endif // RPF_IMPL_PART == 1

@@ -1,14 +1,18 @@
-// rpf_generic.hip -- the layout-generic kernel pair (RPF_FLAG_GENERIC, rpf_query_route 3): n_random and n_feat are run-time
-// values (PassParams::lay), the only template parameter is the storage type of the feature planes.  Compiled with
-// -ffp-contract=off like every kernel TU.
+// rpf_generic.hip -- the layout-generic kernel pair: n_random and n_feat are run-time values (PassParams::lay), the only
+// template parameter is the storage type of the feature planes.  Compiled with -ffp-contract=off like every kernel TU.
 //
-// The arithmetic is filter_pixel_big_kernel's (rpf_filter_impl.inc), statement for statement: reference order of the member
-// list, strict a >= b rejection, in-order sums, one-byte bin ids, 16-bit histogram cells, MI from the 2^-44 k ln k table, the
-// reference's own floating-point expression for in-band tables under REF_ABORT (evaluated in place: no redo list), three exps
-// multiplied.  What differs: every column count is a loop bound and the LDS carve-up comes from the
-// host; the x and x*x chains of column c sit on lane c of waves 0 and 1 (ndim <= 40 does not fit two 32-lane halves); stage 4
-// runs its column loop outermost, so no per-thread array is indexed by a run-time column; stage 1b always runs its own
-// 3-sigma test; member list and bin ids live in LDS when generic_carve says they fit, else in the streaming kernel's HBM slots.
+// filter_pixel_kernel is the streaming kernel of every layout: 256 threads filter one pixel whatever its neighbourhood size
+// (N <= 65535).  It has three callers (rpf_api.hip): the whole pass under RPF_FLAG_GENERIC (rpf_query_route 3: the rows of the
+// slab); the last size class of the size-binned route (N > 3136: that class's pixel list); and, under REF_ABORT, the redo list
+// of the compiled kernels (list size read on the device).
+//
+// The arithmetic follows the reference statement by statement: reference order of the member list, strict a >= b rejection,
+// in-order sums, one-byte bin ids, 16-bit histogram cells, MI from the 2^-44 k ln k table, the reference's own floating-point
+// expression for in-band tables under REF_ABORT (evaluated in place), three exps multiplied.  The layout (DESIGN.md section
+// 11): every column count is a loop bound and the LDS carve-up comes from the host; the x and x*x chains of column c sit on
+// lane c of waves 0 and 1; stage 4 runs its column loop outermost, so no per-thread array is indexed by a run-time column;
+// stage 1b always runs its own 3-sigma test (PassParams::masks is not read); member list and bin ids live in LDS when
+// generic_carve says they fit, else in one HBM slot per workgroup.
 #include "rpf_device_common.h"
 
 #ifndef RPF_GENERIC_OWN
@@ -88,6 +92,7 @@ namespace {
 struct Scratch {
     uint32_t *list; // [slots][nmax]        member list (plane offsets), reference order (spilled mode)
     uint8_t *bins;  // [slots][ndim][nmax]  bin ids
+    const uint32_t *count_dev; // the size of p.pix_list lives in device memory (redo list: no host read-back), else null
 };
 
 template <class T>
@@ -148,7 +153,8 @@ __global__ __launch_bounds__(256) void pixel_stats_kernel(PassParams p, uint64_t
     }
 }
 
-// One workgroup filters one pixel at a time and walks the pixels of rows [row_begin, row_end).
+// One workgroup filters one pixel at a time and walks the pixels of rows [row_begin, row_end) or, when p.pix_list is given,
+// the entries of that list (*gs.count_dev of them when that is given, else p.list_count).
 template <class T>
 __global__ __launch_bounds__(256) void filter_pixel_kernel(PassParams p, GenericCarve cv, Scratch gs) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -173,9 +179,10 @@ __global__ __launch_bounds__(256) void filter_pixel_kernel(PassParams p, Generic
     uint8_t *bins = cv.resident ? smem + cv.off_bins : gs.bins + (uint64_t)blockIdx.x * ndim * p.nmax;
     const double e_eps = (p.policy == RPF_DEGEN_EPS) ? p.eps : 0.0;
 
-    const uint32_t npix = (uint32_t)(p.row_end - p.row_begin) * (uint32_t)W;
+    const uint32_t npix = p.pix_list == nullptr ? (uint32_t)(p.row_end - p.row_begin) * (uint32_t)W
+                                                : (gs.count_dev != nullptr ? *gs.count_dev : p.list_count);
     for (uint32_t e = blockIdx.x; e < npix; e += gridDim.x) {
-        const uint64_t pix = (uint64_t)p.row_begin * W + e;
+        const uint64_t pix = p.pix_list == nullptr ? (uint64_t)p.row_begin * W + e : (uint64_t)p.pix_list[e];
         const int y = (int)(pix / (uint32_t)W), x = (int)(pix - (uint64_t)y * W);
         __syncthreads(); // the previous pixel's LDS is dead
 
@@ -522,8 +529,8 @@ __global__ __launch_bounds__(256) void filter_pixel_kernel(PassParams p, Generic
                         sw[ii] += w; s0[ii] += w * cj[0]; s1[ii] += w * cj[1]; s2[ii] += w * cj[2];   // rpf.cpp:691-692
                     }
                 }
-                // the four sums of an own sample are reduced in the pairing of a halving tree over the 256 threads (what
-                // filter_pixel_big_kernel's reduction adds: v[t] + v[t + 128], + 64 across the waves, then 32 ... 1 inside wave 0)
+                // the four sums of an own sample are reduced in the pairing of a halving tree over the 256 threads:
+                // v[t] + v[t + 128], + 64 across the waves, then 32 ... 1 inside wave 0
 #pragma unroll
                 for (int ii = 0; ii < kOwn; ++ii) {
                     __syncthreads();
@@ -579,17 +586,17 @@ hipError_t launch_pixel_stats(const PassParams &p, uint64_t pix0, uint64_t pix1,
 }
 
 // list / bins: the HBM slots of the spilled mode ([slots][nmax] u32, [slots][ndim][nmax] u8), unused when the carve-up is
-// resident; the grid never exceeds `slots`
-hipError_t launch_filter(const PassParams &p, void *list, void *bins, uint32_t slots, hipStream_t s) {
+// resident; the grid never exceeds `slots`: min(pixels, slots), or `slots` when the list size is on the device
+hipError_t launch_filter(const PassParams &p, void *list, void *bins, uint32_t slots, const uint32_t *count_dev, hipStream_t s) {
     const GenericCarve cv = generic_carve(p.lay, p.nmax);
     if ((int)cv.total > max_lds_per_block()) return hipErrorInvalidValue;
     if (p.row_end <= p.row_begin) return hipSuccess;
-    const uint64_t npix = (uint64_t)(p.row_end - p.row_begin) * p.W;
+    const uint64_t npix = p.pix_list == nullptr ? (uint64_t)(p.row_end - p.row_begin) * p.W : p.list_count;
     if (!cv.resident && (list == nullptr || bins == nullptr)) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned)std::min<uint64_t>(npix, slots);
+    const unsigned grid = p.pix_list != nullptr && count_dev != nullptr ? slots : (unsigned)std::min<uint64_t>(npix, slots);
     if (grid == 0) return hipSuccess;
     Scratch gs;
-    gs.list = (uint32_t *)list; gs.bins = (uint8_t *)bins;
+    gs.list = (uint32_t *)list; gs.bins = (uint8_t *)bins; gs.count_dev = count_dev;
     return p.lay.f16 ? launch_filter_t<__half>(p, cv, gs, grid, s) : launch_filter_t<float>(p, cv, gs, grid, s);
 }
 

@@ -68,7 +68,7 @@ struct PassParams {
     uint8_t *flat;         // [H*W], or null
     int32_t *nan_flag;     // [1]
     uint32_t *redo_list;   // REF_ABORT: pixels whose MI stage met a table inside the rounding band at a non-power-of-two N are
-    uint32_t *redo_count;  //   appended here and filtered again by filter_pixel_big_kernel (reference expression); or null
+    uint32_t *redo_count;  //   appended here and filtered again by generic::filter_pixel_kernel (reference expression); or null
     int32_t *status;       // [0] count of NaN pixels, [1] lowest bad pixel index (atomicMin)
     rpf_debug dbg;         // device pointers, any may be null
 };
@@ -122,10 +122,6 @@ hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, const 
 // probe[0] += how many of them have N <= 64 without being proven flat and probe[1] += how many are proven flat
 hipError_t launch_nbhd_count(const PassParams &p, int step, uint32_t *probe, const uint32_t *list, const uint32_t *list_count,
                              uint32_t list_max, hipStream_t s);
-// the streaming kernel (neighbourhoods of the last size class): global scratch of `slots` workgroups,
-// list [slots][nmax] u32 and bins [slots][ndim][nmax] u8
-// count_dev != null: the size of p.pix_list is read from device memory (redo mode: no host read-back), grid = slots
-hipError_t launch_filter_big(const PassParams &p, void *list, void *bins, uint32_t slots, const uint32_t *count_dev, hipStream_t s);
 // max_class < kNumClasses: pixels of that class and above join the list of rest_class (-1: they are left out)
 hipError_t launch_classify(const PassParams &p, uint32_t *lists /*[kNumClasses][H*W]*/, uint32_t *counts /*[kNumClasses], zeroed*/,
                            int max_class, int rest_class, hipStream_t s);
@@ -164,7 +160,7 @@ hipError_t launch_film_stage(const FilmParams &f, const float *planes, const dou
 hipError_t launch_film_splat(const FilmParams &f, const float *table, const float2 *d_stage, const float *lw_stage,
                              float *tile_rgb, float *tile_w, float *image_rgb, hipStream_t s);
 
-// ---- the layout-generic route (rpf_generic.hip): nR / nF are run-time values of p.lay --------------------------------
+// ---- the layout-generic kernels (rpf_generic.hip): nR / nF are run-time values of p.lay ------------------------------
 // LDS carve-up of its filter kernel, a host-side function of the layout and the neighbourhood capacity only (byte offsets
 // into the dynamic LDS block); resident: member list and bin ids live in LDS (off_list / off_bins), else in HBM slots
 struct GenericCarve {
@@ -174,9 +170,11 @@ struct GenericCarve {
 GenericCarve generic_carve(const SampleLayout &lay, int nmax);
 namespace generic {
 hipError_t launch_pixel_stats(const PassParams &p, uint64_t pix0, uint64_t pix1, hipStream_t s);
-// one launch filters rows [p.row_begin, p.row_end); list / bins: the streaming kernel's scratch layout with `slots` slots
-// (needed when the carve-up is not resident); the grid is min(pixels, slots)
-hipError_t launch_filter(const PassParams &p, void *list, void *bins, uint32_t slots, hipStream_t s);
+// the streaming kernel: one launch filters rows [p.row_begin, p.row_end), or the pixels of p.pix_list when that is given
+// (the last size class of the binned route; the redo list).  list / bins: global scratch of `slots` workgroups, [slots][nmax]
+// u32 and [slots][ndim][nmax] u8 (needed when the carve-up is not resident); the grid is min(pixels, slots).
+// count_dev != null: the size of p.pix_list is read from device memory (redo list: no host read-back), grid = slots
+hipError_t launch_filter(const PassParams &p, void *list, void *bins, uint32_t slots, const uint32_t *count_dev, hipStream_t s);
 } // namespace generic
 
 int max_lds_per_block();

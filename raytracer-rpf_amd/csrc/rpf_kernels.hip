@@ -240,7 +240,6 @@ __global__ __launch_bounds__(256) void nbhd_reduce_kernel(const int32_t *nbhd, u
     hipError_t impl_filter_large(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
     hipError_t impl_pixel_stats(const PassParams &p, uint64_t pix0, uint64_t pix1, hipStream_t s);                        \
     hipError_t impl_nbhd_count(const PassParams &p, int step, uint32_t *probe, const uint32_t *list, const uint32_t *list_count, uint32_t list_max, hipStream_t s); \
-    hipError_t impl_filter_big(const PassParams &p, void *list, void *bins, uint32_t slots, const uint32_t *count_dev, hipStream_t s); \
     hipError_t impl_filter_packed(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s);    \
     }
 RPF_DECLARE_IMPL(d19) // the reference's 19 dims (2 random parameters, 12 features), fp32 planes
@@ -445,11 +444,6 @@ hipError_t launch_nbhd_count(const PassParams &p, int step, uint32_t *probe, con
 hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s) {
     if (!p.lay.supported()) return hipErrorNotSupported;
     return p.lay.is_ref19() ? d19::impl_filter_packed(p, lanes_per_pixel, count_dev, s) : d27::impl_filter_packed(p, lanes_per_pixel, count_dev, s);
-}
-
-hipError_t launch_filter_big(const PassParams &p, void *list, void *bins, uint32_t slots, const uint32_t *count_dev, hipStream_t s) {
-    if (!p.lay.supported() || p.pix_list == nullptr) return hipErrorInvalidValue;
-    return p.lay.is_ref19() ? d19::impl_filter_big(p, list, bins, slots, count_dev, s) : d27::impl_filter_big(p, list, bins, slots, count_dev, s);
 }
 
 hipError_t launch_classify(const PassParams &p, uint32_t *lists, uint32_t *counts, int max_class, int rest_class, hipStream_t s) {

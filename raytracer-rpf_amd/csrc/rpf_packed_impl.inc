@@ -612,7 +612,7 @@ __global__ __launch_bounds__(64 * kPkWaves, kRef19 ? 2 : 1) void filter_packed_k
             }
         }
     }
-    // status: one report per pixel; a pixel on the redo list reports nothing (filter_pixel_big_kernel owns it)
+    // status: one report per pixel; a pixel on the redo list reports nothing (generic::filter_pixel_kernel owns it)
     const unsigned long long badm = __ballot(bad);
     if (t == 0 && gvalid) {
         const unsigned long long gm = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << (g * G);

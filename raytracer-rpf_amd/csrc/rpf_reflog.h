@@ -4,7 +4,7 @@
 // sums pXY * log(pXY / (pX * pY)) over quotients that are 1.0 up to the rounding of three divisions and a product.  With N
 // a power of two every quotient is exactly 1 and the sum is an exact 0; otherwise some quotients are 1 +- a few ulp and
 // the sum is pure rounding residue (+-1e-16), which rpf.cpp:465/470 then divide by each other.  Under RPF_DEGEN_REF_ABORT
-// the device reproduces that residue term by term (filter_pixel_big_kernel, "reference expression"), which needs
+// the device reproduces that residue term by term (generic::filter_pixel_kernel, "reference expression"), which needs
 // log(1 +- k ulp) to come out as glibc's does on the host.  glibc (>= 2.28, sysdeps/ieee754/dbl-64/e_log.c) handles
 // 1 - 2^-4 < x < 1 + 0x1.09p-4 with one polynomial in r = x - 1 whose leading terms r - r*r/2 are formed with an exact
 // hi/lo split; the statement sequence below restates that published algorithm in plain IEEE operations (no contraction:

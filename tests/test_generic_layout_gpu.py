@@ -1,7 +1,8 @@
 """GPU tests of the layout-generic route (RPF_FLAG_GENERIC, rpf_query_route 3): any (n_random, n_feat, plane type) against
 the oracle, stage by stage; the two compiled layouts on the generic kernels against their fused routes and against the
 compiled reference's fixtures; the reference's rounding residue evaluated in place; non-finite inputs; every entry point
-that reaches the pass loop; the refusals.  No tolerance is new: check_pass's bars, or bit equality."""
+that reaches the pass loop; the refusals; and the same filter kernel behind the compiled routes, where it walks a pixel
+list (the streaming size class, the REF_ABORT redo list).  No tolerance is new: check_pass's bars, or bit equality."""
 import numpy as np
 import pytest
 
@@ -94,15 +95,16 @@ def test_every_stage_vs_oracle(ctx, hipmod, oracle, lay, name):
 
 
 # ---- 2. neighbourhoods beyond LDS residency ---------------------------------------------------------------------------
+SHAPES["BOX17"] = (22, 19, 16, 17, SMOOTH, EPS, 0.0)        # N up to 4624: member list and bin ids in the HBM slots
+
+
 @pytest.mark.parametrize("lay,seed", [((3, 7, "f32"), 19), ((2, 12, "f32"), 29)], ids=["3-7-f32", "19dim-seed29"])
 def test_neighbourhoods_beyond_lds_residency(ctx, hipmod, oracle, lay, seed):
     """box 17 at 16 spp: N above 3136, member list and bin ids in the HBM slots"""
-    W, H, S, box = 22, 19, 16, 17
-    planes, p32 = buffers(lay, W, H, S, seed=seed, sigma_f=0.05, sigma_c=1e-4, mode="smooth")
-    want = oracle.filter_pass(p32, oracle.make_desc(W, H, S, box=box, policy=EPS, n_random=lay[0], n_feat=lay[1]))
+    planes, _, want = shape_case(oracle, lay, "BOX17", seed=seed)
     assert want["nbhd_size"].max() > 3136
-    got = ctx.filter_pass_debug(planes, hip_desc(hipmod, lay, W, H, S, policy=EPS), box=box)
-    assert ctx.route() == 3
+    got = run_debug(ctx, hipmod, lay, "BOX17", planes)
+    assert got["route"] == 3
     check_pass(got, want)
 
 
@@ -155,22 +157,32 @@ def test_generic_filter_against_reference_every_case_and_box_list(ctx, hipmod, f
 
 
 # ---- 5. the reference's rounding residue -------------------------------------------------------------------------------------
+def independent_frame(oracle, lay, W, H, S):
+    """the frame of test_independent_tables_in_every_size_class_ref_abort for any layout: every feature of every pixel is a
+    permutation of the same S values (all neighbours pass the 3-sigma test: windows are unions of whole pixels), r0 and f0
+    carry the exactly independent pair of columns.  Returns the stored planes, their fp32 image and the pair's index."""
+    nr, nf, dt = lay
+    rng = np.random.default_rng(17)
+    planes = rng.permuted(np.broadcast_to(np.linspace(0.4, 0.6, S), (5 + nr + nf, H, W, S)), axis=3).astype(np.float32)
+    planes[0] = (np.arange(W)[None, :, None] + rng.random((H, W, S))).astype(np.float32)
+    planes[1] = (np.arange(H)[:, None, None] + rng.random((H, W, S))).astype(np.float32)
+    a, b = _independent_columns(S, 3)
+    planes[5], planes[5 + nr] = a.astype(np.float32), b.astype(np.float32)   # r0, f0: the same pattern in every pixel
+    if dt == "f16":
+        planes = planes.astype(np.float16)
+    pa, pb = oracle.pair_table(nr, nf)
+    indep = [i for i in range(len(pa)) if (pa[i], pb[i]) == (5 + nr, 5)]
+    assert len(indep) == 1
+    return planes, planes.astype(np.float32), indep
+
+
 @pytest.mark.parametrize("lay", [(3, 7, "f32"), (2, 12, "f32")], ids=lay_ids)
 def test_rounding_residue_in_place_ref_abort(ctx, hipmod, oracle, lay):
     """the construction of test_independent_tables_in_every_size_class_ref_abort: every pixel's (f0, r0) table is exactly
     independent at a non-power-of-two N; the generic kernel evaluates mi.cpp:66-86 in place (no redo list)"""
     nr, nf, _ = lay
-    nd = 5 + nr + nf
     W, H, S, box = 11, 11, 15, 9
-    rng = np.random.default_rng(17)
-    planes = rng.permuted(np.broadcast_to(np.linspace(0.4, 0.6, S), (nd, H, W, S)), axis=3).astype(np.float32)
-    planes[0] = (np.arange(W)[None, :, None] + rng.random((H, W, S))).astype(np.float32)
-    planes[1] = (np.arange(H)[:, None, None] + rng.random((H, W, S))).astype(np.float32)
-    a, b = _independent_columns(S, 3)
-    planes[5], planes[5 + nr] = a.astype(np.float32), b.astype(np.float32)   # r0, f0: the same pattern in every pixel
-    pa, pb = oracle.pair_table(nr, nf)
-    indep = [i for i in range(len(pa)) if (pa[i], pb[i]) == (5 + nr, 5)]
-    assert len(indep) == 1
+    planes, _, indep = independent_frame(oracle, lay, W, H, S)
     ref = oracle.filter_pass(planes, oracle.make_desc(W, H, S, box=box, n_random=nr, n_feat=nf))
     got = ctx.filter_pass_debug(planes, hip_desc(hipmod, lay, W, H, S), box=box, allow_nonfinite=True)
     assert ctx.route() == 3
@@ -327,4 +339,53 @@ def test_seeded_sweep(ctx, hipmod, oracle, case):
     assert np.isfinite(want["colour"]).all()       # a non-finite oracle colour here is a failure, not a skip
     got = ctx.filter_pass_debug(planes, hip_desc(hipmod, lay, W, H, S, policy=pol, beta_map=bm), box=box)
     assert ctx.route() == 3
+    check_pass(got, want)
+
+
+# ---- 10. the same kernel behind the compiled routes: a pixel list instead of the rows --------------------------------------
+COMPILED = [(2, 12, "f32"), (4, 18, "f16")]
+
+
+@pytest.mark.parametrize("lay", COMPILED, ids=lay_ids)
+def test_streaming_class_walks_its_list_next_to_resident_classes(ctx, hipmod, oracle, lay):
+    """box 17 at 16 spp without the flag: the size-binned route gives the pixels with N > 3136 to the streaming kernel as a
+    list, the others to the resident kernels.  With the flag the same kernel walks the rows: on the listed pixels every
+    output is the same bits."""
+    planes, _, want = shape_case(oracle, lay, "BOX17", seed=29)
+    binned = run_debug(ctx, hipmod, lay, "BOX17", planes, generic=False)
+    rows = run_debug(ctx, hipmod, lay, "BOX17", planes, generic=True)
+    assert binned["route"] == 2 and rows["route"] == 3
+    big = want["nbhd_size"] > 3136
+    assert big.any() and not big.all()
+    for k in ("nbhd_size", "member_hash", "bin_hash", "mean", "stddev", "mi", "alpha", "beta", "wrc"):
+        assert binned[k][big].tobytes() == rows[k][big].tobytes(), k
+    assert binned["colour"][:, big].tobytes() == rows["colour"][:, big].tobytes()
+    check_pass(binned, want)
+
+
+@pytest.mark.parametrize("lay", COMPILED, ids=lay_ids)
+def test_redo_list_longer_than_its_grid(ctx, hipmod, oracle, lay):
+    """REF_ABORT on a 16x12 frame whose every pixel joins the redo list: 192 entries for the 128 workgroups of the redo
+    launch (list size read on the device, entries e, e + grid, ...; nmax = 1215: member list and bin ids in LDS)"""
+    nr, nf, _ = lay
+    W, H, S, box = 16, 12, 15, 9
+    planes, p32, indep = independent_frame(oracle, lay, W, H, S)
+    ref = oracle.filter_pass(p32, oracle.make_desc(W, H, S, box=box, n_random=nr, n_feat=nf))
+    got = ctx.filter_pass_debug(planes, hip_desc(hipmod, lay, W, H, S, generic=False), box=box, allow_nonfinite=True)
+    assert ctx.route() == 2
+    assert ctx.counters().redo_pixels > 128
+    ri = ref["mi"][..., indep]
+    assert (np.abs(ri) < 1e-14).all() and (ri != 0).sum() > 20                        # residue, not zeros
+    _assert_ref_abort_parity(got, ref, hipmod, indep)
+
+
+def test_empty_redo_list_writes_nothing(ctx, hipmod, oracle):
+    """REF_ABORT on a plain smooth buffer: no pixel joins the redo list, and the redo launch (a fixed grid that reads a
+    count of zero on the device) leaves the resident kernels' results alone"""
+    W, H, S = 12, 10, 8
+    planes = fb.synth_planes(W, H, S, seed=19, sigma_f=0.05, sigma_c=1e-4, mode="smooth")
+    want = oracle.filter_pass(planes, oracle.make_desc(W, H, S, box=7))
+    assert want["status"] == 0
+    got = ctx.filter_pass_debug(planes, hipmod.make_desc(W, H, S), box=7)
+    assert ctx.route() != 3 and ctx.counters().redo_pixels == 0 and got["status"] == hipmod.OK
     check_pass(got, want)

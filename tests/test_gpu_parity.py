@@ -186,7 +186,7 @@ def test_exactly_independent_table_at_non_power_of_two_n(ctx, hipmod, oracle, S,
     independent (J_ij * N == hx_i * hy_j).  For N a power of two mi.cpp returns an exact 0 for such a table; otherwise its
     quotients pXY / (pX * pY) round to 1 +- 2.2e-16 and it returns rounding residue, which rpf.cpp:465/470 then divide by
     each other.  REF_ABORT promises the reference's value: the resident kernel hands such a pixel to
-    filter_pixel_big_kernel, which evaluates mi.cpp:66-86 term by term (round 2 returned 0 here and recorded the
+    generic::filter_pixel_kernel, which evaluates mi.cpp:66-86 term by term (round 2 returned 0 here and recorded the
     deviation).  EPS: both sides return exactly 0 (the residue contract).  S = 24 takes the size-binned route."""
     W, H = 1, 1
     assert int(np.sqrt(S)) == bins
@@ -838,7 +838,7 @@ def test_multi_context_errors_and_nonfinite_pixel(hipmod, oracle):
 ])
 def test_large_boxes_vs_oracle(ctx, hipmod, oracle, W, H, S, box, mode, sf, sc):
     """the reference's commented box list {55, 35, 17, 7} (rpf.cpp:767): neighbourhoods beyond 3136 samples stream
-    their member list and bin ids through global scratch (filter_pixel_big_kernel); pixels of the same pass whose N is
+    their member list and bin ids through global scratch (generic::filter_pixel_kernel); pixels of the same pass whose N is
     small still run the LDS-resident kernels.  Every stage output against the oracle."""
     planes = fb.synth_planes(W, H, S, seed=29, sigma_f=sf, sigma_c=sc, mode=mode)
     got = ctx.filter_pass_debug(planes, hipmod.make_desc(W, H, S, policy=hipmod.DEGEN_EPS), box=box)
