@@ -1,0 +1,105 @@
+"""Frames whose neighbourhood sizes are PLANTED: plant() builds a feature buffer in which chosen pixels have exactly the
+neighbourhood size N asked for, so a test can put N on either side of every kernel-class edge (class_capacity 8, 16, 32, 64,
+128, 256, 448, 832, 1600, 3136 | streaming) instead of taking whatever the 3-sigma test yields on a synthetic frame.
+
+A plain helper module (like pbrt_film_ref.py): tests/test_planted_nbhd_cpu.py checks the frames against the oracle on the
+CPU, tests/test_class_boundaries_gpu.py runs them through the kernels.
+
+How a size is planted.  The frame is one row of disjoint box x box windows, one per target; the target pixel is its window's
+centre, so its window is the whole of its own box and nobody else's.  Every column of every pixel starts as a permutation of
+the same S values: all pixels share mean and sigma (up to the rounding of a sum taken in another order), and every sample
+passes every pixel's 3-sigma test -- N would be box * box * S everywhere.  Then, per window, as many candidates as must go are
+pushed 10 away on ONE feature each: such a sample fails the target's test on that feature and on no other.  The target's
+own samples are never touched, so its statistics stay and it keeps exactly the N asked for; the members lie scattered over
+the window and interleave with rejected candidates in the reference's visiting order.  The window's other pixels, some of
+whose own samples were pushed, get wide sigmas on some features and assorted N: they are compared like every pixel.
+"""
+import numpy as np
+
+# class_capacity of csrc/rpf_kernels.hip: the largest N of each size class (beyond the last one: the streaming kernel)
+CAPACITIES = (8, 16, 32, 64, 128, 256, 448, 832, 1600, 3136)
+PACKED_PIXELS_PER_WAVE = {8: 8, 16: 4, 32: 2}   # packed class capacity -> pixels per wavefront (64: one)
+
+# id: layout (n_random, n_feat, plane type), S, box, planted N per target, seed, size-binned route?
+# (the closing 24 of U8 and H8 makes the pixel count of the packed class N <= 32 odd -- 17, 24, 32 -- so that its last wave,
+# two pixels wide, runs half empty: test_planted_nbhd_cpu.py holds the counts of the three shared-wave classes to that)
+FRAMES = {
+    "U8": ((2, 12, "f32"), 8, 7, (8, 9, 16, 17, 32, 33, 64, 65, 24), 0, False),
+    "U2": ((2, 12, "f32"), 2, 7, (2, 8, 9, 16, 17, 98), 0, False),
+    "U3": ((2, 12, "f32"), 3, 13, (3, 8, 9, 64, 65, 448, 449, 507), 0, False),                  # the unbinned K = 13 kernel
+    "U12": ((2, 12, "f32"), 12, 5, (12, 16, 17, 256, 257, 300), 0, False),                      # the unbinned K = 7 kernel
+    "B16": ((2, 12, "f32"), 16, 7, (16, 17, 32, 33, 64, 65, 128, 129, 256, 257, 448, 449, 784), 0, True),
+    "B32": ((2, 12, "f32"), 32, 7, (832, 833, 1568), 0, True),                                  # four-wave / split K = 25
+    "B64": ((2, 12, "f32"), 64, 7, (1600, 1601, 3135, 3136), 0, True),                          # K = 25 | K = 49
+    "B40": ((2, 12, "f32"), 40, 9, (3136, 3137, 3240), 0, True),                                # resident | streaming
+    "B17": ((2, 12, "f32"), 16, 17, (832, 833, 1600, 1601, 3136, 3137), 0, True),               # window > 4096: one-wave K = 25 / 49
+    "H8": ((4, 18, "f16"), 8, 7, (8, 9, 16, 17, 32, 33, 64, 65, 128, 129, 256, 257, 392, 24), 0, False),
+    "H16": ((4, 18, "f16"), 16, 7, (448, 449, 784), 0, True),
+    "H64": ((4, 18, "f16"), 64, 7, (1600, 1601, 3136), 0, True),
+}
+
+
+def plant(S, box, targets, n_random=2, n_feat=12, seed=0):
+    """float32 planes [5 + n_random + n_feat, box, box * len(targets), S] and the target pixels [(y, x), ...]: pixel
+    targets[t]'s neighbourhood under a box x box window holds exactly targets[t] samples (S <= targets[t] <= box * box * S)."""
+    if S < 2:
+        raise ValueError("S >= 2: one sample per pixel has sigma = 0 and accepts nobody")
+    nt, b = len(targets), (box - 1) // 2
+    H, W, ndim, f0 = box, box * nt, 5 + n_random + n_feat, 5 + n_random
+    rng = np.random.default_rng(seed)
+    planes = rng.permuted(np.broadcast_to(np.linspace(0.4, 0.6, S), (ndim, H, W, S)), axis=3).astype(np.float32)
+    planes[0] = (np.arange(W)[None, :, None] + rng.random((H, W, S))).astype(np.float32)
+    planes[1] = (np.arange(H)[:, None, None] + rng.random((H, W, S))).astype(np.float32)
+    planes[2:5] = rng.random((3, H, W, S)).astype(np.float32)
+    pixels = []
+    for t, n in enumerate(targets):
+        ty, tx = b, t * box + b
+        pixels.append((ty, tx))
+        cand = [(y, x, s) for y in range(box) for x in range(t * box, (t + 1) * box) for s in range(S) if (y, x) != (ty, tx)]
+        n_reject = len(cand) - (n - S)
+        if not 0 <= n_reject <= len(cand):
+            raise ValueError("target %d: N = %d outside [S, box * box * S] = [%d, %d]" % (t, n, S, box * box * S))
+        chosen = rng.permutation(len(cand))[:n_reject]
+        feats = rng.integers(0, n_feat, n_reject)
+        for i, (ci, k) in enumerate(zip(chosen, feats)):
+            y, x, s = cand[ci]
+            planes[f0 + k, y, x, s] += np.float32(10.0 if i % 2 == 0 else -10.0)
+    return planes, pixels
+
+
+_cache = {}
+
+
+def frame(fid):
+    """(stored planes, their fp32 image for the oracle, target pixels, planted sizes) of FRAMES[fid]; built once, read-only.
+    An f16 layout is rounded once: the device reads the halves, the oracle the same halves widened."""
+    if fid not in _cache:
+        (nr, nf, dt), S, box, targets, seed, _ = FRAMES[fid]
+        p32, pixels = plant(S, box, targets, n_random=nr, n_feat=nf, seed=seed)
+        stored = p32.astype(np.float16) if dt == "f16" else p32
+        p32 = stored.astype(np.float32)
+        stored.setflags(write=False)
+        p32.setflags(write=False)
+        _cache[fid] = (stored, p32, pixels, targets)
+    return _cache[fid]
+
+
+# The colours of a planted frame are white noise and its features spread evenly, so at the reference's sigma seed (0.002:
+# sigma_c^2 = sigma_f^2 ~ 1e-5 in z-space) every weight but a sample's own underflows and the filter is the IDENTITY: the
+# discrete outputs, MI, alpha, beta and W_r_c are compared for real, the colours only show that nothing was broken.  With
+# this seed the weights are of order one (the oracle moves the colours by 6 ... 40 %), and a member dropped from, or a stale
+# slot added to, a weight sum shows in the colours.
+ACTIVE_SIGMA_SEED = 0.5
+
+_want = {}
+
+
+def oracle_pass(oracle, fid, policy, sigma_seed=0.002):
+    """the oracle's filter pass of a frame under a policy: computed once per session, shared, never modified"""
+    if (fid, policy, sigma_seed) not in _want:
+        (nr, nf, _), S, box, targets, _, _ = FRAMES[fid]
+        _, p32, _, _ = frame(fid)
+        lay = dict(n_random=nr, n_feat=nf) if (nr, nf) != (2, 12) else {}
+        _want[fid, policy, sigma_seed] = oracle.filter_pass(p32, oracle.make_desc(box * len(targets), box, S, box=box, policy=policy,
+                                                                                  sigma_seed=sigma_seed, **lay))
+    return _want[fid, policy, sigma_seed]
