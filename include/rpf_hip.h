@@ -75,7 +75,13 @@ enum {
     RPF_FLAG_FAST_WEIGHTS = 2, /* opt-in: the S x N pair weights of stage 4 (rpf.cpp:637-678) are evaluated in fp32 on
                                   fp64-formed normalised values, with the hardware exp; everything that decides
                                   discrete outcomes (membership, bins, MI) is unchanged.  Colours move by ~1e-6
-                                  relative (bar 1e-4).  Default off: fp64 throughout, like the reference. */
+                                  relative (bar 1e-4).  Default off: fp64 throughout, like the reference.
+                                  Two kinds of pixel are filtered in fp64 under the flag as well: a neighbourhood above 3136
+                                  samples (the streaming kernel), and, under RPF_DEGEN_REF_ABORT, a pixel on the redo list
+                                  (rpf_counters.redo_pixels), which the reference-expression kernel filters whole.
+                                  The fp32 kernels exist for the reference's 19-dim layout (n_random = 2, n_feat = 12,
+                                  fp32 planes) only: with any other layout the flag is RPF_E_UNSUPPORTED, from every
+                                  filter entry point and from rpf_layout_kernels, before any device work. */
     RPF_FLAG_NO_OVERLAP = 4,   /* rpf_filter(): upload, filter and download one after the other instead of the
                                   row-band pipeline (same results; for A/B timing).  RPF_FLAG_TIMING implies it. */
     RPF_FLAG_GENERIC = 8       /* opt-in: run this call on the layout-generic kernels, which take n_random / n_feat as run-time
@@ -292,7 +298,8 @@ int32_t rpf_multi_halo_plan(int32_t H, int32_t n_slabs, int32_t depth, int32_t *
 
 /* Which kernels the filter entry points will run for the layout and flags of desc, and whether they take it at all: RPF_OK
  * with *generic_out = 0 (the compiled, fused kernels) or 1 (the layout-generic kernels); RPF_E_UNSUPPORTED where every filter
- * entry point refuses the layout / flag combination (same function, so the two cannot drift); RPF_E_BADARG for a NULL desc.
+ * entry point refuses the layout / flag combination (same function, so the two cannot drift) -- a layout without kernels,
+ * RPF_FLAG_FAST_WEIGHTS on a layout other than the reference's 19 dims, or together with RPF_FLAG_GENERIC; RPF_E_BADARG for a NULL desc.
  * Only n_random, n_feat, plane_dtype and flags are read.  Needs no context and no device.  generic_out may be NULL. */
 int32_t rpf_layout_kernels(const rpf_desc *desc, int32_t *generic_out);
 

@@ -54,6 +54,10 @@ int32_t layout_kernels(const rpf_desc *d, int32_t *generic_out, std::string *why
     } else if (!lay.supported()) {
         msg = "sample layout: kernels exist for n_random=2, n_feat=12, fp32 planes (the reference's 19 dims) and n_random=4, "
               "n_feat=18, fp16 planes (27 dims); any other layout needs RPF_FLAG_GENERIC (the layout-generic kernels)";
+    } else if ((d->flags & RPF_FLAG_FAST_WEIGHTS) && !lay.is_ref19()) {
+        // (launch_filter_w, rpf_filter_impl.inc: the FAST instantiations are built for the reference layout alone)
+        msg = "RPF_FLAG_FAST_WEIGHTS: the fp32 pair-weight kernels exist for n_random=2, n_feat=12, fp32 planes (the reference's "
+              "19 dims) only";
     }
     if (msg) {
         if (why) *why = msg;
@@ -420,11 +424,17 @@ int32_t launch_filter_binned(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s
     if (p_in.generic) return route_generic(ctx, p_in, s, launches);
     PassParams p = p_in;
     p.redo_list = nullptr; p.redo_count = nullptr;
-    if (p.policy == RPF_DEGEN_REF_ABORT && !p.fast_weights && ctx->tun.stage_mask == -1) {
-        int32_t e;
-        if ((e = ctx->d_redo_list.ensure(ctx, (size_t)p.W * p.H * sizeof(uint32_t)))) return e;
+    if (p.policy == RPF_DEGEN_REF_ABORT) {
+        // finish_counters reads the count back after every REF_ABORT call: cleared whether or not this pass keeps a list
         HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
-        p.redo_list = ctx->d_redo_list; p.redo_count = ctx->d_redo_count;
+        // RPF_FLAG_FAST_WEIGHTS keeps the list too: MI, alpha, beta and W_r_c are the reference's under the flag as well, and a
+        // redone pixel is filtered whole, in fp64, by the reference-expression kernel (the FAST instantiations test
+        // p.redo_list at run time like the others, stage 3b)
+        if (ctx->tun.stage_mask == -1) {
+            int32_t e;
+            if ((e = ctx->d_redo_list.ensure(ctx, (size_t)p.W * p.H * sizeof(uint32_t)))) return e;
+            p.redo_list = ctx->d_redo_list; p.redo_count = ctx->d_redo_count;
+        }
     }
     bool bin = p.nmax > 512;
     if (ctx->tun.binning >= 0) bin = ctx->tun.binning != 0;

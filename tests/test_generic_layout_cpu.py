@@ -39,6 +39,9 @@ def test_flag_and_max_ndim_match_the_headers(hipmod):
     (dict(), "GF", ("E_UNSUPPORTED", None)),                                     # the generic kernels are fp64 throughout
     (dict(n_random=3, n_feat=7), "GF", ("E_UNSUPPORTED", None)),
     (dict(), "GT", ("OK", 1)),                                                   # the other flags do not matter
+    (dict(), "F", ("OK", 0)),                                                    # fp32 pair weights: the reference's 19 dims only
+    (dict(n_random=4, n_feat=18, plane_dtype=1), "F", ("E_UNSUPPORTED", None)),  # ... no 27-dim instantiation of them exists
+    (dict(n_random=4, n_feat=18, plane_dtype=1), "FT", ("E_UNSUPPORTED", None)),
 ])
 def test_layout_kernels_truth_table(hipmod, lay, flags, want):
     bits = {"G": hipmod.FLAG_GENERIC, "F": hipmod.FLAG_FAST_WEIGHTS, "T": hipmod.FLAG_TIMING}
