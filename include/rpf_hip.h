@@ -84,7 +84,7 @@ enum {
                                   filter entry point and from rpf_layout_kernels, before any device work. */
     RPF_FLAG_NO_OVERLAP = 4,   /* rpf_filter(): upload, filter and download one after the other instead of the
                                   row-band pipeline (same results; for A/B timing).  RPF_FLAG_TIMING implies it. */
-    RPF_FLAG_GENERIC = 8       /* opt-in: run this call on the layout-generic kernels, which take n_random / n_feat as run-time
+    RPF_FLAG_GENERIC = 8,      /* opt-in: run this call on the layout-generic kernels, which take n_random / n_feat as run-time
                                   values: n_random >= 1, n_feat >= 1, 5 + n_random + n_feat <= RPF_MAX_NDIM, fp32 or fp16
                                   planes, neighbourhoods up to 65535 samples.  REQUIRED for a layout without compiled kernels
                                   (without it such a descriptor stays RPF_E_UNSUPPORTED: the refusal also tells a caller that
@@ -92,6 +92,16 @@ enum {
                                   ALLOWED for the two compiled layouts, where it selects the generic kernels instead of the
                                   fused routes (A/B timing, parity).  fp64 throughout: together with RPF_FLAG_FAST_WEIGHTS
                                   it is RPF_E_UNSUPPORTED.  One filter launch per pass; rpf_query_route says 3. */
+    RPF_FLAG_GENERIC_PACKED = 16 /* opt-in, modifies RPF_FLAG_GENERIC: the pixels whose neighbourhood holds N <= 64 samples
+                                  (about 94 % of a path-traced buffer) run on the packed layout-generic kernels -- a pixel gets
+                                  8, 16, 32 or 64 lanes of a wavefront instead of a 256-thread workgroup -- behind a count
+                                  pass of their own; the other pixels stay on the generic filter kernel.  Same layouts as the
+                                  generic flag, the two compiled ones included.  Same membership, bins, statistics, MI, alpha,
+                                  beta and W_r_c as under the generic flag alone; the colours agree to rounding.
+                                  rpf_query_route says 4 (3 for a pass with S > 64, which no packed class can hold and which
+                                  runs exactly as without this flag).  Without RPF_FLAG_GENERIC, or together with
+                                  RPF_FLAG_FAST_WEIGHTS, it is RPF_E_UNSUPPORTED, from every filter entry point and from
+                                  rpf_layout_kernels, before any device work. */
 };
 
 typedef struct rpf_desc {
@@ -198,8 +208,8 @@ int32_t rpf_filter_ex(rpf_ctx *ctx, const rpf_desc *desc, const void *planes, co
  *                      decides per pass), 0 fused, 1 count first.  Same results bit for bit; rpf_query_route tells.
  *   "screen"           far-pair screen of the weight stage (four-wave kernels): 1 on (default), 0 off.  Both settings
  *                      give the same filtered colours bit for bit.
- * These names steer the fused routes only: a call with RPF_FLAG_GENERIC runs one kernel per pass whatever they say (they
- * are accepted and have no effect there; options_active still reports them).
+ * These names steer the fused routes only: a call with RPF_FLAG_GENERIC, with or without RPF_FLAG_GENERIC_PACKED, runs
+ * the same kernels whatever they say (they are accepted and have no effect there; options_active still reports them).
  * rpf_counters.options_active tells whether a result was produced under any override. */
 int32_t rpf_set_option(rpf_ctx *ctx, const char *name, int64_t value);
 
@@ -235,7 +245,11 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *desc, int32_t box, c
 
 /* counters of the most recent rpf_filter / rpf_filter_device / rpf_filter_pass_debug call */
 /* On the generic route (RPF_FLAG_GENERIC) filter_kernel_launches counts one launch per pass and redo_pixels is 0: that
- * kernel evaluates the reference's floating-point MI expression in place. */
+ * kernel evaluates the reference's floating-point MI expression in place.
+ * With RPF_FLAG_GENERIC_PACKED as well (route 4) filter_kernel_launches counts, per pass, one launch per non-empty packed
+ * class (N <= 8, 16, 32, 64), one for the generic filter kernel when some pixel has N > 64, and under RPF_DEGEN_REF_ABORT one
+ * for the redo launch; redo_pixels counts the pixels the packed kernels put on the redo list (the generic filter kernel then
+ * filters them whole, evaluating the reference's expression in place). */
 int32_t rpf_query_counters(rpf_ctx *ctx, rpf_counters *out);
 
 /* neighbourhood size N of every pixel (rpf.cpp:586: the neighbourhood vector's size) as the last pass of the most recent
@@ -247,7 +261,8 @@ int32_t rpf_query_nbhd(rpf_ctx *ctx, int32_t *nbhd_out, int64_t count);
  * 0 = fused (filter_pixel_kernel runs stage 1b itself), 1 = count first (stage 1b as its own launch, then the packed
  * small-neighbourhood kernels take most pixels: the route of path-traced buffers), 2 = size-binned
  * (box*box*S > 512), 3 = the layout-generic kernels (RPF_FLAG_GENERIC; several times slower, same membership, bins and
- * statistics), -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1. */
+ * statistics), 4 = the layout-generic kernels with small neighbourhoods packed (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED
+ * on a pass with S <= 64), -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1. */
 int32_t rpf_query_route(rpf_ctx *ctx, int32_t *route_out);
 
 /* visualizeSF (rpf.cpp:37-101, visualization/vis.cpp:34-51): the reference's six debug images, without the EXR
@@ -299,7 +314,8 @@ int32_t rpf_multi_halo_plan(int32_t H, int32_t n_slabs, int32_t depth, int32_t *
 /* Which kernels the filter entry points will run for the layout and flags of desc, and whether they take it at all: RPF_OK
  * with *generic_out = 0 (the compiled, fused kernels) or 1 (the layout-generic kernels); RPF_E_UNSUPPORTED where every filter
  * entry point refuses the layout / flag combination (same function, so the two cannot drift) -- a layout without kernels,
- * RPF_FLAG_FAST_WEIGHTS on a layout other than the reference's 19 dims, or together with RPF_FLAG_GENERIC; RPF_E_BADARG for a NULL desc.
+ * RPF_FLAG_FAST_WEIGHTS on a layout other than the reference's 19 dims, or together with RPF_FLAG_GENERIC;
+ * RPF_FLAG_GENERIC_PACKED without RPF_FLAG_GENERIC or with RPF_FLAG_FAST_WEIGHTS; RPF_E_BADARG for a NULL desc.
  * Only n_random, n_feat, plane_dtype and flags are read.  Needs no context and no device.  generic_out may be NULL. */
 int32_t rpf_layout_kernels(const rpf_desc *desc, int32_t *generic_out);
 

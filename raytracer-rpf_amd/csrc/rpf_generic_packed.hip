@@ -1,0 +1,512 @@
+// rpf_generic_packed.hip -- the layout-generic kernels of small neighbourhoods (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED,
+// rpf_query_route 4): n_random and n_feat are run-time values (PassParams::lay), the template parameters are the storage
+// type of the feature planes and the lanes a pixel gets.  Compiled with -ffp-contract=off like every kernel TU.
+//
+// nbhd_count_kernel: one wave per pixel applies stage 1b's 3-sigma test of generic::filter_pixel_kernel to the window's
+// candidates, 64 at a time, and leaves N and one acceptance mask per 64 candidates (bit q = candidate q in the reference's
+// visiting order, the numbering of the compiled count pass).
+//
+// filter_packed_kernel<T, G>: the algorithm of rpf_packed_impl.inc with every column count a loop bound.  A pixel of the
+// class list (N <= G) gets G = 8, 16, 32 or 64 lanes, a wave filters 64 / G list entries at a time, lane g * G + t owns the
+// t-th sample of group g's neighbourhood in the reference's order (slot t < S: own sample t; else the (t - S)-th set bit of
+// the pixel's acceptance masks).  No per-thread array is indexed by a run-time column: the sample
+// values stay staged in LDS as [group][column][slot] doubles for the whole unit, bin ids are LDS bytes and bit masks, and
+// the LDS carve-up comes from the host (generic_packed_carve).  After the table load the waves of a workgroup are
+// independent: one wave's LDS operations execute in order, so wsync() is all the hand-over between its lanes needs.
+//
+// The arithmetic is generic::filter_pixel_kernel's, statement by statement: in-order sums of x and x * x (one lane per
+// chain), sd == 0 -> z = 0, B = max(1, (int)sqrt(N)), bin ids by IEEE quotients, joint counts as popcount(mask_a[i] &
+// mask_b[j]) (the same integers as its 16-bit histogram cells), MI from the 2^-44 k ln k table with the same zero band,
+// the beta presets generalised by the stack rule of DESIGN.md section 11, three exps multiplied.  Every stage output up to
+// alpha / beta / W_r_c is the same bits as route 3's; the colours agree to rounding (the weight sums of stage 4 associate
+// differently).  Under
+// REF_ABORT a pixel with a table inside the zero band at a non-power-of-two N and non-degenerate marginals joins the redo
+// list (the rule of rpf_packed_impl.inc) and generic::filter_pixel_kernel filters it again, whole.
+#include "rpf_device_common.h"
+
+#include <algorithm>
+
+namespace rpf {
+
+GenericPackedCarve generic_packed_carve(const SampleLayout &lay) {
+    const uint32_t ndim = (uint32_t)lay.ndim(), npair = (uint32_t)lay.npair(), nF = (uint32_t)lay.nF;
+    auto up16 = [](uint32_t v) { return (v + 15u) & ~15u; };
+    GenericPackedCarve c{};
+    c.off_pairtab = up16(65u * 8u);                  // behind T[0 .. 64]
+    c.table_bytes = up16(c.off_pairtab + 2u * npair);
+    uint32_t o = 64u * ndim * 8u;                    // staged samples
+    c.off_stat = o; o += 8u * ndim * 5u * 8u;
+    c.off_mask = o; o += ndim * 16u * 8u;
+    c.off_hx = o; o += 8u * ndim * 8u;
+    c.off_bins = o; o += up16(64u * ndim);
+    c.off_mi = o; o += 8u * npair * 8u;
+    c.off_w = o; o += 8u * (2u * nF + 16u) * 8u;
+    c.off_flag = o; o += 8u * 4u;
+    c.wave_bytes = up16(o);
+    const uint32_t room = (uint32_t)max_lds_per_block() - c.table_bytes;
+    c.waves = std::max(1u, std::min(4u, room / c.wave_bytes));
+    c.total = c.table_bytes + c.waves * c.wave_bytes;
+    return c;
+}
+
+namespace generic {
+namespace {
+
+struct PkDims {
+    int nR, nF, ndim, nAnc, npairF, npairC, npair, nwt, colF;
+};
+__device__ __forceinline__ PkDims pk_dims(const SampleLayout &l) {
+    PkDims d;
+    d.nR = l.nR; d.nF = l.nF; d.ndim = 5 + l.nR + l.nF;
+    d.nAnc = l.nR + 2;                       // r.. and p.. anchors
+    d.npairF = l.nF * d.nAnc;                // pairs (f_i, r_l | p_l)          rpf.cpp:416-427
+    d.npairC = d.nAnc + l.nF;                // pairs of one colour channel     rpf.cpp:429-442
+    d.npair = d.npairF + 3 * d.npairC;
+    d.nwt = 5 + l.nF;                        // weighted columns of stage 4
+    d.colF = 5 + l.nR;
+    return d;
+}
+
+template <class T>
+__device__ __forceinline__ float pk_ldp(const PassParams &p, int col, uint32_t off) {
+    return (float)reinterpret_cast<const T *>(p.planes)[(uint64_t)col * p.plane_stride + off];
+}
+// value of column c of the sample at plane offset `off`: colours come from the fp64 colour planes
+template <class T>
+__device__ __forceinline__ double pk_load_col(const PassParams &p, int c, uint32_t off) {
+    if (c >= 2 && c < 5) return p.col_in[(uint64_t)(c - 2) * p.plane_stride + off];
+    return (double)pk_ldp<T>(p, c, off);
+}
+// columns of MI pair pr, in ComputeCFWeights call order (rpf.cpp:416-442 with the loop bounds generalised)
+__device__ __forceinline__ void pk_pair_cols(const PkDims &D, int pr, int &ca, int &cb) {
+    if (pr < D.npairF) {
+        const int i = pr / D.nAnc, l = pr - i * D.nAnc;
+        ca = D.colF + i;
+        cb = l < D.nR ? 5 + l : l - D.nR;
+    } else {
+        const int q = pr - D.npairF, c = q / D.npairC, l = q - c * D.npairC;
+        ca = 2 + c;
+        cb = l < D.nR ? 5 + l : (l < D.nAnc ? l - D.nR : D.colF + (l - D.nAnc));
+    }
+}
+
+// all-reduce over the G lanes of a group (G = 8: half a DPP row, 16: a row, 32: a row pair, 64: the wave); EXEC = all lanes
+template <int G>
+__device__ __forceinline__ double group_sum(double v) {
+    using Sum = xl::OpSum;
+    if constexpr (G == 64) return xl::allreduce<Sum>(v);
+    else if constexpr (G == 32) return xl::allreduce_row<Sum>(xl::exch16<Sum>(v, v));
+    else if constexpr (G == 16) return xl::allreduce_row<Sum>(v);
+    else {
+        v = v + xl::dpp<xl::kRowHalfMirror>(v);
+        return xl::allreduce_bits10<Sum>(v);
+    }
+}
+
+// One wave per pixel of rows [row_begin, row_end): the test of generic::filter_pixel_kernel stage 1b on 64 candidates at a
+// time (rpf.cpp:556-586); p.masks[pix][w] bit l = candidate 64 w + l passed, p.nbhd[pix] = S + the passes.
+template <class T>
+__global__ __launch_bounds__(256) void nbhd_count_kernel(PassParams p) {
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t npix = (uint32_t)(p.row_end - p.row_begin) * (uint32_t)p.W;
+    const uint32_t e = blockIdx.x * 4u + (uint32_t)wv;
+    if (e >= npix) return; // wave-uniform; the kernel has no barrier
+    const int W = p.W, H = p.H, S = p.S, b = p.b;
+    const uint64_t HW = (uint64_t)H * W;
+    const uint64_t pix = (uint64_t)p.row_begin * W + e;
+    const int y = (int)(pix / (uint32_t)W), x = (int)(pix - (uint64_t)y * W);
+    const int nF = p.lay.nF, colF = 5 + p.lay.nR;
+    const int x0 = max(x - b, 0), x1 = min(x + b, W - 1), y0 = max(y - b, 0), y1 = min(y + b, H - 1);
+    const int nyv = y1 - y0 + 1;
+    const int centre_rank = (x - x0) * nyv + (y - y0);
+    const int ncand = ((x1 - x0 + 1) * nyv - 1) * S;
+    uint64_t *pm = p.masks + pix * p.mask_stride;
+    int n = S;
+    for (int qb = 0; qb < ncand; qb += 64) {
+        const int qq = qb + lane;
+        bool pass = qq < ncand;
+        uint32_t off = 0u;
+        if (pass) {
+            int cell = qq / S;
+            const int s = qq - cell * S;
+            if (cell >= centre_rank) ++cell;              // rpf.cpp:565: skip the centre pixel
+            const int ix = cell / nyv, iy = cell - ix * nyv; // xn outer, yn inner ascending (rpf.cpp:562-563)
+            off = (uint32_t)(((uint64_t)(y0 + iy) * W + (x0 + ix)) * S + s);
+        }
+        // a rejected candidate stays rejected: the later features are read only while some lane still passes
+        for (int k = 0; k < nF; ++k) {
+            if (!__any(pass)) break;
+            const double m = p.pmean[(uint64_t)k * HW + pix];
+            const double lim = p.pstd[(uint64_t)k * HW + pix] * 3.0;  // multiplyArray(std, 3), rpf.cpp:579
+            if (pass) {
+                const double a = fabs((double)pk_ldp<T>(p, colF + k, off) - m);
+                if (a >= lim) pass = false;           // allLessThan: fails iff a >= b (ops.h:101-104): a NaN never rejects
+            }
+        }
+        const unsigned long long mask = __ballot(pass);
+        if (lane == 0) pm[qb >> 6] = mask;
+        n += __popcll(mask);
+    }
+    if (lane == 0) p.nbhd[pix] = n;
+}
+
+// One wave = one "unit" of 64 / G list entries at a time, units dealt to the waves of the grid with a grid stride.
+template <class T, int G>
+__global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, GenericPackedCarve cv) {
+    constexpr int P = 64 / G;                                   // pixels per wave
+    constexpr int BSTR = G == 8 ? 2 : (G == 16 ? 4 : 8);        // mask slots per (pixel, column): B = floor(sqrt(N)) <= 2, 4, 5, 8
+    constexpr int kOwn = 4;                                     // own samples per sweep of stage 4
+    static_assert(P * BSTR <= 16, "sixteen masks per column and wave");
+    extern __shared__ __align__(16) unsigned char smem[];
+    const PkDims D = pk_dims(p.lay);
+    const int ndim = D.ndim, nF = D.nF, nR = D.nR, nAnc = D.nAnc, npair = D.npair, nwt = D.nwt, colF = D.colF;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nthreads = (int)blockDim.x;
+    uint64_t *sT = reinterpret_cast<uint64_t *>(smem);
+    for (int k = tid; k <= 64; k += nthreads) sT[k] = p.tfix[min(k, p.nmax)];
+    uint16_t *sPairTab = reinterpret_cast<uint16_t *>(smem + cv.off_pairtab);
+    for (int pr = tid; pr < npair; pr += nthreads) {
+        int ca, cb;
+        pk_pair_cols(D, pr, ca, cb);
+        sPairTab[pr] = (uint16_t)(ca | (cb << 8));
+    }
+    __syncthreads(); // the only barrier: from here on the waves are independent
+    unsigned char *wb = smem + cv.table_bytes + (uint32_t)wv * cv.wave_bytes;
+    double *sU = reinterpret_cast<double *>(wb);                                        // [P][ndim][G]
+    double *sStat = reinterpret_cast<double *>(wb + cv.off_stat);                       // [P][ndim][5]
+    unsigned long long *sMask = reinterpret_cast<unsigned long long *>(wb + cv.off_mask); // [P][ndim][BSTR]
+    uint64_t *sHX = reinterpret_cast<uint64_t *>(wb + cv.off_hx);                       // [P][ndim]
+    uint8_t *sBin = wb + cv.off_bins;                                                   // [P][ndim][G]
+    double *sMI = reinterpret_cast<double *>(wb + cv.off_mi);                           // [P][npair]
+    double *sW = reinterpret_cast<double *>(wb + cv.off_w);                             // [P][2 nF + 16]
+    int *sFlag = reinterpret_cast<int *>(wb + cv.off_flag);                             // [P]
+
+    const int W = p.W, H = p.H, S = p.S, b = p.b;
+    const int g = lane / G, t = lane % G;
+    const double e_eps = (p.policy == RPF_DEGEN_EPS) ? p.eps : 0.0;
+    const uint32_t units = (p.list_count + (uint32_t)P - 1u) / (uint32_t)P;
+    const uint32_t nwaves = (uint32_t)nthreads >> 6;
+    for (uint32_t unit = blockIdx.x * nwaves + (uint32_t)wv; unit < units; unit += gridDim.x * nwaves) {
+        wsync(); // the previous unit's LDS is dead
+        const uint32_t e = unit * (uint32_t)P + (uint32_t)g;
+        const bool gvalid = e < p.list_count;             // (only the last unit can be short)
+        const uint32_t pixu = gvalid ? p.pix_list[e] : 0u;
+        const int n = gvalid ? min(p.nbhd[pixu], G) : 0;  // <= G by construction of the list
+        const uint64_t pix = pixu;
+        const bool live = t < n;
+        const int y = (int)(pixu / (uint32_t)W), x = (int)(pixu - (uint32_t)y * (uint32_t)W);
+        const int gbase = g * ndim;                       // first (pixel, column) record of the group
+
+        // ---- stage 1b: the lane's sample (rpf.cpp:556-586), rank select in the acceptance masks --------------------
+        const int x0 = max(x - b, 0), x1 = min(x + b, W - 1), y0 = max(y - b, 0), y1 = min(y + b, H - 1);
+        const int nyv = y1 - y0 + 1;
+        const int centre_rank = (x - x0) * nyv + (y - y0);
+        const int ncand = ((x1 - x0 + 1) * nyv - 1) * S;
+        uint32_t off = (uint32_t)(pix * S) + (uint32_t)min(t, S - 1); // own samples first
+        {
+            int rank = (live && t >= S) ? t - S : -1;        // the rank-th accepted candidate of the window
+            const int nwords = (ncand + 63) >> 6;
+            const uint64_t *pm = p.masks + pix * p.mask_stride;
+            for (int w = 0; __any(rank >= 0) && w < (int)p.mask_stride; ++w) {
+                unsigned long long m = (rank >= 0 && w < nwords) ? pm[w] : 0ull;
+                const int c = __popcll(m);
+                if (rank >= c) {
+                    rank -= c;
+                } else if (rank >= 0) {
+                    for (int k = 0; k < rank; ++k) m &= m - 1ull;  // drop the lower set bits
+                    const int qq = w * 64 + (__ffsll((long long)m) - 1);
+                    int cell = qq / S;
+                    const int s = qq - cell * S;
+                    if (cell >= centre_rank) ++cell;              // rpf.cpp:565: skip the centre pixel
+                    const int ix = cell / nyv, iy = cell - ix * nyv; // xn outer, yn inner ascending (rpf.cpp:562-563)
+                    off = (uint32_t)(((uint64_t)(y0 + iy) * W + (x0 + ix)) * S + s);
+                    rank = -1;
+                }
+            }
+        }
+        if (p.dbg.member_hash != nullptr) { // debug only: hash of the member list in order, by slot 0 of every group
+            uint32_t *sOffD = reinterpret_cast<uint32_t *>(sU);
+            sOffD[lane] = off;
+            wsync();
+            if (t == 0 && gvalid) {
+                uint32_t h = 2166136261u;
+                for (int j = 0; j < n; ++j) {
+                    const uint32_t o = sOffD[g * G + j];
+                    const uint32_t s = o % (uint32_t)S, pp = o / (uint32_t)S;
+                    const int yn = (int)(pp / (uint32_t)W), xn = (int)(pp % (uint32_t)W);
+                    h = fnv1a_u32(h, (uint32_t)(((xn - x + b) * p.box + (yn - y + b)) * S) + s);
+                }
+                p.dbg.member_hash[pix] = h;
+            }
+            wsync();
+        }
+
+        // ---- the lane's sample vector, staged [group][column][slot]; masks and flags cleared ------------------------
+        for (int c = 0; c < ndim; ++c) sU[(gbase + c) * G + t] = live ? pk_load_col<T>(p, c, off) : 0.0;
+        for (int k = lane; k < ndim * 16; k += 64) sMask[k] = 0ull;
+        if (lane < 8) sFlag[lane] = 0;
+        wsync();
+
+        // ---- stage 2: in-order sums over the neighbourhood (rpf.cpp:596-601): lane t walks columns t, t + G, ... of its
+        // group front to back, the column's minimum and maximum ride along; then the constants of the binning
+        // (sd.h:229-232, mi.cpp:47-50)
+        const double dn = (double)n;
+        for (int c = t; c < ndim; c += G) {
+            const double *src = sU + (gbase + c) * G;
+            double sum = 0.0, sq = 0.0, mn = INFINITY, mx = -INFINITY;
+            for (int j = 0; j < n; ++j) {
+                const double v = src[j];
+                sum = sum + v;                               // ops.h:121
+                sq = sq + v * v;                             // ops.h:138
+                mn = fmin(mn, v); mx = fmax(mx, v);
+            }
+            const double mean = sum / dn;                    // ops.h:123
+            double sd = sqrt(sq / dn - mean * mean);         // ops.h:141
+            if (p.policy == RPF_DEGEN_EPS && isnan(sd)) sd = 0.0;
+            const bool sd0 = (sd == 0.0);
+            const double lo = sd0 ? 0.0 : (mn - mean) / sd, hi = sd0 ? 0.0 : (mx - mean) / sd;
+            double *st = sStat + (gbase + c) * 5;
+            st[0] = mean; st[1] = sd; st[2] = lo; st[3] = hi - lo;
+            st[4] = (double)((sd0 ? 1 : 0) | (!(hi != lo) ? 2 : 0)); // mi.cpp:7 / 28 / 34
+            if (gvalid) {
+                if (p.dbg.mean) p.dbg.mean[pix * ndim + c] = mean;
+                if (p.dbg.stddev) p.dbg.stddev[pix * ndim + c] = sd;
+            }
+        }
+        wsync();
+
+        // ---- stage 3a: bin ids (a byte per sample and column); 3b: one bit mask per (pixel, column, bin value) -------
+        const int B = max(1, (int)sqrt(dn));                 // mi.cpp:54
+        for (int c = 0; c < ndim; ++c) {
+            const double *st = sStat + (gbase + c) * 5;
+            const double Mc = st[0], SDc = st[1], lo = st[2], range = st[3];
+            const int flags = (int)st[4];
+            const bool sd0 = flags & 1, flat = flags & 2;
+            int bin = 0;
+            if (!flat) {
+                const double a = sU[(gbase + c) * G + t] - Mc;               // subtractArrays
+                const double z = sd0 ? 0.0 : a / SDc;                        // divideArrays, ops.h:48
+                const double tt = (z - lo) / range * (double)B;              // mi.cpp:14
+                bin = max(min((int)tt, B - 1), 0);
+            }
+            if (live) {
+                sBin[(gbase + c) * G + t] = (uint8_t)bin;
+                atomicOr(&sMask[(gbase + c) * BSTR + bin], 1ull << t);
+            }
+        }
+        wsync();
+        if (p.dbg.bin_hash != nullptr && gvalid) { // debug only: hash per column in sample order
+            for (int c = t; c < ndim; c += G) {
+                uint32_t h = 2166136261u;
+                const uint8_t *bc = sBin + (gbase + c) * G;
+                for (int j = 0; j < n; ++j) h = fnv1a_u16(h, bc[j]);
+                p.dbg.bin_hash[pix * ndim + c] = h;
+            }
+        }
+        // marginals: sum_i T[hx_i] per column
+        for (int c = t; c < ndim; c += G) {
+            const unsigned long long *m = sMask + (gbase + c) * BSTR;
+            uint64_t acc = 0ull;
+            for (int v = 0; v < B; ++v) acc += sT[__popcll(m[v])];
+            sHX[gbase + c] = acc;
+        }
+        wsync();
+        // joint histograms: lane t takes the pairs t, t + G, ...; a cell's count is popcount(mask_a[i] & mask_b[j])
+        bool redo = false;
+        {
+            const int64_t TNf = (int64_t)sT[n];
+            const int64_t zero_band = ((int64_t)B * B + 2 * B + 1) / 2 + 1;   // see filter_pixel_kernel (rpf_filter_impl.inc)
+            for (int pr = t; pr < npair; pr += G) {
+                const uint32_t cc = sPairTab[pr];
+                const int ca = (int)(cc & 255u), cb = (int)(cc >> 8);
+                const unsigned long long *ma = sMask + (gbase + ca) * BSTR, *mb = sMask + (gbase + cb) * BSTR;
+                uint64_t acc = 0ull;
+                for (int i = 0; i < B; ++i) {
+                    const unsigned long long a = ma[i];
+                    for (int j = 0; j < B; ++j) acc += sT[__popcll(a & mb[j])];   // T[J_ij], mi.cpp:39 / 79-86 over integer counts
+                }
+                const int64_t hxa = (int64_t)sHX[gbase + ca], hxb = (int64_t)sHX[gbase + cb];
+                int64_t f = TNf + (int64_t)acc - hxa - hxb;
+                if (f <= zero_band && f >= -zero_band) {
+                    // REF_ABORT: the reference's own value for such a table is rounding residue unless its quotients are
+                    // exact (N a power of two, or a one-bin column): generic::filter_pixel_kernel evaluates it (redo list)
+                    if (p.redo_list != nullptr && (n & (n - 1)) != 0 && hxa != TNf && hxb != TNf) redo = true;
+                    f = 0;
+                }
+                const double mi = ldexp((double)f, -kTFixBits) / dn;
+                sMI[g * npair + pr] = mi;
+                if (p.dbg.mi && gvalid) p.dbg.mi[pix * npair + pr] = mi;
+            }
+        }
+        if (redo) sFlag[g] = 1;
+        wsync();
+
+        // ---- stage 3c: alpha, beta, W_r_c (rpf.cpp:444-487), the sums in filter_pixel_kernel's order of additions ------
+        double *sDrf = sW + g * (2 * nF + 16), *sD9 = sDrf + nF, *sAlpha = sD9 + 12, *sBeta = sAlpha + 4;
+        {
+            const double *mi = sMI + g * npair;
+            if (t < 3) { // colour channel t
+                const int base = D.npairF + t * D.npairC;
+                double Drc = 0.0, Dpc = 0.0, Dfc = 0.0;
+                for (int l = 0; l < nR; ++l) Drc += mi[base + l];                      // rpf.cpp:432
+                for (int l = 0; l < 2; ++l) Dpc += mi[base + nR + l];                  // rpf.cpp:436
+                for (int j = 0; j < nF; ++j) Dfc += mi[base + nAnc + j];               // rpf.cpp:440
+                sD9[t] = Drc; sD9[3 + t] = Dpc; sD9[6 + t] = Dfc;
+            }
+            for (int k = t; k < nF; k += G) {
+                double Drf = 0.0;
+                for (int l = 0; l < nR; ++l) Drf += mi[k * nAnc + l];                  // rpf.cpp:421
+                sDrf[k] = Drf;
+            }
+            wsync();
+            double D_f_c = 0.0, D_r_c = 0.0, D_p_c = 0.0;                              // rpf.cpp:449-456
+            for (int i = 0; i < 3; ++i) { D_f_c += sD9[6 + i]; D_r_c += sD9[i]; D_p_c += sD9[3 + i]; }
+            const double den = D_f_c + D_r_c + D_p_c + e_eps;
+            double wsum = 0.0;
+            for (int i = 0; i < 3; ++i) wsum += sD9[i] / (sD9[i] + sD9[3 + i] + e_eps); // rpf.cpp:470, 485
+            const double wrc = wsum / 3;                                               // rpf.cpp:487
+            if (t < 3) {
+                const double Drc = sD9[t], Dpc = sD9[3 + t];
+                const double alpha_c = 1 - Drc / (Drc + Dpc + e_eps);                  // rpf.cpp:470, 475
+                sAlpha[t] = alpha_c;
+                if (p.dbg.alpha && gvalid) p.dbg.alpha[pix * 3 + t] = alpha_c;
+            }
+            if (t == 0) {
+                sAlpha[3] = wrc;
+                if (p.dbg.wrc && gvalid) p.dbg.wrc[pix] = wrc;
+            }
+            for (int k = t; k < nF; k += G) {
+                const double Drf = sDrf[k];
+                double Dpf = 0.0, Dcf = 0.0;
+                for (int l = 0; l < 2; ++l) Dpf += mi[k * nAnc + nR + l];              // rpf.cpp:425
+                for (int cc = 0; cc < 3; ++cc) Dcf += mi[D.npairF + cc * D.npairC + nAnc + k];
+                // the beta presets keep the reference's stack rule for any nF: k < 3 reads D_f_ck, a gap of zeros, then D_r_fk
+                double num;
+                if (p.beta_map == RPF_BETA_PAPER) num = Dcf;
+                else if (p.beta_map == RPF_BETA_REF_GCC11_O2) num = k < 3 ? sD9[6 + k] : (k < 8 ? 0.0 : sDrf[max(k - 8, 0)]);
+                else num = k < 3 ? sD9[6 + k] : (k < 4 ? 0.0 : sDrf[max(k - 4, 0)]);
+                const double beta_k = (1 - Drf / (Drf + Dpf + e_eps)) * (num / den);   // rpf.cpp:464-465, 479
+                sBeta[k] = beta_k;
+                if (p.dbg.beta && gvalid) p.dbg.beta[pix * nF + k] = beta_k;
+            }
+            wsync();
+        }
+
+        // ---- stage 4: weights and blend, term by term as rpf.cpp:646-717.  Lane = neighbourhood sample j; the weighted
+        // columns are normalised in place (own sample i of the group is its slot i), kOwn own samples per sweep
+        const double cj0 = sU[(gbase + 2) * G + t], cj1 = sU[(gbase + 3) * G + t], cj2 = sU[(gbase + 4) * G + t];
+        for (int k = 0; k < nwt; ++k) {
+            const int col = k < 5 ? k : k + nR;
+            const double *st = sStat + (gbase + col) * 5;
+            const double Mc = st[0], sd = st[1];
+            double *u = sU + (gbase + col) * G + t;
+            const double xv = *u;
+            *u = sd == 0.0 ? 0.0 : (xv - Mc) / sd;
+        }
+        wsync();
+        bool bad = false;
+        {
+            const double wrc = sAlpha[3];
+            const double sigma_c2 = p.seed * p.seed / (1 - wrc) / (1 - wrc);           // rpf.cpp:662
+            const double sigma_p2 = p.sigma_p * p.sigma_p;
+            for (int i0 = 0; i0 < S; i0 += kOwn) {
+                double sp[kOwn], sc[kOwn], sf[kOwn];
+#pragma unroll
+                for (int ii = 0; ii < kOwn; ++ii) { sp[ii] = 0.0; sc[ii] = 0.0; sf[ii] = 0.0; }
+                for (int k = 0; k < 2; ++k) {
+                    const double *zr = sU + (gbase + k) * G;
+                    const double zj = zr[t];
+#pragma unroll
+                    for (int ii = 0; ii < kOwn; ++ii) { const double d = zr[min(i0 + ii, S - 1)] - zj; sp[ii] += d * d; }
+                }
+                for (int k = 0; k < 3; ++k) {
+                    const double *zr = sU + (gbase + 2 + k) * G;
+                    const double zj = zr[t], ak = sAlpha[k];
+#pragma unroll
+                    for (int ii = 0; ii < kOwn; ++ii) { const double d = zr[min(i0 + ii, S - 1)] - zj; sc[ii] += (d * d) * ak; }
+                }
+                for (int k = 0; k < nF; ++k) {
+                    const double *zr = sU + (gbase + colF + k) * G;
+                    const double zj = zr[t], bk = sBeta[k];
+#pragma unroll
+                    for (int ii = 0; ii < kOwn; ++ii) { const double d = zr[min(i0 + ii, S - 1)] - zj; sf[ii] += (d * d) * bk; }
+                }
+#pragma unroll
+                for (int ii = 0; ii < kOwn; ++ii) {
+                    const int i = i0 + ii;
+                    double w = exp(-sp[ii] / (2 * sigma_p2)) * exp(-sc[ii] / (2 * sigma_c2)) * exp(-sf[ii] / (2 * sigma_c2)); // rpf.cpp:667-670
+                    w = (live && i < S) ? w : 0.0;
+                    const double sw = group_sum<G>(w);                                 // rpf.cpp:691
+                    const double s0 = group_sum<G>(w * cj0), s1 = group_sum<G>(w * cj1), s2 = group_sum<G>(w * cj2); // rpf.cpp:692
+                    if (t < 3 && gvalid && i < S) {
+                        double prime = (t == 0 ? s0 : (t == 1 ? s1 : s2)) / sw;       // rpf.cpp:700
+                        if (isnan(prime)) {                                            // rpf.cpp:702: the reference exits here
+                            bad = true;
+                            if (p.policy == RPF_DEGEN_EPS) prime = p.col_in[(uint64_t)t * p.plane_stride + pix * S + i];
+                        }
+                        p.col_out[(uint64_t)t * p.plane_stride + pix * S + i] = prime;
+                    }
+                }
+            }
+        }
+        // status: one report per pixel; a pixel on the redo list reports nothing (generic::filter_pixel_kernel owns it)
+        const unsigned long long badm = __ballot(bad);
+        if (t == 0 && gvalid) {
+            const unsigned long long gm = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << (g * G);
+            if (sFlag[g] != 0) {
+                p.redo_list[atomicAdd(p.redo_count, 1u)] = pixu;
+            } else if (badm & gm) {
+                atomicAdd(&p.status[0], 1);
+                atomicMin(&p.status[1], (int)pixu);
+            }
+        }
+    }
+}
+
+template <class T, int G>
+hipError_t launch_packed_t(const PassParams &p, const GenericPackedCarve &cv, hipStream_t s) {
+    hipError_t e = hipFuncSetAttribute((const void *)filter_packed_kernel<T, G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
+    if (e != hipSuccess) return e;
+    const uint32_t P = 64u / (uint32_t)G, units = (p.list_count + P - 1u) / P;
+    // grid-stride walk: 2048 workgroups keep 256 CUs busy whatever the carve-up lets a CU hold
+    const unsigned grid = (unsigned)std::min<uint32_t>((units + cv.waves - 1u) / cv.waves, 2048u);
+    hipLaunchKernelGGL((filter_packed_kernel<T, G>), dim3(grid), dim3(64u * cv.waves), cv.total, s, p, cv);
+    return hipGetLastError();
+}
+
+template <class T>
+hipError_t launch_packed_g(const PassParams &p, const GenericPackedCarve &cv, int G, hipStream_t s) {
+    switch (G) {
+    case 8: return launch_packed_t<T, 8>(p, cv, s);
+    case 16: return launch_packed_t<T, 16>(p, cv, s);
+    case 32: return launch_packed_t<T, 32>(p, cv, s);
+    case 64: return launch_packed_t<T, 64>(p, cv, s);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+} // namespace
+
+hipError_t launch_nbhd_count(const PassParams &p, hipStream_t s) {
+    if (p.masks == nullptr || p.nbhd == nullptr || !p.lay.generic_ok()) return hipErrorInvalidValue;
+    if (p.row_end <= p.row_begin) return hipSuccess;
+    const uint64_t npix = (uint64_t)(p.row_end - p.row_begin) * p.W;
+    const dim3 grid((unsigned)((npix + 3) / 4));
+    if (p.lay.f16) hipLaunchKernelGGL(nbhd_count_kernel<__half>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(nbhd_count_kernel<float>, grid, dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, hipStream_t s) {
+    if (p.masks == nullptr || p.pix_list == nullptr || p.S > lanes_per_pixel || !p.lay.generic_ok()) return hipErrorInvalidValue;
+    if (p.policy == RPF_DEGEN_REF_ABORT && p.redo_list != nullptr && p.redo_count == nullptr) return hipErrorInvalidValue;
+    if (p.list_count == 0) return hipSuccess;
+    const GenericPackedCarve cv = generic_packed_carve(p.lay);
+    if ((int)cv.total > max_lds_per_block()) return hipErrorInvalidValue;
+    return p.lay.f16 ? launch_packed_g<__half>(p, cv, lanes_per_pixel, s) : launch_packed_g<float>(p, cv, lanes_per_pixel, s);
+}
+
+} // namespace generic
+} // namespace rpf

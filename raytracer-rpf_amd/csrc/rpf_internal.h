@@ -33,7 +33,8 @@ struct PassParams {
     int32_t box, b;        // b = (box-1)/2, rpf.cpp:561
     int32_t beta_map, policy;
     int32_t fast_weights;  // RPF_FLAG_FAST_WEIGHTS: fp32 pair arithmetic in stage 4
-    int32_t generic;       // RPF_FLAG_GENERIC: stage 1a and the filter pass run on the layout-generic kernels (rpf_generic.hip)
+    int32_t generic;       // RPF_FLAG_GENERIC: stage 1a and the filter pass run on the layout-generic kernels (rpf_generic.hip);
+                           //   bit 1: RPF_FLAG_GENERIC_PACKED, small neighbourhoods on the packed generic kernels (rpf_generic_packed.hip)
     int32_t stage_mask;    // diagnostics only (rpf_set_option "stage_mask"): bit0 stats chain, bit1 bins, bit2 MI, bit3 weights; -1 = all
     int32_t screen;        // far-pair screen of the four-wave kernels: 0 off, 1 on
     int32_t strip_w;       // pixels per XCD strip of the pixel walk (slab_pixel)
@@ -175,6 +176,30 @@ hipError_t launch_pixel_stats(const PassParams &p, uint64_t pix0, uint64_t pix1,
 // u32 and [slots][ndim][nmax] u8 (needed when the carve-up is not resident); the grid is min(pixels, slots).
 // count_dev != null: the size of p.pix_list is read from device memory (redo list: no host read-back), grid = slots
 hipError_t launch_filter(const PassParams &p, void *list, void *bins, uint32_t slots, const uint32_t *count_dev, hipStream_t s);
+} // namespace generic
+
+// ---- the packed layout-generic kernels (rpf_generic_packed.hip, RPF_FLAG_GENERIC_PACKED): N <= 64, several pixels per wave --
+// LDS carve-up of generic::filter_packed_kernel, a host-side function of the layout only.  The workgroup holds T[0 .. 64] and
+// the columns of every MI pair (off_pairtab), then `waves` independent per-wave blocks of wave_bytes each; the off_* below
+// are byte offsets from a wave's block, sized for the eight pixels a wave holds at G = 8:
+//   staged samples [8 G-lane groups][ndim][G] fp64 at 0 (64 ndim doubles whatever G is), stat [8][ndim][5] fp64 (M, SD, lo,
+//   range, flags), mask [ndim][16] u64 (one bit mask per pixel, column and bin value), hx [8][ndim] u64, bins [64][ndim] bytes,
+//   mi [8][npair] fp64, w [8][2 nF + 16] fp64 (D_r_fk | the nine colour sums | alpha, W_r_c | beta), flag [8] ints (redo)
+// waves: as many of the four as fit 160 KiB.
+struct GenericPackedCarve {
+    uint32_t off_pairtab, table_bytes;
+    uint32_t off_stat, off_mask, off_hx, off_bins, off_mi, off_w, off_flag, wave_bytes;
+    uint32_t waves, total;
+};
+GenericPackedCarve generic_packed_carve(const SampleLayout &lay);
+namespace generic {
+// stage 1b's test for every pixel of rows [p.row_begin, p.row_end): N into p.nbhd, the acceptance masks into p.masks
+// ([H*W][p.mask_stride] u64, bit q = candidate q in the reference's visiting order -- the numbering of the compiled
+// nbhd_count_kernel)
+hipError_t launch_nbhd_count(const PassParams &p, hipStream_t s);
+// the pixels of p.pix_list (p.list_count of them, N <= lanes_per_pixel = 8, 16, 32 or 64) from p.nbhd and p.masks; under
+// REF_ABORT p.redo_list / p.redo_count take the pixels that generic::filter_pixel_kernel must filter again
+hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, hipStream_t s);
 } // namespace generic
 
 int max_lds_per_block();

@@ -206,6 +206,9 @@ def demangle_short(name):
     g = re.search(r"packed_kernelILi(\d+)E", name)
     if g:
         s += "<G=%s>" % g.group(1)
+    t = re.search(r"3rpf7generic.*packed_kernelI(f|6__half)Li(\d+)E", name)  # ... and of their packed kernels the lanes per pixel
+    if t:
+        s += "<%s,G=%s>" % ("float" if t.group(1) == "f" else "__half", t.group(2))
     return s
 
 
