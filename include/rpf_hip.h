@@ -92,7 +92,7 @@ enum {
                                   ALLOWED for the two compiled layouts, where it selects the generic kernels instead of the
                                   fused routes (A/B timing, parity).  fp64 throughout: together with RPF_FLAG_FAST_WEIGHTS
                                   it is RPF_E_UNSUPPORTED.  One filter launch per pass; rpf_query_route says 3. */
-    RPF_FLAG_GENERIC_PACKED = 16 /* opt-in, modifies RPF_FLAG_GENERIC: the pixels whose neighbourhood holds N <= 64 samples
+    RPF_FLAG_GENERIC_PACKED = 16, /* opt-in, modifies RPF_FLAG_GENERIC: the pixels whose neighbourhood holds N <= 64 samples
                                   (about 94 % of a path-traced buffer) run on the packed layout-generic kernels -- a pixel gets
                                   8, 16, 32 or 64 lanes of a wavefront instead of a 256-thread workgroup -- behind a count
                                   pass of their own; the other pixels stay on the generic filter kernel.  Same layouts as the
@@ -101,6 +101,17 @@ enum {
                                   rpf_query_route says 4 (3 for a pass with S > 64, which no packed class can hold and which
                                   runs exactly as without this flag).  Without RPF_FLAG_GENERIC, or together with
                                   RPF_FLAG_FAST_WEIGHTS, it is RPF_E_UNSUPPORTED, from every filter entry point and from
+                                  rpf_layout_kernels, before any device work. */
+    RPF_FLAG_GENERIC_WAVE = 32 /* opt-in, modifies RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED: the pixels whose neighbourhood
+                                  holds 64 < N <= 832 samples run on the one-wave layout-generic kernels -- one wavefront per
+                                  pixel, no workgroup barrier, size classes N <= 128, 256, 448 and 832 with LDS sized for the
+                                  class -- behind the count pass of the packed flag; only N > 832 stays on the generic filter
+                                  kernel.  Same layouts as the generic flag.  Same membership, bins, statistics, MI, alpha,
+                                  beta and W_r_c as under the generic flag alone; the colours agree to rounding.
+                                  rpf_query_route says 5 (3 for a pass with S > 832, which no class can hold and which runs
+                                  exactly as under RPF_FLAG_GENERIC alone; a pass with 64 < S <= 832 is route 5 with empty
+                                  packed classes).  Without both RPF_FLAG_GENERIC and RPF_FLAG_GENERIC_PACKED, or together
+                                  with RPF_FLAG_FAST_WEIGHTS, it is RPF_E_UNSUPPORTED, from every filter entry point and from
                                   rpf_layout_kernels, before any device work. */
 };
 
@@ -249,7 +260,11 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *desc, int32_t box, c
  * With RPF_FLAG_GENERIC_PACKED as well (route 4) filter_kernel_launches counts, per pass, one launch per non-empty packed
  * class (N <= 8, 16, 32, 64), one for the generic filter kernel when some pixel has N > 64, and under RPF_DEGEN_REF_ABORT one
  * for the redo launch; redo_pixels counts the pixels the packed kernels put on the redo list (the generic filter kernel then
- * filters them whole, evaluating the reference's expression in place). */
+ * filters them whole, evaluating the reference's expression in place).
+ * With RPF_FLAG_GENERIC_WAVE as well (route 5) filter_kernel_launches counts, per pass, one launch per non-empty packed class,
+ * one per non-empty one-wave class (N <= 128, 256, 448, 832), one for the generic filter kernel when some pixel has N > 832,
+ * and under RPF_DEGEN_REF_ABORT one for the redo launch; redo_pixels counts the pixels the packed and the one-wave kernels put
+ * on the redo list. */
 int32_t rpf_query_counters(rpf_ctx *ctx, rpf_counters *out);
 
 /* neighbourhood size N of every pixel (rpf.cpp:586: the neighbourhood vector's size) as the last pass of the most recent
@@ -262,7 +277,8 @@ int32_t rpf_query_nbhd(rpf_ctx *ctx, int32_t *nbhd_out, int64_t count);
  * small-neighbourhood kernels take most pixels: the route of path-traced buffers), 2 = size-binned
  * (box*box*S > 512), 3 = the layout-generic kernels (RPF_FLAG_GENERIC; several times slower, same membership, bins and
  * statistics), 4 = the layout-generic kernels with small neighbourhoods packed (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED
- * on a pass with S <= 64), -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1. */
+ * on a pass with S <= 64), 5 = the same with 64 < N <= 832 on the one-wave layout-generic kernels (... | RPF_FLAG_GENERIC_WAVE
+ * on a pass with S <= 832), -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1. */
 int32_t rpf_query_route(rpf_ctx *ctx, int32_t *route_out);
 
 /* visualizeSF (rpf.cpp:37-101, visualization/vis.cpp:34-51): the reference's six debug images, without the EXR
@@ -315,7 +331,8 @@ int32_t rpf_multi_halo_plan(int32_t H, int32_t n_slabs, int32_t depth, int32_t *
  * with *generic_out = 0 (the compiled, fused kernels) or 1 (the layout-generic kernels); RPF_E_UNSUPPORTED where every filter
  * entry point refuses the layout / flag combination (same function, so the two cannot drift) -- a layout without kernels,
  * RPF_FLAG_FAST_WEIGHTS on a layout other than the reference's 19 dims, or together with RPF_FLAG_GENERIC;
- * RPF_FLAG_GENERIC_PACKED without RPF_FLAG_GENERIC or with RPF_FLAG_FAST_WEIGHTS; RPF_E_BADARG for a NULL desc.
+ * RPF_FLAG_GENERIC_PACKED without RPF_FLAG_GENERIC or with RPF_FLAG_FAST_WEIGHTS; RPF_FLAG_GENERIC_WAVE without both of
+ * those flags or with RPF_FLAG_FAST_WEIGHTS; RPF_E_BADARG for a NULL desc.
  * Only n_random, n_feat, plane_dtype and flags are read.  Needs no context and no device.  generic_out may be NULL. */
 int32_t rpf_layout_kernels(const rpf_desc *desc, int32_t *generic_out);
 

@@ -15,6 +15,7 @@ KERNEL_TUS = ["rpf_impl_%s_%s.hip" % (lay, part) for lay in ("d19", "d27") for p
 KERNEL_TUS += ["rpf_film.hip"]  # the film step (pbrt's reconstruction filter): rpf_filter_film / rpf_film_splat_device
 KERNEL_TUS += ["rpf_generic.hip"]  # the layout-generic kernel pair (RPF_FLAG_GENERIC): n_random / n_feat at run time
 KERNEL_TUS += ["rpf_generic_packed.hip"]  # ... its count pass and packed kernels for N <= 64 (RPF_FLAG_GENERIC_PACKED)
+KERNEL_TUS += ["rpf_generic_wave.hip"]  # ... and its one-wave kernels for 64 < N <= 832 (RPF_FLAG_GENERIC_WAVE)
 # the C ABI (host code only; rpf_api.h is what they share): context, validation, routes and pass loops | film step | multi-GPU
 API_TUS = ["rpf_api.hip", "rpf_api_film.hip", "rpf_api_multi.hip"]
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in KERNEL_TUS + API_TUS]

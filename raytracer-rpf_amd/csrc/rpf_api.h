@@ -64,7 +64,7 @@ struct rpf_ctx {
     rpf::DevBuf<int32_t> d_status;              // [0] bad count [1] first bad
     rpf::DevBuf<unsigned long long> d_nred;     // [0] sum N [1] max N
     rpf::DevBuf<uint32_t> d_lists;              // size binning: [kNumClasses][H*W] pixel lists
-    int last_route = -1;                        // last pass: 1 = count first, 0 = fused, 2 = size-binned, 3 = layout-generic, 4 = layout-generic with small neighbourhoods packed (rpf_query_route)
+    int last_route = -1;                        // last pass: 1 = count first, 0 = fused, 2 = size-binned, 3 = layout-generic, 4 = layout-generic with small neighbourhoods packed, 5 = ... and 64 < N <= 832 on the one-wave kernels (rpf_query_route)
     rpf::DevBuf<uint32_t> d_class_counts;       // [kNumClasses] list sizes + [2] the route probe's counts
     rpf::DevBuf<uint64_t> d_masks;              // size binning: stage-1b acceptance masks [H*W][stride]
     rpf::DevBuf<char> d_big_list;               // streaming kernel: member lists [slots][nmax] u32

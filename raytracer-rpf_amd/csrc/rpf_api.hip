@@ -38,13 +38,17 @@ SampleLayout layout_of(const rpf_desc *d) {
 
 // Which kernels the filter entry points run for the layout and flags of d (rpf_layout_kernels; needs no device): RPF_OK with
 // *generic_out = 0 (the compiled, fused kernels) or 1 (the layout-generic kernels, RPF_FLAG_GENERIC, with or without
-// RPF_FLAG_GENERIC_PACKED), else the refusal and its text in *why.
+// RPF_FLAG_GENERIC_PACKED / RPF_FLAG_GENERIC_WAVE), else the refusal and its text in *why.
 int32_t layout_kernels(const rpf_desc *d, int32_t *generic_out, std::string *why) {
     if (!d) return RPF_E_BADARG;
     const SampleLayout lay = layout_of(d);
     int32_t generic = 0;
     const char *msg = nullptr;
-    if ((d->flags & RPF_FLAG_GENERIC_PACKED) && !(d->flags & RPF_FLAG_GENERIC)) {
+    if ((d->flags & RPF_FLAG_GENERIC_WAVE) && (d->flags & (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) != (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) {
+        msg = "RPF_FLAG_GENERIC_WAVE without RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED: the flag modifies the packed layout-generic route";
+    } else if ((d->flags & RPF_FLAG_GENERIC_WAVE) && (d->flags & RPF_FLAG_FAST_WEIGHTS)) {
+        msg = "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_GENERIC_WAVE: the layout-generic kernels are fp64 throughout";
+    } else if ((d->flags & RPF_FLAG_GENERIC_PACKED) && !(d->flags & RPF_FLAG_GENERIC)) {
         msg = "RPF_FLAG_GENERIC_PACKED without RPF_FLAG_GENERIC: the flag modifies the layout-generic route";
     } else if ((d->flags & RPF_FLAG_GENERIC_PACKED) && (d->flags & RPF_FLAG_FAST_WEIGHTS)) {
         msg = "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_GENERIC_PACKED: the layout-generic kernels are fp64 throughout";
@@ -147,7 +151,7 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     p.box = box; p.b = (box - 1) / 2;
     p.beta_map = d->beta_map; p.policy = d->degenerate_policy;
     p.fast_weights = (d->flags & RPF_FLAG_FAST_WEIGHTS) ? 1 : 0;
-    p.generic = (d->flags & RPF_FLAG_GENERIC) ? ((d->flags & RPF_FLAG_GENERIC_PACKED) ? 3 : 1) : 0;
+    p.generic = (d->flags & RPF_FLAG_GENERIC) ? (1 | ((d->flags & RPF_FLAG_GENERIC_PACKED) ? 2 : 0) | ((d->flags & RPF_FLAG_GENERIC_WAVE) ? 4 : 0)) : 0;
     p.stage_mask = ctx->tun.stage_mask; // timing ablation knob (rpf_set_option); results are wrong unless -1
     p.screen = ctx->tun.screen;
     const int64_t nmax64 = (int64_t)box * box * d->S;
@@ -477,6 +481,67 @@ int32_t route_generic_packed(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s
     return launch_redo(ctx, p, s, launches);
 }
 
+// The packed layout-generic route with the one-wave kernels behind it (... | RPF_FLAG_GENERIC_WAVE, S <= 832): the count pass
+// and the read-back of route_generic_packed, the pixels dealt into eight classes -- N <= 8, 16, 32, 64 for
+// generic::filter_packed_kernel, N <= 128, 256, 448, 832 for generic::filter_wave_kernel (one wave per pixel, member list
+// from the acceptance masks, LDS sized for the class) -- and the rest (N > 832) into the list generic::filter_pixel_kernel
+// walks; then one launch per non-empty list.  REF_ABORT: both kernel families put the pixels with an in-band table on the redo
+// list, which launch_redo filters again.  None of the rpf_set_option names applies here.
+int32_t route_generic_wave(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
+    const size_t HW = (size_t)p_in.W * p_in.H;
+    int32_t st;
+    ctx->last_route = 5;
+    PassParams p = p_in;
+    p.redo_list = nullptr; p.redo_count = nullptr;
+    if (p.policy == RPF_DEGEN_REF_ABORT) {
+        HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
+        if ((st = ctx->d_redo_list.ensure(ctx, HW * sizeof(uint32_t)))) return st;
+        p.redo_list = ctx->d_redo_list; p.redo_count = ctx->d_redo_count;
+    }
+    if (p.row_end <= p.row_begin) return RPF_OK;
+    if ((st = ctx->d_lists.ensure(ctx, (size_t)kNumClasses * HW * sizeof(uint32_t)))) return st;
+    p.mask_stride = mask_stride(p);
+    if ((st = ctx->d_masks.ensure(ctx, HW * p.mask_stride * sizeof(uint64_t)))) return st;
+    p.masks = ctx->d_masks;
+    constexpr int kNumWave = 8; // classes 0 .. 3 packed, 4 .. 7 one wave per pixel (capacities 128, 256, 448, 832)
+    const int rest_class = kNumClasses - 1;
+    uint32_t counts[kNumClasses];
+    {
+        Range rg("rpf:generic count + classify (stage 1b test, lane and wave classes)");
+        HIP_TRY(hipMemsetAsync(ctx->d_class_counts, 0, kNumClasses * sizeof(uint32_t), s));
+        HIP_TRY(generic::launch_nbhd_count(p, s));
+        HIP_TRY(launch_classify(p, ctx->d_lists, ctx->d_class_counts, kNumWave, rest_class, s));
+        HIP_TRY(hipMemcpyAsync(counts, ctx->d_class_counts, sizeof(counts), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    for (int c = 0; c < kNumWave; ++c) {
+        if (counts[c] == 0) continue;
+        Range rg(c < kNumPacked ? "rpf:generic packed class" : "rpf:generic wave class");
+        PassParams q = p;
+        q.pix_list = ctx->d_lists + (size_t)c * HW;
+        q.list_count = counts[c];
+        if (c < kNumPacked) { HIP_TRY(generic::launch_filter_packed(q, class_capacity(c), s)); }
+        else { HIP_TRY(generic::launch_filter_wave(q, class_capacity(c), s)); }
+        if (launches) ++*launches;
+    }
+    if (counts[rest_class] != 0) {
+        Range rg("rpf:generic filter kernel (N > 832)");
+        PassParams q = p;
+        q.pix_list = ctx->d_lists + (size_t)rest_class * HW;
+        q.list_count = counts[rest_class];
+        const GenericCarve cv = generic_carve(q.lay, q.nmax);
+        uint32_t slots = std::min<uint32_t>(q.list_count, 2048u); // resident: eight workgroups on each of 256 CUs
+        if (!cv.resident) {
+            const size_t per_slot = (size_t)q.nmax * (4 + (size_t)q.lay.ndim());
+            slots = (uint32_t)std::min<uint64_t>(q.list_count, std::max<size_t>(64, std::min<size_t>(1024, ((size_t)1 << 30) / per_slot)));
+            if ((st = ensure_big_scratch(ctx, q, slots))) return st;
+        }
+        HIP_TRY(generic::launch_filter(q, ctx->d_big_list, ctx->d_big_bins, slots, nullptr, s));
+        if (launches) ++*launches;
+    }
+    return launch_redo(ctx, p, s, launches);
+}
+
 } // namespace
 
 // One fused-filter pass over rows [p.row_begin, p.row_end).  When box*box*S is above what the one-wave kernels hold
@@ -484,7 +549,8 @@ int32_t route_generic_packed(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s
 // LDS sized for its capacity (rpf_kernels.hip, "neighbourhood-size binning"); option "binning" = 0/1 overrides.
 // Needs stage 1a's planes (pmean / pstd) for those rows.  Synchronises the stream when it bins (list sizes).
 int32_t launch_filter_binned(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
-    // (above 64 spp N >= S fits no packed class: the pass runs as route 3 does)
+    // (above 64 spp N >= S fits no packed class, above 832 spp no one-wave class: the pass runs as route 3 does)
+    if ((p_in.generic & 4) && p_in.S <= 832) return route_generic_wave(ctx, p_in, s, launches);
     if (p_in.generic) return (p_in.generic & 2) && p_in.S <= class_capacity(kNumPacked - 1) ? route_generic_packed(ctx, p_in, s, launches)
                                                                                             : route_generic(ctx, p_in, s, launches);
     PassParams p = p_in;
@@ -1004,7 +1070,7 @@ int32_t rpf_stage_pixel_stats(rpf_ctx *ctx, const rpf_desc *d, const void *plane
     if ((st = upload_frame(ctx, d, planes, nullptr, false, nullptr, s))) return st;
     PassParams p{};
     p.lay = lay;
-    p.generic = (d->flags & RPF_FLAG_GENERIC) ? 1 : 0; // (stage 1a is the same kernel with and without RPF_FLAG_GENERIC_PACKED)
+    p.generic = (d->flags & RPF_FLAG_GENERIC) ? 1 : 0; // (stage 1a is the same kernel with and without RPF_FLAG_GENERIC_PACKED / _WAVE)
     p.W = d->W; p.H = d->H; p.S = d->S; p.policy = d->degenerate_policy;
     p.plane_stride = ps; p.planes = ctx->d_planes; p.pmean = ctx->d_pmean; p.pstd = ctx->d_pstd;
     HIP_TRY(launch_pixel_stats(p, s));

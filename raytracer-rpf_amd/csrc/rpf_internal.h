@@ -35,6 +35,7 @@ struct PassParams {
     int32_t fast_weights;  // RPF_FLAG_FAST_WEIGHTS: fp32 pair arithmetic in stage 4
     int32_t generic;       // RPF_FLAG_GENERIC: stage 1a and the filter pass run on the layout-generic kernels (rpf_generic.hip);
                            //   bit 1: RPF_FLAG_GENERIC_PACKED, small neighbourhoods on the packed generic kernels (rpf_generic_packed.hip)
+                           //   bit 2: RPF_FLAG_GENERIC_WAVE, 64 < N <= 832 on the one-wave generic kernels (rpf_generic_wave.hip)
     int32_t stage_mask;    // diagnostics only (rpf_set_option "stage_mask"): bit0 stats chain, bit1 bins, bit2 MI, bit3 weights; -1 = all
     int32_t screen;        // far-pair screen of the four-wave kernels: 0 off, 1 on
     int32_t strip_w;       // pixels per XCD strip of the pixel walk (slab_pixel)
@@ -200,6 +201,29 @@ hipError_t launch_nbhd_count(const PassParams &p, hipStream_t s);
 // the pixels of p.pix_list (p.list_count of them, N <= lanes_per_pixel = 8, 16, 32 or 64) from p.nbhd and p.masks; under
 // REF_ABORT p.redo_list / p.redo_count take the pixels that generic::filter_pixel_kernel must filter again
 hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, hipStream_t s);
+} // namespace generic
+
+// ---- the one-wave layout-generic kernels (rpf_generic_wave.hip, RPF_FLAG_GENERIC_WAVE): 64 < N <= 832, one wave per pixel --
+// LDS carve-up of generic::filter_wave_kernel, a host-side function of the layout and the class capacity (128, 256, 448 or
+// 832).  The workgroup holds T[0 .. capacity] and the columns of every MI pair (off_pairtab), then `waves` independent
+// per-wave blocks of wave_bytes each; the off_* below are byte offsets from a wave's block:
+//   member list [capacity] u32 at 0; one block shared by the staging chunk [ndim][65] fp64 of the in-order sums (stage 2),
+//   the bin ids [ndim][capacity] bytes (stages 3a, 3b) and the own rows of a sweep of stage 4 (never live together:
+//   off_chunk == off_bins); hist: four joint histograms of floor(sqrt(capacity))^2 16-bit cells (four tables are filled
+//   together); stat (M | SD | min | max [4 ndim], lo | range | flags [3 ndim], sum T[hx] [ndim], pair sums / MI [npair],
+//   D_r_fk | the nine colour sums | alpha | beta | W_r_c [2 nF + 20], all fp64), flag (redo)
+// waves: of the one to four per workgroup that fit 160 KiB, the count that lets a CU hold the most waves (at most the eight
+// its registers allow), the larger count on a tie; 0: none fits, which no layout within RPF_MAX_NDIM reaches.
+struct GenericWaveCarve {
+    uint32_t off_pairtab, table_bytes;
+    uint32_t off_bins, off_hist, off_chunk, off_stat, off_flag, wave_bytes;
+    uint32_t waves, total, capacity;
+};
+GenericWaveCarve generic_wave_carve(const SampleLayout &lay, int capacity);
+namespace generic {
+// the pixels of p.pix_list (p.list_count of them, 64 < N <= capacity = 128, 256, 448 or 832) from p.nbhd and p.masks; under
+// REF_ABORT p.redo_list / p.redo_count take the pixels that generic::filter_pixel_kernel must filter again
+hipError_t launch_filter_wave(const PassParams &p, int capacity, hipStream_t s);
 } // namespace generic
 
 int max_lds_per_block();

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the filter pass of the layout-generic routes (RPF_FLAG_GENERIC alone: route 3; with RPF_FLAG_GENERIC_PACKED: route
-4, the third variant of every case, `generic` = 2) next to the fused routes: seeded buffers generated on
+4, `generic` = 2; with RPF_FLAG_GENERIC_WAVE as well: route 5, `generic` = 3) next to the fused routes: seeded buffers generated on
 the device, rpf_filter_device with RPF_FLAG_TIMING (filter_kernel_ms: events around the pass's filter launches, stage 1a
 excluded), one warm-up call, then --steps calls; one JSON line per case with the min and max over the calls, the route,
 the launches and the mean neighbourhood size.  Cases (--case to pick by name):
@@ -10,8 +10,8 @@ the launches and the mean neighbourhood size.  Cases (--case to pick by name):
   lay4_18      the smooth slab as (4, 18, fp32) with the flag
   box17        256x64x16 smooth, box 17 (N > 3136 for most pixels): 19-dim layout without the flag (the streaming kernel)
                and with it
-Each case's variants run in one process on one context and on the same generated buffer; a route-4 record carries
-ratio_to_route3 next to ratio_to_fused.
+Each case's variants run in one process on one context and on the same generated buffer; a route-4 or route-5 record
+carries ratio_to_route3 next to ratio_to_fused, a route-5 record ratio_to_route4 as well.
 A library loaded through RPF_HIP_LIB (a build variant) is measured by the same script."""
 import argparse
 import json
@@ -30,11 +30,11 @@ from raytracer_rpf_amd import hip  # noqa: E402
 
 # name: (W, H, S, box, flat_frac, [(n_random, n_feat, generic), ...])
 CASES = {
-    "smooth8": (1920, 270, 8, 7, 0.0, [(2, 12, 0), (2, 12, 1), (2, 12, 2)]),
-    "flat8": (1920, 270, 8, 7, 0.94, [(2, 12, 0), (2, 12, 1), (2, 12, 2)]),
-    "lay3_12": (1920, 270, 8, 7, 0.0, [(3, 12, 1), (3, 12, 2)]),
-    "lay4_18": (1920, 270, 8, 7, 0.0, [(4, 18, 1), (4, 18, 2)]),
-    "box17": (256, 64, 16, 17, 0.0, [(2, 12, 0), (2, 12, 1), (2, 12, 2)]),
+    "smooth8": (1920, 270, 8, 7, 0.0, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3)]),
+    "flat8": (1920, 270, 8, 7, 0.94, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3)]),
+    "lay3_12": (1920, 270, 8, 7, 0.0, [(3, 12, 1), (3, 12, 2), (3, 12, 3)]),
+    "lay4_18": (1920, 270, 8, 7, 0.0, [(4, 18, 1), (4, 18, 2), (4, 18, 3)]),
+    "box17": (256, 64, 16, 17, 0.0, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3)]),
 }
 
 
@@ -50,7 +50,8 @@ def run(ctx, name, steps):
                                              mode="smooth", flat_frac=flat, n_random=nr, n_feat=nf)
             made = (nr, nf)
         colour = torch.empty((3, H, W, S), dtype=torch.float64, device=dev)
-        flags = hip.FLAG_TIMING | (hip.FLAG_GENERIC if generic else 0) | (hip.FLAG_GENERIC_PACKED if generic == 2 else 0)
+        flags = hip.FLAG_TIMING | (hip.FLAG_GENERIC if generic else 0) | (hip.FLAG_GENERIC_PACKED if generic >= 2 else 0)
+        flags |= hip.FLAG_GENERIC_WAVE if generic == 3 else 0
         desc = hip.make_desc(W, H, S, boxes=(box,), policy=hip.DEGEN_EPS, flags=flags, n_random=nr, n_feat=nf)
         ms = []
         for it in range(steps + 1):
@@ -69,8 +70,11 @@ def run(ctx, name, steps):
         if generic and base:
             rec["ratio_to_fused"] = round(rec["filter_ms_min"] / base["filter_ms_min"], 2)
         r3 = out.get((nr, nf, 1))
-        if generic == 2 and r3:
+        if generic >= 2 and r3:
             rec["ratio_to_route3"] = round(rec["filter_ms_min"] / r3["filter_ms_min"], 3)
+        r4 = out.get((nr, nf, 2))
+        if generic == 3 and r4:
+            rec["ratio_to_route4"] = round(rec["filter_ms_min"] / r4["filter_ms_min"], 3)
         print(json.dumps(rec), flush=True)
         del colour
 
