@@ -102,7 +102,7 @@ enum {
                                   runs exactly as without this flag).  Without RPF_FLAG_GENERIC, or together with
                                   RPF_FLAG_FAST_WEIGHTS, it is RPF_E_UNSUPPORTED, from every filter entry point and from
                                   rpf_layout_kernels, before any device work. */
-    RPF_FLAG_GENERIC_WAVE = 32 /* opt-in, modifies RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED: the pixels whose neighbourhood
+    RPF_FLAG_GENERIC_WAVE = 32, /* opt-in, modifies RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED: the pixels whose neighbourhood
                                   holds 64 < N <= 832 samples run on the one-wave layout-generic kernels -- one wavefront per
                                   pixel, no workgroup barrier, size classes N <= 128, 256, 448 and 832 with LDS sized for the
                                   class -- behind the count pass of the packed flag; only N > 832 stays on the generic filter
@@ -112,6 +112,18 @@ enum {
                                   exactly as under RPF_FLAG_GENERIC alone; a pass with 64 < S <= 832 is route 5 with empty
                                   packed classes).  Without both RPF_FLAG_GENERIC and RPF_FLAG_GENERIC_PACKED, or together
                                   with RPF_FLAG_FAST_WEIGHTS, it is RPF_E_UNSUPPORTED, from every filter entry point and from
+                                  rpf_layout_kernels, before any device work. */
+    RPF_FLAG_WIDE_NBHD = 64    /* opt-in: passes with 65535 < box*box*S <= 262144 (the reference's box list {55, 35, 17, 7} at
+                                  32 spp: 55*55*32 = 96800) are accepted and run on the wide layout-generic kernel -- 16-bit bin
+                                  ids, 32-bit histogram cells built in bands of rows, MI from a table of k ln k in 2^-41 fixed
+                                  point.  Every pixel of such a pass runs on that kernel: one launch per pass,
+                                  rpf_query_route says 6, redo_pixels is 0 (the reference's MI expression is evaluated in
+                                  place).  A pass of the same call with box*box*S <= 65535 runs exactly as without the flag:
+                                  same route, same bits.  Above 262144 a pass stays RPF_E_UNSUPPORTED; rpf_max_nbhd() tells the
+                                  bound.  The two compiled layouts take the flag without RPF_FLAG_GENERIC, any other layout
+                                  needs RPF_FLAG_GENERIC as before; RPF_FLAG_GENERIC_PACKED / RPF_FLAG_GENERIC_WAVE are accepted
+                                  alongside and do not affect a wide pass.  fp64 throughout: together with
+                                  RPF_FLAG_FAST_WEIGHTS it is RPF_E_UNSUPPORTED, from every filter entry point and from
                                   rpf_layout_kernels, before any device work. */
 };
 
@@ -219,7 +231,11 @@ int32_t rpf_filter_ex(rpf_ctx *ctx, const rpf_desc *desc, const void *planes, co
  *                      decides per pass), 0 fused, 1 count first.  Same results bit for bit; rpf_query_route tells.
  *   "screen"           far-pair screen of the weight stage (four-wave kernels): 1 on (default), 0 off.  Both settings
  *                      give the same filtered colours bit for bit.
- * These names steer the fused routes only: a call with RPF_FLAG_GENERIC, with or without RPF_FLAG_GENERIC_PACKED, runs
+ *   "wide"             passes of a call with RPF_FLAG_WIDE_NBHD: -1 auto (default: the wide kernel takes the passes with
+ *                      box*box*S > 65535), 1 force (it takes every pass of such a call; a test hook: below 48586 samples it
+ *                      then reads the 2^-44 table of the other kernels and gives the bits of route 3).  No effect without
+ *                      the flag.
+ * These names (but "wide") steer the fused routes only: a call with RPF_FLAG_GENERIC, with or without RPF_FLAG_GENERIC_PACKED, runs
  * the same kernels whatever they say (they are accepted and have no effect there; options_active still reports them).
  * rpf_counters.options_active tells whether a result was produced under any override. */
 int32_t rpf_set_option(rpf_ctx *ctx, const char *name, int64_t value);
@@ -264,7 +280,9 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *desc, int32_t box, c
  * With RPF_FLAG_GENERIC_WAVE as well (route 5) filter_kernel_launches counts, per pass, one launch per non-empty packed class,
  * one per non-empty one-wave class (N <= 128, 256, 448, 832), one for the generic filter kernel when some pixel has N > 832,
  * and under RPF_DEGEN_REF_ABORT one for the redo launch; redo_pixels counts the pixels the packed and the one-wave kernels put
- * on the redo list. */
+ * on the redo list.
+ * A wide pass (RPF_FLAG_WIDE_NBHD, box*box*S > 65535: route 6) counts one launch and leaves redo_pixels 0, whatever the other
+ * flags say: it has no count pass and no size classes. */
 int32_t rpf_query_counters(rpf_ctx *ctx, rpf_counters *out);
 
 /* neighbourhood size N of every pixel (rpf.cpp:586: the neighbourhood vector's size) as the last pass of the most recent
@@ -278,7 +296,8 @@ int32_t rpf_query_nbhd(rpf_ctx *ctx, int32_t *nbhd_out, int64_t count);
  * (box*box*S > 512), 3 = the layout-generic kernels (RPF_FLAG_GENERIC; several times slower, same membership, bins and
  * statistics), 4 = the layout-generic kernels with small neighbourhoods packed (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED
  * on a pass with S <= 64), 5 = the same with 64 < N <= 832 on the one-wave layout-generic kernels (... | RPF_FLAG_GENERIC_WAVE
- * on a pass with S <= 832), -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1. */
+ * on a pass with S <= 832), 6 = the wide layout-generic kernel (RPF_FLAG_WIDE_NBHD on a pass with box*box*S > 65535),
+ * -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1. */
 int32_t rpf_query_route(rpf_ctx *ctx, int32_t *route_out);
 
 /* visualizeSF (rpf.cpp:37-101, visualization/vis.cpp:34-51): the reference's six debug images, without the EXR
@@ -332,9 +351,19 @@ int32_t rpf_multi_halo_plan(int32_t H, int32_t n_slabs, int32_t depth, int32_t *
  * entry point refuses the layout / flag combination (same function, so the two cannot drift) -- a layout without kernels,
  * RPF_FLAG_FAST_WEIGHTS on a layout other than the reference's 19 dims, or together with RPF_FLAG_GENERIC;
  * RPF_FLAG_GENERIC_PACKED without RPF_FLAG_GENERIC or with RPF_FLAG_FAST_WEIGHTS; RPF_FLAG_GENERIC_WAVE without both of
- * those flags or with RPF_FLAG_FAST_WEIGHTS; RPF_E_BADARG for a NULL desc.
+ * those flags or with RPF_FLAG_FAST_WEIGHTS; RPF_FLAG_WIDE_NBHD with RPF_FLAG_FAST_WEIGHTS; RPF_E_BADARG for a NULL desc.
  * Only n_random, n_feat, plane_dtype and flags are read.  Needs no context and no device.  generic_out may be NULL. */
 int32_t rpf_layout_kernels(const rpf_desc *desc, int32_t *generic_out);
+
+/* The largest box*box*S a pass may have under the flags of desc: *nmax_out = 65535, or 262144 with RPF_FLAG_WIDE_NBHD; a
+ * larger pass is RPF_E_UNSUPPORTED from every filter entry point (the pass set-up calls this function, so the two cannot
+ * drift).  Only flags is read.  Needs no context and no device.  RPF_E_BADARG for a NULL pointer. */
+int32_t rpf_max_nbhd(const rpf_desc *desc, int32_t *nmax_out);
+
+/* The table the wide kernel forms MI from: table_out[k] = round(k ln k * 2^41), k = 0 .. nmax (nmax + 1 entries), computed on
+ * the host in long double.  Every entry up to nmax = 262144 is below 2^63 (the 2^-44 table of the other kernels stops being
+ * exact at k = 48586).  Host only, for parity checks; RPF_E_BADARG for NULL or nmax outside [0, 262144]. */
+int32_t rpf_wide_table(int32_t nmax, uint64_t *table_out);
 
 /* LDS bytes per workgroup the fused kernel needs for (S, box); > device limit => RPF_E_UNSUPPORTED */
 int64_t rpf_lds_bytes_required(int32_t S, int32_t box);

@@ -59,16 +59,17 @@ struct rpf_ctx {
     rpf::DevBuf<int32_t> d_nbhd;
     rpf::DevBuf<uint64_t> d_tfix; int tfix_n = 0; // round(k ln k * 2^44), k = 0..n
     rpf::DevBuf<uint64_t> d_dfix;               // first differences
+    rpf::DevBuf<uint64_t> d_twide; int twide_n = 0; // the wide kernel's table: round(k ln k * 2^41), k = 0..n (RPF_FLAG_WIDE_NBHD)
     rpf::DevBuf<float> d_srgb, d_prgb;
     rpf::DevBuf<double> d_carry;                // split route of the 32- / 64-spp classes: statistics / weights between its three kernels
     rpf::DevBuf<int32_t> d_status;              // [0] bad count [1] first bad
     rpf::DevBuf<unsigned long long> d_nred;     // [0] sum N [1] max N
     rpf::DevBuf<uint32_t> d_lists;              // size binning: [kNumClasses][H*W] pixel lists
-    int last_route = -1;                        // last pass: 1 = count first, 0 = fused, 2 = size-binned, 3 = layout-generic, 4 = layout-generic with small neighbourhoods packed, 5 = ... and 64 < N <= 832 on the one-wave kernels (rpf_query_route)
+    int last_route = -1;                        // last pass: 1 = count first, 0 = fused, 2 = size-binned, 3 = layout-generic, 4 = layout-generic with small neighbourhoods packed, 5 = ... and 64 < N <= 832 on the one-wave kernels, 6 = the wide kernel (rpf_query_route)
     rpf::DevBuf<uint32_t> d_class_counts;       // [kNumClasses] list sizes + [2] the route probe's counts
     rpf::DevBuf<uint64_t> d_masks;              // size binning: stage-1b acceptance masks [H*W][stride]
     rpf::DevBuf<char> d_big_list;               // streaming kernel: member lists [slots][nmax] u32
-    rpf::DevBuf<char> d_big_bins;               //                   bin ids [slots][ndim][nmax] u8
+    rpf::DevBuf<char> d_big_bins;               //                   bin ids [slots][ndim][nmax] u8 (the wide kernel: u16)
     rpf::DevBuf<uint8_t> d_flat;                // stage 1a by-product: pixels with a zero-variance feature [H*W]
     rpf::DevBuf<int32_t> d_nan_flag;            // ... and whether any feature mean of the buffer is NaN
     rpf::DevBuf<uint32_t> d_redo_list;          // REF_ABORT: pixels handed to the reference-expression kernel [H*W]
@@ -134,6 +135,7 @@ struct Range {
 // defined in rpf_api.hip, where each is described
 SampleLayout layout_of(const rpf_desc *d);
 int32_t layout_kernels(const rpf_desc *d, int32_t *generic_out, std::string *why);
+void wide_table(int nmax, uint64_t *out); // out[k] = round(k ln k * 2^kTWideBits), k = 0 .. nmax
 int32_t validate(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes);
 int32_t enter(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes); // validate, then make the context's device current
 

@@ -38,13 +38,17 @@ SampleLayout layout_of(const rpf_desc *d) {
 
 // Which kernels the filter entry points run for the layout and flags of d (rpf_layout_kernels; needs no device): RPF_OK with
 // *generic_out = 0 (the compiled, fused kernels) or 1 (the layout-generic kernels, RPF_FLAG_GENERIC, with or without
-// RPF_FLAG_GENERIC_PACKED / RPF_FLAG_GENERIC_WAVE), else the refusal and its text in *why.
+// RPF_FLAG_GENERIC_PACKED / RPF_FLAG_GENERIC_WAVE), else the refusal and its text in *why.  RPF_FLAG_WIDE_NBHD changes neither
+// answer (the wide kernel is layout-generic: both compiled layouts take the flag as they are); with RPF_FLAG_FAST_WEIGHTS it
+// is refused.
 int32_t layout_kernels(const rpf_desc *d, int32_t *generic_out, std::string *why) {
     if (!d) return RPF_E_BADARG;
     const SampleLayout lay = layout_of(d);
     int32_t generic = 0;
     const char *msg = nullptr;
-    if ((d->flags & RPF_FLAG_GENERIC_WAVE) && (d->flags & (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) != (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) {
+    if ((d->flags & RPF_FLAG_WIDE_NBHD) && (d->flags & RPF_FLAG_FAST_WEIGHTS)) {
+        msg = "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_WIDE_NBHD: the wide layout-generic kernel is fp64 throughout";
+    } else if ((d->flags & RPF_FLAG_GENERIC_WAVE) && (d->flags & (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) != (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) {
         msg = "RPF_FLAG_GENERIC_WAVE without RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED: the flag modifies the packed layout-generic route";
     } else if ((d->flags & RPF_FLAG_GENERIC_WAVE) && (d->flags & RPF_FLAG_FAST_WEIGHTS)) {
         msg = "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_GENERIC_WAVE: the layout-generic kernels are fp64 throughout";
@@ -116,6 +120,13 @@ int32_t enter(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes) {
     return RPF_OK;
 }
 
+// T_w[k] = k ln k in 2^-41 fixed point (computed in long double, rounded once): 2^18 ln 2^18 * 2^41 = 7.19e18 < 2^63, where
+// the 2^-44 table of ensure_tables is 2^63 and more from k = 48586 on
+void wide_table(int nmax, uint64_t *out) {
+    out[0] = 0;
+    for (int k = 1; k <= nmax; ++k) out[k] = (uint64_t)std::llroundl(std::ldexp((long double)k * std::log((long double)k), kTWideBits));
+}
+
 namespace {
 
 // T[k] = k ln k in 2^-44 fixed point (computed in long double, rounded once) and its first differences
@@ -131,6 +142,18 @@ int32_t ensure_tables(rpf_ctx *ctx, int nmax) {
     HIP_TRY(hipMemcpy(ctx->d_tfix, t.data(), t.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(ctx->d_dfix, d.data(), d.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
     ctx->tfix_n = nmax + 1;
+    return RPF_OK;
+}
+
+// the wide kernel's table (RPF_FLAG_WIDE_NBHD)
+int32_t ensure_wide_table(rpf_ctx *ctx, int nmax) {
+    if (ctx->d_twide && ctx->twide_n >= nmax + 1) return RPF_OK;
+    std::vector<uint64_t> t((size_t)nmax + 1);
+    wide_table(nmax, t.data());
+    int32_t st;
+    if ((st = ctx->d_twide.ensure(ctx, t.size() * sizeof(uint64_t)))) return st;
+    HIP_TRY(hipMemcpy(ctx->d_twide, t.data(), t.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    ctx->twide_n = nmax + 1;
     return RPF_OK;
 }
 
@@ -155,8 +178,16 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     p.stage_mask = ctx->tun.stage_mask; // timing ablation knob (rpf_set_option); results are wrong unless -1
     p.screen = ctx->tun.screen;
     const int64_t nmax64 = (int64_t)box * box * d->S;
-    if (nmax64 > kMaxNbhd) return fail(ctx, RPF_E_UNSUPPORTED, "box*box*S > 65535: neighbourhood too large (16-bit histogram cells, one-byte bin ids)");
+    int32_t nbhd_cap = 0;
+    (void)rpf_max_nbhd(d, &nbhd_cap);
+    if (nmax64 > nbhd_cap)
+        return fail(ctx, RPF_E_UNSUPPORTED, nbhd_cap == kMaxNbhd
+            ? "box*box*S > 65535: neighbourhood too large (16-bit histogram cells, one-byte bin ids) without RPF_FLAG_WIDE_NBHD"
+            : "box*box*S > 262144: neighbourhood too large for the wide kernel of RPF_FLAG_WIDE_NBHD (16-bit bin ids, B <= 512)");
     p.nmax = (int)nmax64;
+    // a wide pass: every pixel on generic::filter_wide_kernel (option "wide" = 1: every pass of a call with the flag)
+    const bool wide = (d->flags & RPF_FLAG_WIDE_NBHD) && (p.nmax > kMaxNbhd || ctx->tun.wide == 1);
+    if (wide) p.generic |= 8;
     // the fused kernels address a window's samples by 32-bit byte offsets from its first sample (Window, rpf_filter_impl.inc)
     if (rpf_check_window_span(d->W, d->S, box) != RPF_OK)
         return fail(ctx, RPF_E_UNSUPPORTED, "box*W*S*8 >= 2^32: a window's span in bytes of an fp64 plane must fit 32 bits (narrower slabs or a smaller box)");
@@ -181,13 +212,17 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     if ((st = ctx->d_pmean.ensure(ctx, HW * kNFeat * sizeof(double)))) return st;
     if ((st = ctx->d_pstd.ensure(ctx, HW * kNFeat * sizeof(double)))) return st;
     if ((st = ctx->d_nbhd.ensure(ctx, HW * sizeof(int32_t)))) return st;
-    if ((st = ensure_tables(ctx, p.nmax))) return st;
+    // (the 2^-44 tables stop at the old cap: a wide pass reads them only where they are exact, launch_filter_binned)
+    if ((st = ensure_tables(ctx, std::min(p.nmax, kMaxNbhd)))) return st;
+    if (wide && (st = ensure_wide_table(ctx, p.nmax))) return st;
     p.pmean = ctx->d_pmean; p.pstd = ctx->d_pstd; p.tfix = ctx->d_tfix; p.dfix = ctx->d_dfix;
     p.nbhd = ctx->d_nbhd; p.status = ctx->d_status;
     if ((st = ctx->d_flat.ensure(ctx, HW))) return st;
     p.flat = ctx->d_flat; p.nan_flag = ctx->d_nan_flag;
     if (dbg_dev) p.dbg = *dbg_dev;
-    if (p.generic) { // the generic kernel's own carve-up (one kernel for every neighbourhood size of the pass)
+    if (wide) { // the wide kernel's carve-up: what 160 KiB leave of the joint table is one band of it
+        out.lds = generic_wide_carve(p.lay, p.nmax).total;
+    } else if (p.generic) { // the generic kernel's own carve-up (one kernel for every neighbourhood size of the pass)
         out.lds = generic_carve(p.lay, p.nmax).total;
     } else { // LDS of the largest resident kernel this pass can launch (larger neighbourhoods stream: generic::filter_pixel_kernel)
         const int nres = std::min(p.nmax, kMaxResident), bres = bmax_of(nres);
@@ -422,6 +457,30 @@ int32_t route_generic(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *lau
     return RPF_OK;
 }
 
+// The wide route (RPF_FLAG_WIDE_NBHD on a pass with box*box*S > 65535, or option "wide" = 1): one launch per pass, every pixel
+// on generic::filter_wide_kernel; no count pass, no classes, no redo list (the kernel evaluates the reference's MI expression
+// in place).  Member lists (u32) and bin ids (u16) in HBM slots sized by route_generic's rule without its floor: at most 1024,
+// within 1 GiB, never more than pixels.  The table: T_w (2^-41), or -- a forced pass below 48586 samples, where that one is
+// exact and three bits finer -- the 2^-44 table of the other kernels, so that such a pass gives route 3's bits.
+int32_t route_generic_wide(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *launches) {
+    Range rg("rpf:wide filter kernel");
+    ctx->last_route = 6;
+    if (p.policy == RPF_DEGEN_REF_ABORT) HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
+    if (p.row_end <= p.row_begin) return RPF_OK;
+    const uint64_t npix = (uint64_t)(p.row_end - p.row_begin) * p.W;
+    const size_t per_slot = (size_t)p.nmax * (4 + 2 * (size_t)p.lay.ndim());
+    const uint32_t slots = (uint32_t)std::min<uint64_t>(npix, std::max<size_t>(1, std::min<size_t>(1024, ((size_t)1 << 30) / per_slot)));
+    int32_t st;
+    if ((st = ctx->d_big_list.ensure(ctx, (size_t)slots * p.nmax * 4))) return st;
+    if ((st = ctx->d_big_bins.ensure(ctx, (size_t)slots * p.nmax * p.lay.ndim() * 2))) return st;
+    const bool fine = p.nmax <= kTFixExact;
+    if (!fine && (!ctx->d_twide || ctx->twide_n < p.nmax + 1)) return fail(ctx, RPF_E_BADARG, "wide pass without its table (setup_pass builds it)");
+    HIP_TRY(generic::launch_filter_wide(p, ctx->d_big_list, ctx->d_big_bins, slots, fine ? ctx->d_tfix.ptr : ctx->d_twide.ptr,
+                                        fine ? 44 : kTWideBits, s));
+    if (launches) ++*launches;
+    return RPF_OK;
+}
+
 // The layout-generic route with small neighbourhoods packed (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED, S <= 64): stage 1b
 // as its own launch (generic::nbhd_count_kernel: N and the acceptance masks), the pixels dealt by N -- the four lane classes
 // of generic::filter_packed_kernel, and the rest (N > 64) into the list generic::filter_pixel_kernel walks (it runs its own
@@ -549,6 +608,7 @@ int32_t route_generic_wave(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, 
 // LDS sized for its capacity (rpf_kernels.hip, "neighbourhood-size binning"); option "binning" = 0/1 overrides.
 // Needs stage 1a's planes (pmean / pstd) for those rows.  Synchronises the stream when it bins (list sizes).
 int32_t launch_filter_binned(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
+    if (p_in.generic & 8) return route_generic_wide(ctx, p_in, s, launches); // a wide pass (setup_pass marked it)
     // (above 64 spp N >= S fits no packed class, above 832 spp no one-wave class: the pass runs as route 3 does)
     if ((p_in.generic & 4) && p_in.S <= 832) return route_generic_wave(ctx, p_in, s, launches);
     if (p_in.generic) return (p_in.generic & 2) && p_in.S <= class_capacity(kNumPacked - 1) ? route_generic_packed(ctx, p_in, s, launches)
@@ -926,6 +986,18 @@ int32_t rpf_check_window_span(int32_t W, int32_t S, int32_t box) {
 
 int32_t rpf_layout_kernels(const rpf_desc *d, int32_t *generic_out) { return layout_kernels(d, generic_out, nullptr); }
 
+int32_t rpf_max_nbhd(const rpf_desc *d, int32_t *nmax_out) {
+    if (!d || !nmax_out) return RPF_E_BADARG;
+    *nmax_out = (d->flags & RPF_FLAG_WIDE_NBHD) ? kMaxWideNbhd : kMaxNbhd;
+    return RPF_OK;
+}
+
+int32_t rpf_wide_table(int32_t nmax, uint64_t *table_out) {
+    if (!table_out || nmax < 0 || nmax > kMaxWideNbhd) return RPF_E_BADARG;
+    wide_table(nmax, table_out);
+    return RPF_OK;
+}
+
 int64_t rpf_lds_bytes_required(int32_t S, int32_t box) {
     if (S <= 0 || box <= 0) return -1;
     const int64_t nmax = (int64_t)box * box * S;
@@ -996,6 +1068,7 @@ int32_t rpf_set_option(rpf_ctx *ctx, const char *name, int64_t value) {
     else if (n == "split_weights" && value >= -1 && value <= 1) t.split_weights = (int32_t)value;
     else if (n == "strip_w" && value >= 0 && value <= 4096 && value % 8 == 0) t.strip_w = (int32_t)value;
     else if (n == "packed" && value >= -1 && value <= 1) t.packed = (int32_t)value;
+    else if (n == "wide" && (value == -1 || value == 1)) t.wide = (int32_t)value;
     else if (n == "split_chunk" && value >= 0 && value <= (1 << 30)) t.split_chunk = (int32_t)value;
     else if (n == "count_first" && value >= -1 && value <= 1) t.count_first = (int32_t)value;
     else if (n == "lds_pad" && value >= 0 && value <= 160 * 1024) t.lds_pad = (int32_t)value;

@@ -36,6 +36,8 @@ struct PassParams {
     int32_t generic;       // RPF_FLAG_GENERIC: stage 1a and the filter pass run on the layout-generic kernels (rpf_generic.hip);
                            //   bit 1: RPF_FLAG_GENERIC_PACKED, small neighbourhoods on the packed generic kernels (rpf_generic_packed.hip)
                            //   bit 2: RPF_FLAG_GENERIC_WAVE, 64 < N <= 832 on the one-wave generic kernels (rpf_generic_wave.hip)
+                           //   bit 3: a wide pass (RPF_FLAG_WIDE_NBHD and box*box*S > 65535, or option "wide" = 1): every pixel on
+                           //          generic::filter_wide_kernel (rpf_generic_wide.hip), whatever the other bits say; stage 1a is not affected
     int32_t stage_mask;    // diagnostics only (rpf_set_option "stage_mask"): bit0 stats chain, bit1 bins, bit2 MI, bit3 weights; -1 = all
     int32_t screen;        // far-pair screen of the four-wave kernels: 0 off, 1 on
     int32_t strip_w;       // pixels per XCD strip of the pixel walk (slab_pixel)
@@ -89,8 +91,9 @@ struct Tuning {
     int32_t split_chunk = 0;     // split route: run its three launches chunk by chunk over this many list entries (0 = the whole list at once); same results
     int32_t strip_w = 0;         // pixels per XCD strip of the pixel walk: 0 auto (by box and spp), else a multiple of 8; same results
     int32_t count_first = -1;    // box*box*S <= 512: stage 1b as its own launch ahead of the filter kernels (the small-N route): -1 auto (probe), 0 off, 1 on; same results
+    int32_t wide = -1;           // RPF_FLAG_WIDE_NBHD: -1 auto (passes with box*box*S > 65535 on the wide kernel), 1 every pass of such a call (test hook)
     int32_t packed = -1;         // small neighbourhoods (N <= 64) on the packed kernels, several pixels per wave: -1 auto (on), 0 off, 1 on
-    bool is_default() const { return waves_per_pixel == 0 && table_in_lds == -1 && lds_pad == 0 && binning == -1 && stage_mask == -1 && screen == 1 && strip_w == 0 && split_chunk == 0 && count_first == -1 && split_weights == -1 && packed == -1; }
+    bool is_default() const { return waves_per_pixel == 0 && table_in_lds == -1 && lds_pad == 0 && binning == -1 && stage_mask == -1 && screen == 1 && strip_w == 0 && split_chunk == 0 && count_first == -1 && split_weights == -1 && packed == -1 && wide == -1; }
 };
 
 struct LdsLayout {
@@ -224,6 +227,27 @@ namespace generic {
 // the pixels of p.pix_list (p.list_count of them, 64 < N <= capacity = 128, 256, 448 or 832) from p.nbhd and p.masks; under
 // REF_ABORT p.redo_list / p.redo_count take the pixels that generic::filter_pixel_kernel must filter again
 hipError_t launch_filter_wave(const PassParams &p, int capacity, hipStream_t s);
+} // namespace generic
+
+// ---- the wide layout-generic kernel (rpf_generic_wide.hip, RPF_FLAG_WIDE_NBHD): 65535 < box*box*S <= 262144 ----------------
+constexpr int kMaxWideNbhd = 1 << 18; // B = floor(sqrt(N)) <= 512: a bin id fits 16 bits with room to spare
+constexpr int kTFixExact = 48585;     // the last k at which round(k ln k * 2^44) is below 2^63 (PassParams::tfix is exact up to here)
+constexpr int kTWideBits = 41;        // the wide table: round(k ln k * 2^41), below 2^63 up to k = 2^18
+// LDS carve-up of generic::filter_wide_kernel, a host-side function of the layout and the neighbourhood capacity only.  The
+// fp64 block and the chunk are generic_carve's, with marginals of 512 entries; member list and bin ids always live in HBM
+// slots; `band_words` 32-bit cells of the joint histogram follow (a band of floor(band_words / B) rows of the B x B table of a
+// pixel: the whole table where it fits, else whatever 160 KiB leave); red4 as in generic_carve.  total > 160 KiB: not even
+// one row of the widest table fits (no layout within RPF_MAX_NDIM reaches that).
+struct GenericWideCarve {
+    uint32_t off_chunk, off_hist, off_red4, band_words, total;
+};
+GenericWideCarve generic_wide_carve(const SampleLayout &lay, int nmax);
+namespace generic {
+// one launch filters rows [p.row_begin, p.row_end).  list / bins: global scratch of `slots` workgroups, [slots][nmax] u32 and
+// [slots][ndim][nmax] u16; the grid is min(pixels, slots).  table: round(k ln k * 2^table_bits), k = 0 .. p.nmax (p.tfix is
+// not read)
+hipError_t launch_filter_wide(const PassParams &p, void *list, void *bins, uint32_t slots, const uint64_t *table, int table_bits,
+                              hipStream_t s);
 } // namespace generic
 
 int max_lds_per_block();

@@ -25,6 +25,7 @@ FLAG_NO_OVERLAP = 4
 FLAG_GENERIC = 8  # the layout-generic kernels: required for a layout without compiled kernels, allowed for the two compiled ones
 FLAG_GENERIC_PACKED = 16  # with FLAG_GENERIC: neighbourhoods of N <= 64 samples on the packed generic kernels (route 4)
 FLAG_GENERIC_WAVE = 32  # with FLAG_GENERIC | FLAG_GENERIC_PACKED: 64 < N <= 832 on the one-wave generic kernels (route 5)
+FLAG_WIDE_NBHD = 64  # passes with 65535 < box*box*S <= 262144 on the wide layout-generic kernel (route 6); max_nbhd() tells the bound
 MAX_NDIM = 40     # the layout-generic kernels take 5 + n_random + n_feat up to this
 PLANES_F32, PLANES_F16 = 0, 1
 
@@ -34,7 +35,8 @@ EXPORTS = ["rpf_version", "rpf_status_string", "rpf_create", "rpf_destroy", "rpf
            "rpf_host_alloc", "rpf_host_free", "rpf_filter_ex", "rpf_set_option", "rpf_multi_create", "rpf_multi_destroy",
            "rpf_multi_last_error", "rpf_multi_device_count", "rpf_multi_set_option", "rpf_multi_filter",
            "rpf_multi_query_counters", "rpf_query_nbhd", "rpf_query_route", "rpf_film_filter_table", "rpf_filter_film",
-           "rpf_film_splat_device", "rpf_film_window", "rpf_multi_halo_plan", "rpf_multi_filter_film", "rpf_layout_kernels"]
+           "rpf_film_splat_device", "rpf_film_window", "rpf_multi_halo_plan", "rpf_multi_filter_film", "rpf_layout_kernels",
+           "rpf_max_nbhd", "rpf_wide_table"]
 
 # the film step: pbrt's PixelFilters (include/rpf_hip.h, rpf_film)
 PIXFILTER_BOX, PIXFILTER_TRIANGLE, PIXFILTER_GAUSSIAN, PIXFILTER_MITCHELL, PIXFILTER_SINC = range(5)
@@ -114,6 +116,23 @@ def layout_kernels(desc):
     g = C.c_int32(-1)
     st = load().rpf_layout_kernels(None if desc is None else C.byref(desc), C.byref(g))
     return st, (g.value if st == OK else None)
+
+
+def max_nbhd(desc):
+    """rpf_max_nbhd (no GPU needed): (status, nmax) -- the largest box*box*S a pass may have under the flags of `desc`: (OK, 65535),
+    or (OK, 262144) with FLAG_WIDE_NBHD; desc None: (E_BADARG, None)"""
+    n = C.c_int32(-1)
+    st = load().rpf_max_nbhd(None if desc is None else C.byref(desc), C.byref(n))
+    return st, (n.value if st == OK else None)
+
+
+def wide_table(nmax):
+    """rpf_wide_table (no GPU needed): uint64 [nmax + 1], round(k ln k * 2^41) -- the table the wide kernel forms MI from"""
+    out = np.empty(nmax + 1, np.uint64)
+    st = load().rpf_wide_table(int(nmax), _p(out))
+    if st != OK:
+        raise RpfError(st, "rpf_wide_table(nmax=%r): nmax outside [0, 262144]" % (nmax,))
+    return out
 
 
 def halo_plan(H, n_slabs, depth):
@@ -214,6 +233,9 @@ def load():
             L.rpf_multi_filter_film.argtypes = [C.c_void_p, C.POINTER(Desc), C.POINTER(Film)] + [C.c_void_p] * 6
         if hasattr(L, "rpf_layout_kernels"):  # (absent from a build of before the generic route, loaded through RPF_HIP_LIB)
             L.rpf_layout_kernels.argtypes = [C.POINTER(Desc), C.POINTER(C.c_int32)]
+        if hasattr(L, "rpf_max_nbhd"):  # (absent from a build of before the wide route, loaded through RPF_HIP_LIB)
+            L.rpf_max_nbhd.argtypes = [C.POINTER(Desc), C.POINTER(C.c_int32)]
+            L.rpf_wide_table.argtypes = [C.c_int32, C.c_void_p]
         L.rpf_host_alloc.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
         L.rpf_host_free.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
@@ -293,7 +315,8 @@ class Context:
     def route(self):
         """kernel route of the last pass: 0 fused, 1 count first, 2 size-binned, 3 the layout-generic kernels
         (FLAG_GENERIC), 4 the same with small neighbourhoods packed (FLAG_GENERIC_PACKED), 5 the same with
-        64 < N <= 832 on the one-wave generic kernels (FLAG_GENERIC_WAVE; 3 for a pass with S > 832); -1 before any pass
+        64 < N <= 832 on the one-wave generic kernels (FLAG_GENERIC_WAVE; 3 for a pass with S > 832), 6 the wide kernel
+        (FLAG_WIDE_NBHD on a pass with box*box*S > 65535); -1 before any pass
         (rpf_query_route)"""
         r = C.c_int32(-1)
         self._check(self._L.rpf_query_route(self._h, C.byref(r)))

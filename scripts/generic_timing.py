@@ -10,6 +10,9 @@ the launches and the mean neighbourhood size.  Cases (--case to pick by name):
   lay4_18      the smooth slab as (4, 18, fp32) with the flag
   box17        256x64x16 smooth, box 17 (N > 3136 for most pixels): 19-dim layout without the flag (the streaming kernel)
                and with it
+  wide57       256x57 smooth, box 57, one generated 21-spp buffer: its first 14 samples per pixel under RPF_FLAG_GENERIC
+               (box*box*S = 45486: route 3, the streaming kernel) and all 21 under RPF_FLAG_GENERIC | RPF_FLAG_WIDE_NBHD
+               (68229: route 6, the wide kernel, `generic` = 6); ns_per_pixel_sample = filter time / (pixels x mean N)
 Each case's variants run in one process on one context and on the same generated buffer; a route-4 or route-5 record
 carries ratio_to_route3 next to ratio_to_fused, a route-5 record ratio_to_route4 as well.
 A library loaded through RPF_HIP_LIB (a build variant) is measured by the same script."""
@@ -28,30 +31,35 @@ rpf_pkg.load()
 from raytracer_rpf_amd import feature_buffer as fb  # noqa: E402
 from raytracer_rpf_amd import hip  # noqa: E402
 
-# name: (W, H, S, box, flat_frac, [(n_random, n_feat, generic), ...])
+# name: (W, H, S, box, flat_frac, [(n_random, n_feat, generic[, S of this variant: the first samples of the buffer]), ...])
 CASES = {
     "smooth8": (1920, 270, 8, 7, 0.0, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3)]),
     "flat8": (1920, 270, 8, 7, 0.94, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3)]),
     "lay3_12": (1920, 270, 8, 7, 0.0, [(3, 12, 1), (3, 12, 2), (3, 12, 3)]),
     "lay4_18": (1920, 270, 8, 7, 0.0, [(4, 18, 1), (4, 18, 2), (4, 18, 3)]),
     "box17": (256, 64, 16, 17, 0.0, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3)]),
+    "wide57": (256, 57, 21, 57, 0.0, [(2, 12, 1, 14), (2, 12, 6, 21)]),
 }
 
 
 def run(ctx, name, steps):
-    W, H, S, box, flat, legs = CASES[name]
+    W, H, S_buf, box, flat, legs = CASES[name]
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream().cuda_stream
     out = {}
-    planes, made = None, None
-    for nr, nf, generic in legs:
+    whole, planes, made = None, None, None
+    for leg in legs:
+        nr, nf, generic = leg[:3]
+        S = leg[3] if len(leg) > 3 else S_buf
         if made != (nr, nf):  # one buffer for the variants of a layout
-            planes = fb.synth_planes_chunked(W, H, S, xp=fb.torch_backend(dev), seed=20261017, sigma_f=0.05, sigma_c=1e-4,
-                                             mode="smooth", flat_frac=flat, n_random=nr, n_feat=nf)
+            whole = fb.synth_planes_chunked(W, H, S_buf, xp=fb.torch_backend(dev), seed=20261017, sigma_f=0.05, sigma_c=1e-4,
+                                            mode="smooth", flat_frac=flat, n_random=nr, n_feat=nf)
             made = (nr, nf)
+        planes = whole if S == S_buf else whole[..., :S].contiguous()
         colour = torch.empty((3, H, W, S), dtype=torch.float64, device=dev)
-        flags = hip.FLAG_TIMING | (hip.FLAG_GENERIC if generic else 0) | (hip.FLAG_GENERIC_PACKED if generic >= 2 else 0)
+        flags = hip.FLAG_TIMING | (hip.FLAG_GENERIC if generic else 0) | (hip.FLAG_GENERIC_PACKED if generic in (2, 3) else 0)
         flags |= hip.FLAG_GENERIC_WAVE if generic == 3 else 0
+        flags |= hip.FLAG_WIDE_NBHD if generic == 6 else 0
         desc = hip.make_desc(W, H, S, boxes=(box,), policy=hip.DEGEN_EPS, flags=flags, n_random=nr, n_feat=nf)
         ms = []
         for it in range(steps + 1):
@@ -65,12 +73,14 @@ def run(ctx, name, steps):
                "mean_nbhd": round(c.sum_nbhd / (W * H), 1), "max_nbhd": c.max_nbhd,
                "filter_ms_min": round(min(ms), 3), "filter_ms_max": round(max(ms), 3), "stats_ms": round(c.stats_kernel_ms, 3),
                "colour_mean": float(colour.mean())}
+        if len(leg) > 3:
+            rec["ns_per_pixel_sample"] = round(rec["filter_ms_min"] * 1e6 / max(c.sum_nbhd, 1), 4)
         out[(nr, nf, generic)] = rec
         base = out.get((nr, nf, 0))
         if generic and base:
             rec["ratio_to_fused"] = round(rec["filter_ms_min"] / base["filter_ms_min"], 2)
         r3 = out.get((nr, nf, 1))
-        if generic >= 2 and r3:
+        if generic in (2, 3) and r3:
             rec["ratio_to_route3"] = round(rec["filter_ms_min"] / r3["filter_ms_min"], 3)
         r4 = out.get((nr, nf, 2))
         if generic == 3 and r4:
