@@ -113,7 +113,7 @@ enum {
                                   packed classes).  Without both RPF_FLAG_GENERIC and RPF_FLAG_GENERIC_PACKED, or together
                                   with RPF_FLAG_FAST_WEIGHTS, it is RPF_E_UNSUPPORTED, from every filter entry point and from
                                   rpf_layout_kernels, before any device work. */
-    RPF_FLAG_WIDE_NBHD = 64    /* opt-in: passes with 65535 < box*box*S <= 262144 (the reference's box list {55, 35, 17, 7} at
+    RPF_FLAG_WIDE_NBHD = 64,   /* opt-in: passes with 65535 < box*box*S <= 262144 (the reference's box list {55, 35, 17, 7} at
                                   32 spp: 55*55*32 = 96800) are accepted and run on the wide layout-generic kernel -- 16-bit bin
                                   ids, 32-bit histogram cells built in bands of rows, MI from a table of k ln k in 2^-41 fixed
                                   point.  Every pixel of such a pass runs on that kernel: one launch per pass,
@@ -125,6 +125,19 @@ enum {
                                   alongside and do not affect a wide pass.  fp64 throughout: together with
                                   RPF_FLAG_FAST_WEIGHTS it is RPF_E_UNSUPPORTED, from every filter entry point and from
                                   rpf_layout_kernels, before any device work. */
+    RPF_FLAG_WIDE_CLASSES = 128 /* opt-in, modifies RPF_FLAG_WIDE_NBHD: a wide pass (box*box*S > 65535, or option "wide" = 1) is
+                                  counted first and dealt by neighbourhood size -- a count kernel of its own lists the members
+                                  of every pixel with N <= 832 (no acceptance masks: the extra memory is O(pixels) plus the sum
+                                  of the listed N) and proves N = S without a walk for a pixel with a zero-variance feature --
+                                  and the packed (N <= 8, 16, 32, 64) and one-wave (N <= 128, 256, 448, 832) layout-generic
+                                  kernels take those pixels; only N > 832 stays on the wide kernel.  Same membership, bins,
+                                  statistics, N and counters sum_nbhd / max_nbhd as under the wide flag alone; MI, alpha, beta
+                                  and W_r_c agree to the rounding of the two k ln k tables, the colours to rounding.
+                                  rpf_query_route says 7 (6 for a wide pass with S > 832, which no class can hold and which
+                                  runs exactly as without this flag).  Every other pass of the call runs exactly as without
+                                  the flag.  It needs neither RPF_FLAG_GENERIC_PACKED nor RPF_FLAG_GENERIC_WAVE, which keep
+                                  steering the non-wide passes only.  Without RPF_FLAG_WIDE_NBHD it is RPF_E_UNSUPPORTED, from
+                                  every filter entry point and from rpf_layout_kernels, before any device work. */
 };
 
 typedef struct rpf_desc {
@@ -235,7 +248,10 @@ int32_t rpf_filter_ex(rpf_ctx *ctx, const rpf_desc *desc, const void *planes, co
  *                      box*box*S > 65535), 1 force (it takes every pass of such a call; a test hook: below 48586 samples it
  *                      then reads the 2^-44 table of the other kernels and gives the bits of route 3).  No effect without
  *                      the flag.
- * These names (but "wide") steer the fused routes only: a call with RPF_FLAG_GENERIC, with or without RPF_FLAG_GENERIC_PACKED, runs
+ *   "wide_pool"        wide passes of a call with RPF_FLAG_WIDE_CLASSES: entries of the member pool at the first count
+ *                      launch: -1 auto (default: 8 per pixel of the slab), else that many (a test hook: a pool the data
+ *                      exceeds is grown to the exact size and the count launch repeated; same results bit for bit)
+ * These names (but "wide" and "wide_pool") steer the fused routes only: a call with RPF_FLAG_GENERIC, with or without RPF_FLAG_GENERIC_PACKED, runs
  * the same kernels whatever they say (they are accepted and have no effect there; options_active still reports them).
  * rpf_counters.options_active tells whether a result was produced under any override. */
 int32_t rpf_set_option(rpf_ctx *ctx, const char *name, int64_t value);
@@ -282,7 +298,11 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *desc, int32_t box, c
  * and under RPF_DEGEN_REF_ABORT one for the redo launch; redo_pixels counts the pixels the packed and the one-wave kernels put
  * on the redo list.
  * A wide pass (RPF_FLAG_WIDE_NBHD, box*box*S > 65535: route 6) counts one launch and leaves redo_pixels 0, whatever the other
- * flags say: it has no count pass and no size classes. */
+ * flags say: it has no count pass and no size classes.
+ * With RPF_FLAG_WIDE_CLASSES as well (route 7) such a pass counts as route 5 does, with the wide kernel in place of the generic
+ * filter kernel: one launch per non-empty packed class, one per non-empty one-wave class, one for the wide kernel when some
+ * pixel has N > 832, and under RPF_DEGEN_REF_ABORT one for the redo launch (the wide kernel again); redo_pixels counts the
+ * pixels the packed and the one-wave kernels put on the redo list. */
 int32_t rpf_query_counters(rpf_ctx *ctx, rpf_counters *out);
 
 /* neighbourhood size N of every pixel (rpf.cpp:586: the neighbourhood vector's size) as the last pass of the most recent
@@ -297,6 +317,7 @@ int32_t rpf_query_nbhd(rpf_ctx *ctx, int32_t *nbhd_out, int64_t count);
  * statistics), 4 = the layout-generic kernels with small neighbourhoods packed (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED
  * on a pass with S <= 64), 5 = the same with 64 < N <= 832 on the one-wave layout-generic kernels (... | RPF_FLAG_GENERIC_WAVE
  * on a pass with S <= 832), 6 = the wide layout-generic kernel (RPF_FLAG_WIDE_NBHD on a pass with box*box*S > 65535),
+ * 7 = such a pass counted first and dealt by size class (... | RPF_FLAG_WIDE_CLASSES, S <= 832),
  * -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1. */
 int32_t rpf_query_route(rpf_ctx *ctx, int32_t *route_out);
 
@@ -351,7 +372,8 @@ int32_t rpf_multi_halo_plan(int32_t H, int32_t n_slabs, int32_t depth, int32_t *
  * entry point refuses the layout / flag combination (same function, so the two cannot drift) -- a layout without kernels,
  * RPF_FLAG_FAST_WEIGHTS on a layout other than the reference's 19 dims, or together with RPF_FLAG_GENERIC;
  * RPF_FLAG_GENERIC_PACKED without RPF_FLAG_GENERIC or with RPF_FLAG_FAST_WEIGHTS; RPF_FLAG_GENERIC_WAVE without both of
- * those flags or with RPF_FLAG_FAST_WEIGHTS; RPF_FLAG_WIDE_NBHD with RPF_FLAG_FAST_WEIGHTS; RPF_E_BADARG for a NULL desc.
+ * those flags or with RPF_FLAG_FAST_WEIGHTS; RPF_FLAG_WIDE_NBHD with RPF_FLAG_FAST_WEIGHTS; RPF_FLAG_WIDE_CLASSES without
+ * RPF_FLAG_WIDE_NBHD; RPF_E_BADARG for a NULL desc.
  * Only n_random, n_feat, plane_dtype and flags are read.  Needs no context and no device.  generic_out may be NULL. */
 int32_t rpf_layout_kernels(const rpf_desc *desc, int32_t *generic_out);
 

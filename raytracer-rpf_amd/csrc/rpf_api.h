@@ -65,7 +65,7 @@ struct rpf_ctx {
     rpf::DevBuf<int32_t> d_status;              // [0] bad count [1] first bad
     rpf::DevBuf<unsigned long long> d_nred;     // [0] sum N [1] max N
     rpf::DevBuf<uint32_t> d_lists;              // size binning: [kNumClasses][H*W] pixel lists
-    int last_route = -1;                        // last pass: 1 = count first, 0 = fused, 2 = size-binned, 3 = layout-generic, 4 = layout-generic with small neighbourhoods packed, 5 = ... and 64 < N <= 832 on the one-wave kernels, 6 = the wide kernel (rpf_query_route)
+    int last_route = -1;                        // last pass: 1 = count first, 0 = fused, 2 = size-binned, 3 = layout-generic, 4 = layout-generic with small neighbourhoods packed, 5 = ... and 64 < N <= 832 on the one-wave kernels, 6 = the wide kernel, 7 = a wide pass dealt by size class (rpf_query_route)
     rpf::DevBuf<uint32_t> d_class_counts;       // [kNumClasses] list sizes + [2] the route probe's counts
     rpf::DevBuf<uint64_t> d_masks;              // size binning: stage-1b acceptance masks [H*W][stride]
     rpf::DevBuf<char> d_big_list;               // streaming kernel: member lists [slots][nmax] u32
@@ -74,6 +74,10 @@ struct rpf_ctx {
     rpf::DevBuf<int32_t> d_nan_flag;            // ... and whether any feature mean of the buffer is NaN
     rpf::DevBuf<uint32_t> d_redo_list;          // REF_ABORT: pixels handed to the reference-expression kernel [H*W]
     rpf::DevBuf<uint32_t> d_redo_count;
+    // a wide pass dealt by size class (RPF_FLAG_WIDE_CLASSES, route 7): what its count kernel leaves for the class kernels
+    rpf::DevBuf<uint32_t> d_wc_pool;            // member pool: the N - S members behind the own samples of every pixel with N <= 832
+    rpf::DevBuf<uint64_t> d_wc_base;            // [H*W] a pixel's first pool entry
+    rpf::DevBuf<unsigned long long> d_wc_cursor; // [0] pool entries reserved, [1] (an int32) the NaN flag of the flat-pixel proof
     // membership depends on the features only, so within one call a pass with the same box and rows re-uses the
     // previous pass's masks and lists (reset at every API entry: the planes may change between calls)
     bool flat_fresh = false;                    // d_flat / d_nan_flag describe the planes of the call in progress (stage 1a ran in it)

@@ -40,13 +40,15 @@ SampleLayout layout_of(const rpf_desc *d) {
 // *generic_out = 0 (the compiled, fused kernels) or 1 (the layout-generic kernels, RPF_FLAG_GENERIC, with or without
 // RPF_FLAG_GENERIC_PACKED / RPF_FLAG_GENERIC_WAVE), else the refusal and its text in *why.  RPF_FLAG_WIDE_NBHD changes neither
 // answer (the wide kernel is layout-generic: both compiled layouts take the flag as they are); with RPF_FLAG_FAST_WEIGHTS it
-// is refused.
+// is refused.  RPF_FLAG_WIDE_CLASSES modifies the wide flag and is refused without it.
 int32_t layout_kernels(const rpf_desc *d, int32_t *generic_out, std::string *why) {
     if (!d) return RPF_E_BADARG;
     const SampleLayout lay = layout_of(d);
     int32_t generic = 0;
     const char *msg = nullptr;
-    if ((d->flags & RPF_FLAG_WIDE_NBHD) && (d->flags & RPF_FLAG_FAST_WEIGHTS)) {
+    if ((d->flags & RPF_FLAG_WIDE_CLASSES) && !(d->flags & RPF_FLAG_WIDE_NBHD)) {
+        msg = "RPF_FLAG_WIDE_CLASSES without RPF_FLAG_WIDE_NBHD: the flag modifies the wide route";
+    } else if ((d->flags & RPF_FLAG_WIDE_NBHD) && (d->flags & RPF_FLAG_FAST_WEIGHTS)) {
         msg = "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_WIDE_NBHD: the wide layout-generic kernel is fp64 throughout";
     } else if ((d->flags & RPF_FLAG_GENERIC_WAVE) && (d->flags & (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) != (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) {
         msg = "RPF_FLAG_GENERIC_WAVE without RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED: the flag modifies the packed layout-generic route";
@@ -188,6 +190,8 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     // a wide pass: every pixel on generic::filter_wide_kernel (option "wide" = 1: every pass of a call with the flag)
     const bool wide = (d->flags & RPF_FLAG_WIDE_NBHD) && (p.nmax > kMaxNbhd || ctx->tun.wide == 1);
     if (wide) p.generic |= 8;
+    // ... counted first and dealt by size class under RPF_FLAG_WIDE_CLASSES (above 832 spp no class can hold a pixel)
+    if (wide && (d->flags & RPF_FLAG_WIDE_CLASSES) && d->S <= 832) p.generic |= 16;
     // the fused kernels address a window's samples by 32-bit byte offsets from its first sample (Window, rpf_filter_impl.inc)
     if (rpf_check_window_span(d->W, d->S, box) != RPF_OK)
         return fail(ctx, RPF_E_UNSUPPORTED, "box*W*S*8 >= 2^32: a window's span in bytes of an fp64 plane must fit 32 bits (narrower slabs or a smaller box)");
@@ -457,6 +461,21 @@ int32_t route_generic(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *lau
     return RPF_OK;
 }
 
+// One launch of the wide kernel, over the slab's rows or over p.pix_list (p.list_count entries, or *count_dev of them), for at
+// most max_pixels pixels at a time: the slots and the table of route_generic_wide's comment.
+int32_t launch_wide(rpf_ctx *ctx, const PassParams &p, uint64_t max_pixels, const uint32_t *count_dev, hipStream_t s) {
+    const size_t per_slot = (size_t)p.nmax * (4 + 2 * (size_t)p.lay.ndim());
+    const uint32_t slots = (uint32_t)std::min<uint64_t>(max_pixels, std::max<size_t>(1, std::min<size_t>(1024, ((size_t)1 << 30) / per_slot)));
+    int32_t st;
+    if ((st = ctx->d_big_list.ensure(ctx, (size_t)slots * p.nmax * 4))) return st;
+    if ((st = ctx->d_big_bins.ensure(ctx, (size_t)slots * p.nmax * p.lay.ndim() * 2))) return st;
+    const bool fine = p.nmax <= kTFixExact;
+    if (!fine && (!ctx->d_twide || ctx->twide_n < p.nmax + 1)) return fail(ctx, RPF_E_BADARG, "wide pass without its table (setup_pass builds it)");
+    HIP_TRY(generic::launch_filter_wide(p, ctx->d_big_list, ctx->d_big_bins, slots, fine ? ctx->d_tfix.ptr : ctx->d_twide.ptr,
+                                        fine ? 44 : kTWideBits, count_dev, s));
+    return RPF_OK;
+}
+
 // The wide route (RPF_FLAG_WIDE_NBHD on a pass with box*box*S > 65535, or option "wide" = 1): one launch per pass, every pixel
 // on generic::filter_wide_kernel; no count pass, no classes, no redo list (the kernel evaluates the reference's MI expression
 // in place).  Member lists (u32) and bin ids (u16) in HBM slots sized by route_generic's rule without its floor: at most 1024,
@@ -467,17 +486,86 @@ int32_t route_generic_wide(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int
     ctx->last_route = 6;
     if (p.policy == RPF_DEGEN_REF_ABORT) HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
     if (p.row_end <= p.row_begin) return RPF_OK;
-    const uint64_t npix = (uint64_t)(p.row_end - p.row_begin) * p.W;
-    const size_t per_slot = (size_t)p.nmax * (4 + 2 * (size_t)p.lay.ndim());
-    const uint32_t slots = (uint32_t)std::min<uint64_t>(npix, std::max<size_t>(1, std::min<size_t>(1024, ((size_t)1 << 30) / per_slot)));
     int32_t st;
-    if ((st = ctx->d_big_list.ensure(ctx, (size_t)slots * p.nmax * 4))) return st;
-    if ((st = ctx->d_big_bins.ensure(ctx, (size_t)slots * p.nmax * p.lay.ndim() * 2))) return st;
-    const bool fine = p.nmax <= kTFixExact;
-    if (!fine && (!ctx->d_twide || ctx->twide_n < p.nmax + 1)) return fail(ctx, RPF_E_BADARG, "wide pass without its table (setup_pass builds it)");
-    HIP_TRY(generic::launch_filter_wide(p, ctx->d_big_list, ctx->d_big_bins, slots, fine ? ctx->d_tfix.ptr : ctx->d_twide.ptr,
-                                        fine ? 44 : kTWideBits, s));
+    if ((st = launch_wide(ctx, p, (uint64_t)(p.row_end - p.row_begin) * p.W, nullptr, s))) return st;
     if (launches) ++*launches;
+    return RPF_OK;
+}
+
+// A wide pass dealt by size class (RPF_FLAG_WIDE_NBHD | RPF_FLAG_WIDE_CLASSES, S <= 832): stage 1b as
+// its own launch (generic::wide_count_kernel: N, and the members of every pixel with N <= 832 in a member pool), the pixels
+// dealt into the eight classes of route_generic_wave and a rest class, one read-back (the list sizes and the pool cursor),
+// then one launch per non-empty class -- generic::filter_packed_kernel / filter_wave_kernel reading the listed members, with
+// the 2^-44 table, exact for N <= 832 -- and the wide kernel over the rest list (N > 832; its own stage 1b, route 6's table).
+// REF_ABORT: the class kernels' redo list goes to the wide kernel as well (generic::filter_pixel_kernel cannot hold the
+// window), its size read on the device.  The pool holds `wide_pool` entries (option; default 8 per pixel of the slab); when
+// the cursor says the data needed more, the pool is grown to exactly that and the count and the classification are repeated:
+// which kernel filters a pixel never depends on the capacity.
+int32_t route_generic_wide_classes(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
+    const size_t HW = (size_t)p_in.W * p_in.H;
+    int32_t st;
+    ctx->last_route = 7;
+    PassParams p = p_in;
+    p.redo_list = nullptr; p.redo_count = nullptr;
+    p.masks = nullptr; p.mask_stride = 0;
+    if (p.policy == RPF_DEGEN_REF_ABORT) {
+        HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
+        if ((st = ctx->d_redo_list.ensure(ctx, HW * sizeof(uint32_t)))) return st;
+        p.redo_list = ctx->d_redo_list; p.redo_count = ctx->d_redo_count;
+    }
+    if (p.row_end <= p.row_begin) return RPF_OK;
+    const uint64_t npix = (uint64_t)(p.row_end - p.row_begin) * p.W;
+    if ((st = ctx->d_lists.ensure(ctx, (size_t)kNumClasses * HW * sizeof(uint32_t)))) return st;
+    if ((st = ctx->d_wc_base.ensure(ctx, HW * sizeof(uint64_t)))) return st;
+    if ((st = ctx->d_wc_cursor.ensure(ctx, 2 * sizeof(unsigned long long)))) return st;
+    uint64_t capacity = ctx->tun.wide_pool >= 0 ? (uint64_t)ctx->tun.wide_pool : 8 * npix;
+    constexpr int kNumWave = 8; // classes 0 .. 3 packed, 4 .. 7 one wave per pixel (capacities 128, 256, 448, 832)
+    const int rest_class = kNumClasses - 1;
+    uint32_t counts[kNumClasses];
+    for (int attempt = 0;; ++attempt) {
+        Range rg("rpf:wide count + classify (stage 1b test, listed members, lane and wave classes)");
+        if ((st = ctx->d_wc_pool.ensure(ctx, (size_t)std::max<uint64_t>(capacity, 1) * sizeof(uint32_t)))) return st;
+        unsigned long long used = 0;
+        HIP_TRY(hipMemsetAsync(ctx->d_class_counts, 0, kNumClasses * sizeof(uint32_t), s));
+        HIP_TRY(generic::launch_wide_count(p, ctx->d_wc_pool, capacity, ctx->d_wc_base, ctx->d_wc_cursor,
+                                           reinterpret_cast<int32_t *>(ctx->d_wc_cursor.ptr + 1), s));
+        HIP_TRY(launch_classify(p, ctx->d_lists, ctx->d_class_counts, kNumWave, rest_class, s));
+        HIP_TRY(hipMemcpyAsync(counts, ctx->d_class_counts, sizeof(counts), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&used, ctx->d_wc_cursor, sizeof(used), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (used <= capacity) break;
+        if (attempt != 0) return fail(ctx, RPF_E_HIP, "wide count pass: the member pool overflowed at its exact size");
+        capacity = used; // the sum of N - S over the listed pixels: the same whatever the capacity was
+    }
+    p.members = ctx->d_wc_pool; p.member_base = ctx->d_wc_base;
+    for (int c = 0; c < kNumWave; ++c) {
+        if (counts[c] == 0) continue;
+        Range rg(c < kNumPacked ? "rpf:wide pass, packed class" : "rpf:wide pass, wave class");
+        PassParams q = p;
+        q.pix_list = ctx->d_lists + (size_t)c * HW;
+        q.list_count = counts[c];
+        if (c < kNumPacked) { HIP_TRY(generic::launch_filter_packed(q, class_capacity(c), s)); }
+        else { HIP_TRY(generic::launch_filter_wave(q, class_capacity(c), s)); }
+        if (launches) ++*launches;
+    }
+    PassParams w = p_in; // the wide kernel: as on route 6, over a list
+    if (counts[rest_class] != 0) {
+        Range rg("rpf:wide filter kernel (N > 832)");
+        w.pix_list = ctx->d_lists + (size_t)rest_class * HW;
+        w.list_count = counts[rest_class];
+        if ((st = launch_wide(ctx, w, w.list_count, nullptr, s))) return st;
+        if (launches) ++*launches;
+    }
+    if (p.redo_list != nullptr) {
+        Range rg("rpf:redo (wide kernel)");
+        w.pix_list = p.redo_list;
+        w.list_count = 0;
+        // (a fixed small grid whose workgroups find the list empty on ordinary frames, as launch_redo's: within 256 MiB of slots)
+        const size_t per_slot = (size_t)w.nmax * (4 + 2 * (size_t)w.lay.ndim());
+        const uint32_t grid = (uint32_t)std::max<size_t>(8, std::min<size_t>(64, ((size_t)256 << 20) / per_slot));
+        if ((st = launch_wide(ctx, w, grid, p.redo_count, s))) return st;
+        if (launches) ++*launches;
+    }
     return RPF_OK;
 }
 
@@ -608,6 +696,7 @@ int32_t route_generic_wave(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, 
 // LDS sized for its capacity (rpf_kernels.hip, "neighbourhood-size binning"); option "binning" = 0/1 overrides.
 // Needs stage 1a's planes (pmean / pstd) for those rows.  Synchronises the stream when it bins (list sizes).
 int32_t launch_filter_binned(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
+    if ((p_in.generic & 24) == 24) return route_generic_wide_classes(ctx, p_in, s, launches); // a wide pass dealt by size class
     if (p_in.generic & 8) return route_generic_wide(ctx, p_in, s, launches); // a wide pass (setup_pass marked it)
     // (above 64 spp N >= S fits no packed class, above 832 spp no one-wave class: the pass runs as route 3 does)
     if ((p_in.generic & 4) && p_in.S <= 832) return route_generic_wave(ctx, p_in, s, launches);
@@ -1069,6 +1158,7 @@ int32_t rpf_set_option(rpf_ctx *ctx, const char *name, int64_t value) {
     else if (n == "strip_w" && value >= 0 && value <= 4096 && value % 8 == 0) t.strip_w = (int32_t)value;
     else if (n == "packed" && value >= -1 && value <= 1) t.packed = (int32_t)value;
     else if (n == "wide" && (value == -1 || value == 1)) t.wide = (int32_t)value;
+    else if (n == "wide_pool" && value >= -1 && value <= ((int64_t)1 << 40)) t.wide_pool = value;
     else if (n == "split_chunk" && value >= 0 && value <= (1 << 30)) t.split_chunk = (int32_t)value;
     else if (n == "count_first" && value >= -1 && value <= 1) t.count_first = (int32_t)value;
     else if (n == "lds_pad" && value >= 0 && value <= 160 * 1024) t.lds_pad = (int32_t)value;

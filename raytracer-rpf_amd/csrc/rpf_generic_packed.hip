@@ -9,7 +9,8 @@
 // filter_packed_kernel<T, G>: the algorithm of rpf_packed_impl.inc with every column count a loop bound.  A pixel of the
 // class list (N <= G) gets G = 8, 16, 32 or 64 lanes, a wave filters 64 / G list entries at a time, lane g * G + t owns the
 // t-th sample of group g's neighbourhood in the reference's order (slot t < S: own sample t; else the (t - S)-th set bit of
-// the pixel's acceptance masks).  No per-thread array is indexed by a run-time column: the sample
+// the pixel's acceptance masks, or -- a wide pass dealt by size class, p.members -- the (t - S)-th listed member).  No
+// per-thread array is indexed by a run-time column: the sample
 // values stay staged in LDS as [group][column][slot] doubles for the whole unit, bin ids are LDS bytes and bit masks, and
 // the LDS carve-up comes from the host (generic_packed_carve).  After the table load the waves of a workgroup are
 // independent: one wave's LDS operations execute in order, so wsync() is all the hand-over between its lanes needs.
@@ -205,7 +206,9 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
         const int centre_rank = (x - x0) * nyv + (y - y0);
         const int ncand = ((x1 - x0 + 1) * nyv - 1) * S;
         uint32_t off = (uint32_t)(pix * S) + (uint32_t)min(t, S - 1); // own samples first
-        {
+        if (p.members != nullptr) { // (uniform) the listed members of a wide pass's count kernel, already in that order
+            if (live && t >= S) off = p.members[p.member_base[pix] + (uint64_t)(t - S)];
+        } else {
             int rank = (live && t >= S) ? t - S : -1;        // the rank-th accepted candidate of the window
             const int nwords = (ncand + 63) >> 6;
             const uint64_t *pm = p.masks + pix * p.mask_stride;
@@ -500,7 +503,9 @@ hipError_t launch_nbhd_count(const PassParams &p, hipStream_t s) {
 }
 
 hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, hipStream_t s) {
-    if (p.masks == nullptr || p.pix_list == nullptr || p.S > lanes_per_pixel || !p.lay.generic_ok()) return hipErrorInvalidValue;
+    if (p.pix_list == nullptr || p.S > lanes_per_pixel || !p.lay.generic_ok()) return hipErrorInvalidValue;
+    if (p.masks == nullptr && p.members == nullptr) return hipErrorInvalidValue; // one source of the member list
+    if (p.members != nullptr && p.member_base == nullptr) return hipErrorInvalidValue;
     if (p.policy == RPF_DEGEN_REF_ABORT && p.redo_list != nullptr && p.redo_count == nullptr) return hipErrorInvalidValue;
     if (p.list_count == 0) return hipSuccess;
     const GenericPackedCarve cv = generic_packed_carve(p.lay);

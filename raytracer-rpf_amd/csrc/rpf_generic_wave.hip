@@ -7,7 +7,8 @@
 // holds up to four such waves (generic_wave_carve: as many as fit 160 KiB), which share T[0 .. capacity] and the column table
 // of the MI pairs and are independent after that one barrier: one wave's LDS operations execute in order, so wsync() is all
 // the hand-over between its lanes needs.  Against generic::filter_pixel_kernel (four waves and a workgroup barrier at every
-// step, whatever N): no barrier; the member list comes from the count pass's acceptance masks (no second 3-sigma test); a
+// step, whatever N): no barrier; the member list comes from the count pass's acceptance masks, or from the members a wide
+// pass's count kernel listed (p.members), with no second 3-sigma test; a
 // member's columns are gathered once for both chains and the column minima / maxima, once for the bin ids and once per sweep
 // of stage 4 (four own samples), where a column's value is normalised once per sweep; the four sums of an own sample are
 // totalled across the 64 lanes by the all-reduce of rpf_xlane.h.
@@ -167,7 +168,10 @@ __global__ __launch_bounds__(256) void filter_wave_kernel(PassParams p, GenericW
         const int ncand = ((x1 - x0 + 1) * nyv - 1) * S;
         for (int s = lane; s < min(S, cap); s += 64) list[s] = (uint32_t)(pix * S + s); // own samples first
         if (lane == 0) sFlag[0] = 0;
-        {
+        if (p.members != nullptr) { // (uniform) the listed members of a wide pass's count kernel, already in that order
+            const uint32_t *src = p.members + p.member_base[pix];
+            for (int j = S + lane; j < n; j += 64) list[j] = src[j - S];
+        } else {
             const int nwords = min((ncand + 63) >> 6, (int)p.mask_stride);
             const uint64_t *pm = p.masks + pix * p.mask_stride;
             int base = S;
@@ -503,7 +507,8 @@ hipError_t launch_wave_t(const PassParams &p, const GenericWaveCarve &cv, hipStr
 } // namespace
 
 hipError_t launch_filter_wave(const PassParams &p, int capacity, hipStream_t s) {
-    if (p.masks == nullptr || p.pix_list == nullptr || p.S > capacity || capacity > 832 || (capacity & 63) != 0 || !p.lay.generic_ok())
+    if ((p.masks == nullptr && p.members == nullptr) || (p.members != nullptr && p.member_base == nullptr)) return hipErrorInvalidValue;
+    if (p.pix_list == nullptr || p.S > capacity || capacity > 832 || (capacity & 63) != 0 || !p.lay.generic_ok())
         return hipErrorInvalidValue;
     if (p.policy == RPF_DEGEN_REF_ABORT && p.redo_list != nullptr && p.redo_count == nullptr) return hipErrorInvalidValue;
     if (p.list_count == 0) return hipSuccess;

@@ -88,6 +88,7 @@ struct WideScratch {
     uint16_t *bins;        // [slots][ndim][nmax]  bin ids
     const uint64_t *table; // round(k ln k * 2^bits), k = 0 .. nmax
     int32_t bits;
+    const uint32_t *count_dev; // size of p.pix_list on the device, or null = p.list_count
 };
 
 template <class T>
@@ -123,7 +124,7 @@ __device__ __forceinline__ V block_reduce(V v, V *sRed4, Op op) {
     return op(op(sRed4[0], sRed4[1]), op(sRed4[2], sRed4[3]));
 }
 
-// One workgroup filters one pixel at a time and walks the pixels of rows [row_begin, row_end).
+// One workgroup filters one pixel at a time and walks the pixels of rows [row_begin, row_end), or those of p.pix_list.
 template <class T>
 __global__ __launch_bounds__(256) void filter_wide_kernel(PassParams p, GenericWideCarve cv, WideScratch gs) {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -149,9 +150,9 @@ __global__ __launch_bounds__(256) void filter_wide_kernel(PassParams p, GenericW
     const uint64_t *tw = gs.table;
     const double e_eps = (p.policy == RPF_DEGEN_EPS) ? p.eps : 0.0;
 
-    const uint32_t npix = (uint32_t)(p.row_end - p.row_begin) * (uint32_t)W;
+    const uint32_t npix = p.pix_list ? (gs.count_dev ? *gs.count_dev : p.list_count) : (uint32_t)(p.row_end - p.row_begin) * (uint32_t)W;
     for (uint32_t e = blockIdx.x; e < npix; e += gridDim.x) {
-        const uint64_t pix = (uint64_t)p.row_begin * W + e;
+        const uint64_t pix = p.pix_list ? (uint64_t)p.pix_list[e] : (uint64_t)p.row_begin * W + e;
         const int y = (int)(pix / (uint32_t)W), x = (int)(pix - (uint64_t)y * W);
         __syncthreads(); // the previous pixel's LDS is dead
 
@@ -554,17 +555,18 @@ hipError_t launch_filter_wide_t(const PassParams &p, const GenericWideCarve &cv,
 } // namespace
 
 hipError_t launch_filter_wide(const PassParams &p, void *list, void *bins, uint32_t slots, const uint64_t *table, int table_bits,
-                              hipStream_t s) {
+                              const uint32_t *count_dev, hipStream_t s) {
     const GenericWideCarve cv = generic_wide_carve(p.lay, p.nmax);
     if ((int)cv.total > max_lds_per_block() || cv.total > kLdsBudget) return hipErrorInvalidValue;
-    if (p.nmax < 1 || p.nmax > kMaxWideNbhd || p.pix_list != nullptr) return hipErrorInvalidValue;
+    if (p.nmax < 1 || p.nmax > kMaxWideNbhd || (count_dev != nullptr && p.pix_list == nullptr)) return hipErrorInvalidValue;
     if (cv.band_words < (uint32_t)std::max(1.0, std::floor(std::sqrt((double)p.nmax)))) return hipErrorInvalidValue; // a band holds a row of the widest table
     if (p.row_end <= p.row_begin) return hipSuccess;
+    if (p.pix_list != nullptr && count_dev == nullptr && p.list_count == 0) return hipSuccess;
     if (list == nullptr || bins == nullptr || table == nullptr || slots == 0) return hipErrorInvalidValue;
-    const uint64_t npix = (uint64_t)(p.row_end - p.row_begin) * p.W;
+    const uint64_t npix = p.pix_list ? (count_dev ? (uint64_t)slots : (uint64_t)p.list_count) : (uint64_t)(p.row_end - p.row_begin) * p.W;
     const unsigned grid = (unsigned)std::min<uint64_t>(npix, slots);
     WideScratch gs;
-    gs.list = (uint32_t *)list; gs.bins = (uint16_t *)bins; gs.table = table; gs.bits = table_bits;
+    gs.list = (uint32_t *)list; gs.bins = (uint16_t *)bins; gs.table = table; gs.bits = table_bits; gs.count_dev = count_dev;
     return p.lay.f16 ? launch_filter_wide_t<__half>(p, cv, gs, grid, s) : launch_filter_wide_t<float>(p, cv, gs, grid, s);
 }
 

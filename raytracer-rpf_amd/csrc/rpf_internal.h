@@ -38,6 +38,8 @@ struct PassParams {
                            //   bit 2: RPF_FLAG_GENERIC_WAVE, 64 < N <= 832 on the one-wave generic kernels (rpf_generic_wave.hip)
                            //   bit 3: a wide pass (RPF_FLAG_WIDE_NBHD and box*box*S > 65535, or option "wide" = 1): every pixel on
                            //          generic::filter_wide_kernel (rpf_generic_wide.hip), whatever the other bits say; stage 1a is not affected
+                           //   bit 4: with bit 3, RPF_FLAG_WIDE_CLASSES and S <= 832: the wide pass is counted first and dealt by size class
+                           //          (route_generic_wide_classes); only N > 832 stays on the wide kernel
     int32_t stage_mask;    // diagnostics only (rpf_set_option "stage_mask"): bit0 stats chain, bit1 bins, bit2 MI, bit3 weights; -1 = all
     int32_t screen;        // far-pair screen of the four-wave kernels: 0 off, 1 on
     int32_t strip_w;       // pixels per XCD strip of the pixel walk (slab_pixel)
@@ -75,6 +77,11 @@ struct PassParams {
     uint32_t *redo_count;  //   appended here and filtered again by generic::filter_pixel_kernel (reference expression); or null
     int32_t *status;       // [0] count of NaN pixels, [1] lowest bad pixel index (atomicMin)
     rpf_debug dbg;         // device pointers, any may be null
+    // a wide pass dealt by size class (route 7): the packed and one-wave layout-generic kernels take a pixel's members behind
+    // its own samples from members[member_base[pix] ..], N - S plane offsets in the reference's order (generic::wide_count_kernel
+    // wrote them), instead of rebuilding them from `masks`; or null
+    const uint32_t *members;
+    const uint64_t *member_base; // [H*W]
 };
 
 // Per-context tuning / diagnostic overrides (rpf_set_option).  Defaults = the library's own choices; nothing here is
@@ -93,7 +100,8 @@ struct Tuning {
     int32_t count_first = -1;    // box*box*S <= 512: stage 1b as its own launch ahead of the filter kernels (the small-N route): -1 auto (probe), 0 off, 1 on; same results
     int32_t wide = -1;           // RPF_FLAG_WIDE_NBHD: -1 auto (passes with box*box*S > 65535 on the wide kernel), 1 every pass of such a call (test hook)
     int32_t packed = -1;         // small neighbourhoods (N <= 64) on the packed kernels, several pixels per wave: -1 auto (on), 0 off, 1 on
-    bool is_default() const { return waves_per_pixel == 0 && table_in_lds == -1 && lds_pad == 0 && binning == -1 && stage_mask == -1 && screen == 1 && strip_w == 0 && split_chunk == 0 && count_first == -1 && split_weights == -1 && packed == -1 && wide == -1; }
+    int64_t wide_pool = -1;      // RPF_FLAG_WIDE_CLASSES: entries of the member pool at the first count launch: -1 auto (8 per pixel of the slab), else that many (test hook: a pool too small is grown to the exact size and the count launch repeated; same results)
+    bool is_default() const { return waves_per_pixel == 0 && table_in_lds == -1 && lds_pad == 0 && binning == -1 && stage_mask == -1 && screen == 1 && strip_w == 0 && split_chunk == 0 && count_first == -1 && split_weights == -1 && packed == -1 && wide == -1 && wide_pool == -1; }
 };
 
 struct LdsLayout {
@@ -243,11 +251,19 @@ struct GenericWideCarve {
 };
 GenericWideCarve generic_wide_carve(const SampleLayout &lay, int nmax);
 namespace generic {
-// one launch filters rows [p.row_begin, p.row_end).  list / bins: global scratch of `slots` workgroups, [slots][nmax] u32 and
-// [slots][ndim][nmax] u16; the grid is min(pixels, slots).  table: round(k ln k * 2^table_bits), k = 0 .. p.nmax (p.tfix is
-// not read)
+// one launch filters rows [p.row_begin, p.row_end), or the pixels of p.pix_list when that is given (the rest class and the
+// redo list of route 7).  list / bins: global scratch of `slots` workgroups, [slots][nmax] u32 and [slots][ndim][nmax] u16; the
+// grid is min(pixels, slots).  table: round(k ln k * 2^table_bits), k = 0 .. p.nmax (p.tfix is not read).  count_dev != null:
+// the size of p.pix_list is read from device memory (redo list: no host read-back), grid = slots
 hipError_t launch_filter_wide(const PassParams &p, void *list, void *bins, uint32_t slots, const uint64_t *table, int table_bits,
-                              hipStream_t s);
+                              const uint32_t *count_dev, hipStream_t s);
+// the count pass of route 7 (rpf_generic_wide_count.hip, S <= 832): for every pixel of rows [p.row_begin, p.row_end) N into
+// p.nbhd -- 833 for any N > 832 -- and, for S < N <= 832, the N - S members behind the own samples into pool[base[pix] ..];
+// *cursor ends at the sum of those N - S, whether or not `capacity` entries held them (a pool too small loses writes only:
+// the caller compares and repeats).  nan_flag: [1], scratch of the flat-pixel proof.  Reads stage 1a's planes of the rows
+// the slab's windows reach
+hipError_t launch_wide_count(const PassParams &p, uint32_t *pool, uint64_t capacity, uint64_t *base, unsigned long long *cursor,
+                             int32_t *nan_flag, hipStream_t s);
 } // namespace generic
 
 int max_lds_per_block();

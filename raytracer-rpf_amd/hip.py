@@ -25,6 +25,7 @@ FLAG_NO_OVERLAP = 4
 FLAG_GENERIC = 8  # the layout-generic kernels: required for a layout without compiled kernels, allowed for the two compiled ones
 FLAG_GENERIC_PACKED = 16  # with FLAG_GENERIC: neighbourhoods of N <= 64 samples on the packed generic kernels (route 4)
 FLAG_GENERIC_WAVE = 32  # with FLAG_GENERIC | FLAG_GENERIC_PACKED: 64 < N <= 832 on the one-wave generic kernels (route 5)
+FLAG_WIDE_CLASSES = 128  # with FLAG_WIDE_NBHD: a wide pass counted first and dealt by size class (route 7; 6 for a pass with S > 832)
 FLAG_WIDE_NBHD = 64  # passes with 65535 < box*box*S <= 262144 on the wide layout-generic kernel (route 6); max_nbhd() tells the bound
 MAX_NDIM = 40     # the layout-generic kernels take 5 + n_random + n_feat up to this
 PLANES_F32, PLANES_F16 = 0, 1
@@ -316,7 +317,8 @@ class Context:
         """kernel route of the last pass: 0 fused, 1 count first, 2 size-binned, 3 the layout-generic kernels
         (FLAG_GENERIC), 4 the same with small neighbourhoods packed (FLAG_GENERIC_PACKED), 5 the same with
         64 < N <= 832 on the one-wave generic kernels (FLAG_GENERIC_WAVE; 3 for a pass with S > 832), 6 the wide kernel
-        (FLAG_WIDE_NBHD on a pass with box*box*S > 65535); -1 before any pass
+        (FLAG_WIDE_NBHD on a pass with box*box*S > 65535), 7 such a pass dealt by size class (FLAG_WIDE_CLASSES); -1 before
+        any pass
         (rpf_query_route)"""
         r = C.c_int32(-1)
         self._check(self._L.rpf_query_route(self._h, C.byref(r)))

@@ -12,7 +12,13 @@ the launches and the mean neighbourhood size.  Cases (--case to pick by name):
                and with it
   wide57       256x57 smooth, box 57, one generated 21-spp buffer: its first 14 samples per pixel under RPF_FLAG_GENERIC
                (box*box*S = 45486: route 3, the streaming kernel) and all 21 under RPF_FLAG_GENERIC | RPF_FLAG_WIDE_NBHD
-               (68229: route 6, the wide kernel, `generic` = 6); ns_per_pixel_sample = filter time / (pixels x mean N)
+               (68229: route 6, the wide kernel, `generic` = 6) and | RPF_FLAG_WIDE_CLASSES (route 7, `generic` = 7: nearly
+               every pixel still goes to the wide kernel, so the difference is what the count pass costs when it buys
+               nothing); ns_per_pixel_sample = filter time / (pixels x mean N)
+  flat57       the same geometry with flat_frac = 0.94 (the captured-like small-N regime) under route 6 and under route 7
+  flat55       a 1920x64 slab at 32 spp, box 55 (96800: the reference's first box), flat_frac = 0.94, routes 6 and 7: many
+               rounds of the wide kernel's slots (seconds per step; not in the default case list's spirit: pick it by name)
+A record of a wide pass carries the class census of its N plane (pixels with N <= 8, 16, ... 832, and the rest).
 Each case's variants run in one process on one context and on the same generated buffer; a route-4 or route-5 record
 carries ratio_to_route3 next to ratio_to_fused, a route-5 record ratio_to_route4 as well.
 A library loaded through RPF_HIP_LIB (a build variant) is measured by the same script."""
@@ -38,8 +44,11 @@ CASES = {
     "lay3_12": (1920, 270, 8, 7, 0.0, [(3, 12, 1), (3, 12, 2), (3, 12, 3)]),
     "lay4_18": (1920, 270, 8, 7, 0.0, [(4, 18, 1), (4, 18, 2), (4, 18, 3)]),
     "box17": (256, 64, 16, 17, 0.0, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3)]),
-    "wide57": (256, 57, 21, 57, 0.0, [(2, 12, 1, 14), (2, 12, 6, 21)]),
+    "wide57": (256, 57, 21, 57, 0.0, [(2, 12, 1, 14), (2, 12, 6, 21), (2, 12, 7, 21)]),
+    "flat57": (256, 57, 21, 57, 0.94, [(2, 12, 6, 21), (2, 12, 7, 21)]),
+    "flat55": (1920, 64, 32, 55, 0.94, [(2, 12, 6, 32), (2, 12, 7, 32)]),
 }
+CLASS_CAPS = (8, 16, 32, 64, 128, 256, 448, 832)
 
 
 def run(ctx, name, steps):
@@ -59,7 +68,8 @@ def run(ctx, name, steps):
         colour = torch.empty((3, H, W, S), dtype=torch.float64, device=dev)
         flags = hip.FLAG_TIMING | (hip.FLAG_GENERIC if generic else 0) | (hip.FLAG_GENERIC_PACKED if generic in (2, 3) else 0)
         flags |= hip.FLAG_GENERIC_WAVE if generic == 3 else 0
-        flags |= hip.FLAG_WIDE_NBHD if generic == 6 else 0
+        flags |= hip.FLAG_WIDE_NBHD if generic in (6, 7) else 0
+        flags |= hip.FLAG_WIDE_CLASSES if generic == 7 else 0
         desc = hip.make_desc(W, H, S, boxes=(box,), policy=hip.DEGEN_EPS, flags=flags, n_random=nr, n_feat=nf)
         ms = []
         for it in range(steps + 1):
@@ -73,6 +83,13 @@ def run(ctx, name, steps):
                "mean_nbhd": round(c.sum_nbhd / (W * H), 1), "max_nbhd": c.max_nbhd,
                "filter_ms_min": round(min(ms), 3), "filter_ms_max": round(max(ms), 3), "stats_ms": round(c.stats_kernel_ms, 3),
                "colour_mean": float(colour.mean())}
+        if generic in (6, 7):
+            n = ctx.nbhd(W, H).ravel()
+            lo = (0,) + CLASS_CAPS[:-1]
+            rec["census"] = [int(((n > a) & (n <= b)).sum()) for a, b in zip(lo, CLASS_CAPS)] + [int((n > CLASS_CAPS[-1]).sum())]
+        r6 = out.get((nr, nf, 6))
+        if generic == 7 and r6:
+            rec["ratio_to_route6"] = round(rec["filter_ms_min"] / r6["filter_ms_min"], 4)
         if len(leg) > 3:
             rec["ns_per_pixel_sample"] = round(rec["filter_ms_min"] * 1e6 / max(c.sum_nbhd, 1), 4)
         out[(nr, nf, generic)] = rec
@@ -92,7 +109,7 @@ def run(ctx, name, steps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--case", nargs="*", default=list(CASES))
+    ap.add_argument("--case", nargs="*", default=[c for c in CASES if c != "flat55"])
     a = ap.parse_args()
     print(json.dumps({"library": hip.LIB_PATH, "version": hip.load().rpf_version().decode()}), flush=True)
     with hip.Context(0) as ctx:
