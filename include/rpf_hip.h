@@ -125,7 +125,7 @@ enum {
                                   alongside and do not affect a wide pass.  fp64 throughout: together with
                                   RPF_FLAG_FAST_WEIGHTS it is RPF_E_UNSUPPORTED, from every filter entry point and from
                                   rpf_layout_kernels, before any device work. */
-    RPF_FLAG_WIDE_CLASSES = 128 /* opt-in, modifies RPF_FLAG_WIDE_NBHD: a wide pass (box*box*S > 65535, or option "wide" = 1) is
+    RPF_FLAG_WIDE_CLASSES = 128, /* opt-in, modifies RPF_FLAG_WIDE_NBHD: a wide pass (box*box*S > 65535, or option "wide" = 1) is
                                   counted first and dealt by neighbourhood size -- a count kernel of its own lists the members
                                   of every pixel with N <= 832 (no acceptance masks: the extra memory is O(pixels) plus the sum
                                   of the listed N) and proves N = S without a walk for a pixel with a zero-variance feature --
@@ -138,6 +138,23 @@ enum {
                                   the flag.  It needs neither RPF_FLAG_GENERIC_PACKED nor RPF_FLAG_GENERIC_WAVE, which keep
                                   steering the non-wide passes only.  Without RPF_FLAG_WIDE_NBHD it is RPF_E_UNSUPPORTED, from
                                   every filter entry point and from rpf_layout_kernels, before any device work. */
+    RPF_FLAG_GENERIC_FAST = 256 /* opt-in, modifies RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED (with or without
+                                  RPF_FLAG_GENERIC_WAVE): on a pass that takes route 4 or 5 the packed kernels (N <= 64) and,
+                                  with the wave flag, the one-wave kernels (64 < N <= 832) evaluate the S x N pair weights of
+                                  stage 4 in fp32 -- z = (x - M) / SD and the 5 + n_feat coefficients formed in fp64 and rounded
+                                  once, differences, squares and the weighted sum in fp32, ONE hardware exponential of the
+                                  summed exponent, the weights widened to fp64, both sums and the quotient in fp64.  Any layout
+                                  the generic flag takes, fp32 or fp16 planes.  Membership, bins, statistics, MI, alpha, beta
+                                  and W_r_c are the bits of the same flags without this one; the colours move by ~1e-8
+                                  relative (bar 1e-4).  Filtered in fp64 under the flag as well, bit for bit as without it: the
+                                  rest list (N > 64, or N > 832 with the wave flag) on the generic filter kernel; under
+                                  RPF_DEGEN_REF_ABORT a pixel on the redo list (rpf_counters.redo_pixels); a pass that falls
+                                  back to route 3 (S > 64, or S > 832 with the wave flag).  rpf_query_route keeps saying 4 / 5,
+                                  filter_kernel_launches and redo_pixels count as without the flag.  RPF_FLAG_FAST_WEIGHTS keeps
+                                  its meaning and its refusals.  Without both RPF_FLAG_GENERIC and RPF_FLAG_GENERIC_PACKED,
+                                  together with RPF_FLAG_FAST_WEIGHTS, or together with RPF_FLAG_WIDE_NBHD (wide passes are fp64
+                                  throughout) it is RPF_E_UNSUPPORTED, from every filter entry point and from
+                                  rpf_layout_kernels, before any device work. */
 };
 
 typedef struct rpf_desc {
@@ -373,7 +390,9 @@ int32_t rpf_multi_halo_plan(int32_t H, int32_t n_slabs, int32_t depth, int32_t *
  * RPF_FLAG_FAST_WEIGHTS on a layout other than the reference's 19 dims, or together with RPF_FLAG_GENERIC;
  * RPF_FLAG_GENERIC_PACKED without RPF_FLAG_GENERIC or with RPF_FLAG_FAST_WEIGHTS; RPF_FLAG_GENERIC_WAVE without both of
  * those flags or with RPF_FLAG_FAST_WEIGHTS; RPF_FLAG_WIDE_NBHD with RPF_FLAG_FAST_WEIGHTS; RPF_FLAG_WIDE_CLASSES without
- * RPF_FLAG_WIDE_NBHD; RPF_E_BADARG for a NULL desc.
+ * RPF_FLAG_WIDE_NBHD; RPF_FLAG_GENERIC_FAST without both RPF_FLAG_GENERIC and RPF_FLAG_GENERIC_PACKED, with
+ * RPF_FLAG_FAST_WEIGHTS or with RPF_FLAG_WIDE_NBHD (where it is accepted, *generic_out is 1 as without it); RPF_E_BADARG for a
+ * NULL desc.
  * Only n_random, n_feat, plane_dtype and flags are read.  Needs no context and no device.  generic_out may be NULL. */
 int32_t rpf_layout_kernels(const rpf_desc *desc, int32_t *generic_out);
 

@@ -40,7 +40,9 @@ SampleLayout layout_of(const rpf_desc *d) {
 // *generic_out = 0 (the compiled, fused kernels) or 1 (the layout-generic kernels, RPF_FLAG_GENERIC, with or without
 // RPF_FLAG_GENERIC_PACKED / RPF_FLAG_GENERIC_WAVE), else the refusal and its text in *why.  RPF_FLAG_WIDE_NBHD changes neither
 // answer (the wide kernel is layout-generic: both compiled layouts take the flag as they are); with RPF_FLAG_FAST_WEIGHTS it
-// is refused.  RPF_FLAG_WIDE_CLASSES modifies the wide flag and is refused without it.
+// is refused.  RPF_FLAG_WIDE_CLASSES modifies the wide flag and is refused without it.  RPF_FLAG_GENERIC_FAST (fp32 pair
+// weights on the packed and one-wave layout-generic kernels) changes no answer either; it is refused without both
+// RPF_FLAG_GENERIC and RPF_FLAG_GENERIC_PACKED, with RPF_FLAG_FAST_WEIGHTS and with RPF_FLAG_WIDE_NBHD.
 int32_t layout_kernels(const rpf_desc *d, int32_t *generic_out, std::string *why) {
     if (!d) return RPF_E_BADARG;
     const SampleLayout lay = layout_of(d);
@@ -48,6 +50,12 @@ int32_t layout_kernels(const rpf_desc *d, int32_t *generic_out, std::string *why
     const char *msg = nullptr;
     if ((d->flags & RPF_FLAG_WIDE_CLASSES) && !(d->flags & RPF_FLAG_WIDE_NBHD)) {
         msg = "RPF_FLAG_WIDE_CLASSES without RPF_FLAG_WIDE_NBHD: the flag modifies the wide route";
+    } else if ((d->flags & RPF_FLAG_GENERIC_FAST) && (d->flags & (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) != (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) {
+        msg = "RPF_FLAG_GENERIC_FAST without RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED: the flag modifies the packed layout-generic route";
+    } else if ((d->flags & RPF_FLAG_GENERIC_FAST) && (d->flags & RPF_FLAG_FAST_WEIGHTS)) {
+        msg = "RPF_FLAG_GENERIC_FAST with RPF_FLAG_FAST_WEIGHTS: that flag selects the fused fp32 kernels of the 19-dim layout, this one the layout-generic ones";
+    } else if ((d->flags & RPF_FLAG_GENERIC_FAST) && (d->flags & RPF_FLAG_WIDE_NBHD)) {
+        msg = "RPF_FLAG_GENERIC_FAST with RPF_FLAG_WIDE_NBHD: wide passes are fp64 throughout";
     } else if ((d->flags & RPF_FLAG_WIDE_NBHD) && (d->flags & RPF_FLAG_FAST_WEIGHTS)) {
         msg = "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_WIDE_NBHD: the wide layout-generic kernel is fp64 throughout";
     } else if ((d->flags & RPF_FLAG_GENERIC_WAVE) && (d->flags & (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) != (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) {
@@ -177,6 +185,7 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     p.beta_map = d->beta_map; p.policy = d->degenerate_policy;
     p.fast_weights = (d->flags & RPF_FLAG_FAST_WEIGHTS) ? 1 : 0;
     p.generic = (d->flags & RPF_FLAG_GENERIC) ? (1 | ((d->flags & RPF_FLAG_GENERIC_PACKED) ? 2 : 0) | ((d->flags & RPF_FLAG_GENERIC_WAVE) ? 4 : 0)) : 0;
+    if (d->flags & RPF_FLAG_GENERIC_FAST) p.generic |= 32; // (validate: only with G | P; read by routes 4 and 5, never by the fused code)
     p.stage_mask = ctx->tun.stage_mask; // timing ablation knob (rpf_set_option); results are wrong unless -1
     p.screen = ctx->tun.screen;
     const int64_t nmax64 = (int64_t)box * box * d->S;
@@ -607,7 +616,7 @@ int32_t route_generic_packed(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s
         PassParams q = p;
         q.pix_list = ctx->d_lists + (size_t)c * HW;
         q.list_count = counts[c];
-        HIP_TRY(generic::launch_filter_packed(q, class_capacity(c), s));
+        HIP_TRY(generic::launch_filter_packed(q, class_capacity(c), s, (p.generic & 32) != 0));
         if (launches) ++*launches;
     }
     if (counts[rest_class] != 0) {
@@ -667,8 +676,8 @@ int32_t route_generic_wave(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, 
         PassParams q = p;
         q.pix_list = ctx->d_lists + (size_t)c * HW;
         q.list_count = counts[c];
-        if (c < kNumPacked) { HIP_TRY(generic::launch_filter_packed(q, class_capacity(c), s)); }
-        else { HIP_TRY(generic::launch_filter_wave(q, class_capacity(c), s)); }
+        if (c < kNumPacked) { HIP_TRY(generic::launch_filter_packed(q, class_capacity(c), s, (p.generic & 32) != 0)); }
+        else { HIP_TRY(generic::launch_filter_wave(q, class_capacity(c), s, (p.generic & 32) != 0)); }
         if (launches) ++*launches;
     }
     if (counts[rest_class] != 0) {

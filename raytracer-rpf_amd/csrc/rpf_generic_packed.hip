@@ -23,6 +23,11 @@
 // differently).  Under
 // REF_ABORT a pixel with a table inside the zero band at a non-power-of-two N and non-degenerate marginals joins the redo
 // list (the rule of rpf_packed_impl.inc) and generic::filter_pixel_kernel filters it again, whole.
+//
+// filter_packed_kernel<T, G, FAST = true> (RPF_FLAG_GENERIC_FAST): the same kernel with stage 4 in fp32 --
+// z and the 5 + n_feat coefficients (log2 e folded in) formed in fp64 and rounded once, one accumulator per own sample, two own
+// samples per packed fp32 instruction, one hardware exponential, the sums and the quotient in fp64.  Every statement outside
+// stage 4 is shared, so the stage outputs are the FAST = false kernel's bits.
 #include "rpf_device_common.h"
 
 #include <algorithm>
@@ -52,6 +57,15 @@ GenericPackedCarve generic_packed_carve(const SampleLayout &lay) {
 
 namespace generic {
 namespace {
+
+// own samples per sweep of stage 4 under RPF_FLAG_GENERIC_FAST (an even number dividing 8: two own samples share a packed
+// fp32 instruction; DESIGN.md section 11e has the trial of 4 against 8)
+#ifndef RPF_PACKED_FAST_OWN
+#define RPF_PACKED_FAST_OWN 8
+#endif
+typedef float __attribute__((may_alias)) zf32;                              // fp32 z values kept in rows the fp64 staging owns
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2a __attribute__((ext_vector_type(2), may_alias));
 
 struct PkDims {
     int nR, nF, ndim, nAnc, npairF, npairC, npair, nwt, colF;
@@ -153,11 +167,12 @@ __global__ __launch_bounds__(256) void nbhd_count_kernel(PassParams p) {
 }
 
 // One wave = one "unit" of 64 / G list entries at a time, units dealt to the waves of the grid with a grid stride.
-template <class T, int G>
+// FAST (RPF_FLAG_GENERIC_FAST): stage 4 alone in the fp32 arithmetic of DESIGN.md section 11e; every other statement is shared.
+template <class T, int G, bool FAST = false>
 __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, GenericPackedCarve cv) {
     constexpr int P = 64 / G;                                   // pixels per wave
     constexpr int BSTR = G == 8 ? 2 : (G == 16 ? 4 : 8);        // mask slots per (pixel, column): B = floor(sqrt(N)) <= 2, 4, 5, 8
-    constexpr int kOwn = 4;                                     // own samples per sweep of stage 4
+    constexpr int kOwn = FAST ? RPF_PACKED_FAST_OWN : 4;        // own samples per sweep of stage 4
     static_assert(P * BSTR <= 16, "sixteen masks per column and wave");
     extern __shared__ __align__(16) unsigned char smem[];
     const PkDims D = pk_dims(p.lay);
@@ -400,46 +415,51 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
         // ---- stage 4: weights and blend, term by term as rpf.cpp:646-717.  Lane = neighbourhood sample j; the weighted
         // columns are normalised in place (own sample i of the group is its slot i), kOwn own samples per sweep
         const double cj0 = sU[(gbase + 2) * G + t], cj1 = sU[(gbase + 3) * G + t], cj2 = sU[(gbase + 4) * G + t];
-        for (int k = 0; k < nwt; ++k) {
-            const int col = k < 5 ? k : k + nR;
-            const double *st = sStat + (gbase + col) * 5;
-            const double Mc = st[0], sd = st[1];
-            double *u = sU + (gbase + col) * G + t;
-            const double xv = *u;
-            *u = sd == 0.0 ? 0.0 : (xv - Mc) / sd;
-        }
-        wsync();
         bool bad = false;
-        {
-            const double wrc = sAlpha[3];
-            const double sigma_c2 = p.seed * p.seed / (1 - wrc) / (1 - wrc);           // rpf.cpp:662
-            const double sigma_p2 = p.sigma_p * p.sigma_p;
+        if constexpr (FAST) {
+            // z = (x - M) / SD in fp64, rounded once and kept as the group's row of floats [column][slot] in the first half of
+            // the column's fp64 row (a lane's store follows its own load; the rows of two columns are disjoint)
+            for (int k = 0; k < nwt; ++k) {
+                const int col = k < 5 ? k : k + nR;
+                const double *st = sStat + (gbase + col) * 5;
+                const double Mc = st[0], sd = st[1];
+                const double xv = sU[(gbase + col) * G + t];
+                wsync(); // every lane of the group has read its fp64 slot
+                reinterpret_cast<zf32 *>(sU + (gbase + col) * G)[t] = (float)(sd == 0.0 ? 0.0 : (xv - Mc) / sd);
+            }
+            // the coefficients of the summed exponent with log2 e folded in, formed in fp64 and rounded once (the sums of
+            // stage 3c they overwrite are dead)
+            {
+                const double wrc = sAlpha[3];
+                const double sigma_c2 = p.seed * p.seed / (1 - wrc) / (1 - wrc);       // rpf.cpp:662
+                const double sigma_p2 = p.sigma_p * p.sigma_p;
+                const double kLog2e = 1.4426950408889634;
+                zf32 *sCoefW = reinterpret_cast<zf32 *>(sDrf);
+                for (int k = t; k < nwt; k += G)
+                    sCoefW[k] = (float)((k < 2 ? 1.0 / (2 * sigma_p2) : (k < 5 ? sAlpha[k - 2] : sBeta[k - 5]) / (2 * sigma_c2)) * kLog2e);
+            }
+            wsync();
+            const zf32 *sCoef = reinterpret_cast<const zf32 *>(sDrf);
             for (int i0 = 0; i0 < S; i0 += kOwn) {
-                double sp[kOwn], sc[kOwn], sf[kOwn];
+                f32x2 E[kOwn / 2];
 #pragma unroll
-                for (int ii = 0; ii < kOwn; ++ii) { sp[ii] = 0.0; sc[ii] = 0.0; sf[ii] = 0.0; }
-                for (int k = 0; k < 2; ++k) {
-                    const double *zr = sU + (gbase + k) * G;
-                    const double zj = zr[t];
+                for (int q = 0; q < kOwn / 2; ++q) E[q] = f32x2{0.f, 0.f};
+                for (int k = 0; k < nwt; ++k) {
+                    const int col = k < 5 ? k : k + nR;
+                    const zf32 *zr = reinterpret_cast<const zf32 *>(sU + (gbase + col) * G);
+                    const float zj = zr[t], ck = sCoef[k];
+                    const f32x2 zj2 = f32x2{zj, zj}, ck2 = f32x2{ck, ck};
 #pragma unroll
-                    for (int ii = 0; ii < kOwn; ++ii) { const double d = zr[min(i0 + ii, S - 1)] - zj; sp[ii] += d * d; }
-                }
-                for (int k = 0; k < 3; ++k) {
-                    const double *zr = sU + (gbase + 2 + k) * G;
-                    const double zj = zr[t], ak = sAlpha[k];
-#pragma unroll
-                    for (int ii = 0; ii < kOwn; ++ii) { const double d = zr[min(i0 + ii, S - 1)] - zj; sc[ii] += (d * d) * ak; }
-                }
-                for (int k = 0; k < nF; ++k) {
-                    const double *zr = sU + (gbase + colF + k) * G;
-                    const double zj = zr[t], bk = sBeta[k];
-#pragma unroll
-                    for (int ii = 0; ii < kOwn; ++ii) { const double d = zr[min(i0 + ii, S - 1)] - zj; sf[ii] += (d * d) * bk; }
+                    for (int q = 0; q < kOwn / 2; ++q) {
+                        // (slots i0 .. i0 + kOwn - 1 lie inside the group's row: G is a multiple of kOwn; one past S - 1 weighs 0)
+                        const f32x2 d = *reinterpret_cast<const f32x2a *>(zr + i0 + 2 * q) - zj2;
+                        E[q] = __builtin_elementwise_fma(d * d, ck2, E[q]);
+                    }
                 }
 #pragma unroll
                 for (int ii = 0; ii < kOwn; ++ii) {
                     const int i = i0 + ii;
-                    double w = exp(-sp[ii] / (2 * sigma_p2)) * exp(-sc[ii] / (2 * sigma_c2)) * exp(-sf[ii] / (2 * sigma_c2)); // rpf.cpp:667-670
+                    double w = (double)__builtin_amdgcn_exp2f(-E[ii >> 1][ii & 1]);
                     w = (live && i < S) ? w : 0.0;
                     const double sw = group_sum<G>(w);                                 // rpf.cpp:691
                     const double s0 = group_sum<G>(w * cj0), s1 = group_sum<G>(w * cj1), s2 = group_sum<G>(w * cj2); // rpf.cpp:692
@@ -450,6 +470,60 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
                             if (p.policy == RPF_DEGEN_EPS) prime = p.col_in[(uint64_t)t * p.plane_stride + pix * S + i];
                         }
                         p.col_out[(uint64_t)t * p.plane_stride + pix * S + i] = prime;
+                    }
+                }
+            }
+        } else {
+            for (int k = 0; k < nwt; ++k) {
+                const int col = k < 5 ? k : k + nR;
+                const double *st = sStat + (gbase + col) * 5;
+                const double Mc = st[0], sd = st[1];
+                double *u = sU + (gbase + col) * G + t;
+                const double xv = *u;
+                *u = sd == 0.0 ? 0.0 : (xv - Mc) / sd;
+            }
+            wsync();
+                {
+                const double wrc = sAlpha[3];
+                const double sigma_c2 = p.seed * p.seed / (1 - wrc) / (1 - wrc);           // rpf.cpp:662
+                const double sigma_p2 = p.sigma_p * p.sigma_p;
+                for (int i0 = 0; i0 < S; i0 += kOwn) {
+                    double sp[kOwn], sc[kOwn], sf[kOwn];
+#pragma unroll
+                    for (int ii = 0; ii < kOwn; ++ii) { sp[ii] = 0.0; sc[ii] = 0.0; sf[ii] = 0.0; }
+                    for (int k = 0; k < 2; ++k) {
+                        const double *zr = sU + (gbase + k) * G;
+                        const double zj = zr[t];
+#pragma unroll
+                        for (int ii = 0; ii < kOwn; ++ii) { const double d = zr[min(i0 + ii, S - 1)] - zj; sp[ii] += d * d; }
+                    }
+                    for (int k = 0; k < 3; ++k) {
+                        const double *zr = sU + (gbase + 2 + k) * G;
+                        const double zj = zr[t], ak = sAlpha[k];
+#pragma unroll
+                        for (int ii = 0; ii < kOwn; ++ii) { const double d = zr[min(i0 + ii, S - 1)] - zj; sc[ii] += (d * d) * ak; }
+                    }
+                    for (int k = 0; k < nF; ++k) {
+                        const double *zr = sU + (gbase + colF + k) * G;
+                        const double zj = zr[t], bk = sBeta[k];
+#pragma unroll
+                        for (int ii = 0; ii < kOwn; ++ii) { const double d = zr[min(i0 + ii, S - 1)] - zj; sf[ii] += (d * d) * bk; }
+                    }
+#pragma unroll
+                    for (int ii = 0; ii < kOwn; ++ii) {
+                        const int i = i0 + ii;
+                        double w = exp(-sp[ii] / (2 * sigma_p2)) * exp(-sc[ii] / (2 * sigma_c2)) * exp(-sf[ii] / (2 * sigma_c2)); // rpf.cpp:667-670
+                        w = (live && i < S) ? w : 0.0;
+                        const double sw = group_sum<G>(w);                                 // rpf.cpp:691
+                        const double s0 = group_sum<G>(w * cj0), s1 = group_sum<G>(w * cj1), s2 = group_sum<G>(w * cj2); // rpf.cpp:692
+                        if (t < 3 && gvalid && i < S) {
+                            double prime = (t == 0 ? s0 : (t == 1 ? s1 : s2)) / sw;       // rpf.cpp:700
+                            if (isnan(prime)) {                                            // rpf.cpp:702: the reference exits here
+                                bad = true;
+                                if (p.policy == RPF_DEGEN_EPS) prime = p.col_in[(uint64_t)t * p.plane_stride + pix * S + i];
+                            }
+                            p.col_out[(uint64_t)t * p.plane_stride + pix * S + i] = prime;
+                        }
                     }
                 }
             }
@@ -468,24 +542,24 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
     }
 }
 
-template <class T, int G>
+template <class T, int G, bool FAST>
 hipError_t launch_packed_t(const PassParams &p, const GenericPackedCarve &cv, hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute((const void *)filter_packed_kernel<T, G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
+    hipError_t e = hipFuncSetAttribute((const void *)filter_packed_kernel<T, G, FAST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
     if (e != hipSuccess) return e;
     const uint32_t P = 64u / (uint32_t)G, units = (p.list_count + P - 1u) / P;
     // grid-stride walk: 2048 workgroups keep 256 CUs busy whatever the carve-up lets a CU hold
     const unsigned grid = (unsigned)std::min<uint32_t>((units + cv.waves - 1u) / cv.waves, 2048u);
-    hipLaunchKernelGGL((filter_packed_kernel<T, G>), dim3(grid), dim3(64u * cv.waves), cv.total, s, p, cv);
+    hipLaunchKernelGGL((filter_packed_kernel<T, G, FAST>), dim3(grid), dim3(64u * cv.waves), cv.total, s, p, cv);
     return hipGetLastError();
 }
 
-template <class T>
+template <class T, bool FAST>
 hipError_t launch_packed_g(const PassParams &p, const GenericPackedCarve &cv, int G, hipStream_t s) {
     switch (G) {
-    case 8: return launch_packed_t<T, 8>(p, cv, s);
-    case 16: return launch_packed_t<T, 16>(p, cv, s);
-    case 32: return launch_packed_t<T, 32>(p, cv, s);
-    case 64: return launch_packed_t<T, 64>(p, cv, s);
+    case 8: return launch_packed_t<T, 8, FAST>(p, cv, s);
+    case 16: return launch_packed_t<T, 16, FAST>(p, cv, s);
+    case 32: return launch_packed_t<T, 32, FAST>(p, cv, s);
+    case 64: return launch_packed_t<T, 64, FAST>(p, cv, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -502,7 +576,7 @@ hipError_t launch_nbhd_count(const PassParams &p, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, hipStream_t s) {
+hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, hipStream_t s, bool fast) {
     if (p.pix_list == nullptr || p.S > lanes_per_pixel || !p.lay.generic_ok()) return hipErrorInvalidValue;
     if (p.masks == nullptr && p.members == nullptr) return hipErrorInvalidValue; // one source of the member list
     if (p.members != nullptr && p.member_base == nullptr) return hipErrorInvalidValue;
@@ -510,7 +584,8 @@ hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, hipStr
     if (p.list_count == 0) return hipSuccess;
     const GenericPackedCarve cv = generic_packed_carve(p.lay);
     if ((int)cv.total > max_lds_per_block()) return hipErrorInvalidValue;
-    return p.lay.f16 ? launch_packed_g<__half>(p, cv, lanes_per_pixel, s) : launch_packed_g<float>(p, cv, lanes_per_pixel, s);
+    if (fast) return p.lay.f16 ? launch_packed_g<__half, true>(p, cv, lanes_per_pixel, s) : launch_packed_g<float, true>(p, cv, lanes_per_pixel, s);
+    return p.lay.f16 ? launch_packed_g<__half, false>(p, cv, lanes_per_pixel, s) : launch_packed_g<float, false>(p, cv, lanes_per_pixel, s);
 }
 
 } // namespace generic

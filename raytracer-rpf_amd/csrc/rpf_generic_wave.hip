@@ -20,6 +20,11 @@
 // colours agree to rounding (the weight sums of stage 4 associate differently).  Under REF_ABORT a pixel with a table inside
 // the zero band at a non-power-of-two N and non-degenerate marginals joins the redo list (the rule of
 // rpf_generic_packed.hip) and generic::filter_pixel_kernel filters it again, whole.
+//
+// filter_wave_kernel<T, FAST = true> (RPF_FLAG_GENERIC_FAST): the same kernel with stage 4 in fp32 -- a
+// member's z = (x - M) * (1 / SD) in fp64 with 1 / SD formed once per pixel and column, rounded once; the coefficients (log2 e
+// folded in) formed in fp64 and rounded once; one accumulator per own sample, two own samples per packed fp32 instruction, one
+// hardware exponential, the sums and the quotient in fp64.  Every statement outside stage 4 is shared.
 #include "rpf_device_common.h"
 
 #include <algorithm>
@@ -38,6 +43,15 @@ constexpr int kWvGather = 4; // columns of a member gathered together (their lat
 #define RPF_WAVE_OWN 4
 #endif
 constexpr int kWvOwn = RPF_WAVE_OWN;
+// ... under RPF_FLAG_GENERIC_FAST (an even number: two own samples share a packed fp32 instruction; the sweep's own rows are
+// floats, so eight fit the LDS block that holds four fp64 rows; DESIGN.md section 11e has the trial of 4 against 8)
+#ifndef RPF_WAVE_FAST_OWN
+#define RPF_WAVE_FAST_OWN 8
+#endif
+constexpr int kWvFastOwn = RPF_WAVE_FAST_OWN;
+static_assert(kWvFastOwn % 4 == 0 && kWvFastOwn * 4 <= kWvOwn * 8, "the fp32 own rows of a sweep fit the block of the fp64 ones; read 16 bytes at a time");
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4a __attribute__((ext_vector_type(4), may_alias));
 } // namespace
 } // namespace generic
 
@@ -119,9 +133,10 @@ __device__ __forceinline__ void wv_pair_cols(const WvDims &D, int pr, int &ca, i
 }
 
 // One wave = one pixel of the class list at a time, the entries dealt to the waves of the grid with a grid stride.
-template <class T>
+// FAST (RPF_FLAG_GENERIC_FAST): stage 4 alone in the fp32 arithmetic of DESIGN.md section 11e; every other statement is shared.
+template <class T, bool FAST = false>
 __global__ __launch_bounds__(256) void filter_wave_kernel(PassParams p, GenericWaveCarve cv) {
-    constexpr int kOwn = kWvOwn;
+    constexpr int kOwn = FAST ? kWvFastOwn : kWvOwn;
     extern __shared__ __align__(16) unsigned char smem[];
     const WvDims D = wv_dims(p.lay);
     const int ndim = D.ndim, nF = D.nF, nR = D.nR, nAnc = D.nAnc, npair = D.npair, nwt = D.nwt, colF = D.colF;
@@ -395,88 +410,189 @@ __global__ __launch_bounds__(256) void filter_wave_kernel(PassParams p, GenericW
         // kOwn own samples' sp / sc / sf take its term -- each accumulator still receives its terms in ascending k (the
         // reference's order).  A pixel on the redo list is filtered whole by generic::filter_pixel_kernel: nothing to do here.
         bool bad = false;
-        if (!redo_pixel) {
-            const double wrc = sWrc[0];
-            const double sigma_c2 = p.seed * p.seed / (1 - wrc) / (1 - wrc);                                  // rpf.cpp:662
-            const double sigma_p2 = p.sigma_p * p.sigma_p;
-            auto znorm = [&](int c, double xv) { const double sd = sStat[ndim + c]; return sd == 0.0 ? 0.0 : (xv - sStat[c]) / sd; };
-            double *sOwnZ = sChunk; // [nwt][kOwn] normalised own samples of the sweep (the staging chunk is dead)
-            for (int i0 = 0; i0 < S; i0 += kOwn) {
-                wsync();
-                for (int t = lane; t < kOwn * nwt; t += 64) {
-                    const int k = t / kOwn, ii = t % kOwn, i = min(i0 + ii, S - 1);
-                    const int col = k < 5 ? k : k + nR;
-                    sOwnZ[t] = znorm(col, wv_load_col<T>(p, col, (uint32_t)(pix * S + i)));
-                }
-                wsync();
-                double sw[kOwn], s0[kOwn], s1[kOwn], s2[kOwn];
-#pragma unroll
-                for (int ii = 0; ii < kOwn; ++ii) { sw[ii] = 0.0; s0[ii] = 0.0; s1[ii] = 0.0; s2[ii] = 0.0; }
-                for (int kk = 0; kk < nk; ++kk) {
-                    const int j = lane + 64 * kk;
-                    const bool live = j < n;
-                    const uint32_t off = list[live ? j : 0];
-                    double sp[kOwn], sc[kOwn], sf[kOwn], cj[3];
-#pragma unroll
-                    for (int ii = 0; ii < kOwn; ++ii) { sp[ii] = 0.0; sc[ii] = 0.0; sf[ii] = 0.0; }
-                    // every gather of the member that needs no loop is issued here, the features kWvGather at a time with the
-                    // next group in flight while this one is weighed
-                    const float pf0 = wv_ldp<T>(p, 0, off), pf1 = wv_ldp<T>(p, 1, off);
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) cj[k] = p.col_in[(uint64_t)k * p.plane_stride + off];
-                    float fv[kWvGather];
-#pragma unroll
-                    for (int u = 0; u < kWvGather; ++u) fv[u] = wv_ldp<T>(p, colF + min(u, nF - 1), off);
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const double zj = znorm(k, (double)(k == 0 ? pf0 : pf1));
-#pragma unroll
-                        for (int ii = 0; ii < kOwn; ++ii) { const double t = sOwnZ[k * kOwn + ii] - zj; sp[ii] += t * t; }
+        if constexpr (FAST) {
+            if (!redo_pixel) {
+                // per column: M and 1 / SD once per pixel (fp64; the slots of the column minima and maxima are dead), which
+                // columns have SD == 0 (z = 0 there) as one wave-uniform mask, and the coefficients of the summed exponent with
+                // log2 e folded in, formed in fp64 and rounded once (the sums of stage 3c they overwrite are dead)
+                double *sInv = sStat + 2 * ndim;
+                float *sCoef = reinterpret_cast<float *>(sDrf);
+                const double wrc = sWrc[0];
+                const double sigma_c2 = p.seed * p.seed / (1 - wrc) / (1 - wrc);                              // rpf.cpp:662
+                const double sigma_p2 = p.sigma_p * p.sigma_p;
+                const double kLog2e = 1.4426950408889634;
+                const double sdl = sStat[ndim + min(lane, ndim - 1)];
+                const unsigned long long sd0mask = __ballot(lane < ndim && sdl == 0.0);
+                if (lane < ndim) sInv[lane] = 1.0 / sdl;
+                if (lane < nwt)
+                    sCoef[lane] = (float)((lane < 2 ? 1.0 / (2 * sigma_p2) : (lane < 5 ? sAlpha[lane - 2] : sBeta[lane - 5]) / (2 * sigma_c2)) * kLog2e);
+                auto zfast = [&](int c, double xv) { return ((sd0mask >> c) & 1ull) ? 0.f : (float)((xv - sStat[c]) * sInv[c]); };
+                float *sOwnZ = reinterpret_cast<float *>(sChunk); // [nwt][kOwn] normalised own samples of the sweep (the staging chunk is dead)
+                for (int i0 = 0; i0 < S; i0 += kOwn) {
+                    wsync();
+                    for (int t = lane; t < kOwn * nwt; t += 64) {
+                        const int k = t / kOwn, ii = t % kOwn, i = min(i0 + ii, S - 1);
+                        const int col = k < 5 ? k : k + nR;
+                        sOwnZ[t] = zfast(col, wv_load_col<T>(p, col, (uint32_t)(pix * S + i)));
                     }
+                    wsync();
+                    double sw[kOwn], s0[kOwn], s1[kOwn], s2[kOwn];
 #pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        const double zj = znorm(2 + k, cj[k]), ak = sAlpha[k];
+                    for (int ii = 0; ii < kOwn; ++ii) { sw[ii] = 0.0; s0[ii] = 0.0; s1[ii] = 0.0; s2[ii] = 0.0; }
+                    for (int kk = 0; kk < nk; ++kk) {
+                        const int j = lane + 64 * kk;
+                        const bool live = j < n;
+                        const uint32_t off = list[live ? j : 0];
+                        f32x2 E[kOwn / 2];
 #pragma unroll
-                        for (int ii = 0; ii < kOwn; ++ii) { const double t = sOwnZ[(2 + k) * kOwn + ii] - zj; sc[ii] += (t * t) * ak; }
-                    }
-                    for (int k0 = 0; k0 < nF; k0 += kWvGather) {
-                        float cur[kWvGather];
+                        for (int q = 0; q < kOwn / 2; ++q) E[q] = f32x2{0.f, 0.f};
+                        double cj[3];
+                        // one accumulator per own sample takes the column's term: d = z_i - z_j, E += (d * d) * coef, two own
+                        // samples to a packed instruction
+                        auto term = [&](int k, float zj) {
+                            const float ck = sCoef[k];
+                            const f32x2 zj2 = f32x2{zj, zj}, ck2 = f32x2{ck, ck};
 #pragma unroll
-                        for (int u = 0; u < kWvGather; ++u) cur[u] = fv[u];
-                        if (k0 + kWvGather < nF) {
+                            for (int q4 = 0; q4 < kOwn / 4; ++q4) {
+                                const f32x4a zo = *reinterpret_cast<const f32x4a *>(sOwnZ + k * kOwn + 4 * q4);
+                                const f32x2 da = f32x2{zo[0], zo[1]} - zj2, db = f32x2{zo[2], zo[3]} - zj2;
+                                E[2 * q4] = __builtin_elementwise_fma(da * da, ck2, E[2 * q4]);
+                                E[2 * q4 + 1] = __builtin_elementwise_fma(db * db, ck2, E[2 * q4 + 1]);
+                            }
+                        };
+                        const float pf0 = wv_ldp<T>(p, 0, off), pf1 = wv_ldp<T>(p, 1, off);
 #pragma unroll
-                            for (int u = 0; u < kWvGather; ++u) fv[u] = wv_ldp<T>(p, colF + min(k0 + kWvGather + u, nF - 1), off);
+                        for (int k = 0; k < 3; ++k) cj[k] = p.col_in[(uint64_t)k * p.plane_stride + off];
+                        float fv[kWvGather];
+#pragma unroll
+                        for (int u = 0; u < kWvGather; ++u) fv[u] = wv_ldp<T>(p, colF + min(u, nF - 1), off);
+                        term(0, zfast(0, (double)pf0));
+                        term(1, zfast(1, (double)pf1));
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) term(2 + k, zfast(2 + k, cj[k]));
+                        for (int k0 = 0; k0 < nF; k0 += kWvGather) {
+                            float cur[kWvGather];
+#pragma unroll
+                            for (int u = 0; u < kWvGather; ++u) cur[u] = fv[u];
+                            if (k0 + kWvGather < nF) {
+#pragma unroll
+                                for (int u = 0; u < kWvGather; ++u) fv[u] = wv_ldp<T>(p, colF + min(k0 + kWvGather + u, nF - 1), off);
+                            }
+#pragma unroll
+                            for (int u = 0; u < kWvGather; ++u) {
+                                const int k = k0 + u;
+                                if (k >= nF) break;
+                                term(5 + k, zfast(colF + k, (double)cur[u]));
+                            }
                         }
+                        if (!live) { cj[0] = 0.0; cj[1] = 0.0; cj[2] = 0.0; } // (a padding lane adds exact zeros whatever slot 0 holds)
 #pragma unroll
-                        for (int u = 0; u < kWvGather; ++u) {
-                            const int k = k0 + u;
-                            if (k >= nF) break;
-                            const double zj = znorm(colF + k, (double)cur[u]), bk = sBeta[k];
-#pragma unroll
-                            for (int ii = 0; ii < kOwn; ++ii) { const double t = sOwnZ[(5 + k) * kOwn + ii] - zj; sf[ii] += (t * t) * bk; }
+                        for (int ii = 0; ii < kOwn; ++ii) {
+                            double w = (double)__builtin_amdgcn_exp2f(-E[ii >> 1][ii & 1]);
+                            w = (live && i0 + ii < S) ? w : 0.0;
+                            sw[ii] += w; s0[ii] += w * cj[0]; s1[ii] += w * cj[1]; s2[ii] += w * cj[2];   // rpf.cpp:691-692
                         }
                     }
-                    if (!live) { cj[0] = 0.0; cj[1] = 0.0; cj[2] = 0.0; } // (a padding lane adds exact zeros whatever slot 0 holds)
 #pragma unroll
                     for (int ii = 0; ii < kOwn; ++ii) {
-                        double w = exp(-sp[ii] / (2 * sigma_p2)) * exp(-sc[ii] / (2 * sigma_c2)) * exp(-sf[ii] / (2 * sigma_c2)); // rpf.cpp:667-670
-                        w = (live && i0 + ii < S) ? w : 0.0;
-                        sw[ii] += w; s0[ii] += w * cj[0]; s1[ii] += w * cj[1]; s2[ii] += w * cj[2];   // rpf.cpp:691-692
+                        const double vw = xl::allreduce<xl::OpSum>(sw[ii]);
+                        const double v0 = xl::allreduce<xl::OpSum>(s0[ii]), v1 = xl::allreduce<xl::OpSum>(s1[ii]), v2 = xl::allreduce<xl::OpSum>(s2[ii]);
+                        const int i = i0 + ii;
+                        if (lane < 3 && i < S) {
+                            double prime = (lane == 0 ? v0 : (lane == 1 ? v1 : v2)) / vw;                             // rpf.cpp:700
+                            if (isnan(prime)) {                                                                    // rpf.cpp:702
+                                bad = true;
+                                if (p.policy == RPF_DEGEN_EPS) prime = p.col_in[(uint64_t)lane * p.plane_stride + pix * S + i];
+                            }
+                            p.col_out[(uint64_t)lane * p.plane_stride + pix * S + i] = prime;
+                        }
                     }
                 }
-                // the four sums of an own sample, totalled over the 64 lanes (every lane receives the totals)
+            }
+        } else {
+            if (!redo_pixel) {
+                const double wrc = sWrc[0];
+                const double sigma_c2 = p.seed * p.seed / (1 - wrc) / (1 - wrc);                                  // rpf.cpp:662
+                const double sigma_p2 = p.sigma_p * p.sigma_p;
+                auto znorm = [&](int c, double xv) { const double sd = sStat[ndim + c]; return sd == 0.0 ? 0.0 : (xv - sStat[c]) / sd; };
+                double *sOwnZ = sChunk; // [nwt][kOwn] normalised own samples of the sweep (the staging chunk is dead)
+                for (int i0 = 0; i0 < S; i0 += kOwn) {
+                    wsync();
+                    for (int t = lane; t < kOwn * nwt; t += 64) {
+                        const int k = t / kOwn, ii = t % kOwn, i = min(i0 + ii, S - 1);
+                        const int col = k < 5 ? k : k + nR;
+                        sOwnZ[t] = znorm(col, wv_load_col<T>(p, col, (uint32_t)(pix * S + i)));
+                    }
+                    wsync();
+                    double sw[kOwn], s0[kOwn], s1[kOwn], s2[kOwn];
 #pragma unroll
-                for (int ii = 0; ii < kOwn; ++ii) {
-                    const double vw = xl::allreduce<xl::OpSum>(sw[ii]);
-                    const double v0 = xl::allreduce<xl::OpSum>(s0[ii]), v1 = xl::allreduce<xl::OpSum>(s1[ii]), v2 = xl::allreduce<xl::OpSum>(s2[ii]);
-                    const int i = i0 + ii;
-                    if (lane < 3 && i < S) {
-                        double prime = (lane == 0 ? v0 : (lane == 1 ? v1 : v2)) / vw;                             // rpf.cpp:700
-                        if (isnan(prime)) {                                                                    // rpf.cpp:702
-                            bad = true;
-                            if (p.policy == RPF_DEGEN_EPS) prime = p.col_in[(uint64_t)lane * p.plane_stride + pix * S + i];
+                    for (int ii = 0; ii < kOwn; ++ii) { sw[ii] = 0.0; s0[ii] = 0.0; s1[ii] = 0.0; s2[ii] = 0.0; }
+                    for (int kk = 0; kk < nk; ++kk) {
+                        const int j = lane + 64 * kk;
+                        const bool live = j < n;
+                        const uint32_t off = list[live ? j : 0];
+                        double sp[kOwn], sc[kOwn], sf[kOwn], cj[3];
+#pragma unroll
+                        for (int ii = 0; ii < kOwn; ++ii) { sp[ii] = 0.0; sc[ii] = 0.0; sf[ii] = 0.0; }
+                        // every gather of the member that needs no loop is issued here, the features kWvGather at a time with the
+                        // next group in flight while this one is weighed
+                        const float pf0 = wv_ldp<T>(p, 0, off), pf1 = wv_ldp<T>(p, 1, off);
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) cj[k] = p.col_in[(uint64_t)k * p.plane_stride + off];
+                        float fv[kWvGather];
+#pragma unroll
+                        for (int u = 0; u < kWvGather; ++u) fv[u] = wv_ldp<T>(p, colF + min(u, nF - 1), off);
+#pragma unroll
+                        for (int k = 0; k < 2; ++k) {
+                            const double zj = znorm(k, (double)(k == 0 ? pf0 : pf1));
+#pragma unroll
+                            for (int ii = 0; ii < kOwn; ++ii) { const double t = sOwnZ[k * kOwn + ii] - zj; sp[ii] += t * t; }
                         }
-                        p.col_out[(uint64_t)lane * p.plane_stride + pix * S + i] = prime;
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) {
+                            const double zj = znorm(2 + k, cj[k]), ak = sAlpha[k];
+#pragma unroll
+                            for (int ii = 0; ii < kOwn; ++ii) { const double t = sOwnZ[(2 + k) * kOwn + ii] - zj; sc[ii] += (t * t) * ak; }
+                        }
+                        for (int k0 = 0; k0 < nF; k0 += kWvGather) {
+                            float cur[kWvGather];
+#pragma unroll
+                            for (int u = 0; u < kWvGather; ++u) cur[u] = fv[u];
+                            if (k0 + kWvGather < nF) {
+#pragma unroll
+                                for (int u = 0; u < kWvGather; ++u) fv[u] = wv_ldp<T>(p, colF + min(k0 + kWvGather + u, nF - 1), off);
+                            }
+#pragma unroll
+                            for (int u = 0; u < kWvGather; ++u) {
+                                const int k = k0 + u;
+                                if (k >= nF) break;
+                                const double zj = znorm(colF + k, (double)cur[u]), bk = sBeta[k];
+#pragma unroll
+                                for (int ii = 0; ii < kOwn; ++ii) { const double t = sOwnZ[(5 + k) * kOwn + ii] - zj; sf[ii] += (t * t) * bk; }
+                            }
+                        }
+                        if (!live) { cj[0] = 0.0; cj[1] = 0.0; cj[2] = 0.0; } // (a padding lane adds exact zeros whatever slot 0 holds)
+#pragma unroll
+                        for (int ii = 0; ii < kOwn; ++ii) {
+                            double w = exp(-sp[ii] / (2 * sigma_p2)) * exp(-sc[ii] / (2 * sigma_c2)) * exp(-sf[ii] / (2 * sigma_c2)); // rpf.cpp:667-670
+                            w = (live && i0 + ii < S) ? w : 0.0;
+                            sw[ii] += w; s0[ii] += w * cj[0]; s1[ii] += w * cj[1]; s2[ii] += w * cj[2];   // rpf.cpp:691-692
+                        }
+                    }
+                    // the four sums of an own sample, totalled over the 64 lanes (every lane receives the totals)
+#pragma unroll
+                    for (int ii = 0; ii < kOwn; ++ii) {
+                        const double vw = xl::allreduce<xl::OpSum>(sw[ii]);
+                        const double v0 = xl::allreduce<xl::OpSum>(s0[ii]), v1 = xl::allreduce<xl::OpSum>(s1[ii]), v2 = xl::allreduce<xl::OpSum>(s2[ii]);
+                        const int i = i0 + ii;
+                        if (lane < 3 && i < S) {
+                            double prime = (lane == 0 ? v0 : (lane == 1 ? v1 : v2)) / vw;                             // rpf.cpp:700
+                            if (isnan(prime)) {                                                                    // rpf.cpp:702
+                                bad = true;
+                                if (p.policy == RPF_DEGEN_EPS) prime = p.col_in[(uint64_t)lane * p.plane_stride + pix * S + i];
+                            }
+                            p.col_out[(uint64_t)lane * p.plane_stride + pix * S + i] = prime;
+                        }
                     }
                 }
             }
@@ -494,19 +610,19 @@ __global__ __launch_bounds__(256) void filter_wave_kernel(PassParams p, GenericW
     }
 }
 
-template <class T>
+template <class T, bool FAST>
 hipError_t launch_wave_t(const PassParams &p, const GenericWaveCarve &cv, hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute((const void *)filter_wave_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
+    hipError_t e = hipFuncSetAttribute((const void *)filter_wave_kernel<T, FAST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
     if (e != hipSuccess) return e;
     // grid-stride walk: 2048 workgroups keep 256 CUs busy whatever the carve-up lets a CU hold
     const unsigned grid = (unsigned)std::min<uint32_t>((p.list_count + cv.waves - 1u) / cv.waves, 2048u);
-    hipLaunchKernelGGL(filter_wave_kernel<T>, dim3(grid), dim3(64u * cv.waves), cv.total, s, p, cv);
+    hipLaunchKernelGGL((filter_wave_kernel<T, FAST>), dim3(grid), dim3(64u * cv.waves), cv.total, s, p, cv);
     return hipGetLastError();
 }
 
 } // namespace
 
-hipError_t launch_filter_wave(const PassParams &p, int capacity, hipStream_t s) {
+hipError_t launch_filter_wave(const PassParams &p, int capacity, hipStream_t s, bool fast) {
     if ((p.masks == nullptr && p.members == nullptr) || (p.members != nullptr && p.member_base == nullptr)) return hipErrorInvalidValue;
     if (p.pix_list == nullptr || p.S > capacity || capacity > 832 || (capacity & 63) != 0 || !p.lay.generic_ok())
         return hipErrorInvalidValue;
@@ -514,7 +630,8 @@ hipError_t launch_filter_wave(const PassParams &p, int capacity, hipStream_t s) 
     if (p.list_count == 0) return hipSuccess;
     const GenericWaveCarve cv = generic_wave_carve(p.lay, capacity);
     if (cv.waves == 0 || (int)cv.total > max_lds_per_block()) return hipErrorInvalidValue;
-    return p.lay.f16 ? launch_wave_t<__half>(p, cv, s) : launch_wave_t<float>(p, cv, s);
+    if (fast) return p.lay.f16 ? launch_wave_t<__half, true>(p, cv, s) : launch_wave_t<float, true>(p, cv, s);
+    return p.lay.f16 ? launch_wave_t<__half, false>(p, cv, s) : launch_wave_t<float, false>(p, cv, s);
 }
 
 } // namespace generic

@@ -40,6 +40,8 @@ struct PassParams {
                            //          generic::filter_wide_kernel (rpf_generic_wide.hip), whatever the other bits say; stage 1a is not affected
                            //   bit 4: with bit 3, RPF_FLAG_WIDE_CLASSES and S <= 832: the wide pass is counted first and dealt by size class
                            //          (route_generic_wide_classes); only N > 832 stays on the wide kernel
+                           //   bit 5: RPF_FLAG_GENERIC_FAST: routes 4 and 5 launch the fp32-weight instantiations of their packed and
+                           //          one-wave kernels (host-side only: no kernel reads the bit, and fast_weights stays 0)
     int32_t stage_mask;    // diagnostics only (rpf_set_option "stage_mask"): bit0 stats chain, bit1 bins, bit2 MI, bit3 weights; -1 = all
     int32_t screen;        // far-pair screen of the four-wave kernels: 0 off, 1 on
     int32_t strip_w;       // pixels per XCD strip of the pixel walk (slab_pixel)
@@ -210,8 +212,9 @@ namespace generic {
 // nbhd_count_kernel)
 hipError_t launch_nbhd_count(const PassParams &p, hipStream_t s);
 // the pixels of p.pix_list (p.list_count of them, N <= lanes_per_pixel = 8, 16, 32 or 64) from p.nbhd and p.masks; under
-// REF_ABORT p.redo_list / p.redo_count take the pixels that generic::filter_pixel_kernel must filter again
-hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, hipStream_t s);
+// REF_ABORT p.redo_list / p.redo_count take the pixels that generic::filter_pixel_kernel must filter again.  fast: stage 4 in
+// the fp32 arithmetic of RPF_FLAG_GENERIC_FAST (routes 4 and 5 pass it; nothing else of PassParams says so)
+hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, hipStream_t s, bool fast = false);
 } // namespace generic
 
 // ---- the one-wave layout-generic kernels (rpf_generic_wave.hip, RPF_FLAG_GENERIC_WAVE): 64 < N <= 832, one wave per pixel --
@@ -233,8 +236,9 @@ struct GenericWaveCarve {
 GenericWaveCarve generic_wave_carve(const SampleLayout &lay, int capacity);
 namespace generic {
 // the pixels of p.pix_list (p.list_count of them, 64 < N <= capacity = 128, 256, 448 or 832) from p.nbhd and p.masks; under
-// REF_ABORT p.redo_list / p.redo_count take the pixels that generic::filter_pixel_kernel must filter again
-hipError_t launch_filter_wave(const PassParams &p, int capacity, hipStream_t s);
+// REF_ABORT p.redo_list / p.redo_count take the pixels that generic::filter_pixel_kernel must filter again.  fast: as for
+// launch_filter_packed
+hipError_t launch_filter_wave(const PassParams &p, int capacity, hipStream_t s, bool fast = false);
 } // namespace generic
 
 // ---- the wide layout-generic kernel (rpf_generic_wide.hip, RPF_FLAG_WIDE_NBHD): 65535 < box*box*S <= 262144 ----------------

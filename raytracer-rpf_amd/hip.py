@@ -26,6 +26,10 @@ FLAG_GENERIC = 8  # the layout-generic kernels: required for a layout without co
 FLAG_GENERIC_PACKED = 16  # with FLAG_GENERIC: neighbourhoods of N <= 64 samples on the packed generic kernels (route 4)
 FLAG_GENERIC_WAVE = 32  # with FLAG_GENERIC | FLAG_GENERIC_PACKED: 64 < N <= 832 on the one-wave generic kernels (route 5)
 FLAG_WIDE_CLASSES = 128  # with FLAG_WIDE_NBHD: a wide pass counted first and dealt by size class (route 7; 6 for a pass with S > 832)
+# with FLAG_GENERIC | FLAG_GENERIC_PACKED (with or without FLAG_GENERIC_WAVE): the pair weights of stage 4 in fp32 on the packed and
+# one-wave generic kernels (routes 4 / 5 as without it; the rest list, the redo list and a route-3 pass stay fp64, same bits);
+# refused without both flags, with FLAG_FAST_WEIGHTS (which keeps its meaning: the fused 19-dim kernels) and with FLAG_WIDE_NBHD
+FLAG_GENERIC_FAST = 256
 FLAG_WIDE_NBHD = 64  # passes with 65535 < box*box*S <= 262144 on the wide layout-generic kernel (route 6); max_nbhd() tells the bound
 MAX_NDIM = 40     # the layout-generic kernels take 5 + n_random + n_feat up to this
 PLANES_F32, PLANES_F16 = 0, 1
@@ -112,8 +116,9 @@ def film_window(desc, film):
 
 def layout_kernels(desc):
     """rpf_layout_kernels (no GPU needed): (status, generic) for the layout and flags of `desc` -- (OK, 0) the compiled fused
-    kernels, (OK, 1) the layout-generic kernels (FLAG_GENERIC), (E_UNSUPPORTED, None) where the filter entry points refuse
-    it; desc None: (E_BADARG, None)"""
+    kernels, (OK, 1) the layout-generic kernels (FLAG_GENERIC; FLAG_GENERIC_FAST does not change the answer),
+    (E_UNSUPPORTED, None) where the filter entry points refuse it -- FLAG_GENERIC_FAST without FLAG_GENERIC | FLAG_GENERIC_PACKED,
+    with FLAG_FAST_WEIGHTS or with FLAG_WIDE_NBHD among them; desc None: (E_BADARG, None)"""
     g = C.c_int32(-1)
     st = load().rpf_layout_kernels(None if desc is None else C.byref(desc), C.byref(g))
     return st, (g.value if st == OK else None)
@@ -318,7 +323,7 @@ class Context:
         (FLAG_GENERIC), 4 the same with small neighbourhoods packed (FLAG_GENERIC_PACKED), 5 the same with
         64 < N <= 832 on the one-wave generic kernels (FLAG_GENERIC_WAVE; 3 for a pass with S > 832), 6 the wide kernel
         (FLAG_WIDE_NBHD on a pass with box*box*S > 65535), 7 such a pass dealt by size class (FLAG_WIDE_CLASSES); -1 before
-        any pass
+        any pass.  FLAG_GENERIC_FAST changes no route: 4 / 5 (or 3) as without it
         (rpf_query_route)"""
         r = C.c_int32(-1)
         self._check(self._L.rpf_query_route(self._h, C.byref(r)))

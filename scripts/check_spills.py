@@ -200,15 +200,16 @@ def demangle_short(name):
     s = (ns.group(1) + "::" if ns else "") + (base.group(1) if base else name[:60])
     if k:
         s += "<K=%s,TL=%s,FAST=%s,NW=%s,PHASE=%s>" % k.groups()
-    t = re.search(r"3rpf7generic.*kernelI(f|6__half)E", name)  # the layout-generic kernels: the plane type is the only parameter
+    # the layout-generic kernels: the plane type, and FAST where a kernel has the fp32 stage-4 instantiation (RPF_FLAG_GENERIC_FAST)
+    t = re.search(r"3rpf7generic.*kernelI(f|6__half)(?:Lb([01])E)?E", name)
     if t:
-        s += "<%s>" % ("float" if t.group(1) == "f" else "__half")
+        s += "<%s%s>" % ("float" if t.group(1) == "f" else "__half", ",FAST" if t.group(2) == "1" else "")
     g = re.search(r"packed_kernelILi(\d+)E", name)
     if g:
         s += "<G=%s>" % g.group(1)
-    t = re.search(r"3rpf7generic.*packed_kernelI(f|6__half)Li(\d+)E", name)  # ... and of their packed kernels the lanes per pixel
+    t = re.search(r"3rpf7generic.*packed_kernelI(f|6__half)Li(\d+)E(?:Lb([01])E)?", name)  # ... and of their packed kernels the lanes per pixel
     if t:
-        s += "<%s,G=%s>" % ("float" if t.group(1) == "f" else "__half", t.group(2))
+        s += "<%s,G=%s%s>" % ("float" if t.group(1) == "f" else "__half", t.group(2), ",FAST" if t.group(3) == "1" else "")
     return s
 
 

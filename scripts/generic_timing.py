@@ -18,6 +18,10 @@ the launches and the mean neighbourhood size.  Cases (--case to pick by name):
   flat57       the same geometry with flat_frac = 0.94 (the captured-like small-N regime) under route 6 and under route 7
   flat55       a 1920x64 slab at 32 spp, box 55 (96800: the reference's first box), flat_frac = 0.94, routes 6 and 7: many
                rounds of the wide kernel's slots (seconds per step; not in the default case list's spirit: pick it by name)
+  lay4_18_f16  the smooth slab as (4, 18) stored as fp16 halves: routes 3, 4, 5 and the fp32-weight legs of 4 and 5
+smooth8, flat8, lay3_12, lay4_18 and lay4_18_f16 end with the legs of RPF_FLAG_GENERIC_FAST (`generic` = 12: route 4 with the
+flag, 13: route 5 with it; skipped on a library from before the flag): such a record carries ratio_to_fp64, its time over the
+same route's without the flag.
 A record of a wide pass carries the class census of its N plane (pixels with N <= 8, 16, ... 832, and the rest).
 Each case's variants run in one process on one context and on the same generated buffer; a route-4 or route-5 record
 carries ratio_to_route3 next to ratio_to_fused, a route-5 record ratio_to_route4 as well.
@@ -39,16 +43,23 @@ from raytracer_rpf_amd import hip  # noqa: E402
 
 # name: (W, H, S, box, flat_frac, [(n_random, n_feat, generic[, S of this variant: the first samples of the buffer]), ...])
 CASES = {
-    "smooth8": (1920, 270, 8, 7, 0.0, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3)]),
-    "flat8": (1920, 270, 8, 7, 0.94, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3)]),
-    "lay3_12": (1920, 270, 8, 7, 0.0, [(3, 12, 1), (3, 12, 2), (3, 12, 3)]),
-    "lay4_18": (1920, 270, 8, 7, 0.0, [(4, 18, 1), (4, 18, 2), (4, 18, 3)]),
+    "smooth8": (1920, 270, 8, 7, 0.0, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3), (2, 12, 12), (2, 12, 13)]),
+    "flat8": (1920, 270, 8, 7, 0.94, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3), (2, 12, 12), (2, 12, 13)]),
+    "lay3_12": (1920, 270, 8, 7, 0.0, [(3, 12, 1), (3, 12, 2), (3, 12, 3), (3, 12, 12), (3, 12, 13)]),
+    "lay4_18": (1920, 270, 8, 7, 0.0, [(4, 18, 1), (4, 18, 2), (4, 18, 3), (4, 18, 12), (4, 18, 13)]),
+    "lay4_18_f16": (1920, 270, 8, 7, 0.0, [(4, 18, 1), (4, 18, 2), (4, 18, 3), (4, 18, 12), (4, 18, 13)]),
     "box17": (256, 64, 16, 17, 0.0, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3)]),
     "wide57": (256, 57, 21, 57, 0.0, [(2, 12, 1, 14), (2, 12, 6, 21), (2, 12, 7, 21)]),
     "flat57": (256, 57, 21, 57, 0.94, [(2, 12, 6, 21), (2, 12, 7, 21)]),
     "flat55": (1920, 64, 32, 55, 0.94, [(2, 12, 6, 32), (2, 12, 7, 32)]),
 }
+F16_CASES = ("lay4_18_f16",)  # planes stored as fp16 halves
 CLASS_CAPS = (8, 16, 32, 64, 128, 256, 448, 832)
+
+
+def has_generic_fast():
+    """the flag alone is refused by a library that knows it; one from before it ignores the bit"""
+    return hasattr(hip, "FLAG_GENERIC_FAST") and hip.layout_kernels(hip.make_desc(8, 8, 4, flags=hip.FLAG_GENERIC_FAST))[0] == hip.E_UNSUPPORTED
 
 
 def run(ctx, name, steps):
@@ -57,12 +68,17 @@ def run(ctx, name, steps):
     stream = torch.cuda.current_stream().cuda_stream
     out = {}
     whole, planes, made = None, None, None
+    f16 = name in F16_CASES
     for leg in legs:
         nr, nf, generic = leg[:3]
+        fast = generic in (12, 13)   # RPF_FLAG_GENERIC_FAST on route 4 / 5
+        if fast and not has_generic_fast():
+            continue
+        generic = generic - 10 if fast else generic
         S = leg[3] if len(leg) > 3 else S_buf
         if made != (nr, nf):  # one buffer for the variants of a layout
             whole = fb.synth_planes_chunked(W, H, S_buf, xp=fb.torch_backend(dev), seed=20261017, sigma_f=0.05, sigma_c=1e-4,
-                                            mode="smooth", flat_frac=flat, n_random=nr, n_feat=nf)
+                                            mode="smooth", flat_frac=flat, n_random=nr, n_feat=nf, **({"dtype": "f16"} if f16 else {}))
             made = (nr, nf)
         planes = whole if S == S_buf else whole[..., :S].contiguous()
         colour = torch.empty((3, H, W, S), dtype=torch.float64, device=dev)
@@ -70,7 +86,9 @@ def run(ctx, name, steps):
         flags |= hip.FLAG_GENERIC_WAVE if generic == 3 else 0
         flags |= hip.FLAG_WIDE_NBHD if generic in (6, 7) else 0
         flags |= hip.FLAG_WIDE_CLASSES if generic == 7 else 0
-        desc = hip.make_desc(W, H, S, boxes=(box,), policy=hip.DEGEN_EPS, flags=flags, n_random=nr, n_feat=nf)
+        flags |= hip.FLAG_GENERIC_FAST if fast else 0
+        desc = hip.make_desc(W, H, S, boxes=(box,), policy=hip.DEGEN_EPS, flags=flags, n_random=nr, n_feat=nf,
+                             **({"plane_dtype": hip.PLANES_F16} if f16 else {}))
         ms = []
         for it in range(steps + 1):
             ctx.colour_from_planes_device(desc, planes.data_ptr(), colour.data_ptr(), stream)
@@ -78,8 +96,8 @@ def run(ctx, name, steps):
             if it:  # the first call warms up (allocations, tables)
                 ms.append(ctx.counters().filter_kernel_ms)
         c = ctx.counters()
-        rec = {"case": name, "shape": "%dx%dx%d box %d" % (W, H, S, box), "flat_frac": flat, "layout": [nr, nf, "f32"],
-               "generic": generic, "route": ctx.route(), "launches": c.filter_kernel_launches,
+        rec = {"case": name, "shape": "%dx%dx%d box %d" % (W, H, S, box), "flat_frac": flat, "layout": [nr, nf, "f16" if f16 else "f32"],
+               "generic": generic, "fp32_weights": int(fast), "route": ctx.route(), "launches": c.filter_kernel_launches,
                "mean_nbhd": round(c.sum_nbhd / (W * H), 1), "max_nbhd": c.max_nbhd,
                "filter_ms_min": round(min(ms), 3), "filter_ms_max": round(max(ms), 3), "stats_ms": round(c.stats_kernel_ms, 3),
                "colour_mean": float(colour.mean())}
@@ -92,6 +110,11 @@ def run(ctx, name, steps):
             rec["ratio_to_route6"] = round(rec["filter_ms_min"] / r6["filter_ms_min"], 4)
         if len(leg) > 3:
             rec["ns_per_pixel_sample"] = round(rec["filter_ms_min"] * 1e6 / max(c.sum_nbhd, 1), 4)
+        if fast:  # the same route without the flag, measured a moment ago on the same buffer
+            rec["ratio_to_fp64"] = round(rec["filter_ms_min"] / out[(nr, nf, generic)]["filter_ms_min"], 3)
+            print(json.dumps(rec), flush=True)
+            del colour
+            continue
         out[(nr, nf, generic)] = rec
         base = out.get((nr, nf, 0))
         if generic and base:
