@@ -34,13 +34,16 @@ def weighted_columns(n_random=2, n_feat=12):
     return np.array([0, 1, 2, 3, 4] + [5 + n_random + k for k in range(n_feat)])
 
 
-def neighbourhood(planes, pmean, pstd, y, x, box, n_random=2, n_feat=12):
+def neighbourhood(planes, pmean, pstd, y, x, box, n_random=2, n_feat=12, colour64=None):
     """the member samples of pixel (y, x) as rows [N, ndim] in fp64, in the oracle's order: the own samples, then the window
-    x outer / y inner / s, every candidate that fails no feature's |f - m| >= 3 sd test (a NaN never rejects)"""
+    x outer / y inner / s, every candidate that fails no feature's |f - m| >= 3 sd test (a NaN never rejects); colour64
+    (three fp64 planes [3, H, W, S], the colours an earlier pass left) replaces columns 2..4"""
     _, H, W, S = planes.shape
     b, f0 = (box - 1) // 2, 5 + n_random
     x0, x1, y0, y1 = max(x - b, 0), min(x + b, W - 1), max(y - b, 0), min(y + b, H - 1)
     win = planes[:, y0:y1 + 1, x0:x1 + 1, :].transpose(2, 1, 3, 0).astype(np.float64)      # [x, y, s, dim]
+    if colour64 is not None:
+        win[..., 2:5] = np.asarray(colour64, np.float64)[:, y0:y1 + 1, x0:x1 + 1, :].transpose(2, 1, 3, 0)
     with np.errstate(invalid="ignore"):
         rejected = (np.abs(win[..., f0:] - pmean[y, x]) >= pstd[y, x] * 3).any(axis=-1)
     keep = ~rejected
@@ -48,9 +51,20 @@ def neighbourhood(planes, pmean, pstd, y, x, box, n_random=2, n_feat=12):
     return np.concatenate([win[x - x0, y - y0], win[keep]], axis=0)
 
 
-def pixel_colours(nb, S, M, SD, alpha, beta, wrc, box, seed, policy, dtype, n_random=2, n_feat=12, fallback=True):
+def pixel_colours(nb, S, M, SD, alpha, beta, wrc, box, seed, policy, dtype, n_random=2, n_feat=12, fallback=True,
+                  form="direct", mutate=None):
     """filtered colours [3, S] of the pixel whose neighbourhood is nb (own samples first); fallback: under the EPS policy a NaN
-    colour is replaced by the sample's input colour, as the oracle does"""
+    colour is replaced by the sample's input colour, as the oracle does.
+
+    form = "direct"    E_ij = sum_k cz_k (z_ik - z_jk)^2, term by term: the oracle's and the generic kernels' expression.
+    form = "expanded"  E_ij = A_i + B_j + sum_k u_ik z_jk with cz_k = weight_k / (2 sigma^2), A_i = sum_k cz_k z_ik^2,
+                       B_j = sum_k cz_k z_jk^2, u_ik = -2 cz_k z_ik (the fused kernels).  Used by
+                       the CPU checks of the per-sample bar (tests/stage4_bars.py) alone.
+
+    mutate: None, or a function w[S, N] -> w[S, N] applied to the fp64 weights before the sums -- the planted faults of
+    tests/test_stage4_per_sample_cpu.py; no other caller passes it."""
+    if form not in ("direct", "expanded"):
+        raise ValueError(form)
     cols = weighted_columns(n_random, n_feat)
     with np.errstate(invalid="ignore", divide="ignore"):
         z = np.where(SD == 0, 0.0, (nb - M) / SD)[:, cols]
@@ -58,14 +72,24 @@ def pixel_colours(nb, S, M, SD, alpha, beta, wrc, box, seed, policy, dtype, n_ra
         sigma_c2 = seed * seed / (1 - wrc) / (1 - wrc)                                   # = sigma_f^2
         coef = np.concatenate([np.full(2, 1 / (2 * sigma_p * sigma_p)), alpha / (2 * sigma_c2), beta / (2 * sigma_c2)])
         z, coef = z.astype(dtype), coef.astype(dtype)
-        E = np.zeros((S, nb.shape[0]), dtype)
-        for k in range(len(cols)):
-            d = z[:S, k, None] - z[None, :, k]
-            E += (d * d) * coef[k]
+        if form == "direct":
+            E = np.zeros((S, nb.shape[0]), dtype)
+            for k in range(len(cols)):
+                d = z[:S, k, None] - z[None, :, k]
+                E += (d * d) * coef[k]
+        else:
+            B = np.zeros(nb.shape[0], dtype)
+            for k in range(len(cols)):
+                B += (coef[k] * z[:, k]) * z[:, k]
+            E = B[:S, None] + B[None, :]                                                  # A_i: the same sum of the same products
+            for k in range(len(cols)):
+                E += (dtype(-2.0) * (coef[k] * z[:S, k]))[:, None] * z[None, :, k]
         assert E.dtype == dtype
         w = np.exp(-E)
         assert w.dtype == dtype
         w = w.astype(np.float64)
+        if mutate is not None:
+            w = mutate(w)
         c = nb[:, 2:5]
         prime = (w @ c) / w.sum(axis=1)[:, None]                                          # [S, 3]
     if policy == EPS and fallback:
@@ -73,18 +97,30 @@ def pixel_colours(nb, S, M, SD, alpha, beta, wrc, box, seed, policy, dtype, n_ra
     return prime.T
 
 
-def stage4(oracle, planes, want, box, seed, pixels, dtype, policy=EPS, n_random=2, n_feat=12, fallback=True):
-    """colours [3, len(pixels), S] of `pixels` = [(y, x), ...] of the fp32 `planes`, from the debug outputs `want` of the
-    oracle's pass over them (box, sigma seed, policy and layout as given to that pass)"""
+def stage4(oracle, planes, want, box, seed, pixels, dtype, policy=EPS, n_random=2, n_feat=12, fallback=True, colour64=None,
+           form="direct", mutate=None):
+    """colours [3, len(pixels), S] of `pixels` = [(y, x), ...] of the fp32 `planes`, from the debug outputs `want` of a pass
+    over them (box, sigma seed, policy and layout as given to that pass).
+
+    `want` is any dict with nbhd_size, mean, stddev, alpha, beta, wrc.  The oracle's outputs make this the restatement of the
+    oracle's stage 4.  The DEVICE's own debug outputs work as they stand, and that is the point of the design of
+    tests/test_stage4_per_sample_gpu.py: check_pass already holds the device's stage 1 to 3 outputs to the oracle, so what
+    remains between the device's colours and stage4(..., got, ..., np.float64) is the device's pair arithmetic and blend alone
+    -- the 1e-9 slack allowed on alpha / beta, times an exponent of up to 745, does not pollute the comparison.
+
+    colour64: three fp64 planes, the colours an earlier pass left: a second pass reads them both as the blended values and
+    as the colour columns of z (planes[2:5] is then not read).  form: see pixel_colours.  mutate(w, index of the pixel in
+    `pixels`) -> w: a planted fault (tests/test_stage4_per_sample_cpu.py)."""
     _, H, W, S = planes.shape
     lay = dict(n_random=n_random, n_feat=n_feat) if (n_random, n_feat) != (2, 12) else {}
     pmean, pstd = oracle.pixel_stats(planes, oracle.make_desc(W, H, S, policy=policy, **lay))    # (EPS clamps a NaN sigma to 0)
     out = np.empty((3, len(pixels), S))
     for i, (y, x) in enumerate(pixels):
-        nb = neighbourhood(planes, pmean, pstd, y, x, box, n_random, n_feat)
+        nb = neighbourhood(planes, pmean, pstd, y, x, box, n_random, n_feat, colour64)
         assert nb.shape[0] == want["nbhd_size"][y, x], ((y, x), nb.shape[0], int(want["nbhd_size"][y, x]))
         out[:, i] = pixel_colours(nb, S, want["mean"][y, x], want["stddev"][y, x], want["alpha"][y, x], want["beta"][y, x],
-                                  want["wrc"][y, x], box, seed, policy, dtype, n_random, n_feat, fallback)
+                                  want["wrc"][y, x], box, seed, policy, dtype, n_random, n_feat, fallback, form,
+                                  None if mutate is None else (lambda w, i=i: mutate(w, i)))
     return out
 
 

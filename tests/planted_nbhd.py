@@ -89,6 +89,8 @@ def frame(fid):
 # discrete outputs, MI, alpha, beta and W_r_c are compared for real, the colours only show that nothing was broken.  With
 # this seed the weights are of order one (the oracle moves the colours by 6 ... 40 %), and a member dropped from, or a stale
 # slot added to, a weight sum shows in the colours.
+# Where stage 4 is actually held -- sample by sample, against a bar derived from the roundings -- is
+# tests/test_stage4_per_sample_gpu.py (tests/stage4_bars.py), at this seed.
 ACTIVE_SIGMA_SEED = 0.5
 
 _want = {}

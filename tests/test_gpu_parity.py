@@ -3,6 +3,10 @@
 Bars: bit-exact for integer/index work (neighbourhood membership and order, histogram bin ids) and for the
 fp64 statistics whose rounding decides them; MI / alpha / beta within 1e-10; filtered RGB <= 1e-4 relative
 L2 (BASELINE.json north_star), in practice ~1e-13.
+
+That norm is taken over a whole frame, and at the reference's sigma seed the filter is close to the identity on most frames
+here: the colours then only show that nothing was broken.  Stage 4 is held sample by sample, on filter-active frames of every
+route, by tests/test_stage4_per_sample_gpu.py against the bar of tests/stage4_bars.py.
 """
 import numpy as np
 import pytest
@@ -18,7 +22,10 @@ def rel_l2(a, b):
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
-def check_pass(got, want, rows=None, ab_rtol=1e-9):
+def check_pass(got, want, rows=None, ab_rtol=1e-9, sample_bar=None):
+    """sample_bar: None, or the bar of tests/stage4_bars.py -- in addition to everything below, every finite colour lies within
+    sample_bar * max finite |want colour| of the oracle's (valid where alpha, beta and W_r_c are the oracle's bits: their 1e-9
+    slack, times an exponent of up to 745, would otherwise be what is measured)"""
     sl = slice(None) if rows is None else slice(*rows)
     assert (got["nbhd_size"][sl] == want["nbhd_size"][sl]).all()
     assert (got["member_hash"][sl] == want["member_hash"][sl]).all()
@@ -33,6 +40,11 @@ def check_pass(got, want, rows=None, ab_rtol=1e-9):
     np.testing.assert_allclose(got["wrc"][sl], want["wrc"][sl], rtol=ab_rtol, atol=1e-12)
     r = rel_l2(got["colour"], want["colour"])
     assert r <= REL_L2_BAR, r
+    if sample_bar is not None:
+        fin = np.isfinite(got["colour"]) & np.isfinite(want["colour"])
+        worst = float(np.abs(got["colour"][fin] - want["colour"][fin]).max())
+        cmax = float(np.abs(want["colour"][np.isfinite(want["colour"])]).max())
+        assert worst <= sample_bar * cmax, (worst / cmax, sample_bar)
     return r
 
 
