@@ -24,6 +24,8 @@ SOURCES = [os.path.join(_HERE, "csrc", f) for f in KERNEL_TUS + API_TUS]
 HEADERS = [os.path.join(_HERE, "csrc", "rpf_internal.h"), os.path.join(_HERE, "csrc", "rpf_api.h"), os.path.join(_HERE, "csrc", "rpf_xlane.h"),
            os.path.join(_HERE, "csrc", "rpf_filter_impl.inc"), os.path.join(_HERE, "csrc", "rpf_packed_impl.inc"),
            os.path.join(_HERE, "csrc", "rpf_device_common.h"), os.path.join(_HERE, "csrc", "rpf_reflog.h"),
+           os.path.join(_HERE, "csrc", "rpf_generic_common.h"),  # what the five rpf_generic*.hip share
+           os.path.join(_HERE, "csrc", "rpf_generic_stream_stages.inc"),  # ... and the stage bodies of rpf_generic.hip and rpf_generic_wide.hip
            os.path.join(_ROOT, "include", "rpf_hip.h")]
 
 

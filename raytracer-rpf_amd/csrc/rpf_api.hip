@@ -257,6 +257,34 @@ int32_t ensure_big_scratch(rpf_ctx *ctx, const PassParams &p, uint32_t slots) {
     return ctx->d_big_bins.ensure(ctx, (size_t)slots * p.nmax * p.lay.ndim());
 }
 
+// How many workgroups (= scratch slots) a launch of the streaming kernel gets: min(pixels, resident) when its carve-up keeps
+// member list and bin ids in LDS, else -- and always under kSameWhenResident -- min(pixels, max(lo, min(hi, budget / bytes of a slot)))
+struct SlotRule {
+    uint32_t resident, lo, hi;
+    size_t budget;
+};
+constexpr uint32_t kSameWhenResident = 0;        // SlotRule::resident: the carve-up does not change the rule
+constexpr uint64_t kCountOnDevice = UINT64_MAX;  // launch_streaming's `pixels`: the list size is on the device, nothing to clamp to
+constexpr SlotRule kPassSlots = {2048, 64, 1024, (size_t)1 << 30};           // resident: eight workgroups on each of 256 CUs
+constexpr SlotRule kRedoSlots = {kSameWhenResident, 8, 128, (size_t)64 << 20}; // a fixed small grid: ordinary frames leave the list empty
+
+// One launch of the streaming kernel over p's rows or pixel list (`pixels` of them; kCountOnDevice with count_dev: the list size
+// is read on the device and the grid is the rule's slots): the slots by `rule`, the scratch, the launch
+int32_t launch_streaming(rpf_ctx *ctx, const PassParams &p, uint64_t pixels, const SlotRule &rule, const uint32_t *count_dev,
+                         hipStream_t s, int *launches) {
+    uint64_t slots = rule.resident;
+    if (rule.resident == kSameWhenResident || !generic_carve(p.lay, p.nmax).resident) {
+        const size_t per_slot = (size_t)p.nmax * (4 + (size_t)p.lay.ndim());
+        slots = std::max<size_t>(rule.lo, std::min<size_t>(rule.hi, rule.budget / per_slot));
+    }
+    slots = std::min<uint64_t>(pixels, slots);
+    int32_t st;
+    if ((st = ensure_big_scratch(ctx, p, (uint32_t)slots))) return st;
+    HIP_TRY(generic::launch_filter(p, ctx->d_big_list, ctx->d_big_bins, (uint32_t)slots, count_dev, s));
+    if (launches) ++*launches;
+    return RPF_OK;
+}
+
 // REF_ABORT: the pixels the resident kernels appended to the redo list (an MI table inside the fixed-point rounding band at
 // a non-power-of-two N: the reference returns rounding residue there, rpf_filter_impl.inc stage 3b) are filtered again,
 // whole, by the streaming kernel, which evaluates the reference's floating-point expression for such tables.  The list
@@ -267,13 +295,7 @@ int32_t launch_redo(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *launc
     PassParams q = p;
     q.pix_list = p.redo_list;
     q.list_count = 0;
-    const size_t per_slot = (size_t)q.nmax * (4 + (size_t)p.lay.ndim());
-    const uint32_t slots = (uint32_t)std::max<size_t>(8, std::min<size_t>(128, (64u << 20) / per_slot));
-    int32_t st;
-    if ((st = ensure_big_scratch(ctx, q, slots))) return st;
-    HIP_TRY(generic::launch_filter(q, ctx->d_big_list, ctx->d_big_bins, slots, p.redo_count, s));
-    if (launches) ++*launches;
-    return RPF_OK;
+    return launch_streaming(ctx, q, kCountOnDevice, kRedoSlots, p.redo_count, s, launches);
 }
 
 // u64 acceptance masks per pixel: one bit per candidate of the window (the pixel's own samples are members without a test)
@@ -456,18 +478,7 @@ int32_t route_generic(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *lau
     ctx->last_route = 3;
     if (p.policy == RPF_DEGEN_REF_ABORT) HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
     if (p.row_end <= p.row_begin) return RPF_OK;
-    const GenericCarve cv = generic_carve(p.lay, p.nmax);
-    const uint64_t npix = (uint64_t)(p.row_end - p.row_begin) * p.W;
-    uint32_t slots = (uint32_t)std::min<uint64_t>(npix, 2048); // resident: eight workgroups on each of 256 CUs
-    if (!cv.resident) {
-        const size_t per_slot = (size_t)p.nmax * (4 + (size_t)p.lay.ndim());
-        slots = (uint32_t)std::min<uint64_t>(npix, std::max<size_t>(64, std::min<size_t>(1024, ((size_t)1 << 30) / per_slot)));
-        int32_t st;
-        if ((st = ensure_big_scratch(ctx, p, slots))) return st;
-    }
-    HIP_TRY(generic::launch_filter(p, ctx->d_big_list, ctx->d_big_bins, slots, nullptr, s));
-    if (launches) ++*launches;
-    return RPF_OK;
+    return launch_streaming(ctx, p, (uint64_t)(p.row_end - p.row_begin) * p.W, kPassSlots, nullptr, s, launches);
 }
 
 // One launch of the wide kernel, over the slab's rows or over p.pix_list (p.list_count entries, or *count_dev of them), for at
@@ -624,15 +635,7 @@ int32_t route_generic_packed(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s
         PassParams q = p;
         q.pix_list = ctx->d_lists + (size_t)rest_class * HW;
         q.list_count = counts[rest_class];
-        const GenericCarve cv = generic_carve(q.lay, q.nmax);
-        uint32_t slots = std::min<uint32_t>(q.list_count, 2048u); // resident: eight workgroups on each of 256 CUs
-        if (!cv.resident) {
-            const size_t per_slot = (size_t)q.nmax * (4 + (size_t)q.lay.ndim());
-            slots = (uint32_t)std::min<uint64_t>(q.list_count, std::max<size_t>(64, std::min<size_t>(1024, ((size_t)1 << 30) / per_slot)));
-            if ((st = ensure_big_scratch(ctx, q, slots))) return st;
-        }
-        HIP_TRY(generic::launch_filter(q, ctx->d_big_list, ctx->d_big_bins, slots, nullptr, s));
-        if (launches) ++*launches;
+        if ((st = launch_streaming(ctx, q, q.list_count, kPassSlots, nullptr, s, launches))) return st;
     }
     return launch_redo(ctx, p, s, launches);
 }
@@ -685,15 +688,7 @@ int32_t route_generic_wave(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, 
         PassParams q = p;
         q.pix_list = ctx->d_lists + (size_t)rest_class * HW;
         q.list_count = counts[rest_class];
-        const GenericCarve cv = generic_carve(q.lay, q.nmax);
-        uint32_t slots = std::min<uint32_t>(q.list_count, 2048u); // resident: eight workgroups on each of 256 CUs
-        if (!cv.resident) {
-            const size_t per_slot = (size_t)q.nmax * (4 + (size_t)q.lay.ndim());
-            slots = (uint32_t)std::min<uint64_t>(q.list_count, std::max<size_t>(64, std::min<size_t>(1024, ((size_t)1 << 30) / per_slot)));
-            if ((st = ensure_big_scratch(ctx, q, slots))) return st;
-        }
-        HIP_TRY(generic::launch_filter(q, ctx->d_big_list, ctx->d_big_bins, slots, nullptr, s));
-        if (launches) ++*launches;
+        if ((st = launch_streaming(ctx, q, q.list_count, kPassSlots, nullptr, s, launches))) return st;
     }
     return launch_redo(ctx, p, s, launches);
 }

@@ -1,0 +1,217 @@
+// rpf_generic_common.h -- what the five layout-generic translation units share (rpf_generic.hip, rpf_generic_packed.hip,
+// rpf_generic_wave.hip, rpf_generic_wide.hip, rpf_generic_wide_count.hip; routes 3 to 7).  Only they include it.  Device
+// code has internal linkage, like rpf_device_common.h: each TU carries its own copy.
+//
+// For every TU: the column counts of a layout (GenericDims), up16 and the size of the fp64 block of the LDS carve-ups (host side), the
+// plane loaders, pair_cols and block_reduce.  Moving these here left the device assembly of every kernel as it was.
+//
+// For the packed kernels and the two count kernels, whose stage bodies call them: the window of stage 1b and the decode of a
+// candidate, the 3-sigma test of a wave, the column constants and the bin id, the zero band of stage 3b, the beta numerator, the
+// debug hashes and the store of a filtered colour -- the statements the routes promise the same bits for.
+//
+// filter_pixel_kernel, filter_wide_kernel and filter_wave_kernel spell the same statements inside their stage bodies and do not
+// call these functions.  Two forms that do were built and held to the bars (profiles/generic_refactor_parent_vs_new.txt): (a)
+// stage 3c and the streaming kernels' stages as __forceinline__ functions, (b) the stage bodies inline, calling the small functions
+// and an offsets struct of the fp64 block.  Both: same bits, waves per SIMD kept, no scratch; both outside the parent's spread
+// on scripts/generic_timing.py.  filter_pixel_kernel<float>, route-3 legs of the 1920x270x8 slabs: (a) +0.43 to +0.65 %, (b) +0.7 to
+// +1.8 % (142.62 -> 143.60 ms, 189.84 -> 192.33 ms).  filter_wave_kernel, route-5 legs: (a) +0.2 to +0.8 %, (b) +0.2 to +1.7 %
+// (fp16 planes 155.66 -> 157.56 ms, FAST 135.88 -> 138.22 ms).  filter_wide_kernel passed in form (b) (wide57 583.15 -> 580.22 ms,
+// flat57 126.19 -> 126.19 ms) but shares its stage text with filter_pixel_kernel (rpf_generic_stream_stages.inc), which did not.
+// So the three keep their bodies, with the parent's assembly byte for byte.
+#pragma once
+#include "rpf_device_common.h"
+
+#ifndef RPF_GENERIC_OWN
+#define RPF_GENERIC_OWN 4 // own samples per sweep of stage 4 (their accumulators are registers; same bits at any value)
+#endif
+
+namespace rpf {
+
+// column counts of a layout, as the kernels and the host carve-ups use them
+struct GenericDims {
+    int nR, nF, ndim, nAnc, npairF, npairC, npair, nwt, colF;
+};
+__host__ __device__ inline GenericDims generic_dims(const SampleLayout &l) {
+    GenericDims d;
+    d.nR = l.nR; d.nF = l.nF; d.ndim = 5 + l.nR + l.nF;
+    d.nAnc = l.nR + 2;                       // r.. and p.. anchors
+    d.npairF = l.nF * d.nAnc;                // pairs (f_i, r_l | p_l)          rpf.cpp:416-427
+    d.npairC = d.nAnc + l.nF;                // pairs of one colour channel     rpf.cpp:429-442
+    d.npair = d.npairF + 3 * d.npairC;
+    d.nwt = 5 + l.nF;                        // weighted columns of stage 4
+    d.colF = 5 + l.nR;
+    return d;
+}
+
+__host__ __device__ constexpr uint32_t up16(uint32_t v) { return (v + 15u) & ~15u; }
+
+// Doubles in the fp64 block of the stream, wide and one-wave kernels, which their carve-ups size and the kernels walk in this order:
+//   sStat M | SD | min | max [4 ndim], sZ lo | range | flags(sd0 | flat << 1) [3 ndim], sHX sum_i T[hx_i] [ndim],
+//   sPair sum_ij T[J_ij] per pair, then the MI values [npair], sW Drf[nF] | D9[12] | alpha[4] | beta[nF] | wrc[4]
+// (the streaming kernels keep 256 doubles of reduction scratch, sRedD, behind it)
+inline uint32_t generic_f64_doubles(const GenericDims &D) { return (uint32_t)(8 * D.ndim + D.npair + 2 * D.nF + 20); }
+
+namespace generic {
+namespace {
+
+constexpr int kThreads = 256, kChunk = 64; // the streaming kernels: threads of a workgroup, members staged per step of stage 2
+constexpr int kOwn = RPF_GENERIC_OWN;      // ... and own samples per sweep of stage 4
+
+template <class T>
+__device__ __forceinline__ float ldp(const PassParams &p, int col, uint32_t off) {
+    return (float)reinterpret_cast<const T *>(p.planes)[(uint64_t)col * p.plane_stride + off];
+}
+// value of column c of the sample at plane offset `off`: colours come from the fp64 colour planes
+template <class T>
+__device__ __forceinline__ double load_col(const PassParams &p, int c, uint32_t off) {
+    if (c >= 2 && c < 5) return p.col_in[(uint64_t)(c - 2) * p.plane_stride + off];
+    return (double)ldp<T>(p, c, off);
+}
+// columns of MI pair pr, in ComputeCFWeights call order (rpf.cpp:416-442 with the loop bounds generalised)
+__device__ __forceinline__ void pair_cols(const GenericDims &D, int pr, int &ca, int &cb) {
+    if (pr < D.npairF) {
+        const int i = pr / D.nAnc, l = pr - i * D.nAnc;
+        ca = D.colF + i;
+        cb = l < D.nR ? 5 + l : l - D.nR;
+    } else {
+        const int q = pr - D.npairF, c = q / D.npairC, l = q - c * D.npairC;
+        ca = 2 + c;
+        cb = l < D.nR ? 5 + l : (l < D.nAnc ? l - D.nR : D.colF + (l - D.nAnc));
+    }
+}
+
+// order-free reductions (min, max, integer sums) over a workgroup of 256; result in every thread.  sRed4: 4 slots
+template <class V, class Op>
+__device__ __forceinline__ V block_reduce(V v, V *sRed4, Op op) {
+    for (int s = 32; s > 0; s >>= 1) v = op(v, __shfl_down(v, s, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sRed4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return op(op(sRed4[0], sRed4[1]), op(sRed4[2], sRed4[3]));
+}
+
+// ---- stage 1b: the window of pixel (x, y) and its candidates in the reference's visiting order (rpf.cpp:556-586) ---------
+struct Window {
+    int x0, y0, nyv, centre_rank, ncand;
+};
+__device__ __forceinline__ Window make_window(int x, int y, int b, int W, int H, int S) {
+    const int x0 = max(x - b, 0), x1 = min(x + b, W - 1), y0 = max(y - b, 0), y1 = min(y + b, H - 1);
+    const int nyv = y1 - y0 + 1;
+    const int centre_rank = (x - x0) * nyv + (y - y0);
+    const int ncand = ((x1 - x0 + 1) * nyv - 1) * S;
+    return Window{x0, y0, nyv, centre_rank, ncand};
+}
+// plane offset of candidate qq < ncand
+__device__ __forceinline__ uint32_t candidate_offset(const Window &w, int W, int S, int qq) {
+    int cell = qq / S;
+    const int s = qq - cell * S;
+    if (cell >= w.centre_rank) ++cell;              // rpf.cpp:565: skip the centre pixel
+    const int ix = cell / w.nyv, iy = cell - ix * w.nyv; // xn outer, yn inner ascending (rpf.cpp:562-563)
+    return (uint32_t)(((uint64_t)(w.y0 + iy) * W + (w.x0 + ix)) * S + s);
+}
+// the strict 3-sigma test as the count kernels run it, a wave on 64 candidates of pixel `pix`: a rejected candidate stays
+// rejected, so the later features are read only while some lane still passes
+template <class T>
+__device__ __forceinline__ bool passes_3sigma_wave(const PassParams &p, int colF, int nF, uint32_t off, uint64_t HW, uint64_t pix, bool pass) {
+    for (int k = 0; k < nF; ++k) {
+        if (!__any(pass)) break;
+        const double m = p.pmean[(uint64_t)k * HW + pix];
+        const double lim = p.pstd[(uint64_t)k * HW + pix] * 3.0;  // multiplyArray(std, 3), rpf.cpp:579
+        if (pass) {
+            const double a = fabs((double)ldp<T>(p, colF + k, off) - m);
+            if (a >= lim) pass = false;           // allLessThan: fails iff a >= b (ops.h:101-104): a NaN never rejects
+        }
+    }
+    return pass;
+}
+
+// ---- stage 2: the constants of a column from its in-order sums and its extrema (sd.h:229-232, mi.cpp:47-50) -----------
+__device__ __forceinline__ void column_mean_sd(double sum, double sq, double dn, int policy, double &mean, double &sd) {
+    mean = sum / dn;                                    // ops.h:123
+    sd = sqrt(sq / dn - mean * mean);                   // ops.h:141
+    if (policy == RPF_DEGEN_EPS && isnan(sd)) sd = 0.0;
+}
+// lo, range and the flags sd0 | flat << 1 of the binning
+__device__ __forceinline__ void column_bin_range(double Mc, double SDc, double mn, double mx, double &lo, double &range, double &flags) {
+    const bool sd0 = (SDc == 0.0);
+    lo = sd0 ? 0.0 : (mn - Mc) / SDc;
+    const double hi = sd0 ? 0.0 : (mx - Mc) / SDc;
+    range = hi - lo;
+    flags = (double)((sd0 ? 1 : 0) | (!(hi != lo) ? 2 : 0)); // mi.cpp:7 / 28 / 34
+}
+struct ColumnConst {
+    double mean, sd, lo, range, flags;
+};
+__device__ __forceinline__ ColumnConst column_constants(double sum, double sq, double mn, double mx, double dn, int policy) {
+    ColumnConst c;
+    column_mean_sd(sum, sq, dn, policy, c.mean, c.sd);
+    column_bin_range(c.mean, c.sd, mn, mx, c.lo, c.range, c.flags);
+    return c;
+}
+
+// ---- stage 3a: the bin id of value v in a column with those constants, B bins ----------------------------------------------
+__device__ __forceinline__ int bin_id(double v, double Mc, double SDc, double lo, double range, int flags, int B) {
+    const bool sd0 = flags & 1, flat = flags & 2;
+    int bin = 0;
+    if (!flat) {
+        const double a = v - Mc;                                   // subtractArrays
+        const double z = sd0 ? 0.0 : a / SDc;                      // divideArrays, ops.h:48
+        const double t = (z - lo) / range * (double)B;             // mi.cpp:14
+        bin = max(min((int)t, B - 1), 0);
+    }
+    return bin;
+}
+
+// ---- stage 3b: MI of a pair from f = T[N] + sum T[J] - sum T[hx] - sum T[hy] in units of 2^-bits, with the zero band of the
+// fixed-point sums (rpf_filter_impl.inc, filter_pixel_kernel).  inexact: the table is inside the band at a non-power-of-two N
+// with non-degenerate marginals -- the reference's own value for it is rounding residue, not zero (REF_ABORT: the packed
+// kernel puts the pixel on the redo list, and generic::filter_pixel_kernel evaluates the reference's expression)
+__device__ __forceinline__ double zero_band_mi(int64_t f, int B, int n, uint64_t hxa, uint64_t hxb, uint64_t TN, int bits, double dn,
+                                               bool &inexact) {
+    const int64_t zero_band = ((int64_t)B * B + 2 * B + 1) / 2 + 1;
+    inexact = false;
+    if (f <= zero_band && f >= -zero_band) {
+        inexact = (n & (n - 1)) != 0 && hxa != TN && hxb != TN;
+        f = 0;
+    }
+    return ldexp((double)f, -bits) / dn;
+}
+
+// ---- stage 3c: the numerator of beta_k.  The presets keep the reference's stack rule for any nF: k < 3 reads D_f_ck (c = k on
+// every lane whose beta is kept), a gap of zeros, then D_r_fk
+__device__ __forceinline__ double beta_numerator(int beta_map, int k, int c, double Dcf, const double *sD9, const double *sDrf) {
+    if (beta_map == RPF_BETA_PAPER) return Dcf;
+    if (beta_map == RPF_BETA_REF_GCC11_O2) return k < 3 ? sD9[6 + c] : (k < 8 ? 0.0 : sDrf[max(k - 8, 0)]);
+    return k < 3 ? sD9[6 + c] : (k < 4 ? 0.0 : sDrf[max(k - 4, 0)]);
+}
+
+// ---- debug outputs: FNV-1a of the member list in order (window coordinates of each member), and of a column's bin ids ------
+__device__ __forceinline__ uint32_t member_hash(const uint32_t *list, int n, int x, int y, int b, int box, int S, int W) {
+    uint32_t h = 2166136261u;
+    for (int j = 0; j < n; ++j) {
+        const uint32_t o = list[j], s = o % (uint32_t)S, q = o / (uint32_t)S;
+        const int yn = (int)(q / (uint32_t)W), xn = (int)(q % (uint32_t)W);
+        h = fnv1a_u32(h, (uint32_t)(((xn - x + b) * box + (yn - y + b)) * S) + s);
+    }
+    return h;
+}
+template <class Bin>
+__device__ __forceinline__ uint32_t bin_hash(const Bin *bc, int n) {
+    uint32_t h = 2166136261u;
+    for (int j = 0; j < n; ++j) h = fnv1a_u16(h, bc[j]);
+    return h;
+}
+
+// ---- stage 4: channel ch of own sample i of pixel pix = num / den (rpf.cpp:700); a NaN (rpf.cpp:702: the reference exits
+// there) is reported by the return value and, under EPS, replaced by the input colour
+__device__ __forceinline__ bool store_filtered(const PassParams &p, int ch, uint64_t pix, int S, int i, double num, double den) {
+    double prime = num / den;
+    const bool bad = isnan(prime);
+    if (bad && p.policy == RPF_DEGEN_EPS) prime = p.col_in[(uint64_t)ch * p.plane_stride + pix * S + i];
+    p.col_out[(uint64_t)ch * p.plane_stride + pix * S + i] = prime;
+    return bad;
+}
+
+} // namespace
+} // namespace generic
+} // namespace rpf

@@ -28,15 +28,15 @@
 // z and the 5 + n_feat coefficients (log2 e folded in) formed in fp64 and rounded once, one accumulator per own sample, two own
 // samples per packed fp32 instruction, one hardware exponential, the sums and the quotient in fp64.  Every statement outside
 // stage 4 is shared, so the stage outputs are the FAST = false kernel's bits.
-#include "rpf_device_common.h"
+#include "rpf_generic_common.h"
 
 #include <algorithm>
 
 namespace rpf {
 
 GenericPackedCarve generic_packed_carve(const SampleLayout &lay) {
-    const uint32_t ndim = (uint32_t)lay.ndim(), npair = (uint32_t)lay.npair(), nF = (uint32_t)lay.nF;
-    auto up16 = [](uint32_t v) { return (v + 15u) & ~15u; };
+    const GenericDims D = generic_dims(lay);
+    const uint32_t ndim = (uint32_t)D.ndim, npair = (uint32_t)D.npair, nF = (uint32_t)D.nF;
     GenericPackedCarve c{};
     c.off_pairtab = up16(65u * 8u);                  // behind T[0 .. 64]
     c.table_bytes = up16(c.off_pairtab + 2u * npair);
@@ -67,44 +67,6 @@ typedef float __attribute__((may_alias)) zf32;                              // f
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2a __attribute__((ext_vector_type(2), may_alias));
 
-struct PkDims {
-    int nR, nF, ndim, nAnc, npairF, npairC, npair, nwt, colF;
-};
-__device__ __forceinline__ PkDims pk_dims(const SampleLayout &l) {
-    PkDims d;
-    d.nR = l.nR; d.nF = l.nF; d.ndim = 5 + l.nR + l.nF;
-    d.nAnc = l.nR + 2;                       // r.. and p.. anchors
-    d.npairF = l.nF * d.nAnc;                // pairs (f_i, r_l | p_l)          rpf.cpp:416-427
-    d.npairC = d.nAnc + l.nF;                // pairs of one colour channel     rpf.cpp:429-442
-    d.npair = d.npairF + 3 * d.npairC;
-    d.nwt = 5 + l.nF;                        // weighted columns of stage 4
-    d.colF = 5 + l.nR;
-    return d;
-}
-
-template <class T>
-__device__ __forceinline__ float pk_ldp(const PassParams &p, int col, uint32_t off) {
-    return (float)reinterpret_cast<const T *>(p.planes)[(uint64_t)col * p.plane_stride + off];
-}
-// value of column c of the sample at plane offset `off`: colours come from the fp64 colour planes
-template <class T>
-__device__ __forceinline__ double pk_load_col(const PassParams &p, int c, uint32_t off) {
-    if (c >= 2 && c < 5) return p.col_in[(uint64_t)(c - 2) * p.plane_stride + off];
-    return (double)pk_ldp<T>(p, c, off);
-}
-// columns of MI pair pr, in ComputeCFWeights call order (rpf.cpp:416-442 with the loop bounds generalised)
-__device__ __forceinline__ void pk_pair_cols(const PkDims &D, int pr, int &ca, int &cb) {
-    if (pr < D.npairF) {
-        const int i = pr / D.nAnc, l = pr - i * D.nAnc;
-        ca = D.colF + i;
-        cb = l < D.nR ? 5 + l : l - D.nR;
-    } else {
-        const int q = pr - D.npairF, c = q / D.npairC, l = q - c * D.npairC;
-        ca = 2 + c;
-        cb = l < D.nR ? 5 + l : (l < D.nAnc ? l - D.nR : D.colF + (l - D.nAnc));
-    }
-}
-
 // all-reduce over the G lanes of a group (G = 8: half a DPP row, 16: a row, 32: a row pair, 64: the wave); EXEC = all lanes
 template <int G>
 __device__ __forceinline__ double group_sum(double v) {
@@ -132,33 +94,15 @@ __global__ __launch_bounds__(256) void nbhd_count_kernel(PassParams p) {
     const uint64_t pix = (uint64_t)p.row_begin * W + e;
     const int y = (int)(pix / (uint32_t)W), x = (int)(pix - (uint64_t)y * W);
     const int nF = p.lay.nF, colF = 5 + p.lay.nR;
-    const int x0 = max(x - b, 0), x1 = min(x + b, W - 1), y0 = max(y - b, 0), y1 = min(y + b, H - 1);
-    const int nyv = y1 - y0 + 1;
-    const int centre_rank = (x - x0) * nyv + (y - y0);
-    const int ncand = ((x1 - x0 + 1) * nyv - 1) * S;
+    const Window win = make_window(x, y, b, W, H, S);
+    const int ncand = win.ncand;
     uint64_t *pm = p.masks + pix * p.mask_stride;
     int n = S;
     for (int qb = 0; qb < ncand; qb += 64) {
         const int qq = qb + lane;
         bool pass = qq < ncand;
-        uint32_t off = 0u;
-        if (pass) {
-            int cell = qq / S;
-            const int s = qq - cell * S;
-            if (cell >= centre_rank) ++cell;              // rpf.cpp:565: skip the centre pixel
-            const int ix = cell / nyv, iy = cell - ix * nyv; // xn outer, yn inner ascending (rpf.cpp:562-563)
-            off = (uint32_t)(((uint64_t)(y0 + iy) * W + (x0 + ix)) * S + s);
-        }
-        // a rejected candidate stays rejected: the later features are read only while some lane still passes
-        for (int k = 0; k < nF; ++k) {
-            if (!__any(pass)) break;
-            const double m = p.pmean[(uint64_t)k * HW + pix];
-            const double lim = p.pstd[(uint64_t)k * HW + pix] * 3.0;  // multiplyArray(std, 3), rpf.cpp:579
-            if (pass) {
-                const double a = fabs((double)pk_ldp<T>(p, colF + k, off) - m);
-                if (a >= lim) pass = false;           // allLessThan: fails iff a >= b (ops.h:101-104): a NaN never rejects
-            }
-        }
+        const uint32_t off = pass ? candidate_offset(win, W, S, qq) : 0u;
+        pass = passes_3sigma_wave<T>(p, colF, nF, off, HW, pix, pass);
         const unsigned long long mask = __ballot(pass);
         if (lane == 0) pm[qb >> 6] = mask;
         n += __popcll(mask);
@@ -175,7 +119,7 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
     constexpr int kOwn = FAST ? RPF_PACKED_FAST_OWN : 4;        // own samples per sweep of stage 4
     static_assert(P * BSTR <= 16, "sixteen masks per column and wave");
     extern __shared__ __align__(16) unsigned char smem[];
-    const PkDims D = pk_dims(p.lay);
+    const GenericDims D = generic_dims(p.lay);
     const int ndim = D.ndim, nF = D.nF, nR = D.nR, nAnc = D.nAnc, npair = D.npair, nwt = D.nwt, colF = D.colF;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -185,7 +129,7 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
     uint16_t *sPairTab = reinterpret_cast<uint16_t *>(smem + cv.off_pairtab);
     for (int pr = tid; pr < npair; pr += nthreads) {
         int ca, cb;
-        pk_pair_cols(D, pr, ca, cb);
+        pair_cols(D, pr, ca, cb);
         sPairTab[pr] = (uint16_t)(ca | (cb << 8));
     }
     __syncthreads(); // the only barrier: from here on the waves are independent
@@ -216,16 +160,13 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
         const int gbase = g * ndim;                       // first (pixel, column) record of the group
 
         // ---- stage 1b: the lane's sample (rpf.cpp:556-586), rank select in the acceptance masks --------------------
-        const int x0 = max(x - b, 0), x1 = min(x + b, W - 1), y0 = max(y - b, 0), y1 = min(y + b, H - 1);
-        const int nyv = y1 - y0 + 1;
-        const int centre_rank = (x - x0) * nyv + (y - y0);
-        const int ncand = ((x1 - x0 + 1) * nyv - 1) * S;
+        const Window win = make_window(x, y, b, W, H, S);
         uint32_t off = (uint32_t)(pix * S) + (uint32_t)min(t, S - 1); // own samples first
         if (p.members != nullptr) { // (uniform) the listed members of a wide pass's count kernel, already in that order
             if (live && t >= S) off = p.members[p.member_base[pix] + (uint64_t)(t - S)];
         } else {
             int rank = (live && t >= S) ? t - S : -1;        // the rank-th accepted candidate of the window
-            const int nwords = (ncand + 63) >> 6;
+            const int nwords = (win.ncand + 63) >> 6;
             const uint64_t *pm = p.masks + pix * p.mask_stride;
             for (int w = 0; __any(rank >= 0) && w < (int)p.mask_stride; ++w) {
                 unsigned long long m = (rank >= 0 && w < nwords) ? pm[w] : 0ull;
@@ -234,12 +175,7 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
                     rank -= c;
                 } else if (rank >= 0) {
                     for (int k = 0; k < rank; ++k) m &= m - 1ull;  // drop the lower set bits
-                    const int qq = w * 64 + (__ffsll((long long)m) - 1);
-                    int cell = qq / S;
-                    const int s = qq - cell * S;
-                    if (cell >= centre_rank) ++cell;              // rpf.cpp:565: skip the centre pixel
-                    const int ix = cell / nyv, iy = cell - ix * nyv; // xn outer, yn inner ascending (rpf.cpp:562-563)
-                    off = (uint32_t)(((uint64_t)(y0 + iy) * W + (x0 + ix)) * S + s);
+                    off = candidate_offset(win, W, S, w * 64 + (__ffsll((long long)m) - 1));
                     rank = -1;
                 }
             }
@@ -248,21 +184,12 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
             uint32_t *sOffD = reinterpret_cast<uint32_t *>(sU);
             sOffD[lane] = off;
             wsync();
-            if (t == 0 && gvalid) {
-                uint32_t h = 2166136261u;
-                for (int j = 0; j < n; ++j) {
-                    const uint32_t o = sOffD[g * G + j];
-                    const uint32_t s = o % (uint32_t)S, pp = o / (uint32_t)S;
-                    const int yn = (int)(pp / (uint32_t)W), xn = (int)(pp % (uint32_t)W);
-                    h = fnv1a_u32(h, (uint32_t)(((xn - x + b) * p.box + (yn - y + b)) * S) + s);
-                }
-                p.dbg.member_hash[pix] = h;
-            }
+            if (t == 0 && gvalid) p.dbg.member_hash[pix] = member_hash(sOffD + g * G, n, x, y, b, p.box, S, W);
             wsync();
         }
 
         // ---- the lane's sample vector, staged [group][column][slot]; masks and flags cleared ------------------------
-        for (int c = 0; c < ndim; ++c) sU[(gbase + c) * G + t] = live ? pk_load_col<T>(p, c, off) : 0.0;
+        for (int c = 0; c < ndim; ++c) sU[(gbase + c) * G + t] = live ? load_col<T>(p, c, off) : 0.0;
         for (int k = lane; k < ndim * 16; k += 64) sMask[k] = 0ull;
         if (lane < 8) sFlag[lane] = 0;
         wsync();
@@ -280,17 +207,12 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
                 sq = sq + v * v;                             // ops.h:138
                 mn = fmin(mn, v); mx = fmax(mx, v);
             }
-            const double mean = sum / dn;                    // ops.h:123
-            double sd = sqrt(sq / dn - mean * mean);         // ops.h:141
-            if (p.policy == RPF_DEGEN_EPS && isnan(sd)) sd = 0.0;
-            const bool sd0 = (sd == 0.0);
-            const double lo = sd0 ? 0.0 : (mn - mean) / sd, hi = sd0 ? 0.0 : (mx - mean) / sd;
+            const ColumnConst cc = column_constants(sum, sq, mn, mx, dn, p.policy);
             double *st = sStat + (gbase + c) * 5;
-            st[0] = mean; st[1] = sd; st[2] = lo; st[3] = hi - lo;
-            st[4] = (double)((sd0 ? 1 : 0) | (!(hi != lo) ? 2 : 0)); // mi.cpp:7 / 28 / 34
+            st[0] = cc.mean; st[1] = cc.sd; st[2] = cc.lo; st[3] = cc.range; st[4] = cc.flags;
             if (gvalid) {
-                if (p.dbg.mean) p.dbg.mean[pix * ndim + c] = mean;
-                if (p.dbg.stddev) p.dbg.stddev[pix * ndim + c] = sd;
+                if (p.dbg.mean) p.dbg.mean[pix * ndim + c] = cc.mean;
+                if (p.dbg.stddev) p.dbg.stddev[pix * ndim + c] = cc.sd;
             }
         }
         wsync();
@@ -299,16 +221,7 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
         const int B = max(1, (int)sqrt(dn));                 // mi.cpp:54
         for (int c = 0; c < ndim; ++c) {
             const double *st = sStat + (gbase + c) * 5;
-            const double Mc = st[0], SDc = st[1], lo = st[2], range = st[3];
-            const int flags = (int)st[4];
-            const bool sd0 = flags & 1, flat = flags & 2;
-            int bin = 0;
-            if (!flat) {
-                const double a = sU[(gbase + c) * G + t] - Mc;               // subtractArrays
-                const double z = sd0 ? 0.0 : a / SDc;                        // divideArrays, ops.h:48
-                const double tt = (z - lo) / range * (double)B;              // mi.cpp:14
-                bin = max(min((int)tt, B - 1), 0);
-            }
+            const int bin = bin_id(sU[(gbase + c) * G + t], st[0], st[1], st[2], st[3], (int)st[4], B);
             if (live) {
                 sBin[(gbase + c) * G + t] = (uint8_t)bin;
                 atomicOr(&sMask[(gbase + c) * BSTR + bin], 1ull << t);
@@ -316,12 +229,7 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
         }
         wsync();
         if (p.dbg.bin_hash != nullptr && gvalid) { // debug only: hash per column in sample order
-            for (int c = t; c < ndim; c += G) {
-                uint32_t h = 2166136261u;
-                const uint8_t *bc = sBin + (gbase + c) * G;
-                for (int j = 0; j < n; ++j) h = fnv1a_u16(h, bc[j]);
-                p.dbg.bin_hash[pix * ndim + c] = h;
-            }
+            for (int c = t; c < ndim; c += G) p.dbg.bin_hash[pix * ndim + c] = bin_hash(sBin + (gbase + c) * G, n);
         }
         // marginals: sum_i T[hx_i] per column
         for (int c = t; c < ndim; c += G) {
@@ -334,8 +242,7 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
         // joint histograms: lane t takes the pairs t, t + G, ...; a cell's count is popcount(mask_a[i] & mask_b[j])
         bool redo = false;
         {
-            const int64_t TNf = (int64_t)sT[n];
-            const int64_t zero_band = ((int64_t)B * B + 2 * B + 1) / 2 + 1;   // see filter_pixel_kernel (rpf_filter_impl.inc)
+            const uint64_t TN = sT[n];
             for (int pr = t; pr < npair; pr += G) {
                 const uint32_t cc = sPairTab[pr];
                 const int ca = (int)(cc & 255u), cb = (int)(cc >> 8);
@@ -345,15 +252,13 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
                     const unsigned long long a = ma[i];
                     for (int j = 0; j < B; ++j) acc += sT[__popcll(a & mb[j])];   // T[J_ij], mi.cpp:39 / 79-86 over integer counts
                 }
-                const int64_t hxa = (int64_t)sHX[gbase + ca], hxb = (int64_t)sHX[gbase + cb];
-                int64_t f = TNf + (int64_t)acc - hxa - hxb;
-                if (f <= zero_band && f >= -zero_band) {
-                    // REF_ABORT: the reference's own value for such a table is rounding residue unless its quotients are
-                    // exact (N a power of two, or a one-bin column): generic::filter_pixel_kernel evaluates it (redo list)
-                    if (p.redo_list != nullptr && (n & (n - 1)) != 0 && hxa != TNf && hxb != TNf) redo = true;
-                    f = 0;
-                }
-                const double mi = ldexp((double)f, -kTFixBits) / dn;
+                const uint64_t hxa = sHX[gbase + ca], hxb = sHX[gbase + cb];
+                const int64_t f = (int64_t)TN + (int64_t)acc - (int64_t)hxa - (int64_t)hxb;
+                // REF_ABORT: the reference's own value for an in-band table is rounding residue unless its quotients are
+                // exact (N a power of two, or a one-bin column): generic::filter_pixel_kernel evaluates it (redo list)
+                bool inexact;
+                const double mi = zero_band_mi(f, B, n, hxa, hxb, TN, kTFixBits, dn, inexact);
+                if (p.redo_list != nullptr && inexact) redo = true;
                 sMI[g * npair + pr] = mi;
                 if (p.dbg.mi && gvalid) p.dbg.mi[pix * npair + pr] = mi;
             }
@@ -400,11 +305,7 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
                 double Dpf = 0.0, Dcf = 0.0;
                 for (int l = 0; l < 2; ++l) Dpf += mi[k * nAnc + nR + l];              // rpf.cpp:425
                 for (int cc = 0; cc < 3; ++cc) Dcf += mi[D.npairF + cc * D.npairC + nAnc + k];
-                // the beta presets keep the reference's stack rule for any nF: k < 3 reads D_f_ck, a gap of zeros, then D_r_fk
-                double num;
-                if (p.beta_map == RPF_BETA_PAPER) num = Dcf;
-                else if (p.beta_map == RPF_BETA_REF_GCC11_O2) num = k < 3 ? sD9[6 + k] : (k < 8 ? 0.0 : sDrf[max(k - 8, 0)]);
-                else num = k < 3 ? sD9[6 + k] : (k < 4 ? 0.0 : sDrf[max(k - 4, 0)]);
+                const double num = beta_numerator(p.beta_map, k, k, Dcf, sD9, sDrf);
                 const double beta_k = (1 - Drf / (Drf + Dpf + e_eps)) * (num / den);   // rpf.cpp:464-465, 479
                 sBeta[k] = beta_k;
                 if (p.dbg.beta && gvalid) p.dbg.beta[pix * nF + k] = beta_k;
@@ -416,6 +317,13 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
         // columns are normalised in place (own sample i of the group is its slot i), kOwn own samples per sweep
         const double cj0 = sU[(gbase + 2) * G + t], cj1 = sU[(gbase + 3) * G + t], cj2 = sU[(gbase + 4) * G + t];
         bool bad = false;
+        // own sample i of the group takes this lane's weight w: the four sums over the group, the quotient, the store
+        auto blend = [&](int i, double w) {
+            w = (live && i < S) ? w : 0.0;
+            const double sw = group_sum<G>(w);                                 // rpf.cpp:691
+            const double s0 = group_sum<G>(w * cj0), s1 = group_sum<G>(w * cj1), s2 = group_sum<G>(w * cj2); // rpf.cpp:692
+            if (t < 3 && gvalid && i < S && store_filtered(p, t, pix, S, i, t == 0 ? s0 : (t == 1 ? s1 : s2), sw)) bad = true;
+        };
         if constexpr (FAST) {
             // z = (x - M) / SD in fp64, rounded once and kept as the group's row of floats [column][slot] in the first half of
             // the column's fp64 row (a lane's store follows its own load; the rows of two columns are disjoint)
@@ -457,21 +365,7 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
                     }
                 }
 #pragma unroll
-                for (int ii = 0; ii < kOwn; ++ii) {
-                    const int i = i0 + ii;
-                    double w = (double)__builtin_amdgcn_exp2f(-E[ii >> 1][ii & 1]);
-                    w = (live && i < S) ? w : 0.0;
-                    const double sw = group_sum<G>(w);                                 // rpf.cpp:691
-                    const double s0 = group_sum<G>(w * cj0), s1 = group_sum<G>(w * cj1), s2 = group_sum<G>(w * cj2); // rpf.cpp:692
-                    if (t < 3 && gvalid && i < S) {
-                        double prime = (t == 0 ? s0 : (t == 1 ? s1 : s2)) / sw;       // rpf.cpp:700
-                        if (isnan(prime)) {                                            // rpf.cpp:702: the reference exits here
-                            bad = true;
-                            if (p.policy == RPF_DEGEN_EPS) prime = p.col_in[(uint64_t)t * p.plane_stride + pix * S + i];
-                        }
-                        p.col_out[(uint64_t)t * p.plane_stride + pix * S + i] = prime;
-                    }
-                }
+                for (int ii = 0; ii < kOwn; ++ii) blend(i0 + ii, (double)__builtin_amdgcn_exp2f(-E[ii >> 1][ii & 1]));
             }
         } else {
             for (int k = 0; k < nwt; ++k) {
@@ -483,49 +377,34 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
                 *u = sd == 0.0 ? 0.0 : (xv - Mc) / sd;
             }
             wsync();
-                {
-                const double wrc = sAlpha[3];
-                const double sigma_c2 = p.seed * p.seed / (1 - wrc) / (1 - wrc);           // rpf.cpp:662
-                const double sigma_p2 = p.sigma_p * p.sigma_p;
-                for (int i0 = 0; i0 < S; i0 += kOwn) {
-                    double sp[kOwn], sc[kOwn], sf[kOwn];
+            const double wrc = sAlpha[3];
+            const double sigma_c2 = p.seed * p.seed / (1 - wrc) / (1 - wrc);           // rpf.cpp:662
+            const double sigma_p2 = p.sigma_p * p.sigma_p;
+            for (int i0 = 0; i0 < S; i0 += kOwn) {
+                double sp[kOwn], sc[kOwn], sf[kOwn];
 #pragma unroll
-                    for (int ii = 0; ii < kOwn; ++ii) { sp[ii] = 0.0; sc[ii] = 0.0; sf[ii] = 0.0; }
-                    for (int k = 0; k < 2; ++k) {
-                        const double *zr = sU + (gbase + k) * G;
-                        const double zj = zr[t];
+                for (int ii = 0; ii < kOwn; ++ii) { sp[ii] = 0.0; sc[ii] = 0.0; sf[ii] = 0.0; }
+                for (int k = 0; k < 2; ++k) {
+                    const double *zr = sU + (gbase + k) * G;
+                    const double zj = zr[t];
 #pragma unroll
-                        for (int ii = 0; ii < kOwn; ++ii) { const double d = zr[min(i0 + ii, S - 1)] - zj; sp[ii] += d * d; }
-                    }
-                    for (int k = 0; k < 3; ++k) {
-                        const double *zr = sU + (gbase + 2 + k) * G;
-                        const double zj = zr[t], ak = sAlpha[k];
-#pragma unroll
-                        for (int ii = 0; ii < kOwn; ++ii) { const double d = zr[min(i0 + ii, S - 1)] - zj; sc[ii] += (d * d) * ak; }
-                    }
-                    for (int k = 0; k < nF; ++k) {
-                        const double *zr = sU + (gbase + colF + k) * G;
-                        const double zj = zr[t], bk = sBeta[k];
-#pragma unroll
-                        for (int ii = 0; ii < kOwn; ++ii) { const double d = zr[min(i0 + ii, S - 1)] - zj; sf[ii] += (d * d) * bk; }
-                    }
-#pragma unroll
-                    for (int ii = 0; ii < kOwn; ++ii) {
-                        const int i = i0 + ii;
-                        double w = exp(-sp[ii] / (2 * sigma_p2)) * exp(-sc[ii] / (2 * sigma_c2)) * exp(-sf[ii] / (2 * sigma_c2)); // rpf.cpp:667-670
-                        w = (live && i < S) ? w : 0.0;
-                        const double sw = group_sum<G>(w);                                 // rpf.cpp:691
-                        const double s0 = group_sum<G>(w * cj0), s1 = group_sum<G>(w * cj1), s2 = group_sum<G>(w * cj2); // rpf.cpp:692
-                        if (t < 3 && gvalid && i < S) {
-                            double prime = (t == 0 ? s0 : (t == 1 ? s1 : s2)) / sw;       // rpf.cpp:700
-                            if (isnan(prime)) {                                            // rpf.cpp:702: the reference exits here
-                                bad = true;
-                                if (p.policy == RPF_DEGEN_EPS) prime = p.col_in[(uint64_t)t * p.plane_stride + pix * S + i];
-                            }
-                            p.col_out[(uint64_t)t * p.plane_stride + pix * S + i] = prime;
-                        }
-                    }
+                    for (int ii = 0; ii < kOwn; ++ii) { const double d = zr[min(i0 + ii, S - 1)] - zj; sp[ii] += d * d; }
                 }
+                for (int k = 0; k < 3; ++k) {
+                    const double *zr = sU + (gbase + 2 + k) * G;
+                    const double zj = zr[t], ak = sAlpha[k];
+#pragma unroll
+                    for (int ii = 0; ii < kOwn; ++ii) { const double d = zr[min(i0 + ii, S - 1)] - zj; sc[ii] += (d * d) * ak; }
+                }
+                for (int k = 0; k < nF; ++k) {
+                    const double *zr = sU + (gbase + colF + k) * G;
+                    const double zj = zr[t], bk = sBeta[k];
+#pragma unroll
+                    for (int ii = 0; ii < kOwn; ++ii) { const double d = zr[min(i0 + ii, S - 1)] - zj; sf[ii] += (d * d) * bk; }
+                }
+#pragma unroll
+                for (int ii = 0; ii < kOwn; ++ii)
+                    blend(i0 + ii, exp(-sp[ii] / (2 * sigma_p2)) * exp(-sc[ii] / (2 * sigma_c2)) * exp(-sf[ii] / (2 * sigma_c2))); // rpf.cpp:667-670
             }
         }
         // status: one report per pixel; a pixel on the redo list reports nothing (generic::filter_pixel_kernel owns it)

@@ -25,7 +25,7 @@
 // member's z = (x - M) * (1 / SD) in fp64 with 1 / SD formed once per pixel and column, rounded once; the coefficients (log2 e
 // folded in) formed in fp64 and rounded once; one accumulator per own sample, two own samples per packed fp32 instruction, one
 // hardware exponential, the sums and the quotient in fp64.  Every statement outside stage 4 is shared.
-#include "rpf_device_common.h"
+#include "rpf_generic_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -56,8 +56,8 @@ typedef float f32x4a __attribute__((ext_vector_type(4), may_alias));
 } // namespace generic
 
 GenericWaveCarve generic_wave_carve(const SampleLayout &lay, int capacity) {
-    const uint32_t ndim = (uint32_t)lay.ndim(), npair = (uint32_t)lay.npair(), nF = (uint32_t)lay.nF, cap = (uint32_t)capacity;
-    auto up16 = [](uint32_t v) { return (v + 15u) & ~15u; };
+    const GenericDims D = generic_dims(lay);
+    const uint32_t ndim = (uint32_t)D.ndim, npair = (uint32_t)D.npair, cap = (uint32_t)capacity;
     GenericWaveCarve c{};
     c.capacity = cap;
     c.off_pairtab = up16((cap + 1u) * 8u);           // behind T[0 .. capacity]
@@ -68,13 +68,13 @@ GenericWaveCarve generic_wave_carve(const SampleLayout &lay, int capacity) {
     c.off_bins = o; c.off_chunk = o;
     uint32_t shared = ndim * (uint32_t)(generic::kWvChunk + 1) * 8u;
     shared = std::max(shared, ndim * cap);
-    shared = std::max(shared, (uint32_t)generic::kWvOwn * (uint32_t)lay.nwt() * 8u);
+    shared = std::max(shared, (uint32_t)generic::kWvOwn * (uint32_t)D.nwt * 8u);
     o += up16(shared);
     c.off_hist = o;
     const uint32_t bmax = (uint32_t)std::sqrt((double)cap);
     o += up16((uint32_t)generic::kWvHist * ((bmax * bmax + 1u) / 2u) * 4u);
     c.off_stat = o;
-    o += (8u * ndim + npair + 2u * nF + 20u) * 8u;   // M | SD | min | max, lo | range | flags, sum T[hx], pair sums / MI, weights
+    o += generic_f64_doubles(D) * 8u;                    // M | SD | min | max, lo | range | flags, sum T[hx], pair sums / MI, weights
     c.off_flag = o; o += 16u;
     c.wave_bytes = up16(o);
     const uint32_t lds = (uint32_t)max_lds_per_block();
@@ -94,51 +94,13 @@ GenericWaveCarve generic_wave_carve(const SampleLayout &lay, int capacity) {
 namespace generic {
 namespace {
 
-struct WvDims {
-    int nR, nF, ndim, nAnc, npairF, npairC, npair, nwt, colF;
-};
-__device__ __forceinline__ WvDims wv_dims(const SampleLayout &l) {
-    WvDims d;
-    d.nR = l.nR; d.nF = l.nF; d.ndim = 5 + l.nR + l.nF;
-    d.nAnc = l.nR + 2;                       // r.. and p.. anchors
-    d.npairF = l.nF * d.nAnc;                // pairs (f_i, r_l | p_l)          rpf.cpp:416-427
-    d.npairC = d.nAnc + l.nF;                // pairs of one colour channel     rpf.cpp:429-442
-    d.npair = d.npairF + 3 * d.npairC;
-    d.nwt = 5 + l.nF;                        // weighted columns of stage 4
-    d.colF = 5 + l.nR;
-    return d;
-}
-
-template <class T>
-__device__ __forceinline__ float wv_ldp(const PassParams &p, int col, uint32_t off) {
-    return (float)reinterpret_cast<const T *>(p.planes)[(uint64_t)col * p.plane_stride + off];
-}
-// value of column c of the sample at plane offset `off`: colours come from the fp64 colour planes
-template <class T>
-__device__ __forceinline__ double wv_load_col(const PassParams &p, int c, uint32_t off) {
-    if (c >= 2 && c < 5) return p.col_in[(uint64_t)(c - 2) * p.plane_stride + off];
-    return (double)wv_ldp<T>(p, c, off);
-}
-// columns of MI pair pr, in ComputeCFWeights call order (rpf.cpp:416-442 with the loop bounds generalised)
-__device__ __forceinline__ void wv_pair_cols(const WvDims &D, int pr, int &ca, int &cb) {
-    if (pr < D.npairF) {
-        const int i = pr / D.nAnc, l = pr - i * D.nAnc;
-        ca = D.colF + i;
-        cb = l < D.nR ? 5 + l : l - D.nR;
-    } else {
-        const int q = pr - D.npairF, c = q / D.npairC, l = q - c * D.npairC;
-        ca = 2 + c;
-        cb = l < D.nR ? 5 + l : (l < D.nAnc ? l - D.nR : D.colF + (l - D.nAnc));
-    }
-}
-
 // One wave = one pixel of the class list at a time, the entries dealt to the waves of the grid with a grid stride.
 // FAST (RPF_FLAG_GENERIC_FAST): stage 4 alone in the fp32 arithmetic of DESIGN.md section 11e; every other statement is shared.
 template <class T, bool FAST = false>
 __global__ __launch_bounds__(256) void filter_wave_kernel(PassParams p, GenericWaveCarve cv) {
     constexpr int kOwn = FAST ? kWvFastOwn : kWvOwn;
     extern __shared__ __align__(16) unsigned char smem[];
-    const WvDims D = wv_dims(p.lay);
+    const GenericDims D = generic_dims(p.lay);
     const int ndim = D.ndim, nF = D.nF, nR = D.nR, nAnc = D.nAnc, npair = D.npair, nwt = D.nwt, colF = D.colF;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -149,7 +111,7 @@ __global__ __launch_bounds__(256) void filter_wave_kernel(PassParams p, GenericW
     uint16_t *sPairTab = reinterpret_cast<uint16_t *>(smem + cv.off_pairtab);
     for (int pr = tid; pr < npair; pr += nthreads) {
         int ca, cb;
-        wv_pair_cols(D, pr, ca, cb);
+        pair_cols(D, pr, ca, cb);
         sPairTab[pr] = (uint16_t)(ca | (cb << 8));
     }
     __syncthreads(); // the only barrier: from here on the waves are independent
@@ -222,7 +184,7 @@ __global__ __launch_bounds__(256) void filter_wave_kernel(PassParams p, GenericW
                     for (int c0 = 0; c0 < ndim; c0 += kWvGather) { // kWvGather gathers in flight, then their stores
                         double v[kWvGather];
 #pragma unroll
-                        for (int u = 0; u < kWvGather; ++u) v[u] = wv_load_col<T>(p, min(c0 + u, ndim - 1), off);
+                        for (int u = 0; u < kWvGather; ++u) v[u] = load_col<T>(p, min(c0 + u, ndim - 1), off);
 #pragma unroll
                         for (int u = 0; u < kWvGather; ++u)
                             if (c0 + u < ndim) sChunk[(c0 + u) * (kWvChunk + 1) + lane] = v[u];
@@ -265,7 +227,7 @@ __global__ __launch_bounds__(256) void filter_wave_kernel(PassParams p, GenericW
                 for (int c0 = 0; c0 < ndim; c0 += kWvGather) {
                     double v[kWvGather];
 #pragma unroll
-                    for (int u = 0; u < kWvGather; ++u) v[u] = wv_load_col<T>(p, min(c0 + u, ndim - 1), off);
+                    for (int u = 0; u < kWvGather; ++u) v[u] = load_col<T>(p, min(c0 + u, ndim - 1), off);
 #pragma unroll
                     for (int u = 0; u < kWvGather; ++u) {
                         const int c = c0 + u;
@@ -433,7 +395,7 @@ __global__ __launch_bounds__(256) void filter_wave_kernel(PassParams p, GenericW
                     for (int t = lane; t < kOwn * nwt; t += 64) {
                         const int k = t / kOwn, ii = t % kOwn, i = min(i0 + ii, S - 1);
                         const int col = k < 5 ? k : k + nR;
-                        sOwnZ[t] = zfast(col, wv_load_col<T>(p, col, (uint32_t)(pix * S + i)));
+                        sOwnZ[t] = zfast(col, load_col<T>(p, col, (uint32_t)(pix * S + i)));
                     }
                     wsync();
                     double sw[kOwn], s0[kOwn], s1[kOwn], s2[kOwn];
@@ -460,12 +422,12 @@ __global__ __launch_bounds__(256) void filter_wave_kernel(PassParams p, GenericW
                                 E[2 * q4 + 1] = __builtin_elementwise_fma(db * db, ck2, E[2 * q4 + 1]);
                             }
                         };
-                        const float pf0 = wv_ldp<T>(p, 0, off), pf1 = wv_ldp<T>(p, 1, off);
+                        const float pf0 = ldp<T>(p, 0, off), pf1 = ldp<T>(p, 1, off);
 #pragma unroll
                         for (int k = 0; k < 3; ++k) cj[k] = p.col_in[(uint64_t)k * p.plane_stride + off];
                         float fv[kWvGather];
 #pragma unroll
-                        for (int u = 0; u < kWvGather; ++u) fv[u] = wv_ldp<T>(p, colF + min(u, nF - 1), off);
+                        for (int u = 0; u < kWvGather; ++u) fv[u] = ldp<T>(p, colF + min(u, nF - 1), off);
                         term(0, zfast(0, (double)pf0));
                         term(1, zfast(1, (double)pf1));
 #pragma unroll
@@ -476,7 +438,7 @@ __global__ __launch_bounds__(256) void filter_wave_kernel(PassParams p, GenericW
                             for (int u = 0; u < kWvGather; ++u) cur[u] = fv[u];
                             if (k0 + kWvGather < nF) {
 #pragma unroll
-                                for (int u = 0; u < kWvGather; ++u) fv[u] = wv_ldp<T>(p, colF + min(k0 + kWvGather + u, nF - 1), off);
+                                for (int u = 0; u < kWvGather; ++u) fv[u] = ldp<T>(p, colF + min(k0 + kWvGather + u, nF - 1), off);
                             }
 #pragma unroll
                             for (int u = 0; u < kWvGather; ++u) {
@@ -521,7 +483,7 @@ __global__ __launch_bounds__(256) void filter_wave_kernel(PassParams p, GenericW
                     for (int t = lane; t < kOwn * nwt; t += 64) {
                         const int k = t / kOwn, ii = t % kOwn, i = min(i0 + ii, S - 1);
                         const int col = k < 5 ? k : k + nR;
-                        sOwnZ[t] = znorm(col, wv_load_col<T>(p, col, (uint32_t)(pix * S + i)));
+                        sOwnZ[t] = znorm(col, load_col<T>(p, col, (uint32_t)(pix * S + i)));
                     }
                     wsync();
                     double sw[kOwn], s0[kOwn], s1[kOwn], s2[kOwn];
@@ -536,12 +498,12 @@ __global__ __launch_bounds__(256) void filter_wave_kernel(PassParams p, GenericW
                         for (int ii = 0; ii < kOwn; ++ii) { sp[ii] = 0.0; sc[ii] = 0.0; sf[ii] = 0.0; }
                         // every gather of the member that needs no loop is issued here, the features kWvGather at a time with the
                         // next group in flight while this one is weighed
-                        const float pf0 = wv_ldp<T>(p, 0, off), pf1 = wv_ldp<T>(p, 1, off);
+                        const float pf0 = ldp<T>(p, 0, off), pf1 = ldp<T>(p, 1, off);
 #pragma unroll
                         for (int k = 0; k < 3; ++k) cj[k] = p.col_in[(uint64_t)k * p.plane_stride + off];
                         float fv[kWvGather];
 #pragma unroll
-                        for (int u = 0; u < kWvGather; ++u) fv[u] = wv_ldp<T>(p, colF + min(u, nF - 1), off);
+                        for (int u = 0; u < kWvGather; ++u) fv[u] = ldp<T>(p, colF + min(u, nF - 1), off);
 #pragma unroll
                         for (int k = 0; k < 2; ++k) {
                             const double zj = znorm(k, (double)(k == 0 ? pf0 : pf1));
@@ -560,7 +522,7 @@ __global__ __launch_bounds__(256) void filter_wave_kernel(PassParams p, GenericW
                             for (int u = 0; u < kWvGather; ++u) cur[u] = fv[u];
                             if (k0 + kWvGather < nF) {
 #pragma unroll
-                                for (int u = 0; u < kWvGather; ++u) fv[u] = wv_ldp<T>(p, colF + min(k0 + kWvGather + u, nF - 1), off);
+                                for (int u = 0; u < kWvGather; ++u) fv[u] = ldp<T>(p, colF + min(k0 + kWvGather + u, nF - 1), off);
                             }
 #pragma unroll
                             for (int u = 0; u < kWvGather; ++u) {

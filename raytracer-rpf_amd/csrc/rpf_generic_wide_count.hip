@@ -15,7 +15,7 @@
 //     the strict test then rejects every finite and every infinite candidate -- and no feature mean is NaN in the rows the
 //     slab's windows reach (wide_nan_scan_kernel: a NaN sample makes its own pixel's mean NaN, and a NaN candidate is the one
 //     kind that passes a zero-width test).  A mean of +-inf proves nothing: |inf - inf| is NaN, which never rejects.
-#include "rpf_device_common.h"
+#include "rpf_generic_common.h"
 
 #include <algorithm>
 
@@ -32,11 +32,6 @@ struct WideCountOut {
     unsigned long long *cursor;  // [1] entries reserved so far
     const int32_t *nan_flag;     // [1] != 0: some feature mean in reach of the slab is NaN
 };
-
-template <class T>
-__device__ __forceinline__ float wc_ldp(const PassParams &p, int col, uint32_t off) {
-    return (float)reinterpret_cast<const T *>(p.planes)[(uint64_t)col * p.plane_stride + off];
-}
 
 // *flag |= 1 when a feature mean of pixels [pix0, pix1) is NaN (stage 1a's planes, [nF][H*W])
 __global__ __launch_bounds__(256) void wide_nan_scan_kernel(const double *pmean, uint64_t HW, uint64_t pix0, uint64_t pix1, int nF,
@@ -75,32 +70,14 @@ __global__ __launch_bounds__(256) void wide_count_kernel(PassParams p, WideCount
     }
 
     // ---- stage 1b's test, 64 candidates at a time (rpf.cpp:556-586) -------------------------------------------------
-    const int x0 = max(x - b, 0), x1 = min(x + b, W - 1), y0 = max(y - b, 0), y1 = min(y + b, H - 1);
-    const int nyv = y1 - y0 + 1;
-    const int centre_rank = (x - x0) * nyv + (y - y0);
-    const int ncand = flat ? 0 : ((x1 - x0 + 1) * nyv - 1) * S;
+    const Window win = make_window(x, y, b, W, H, S);
+    const int ncand = flat ? 0 : win.ncand;
     int acc = 0; // accepted so far
     for (int qb = 0; qb < ncand && acc <= limit; qb += 64) {
         const int qq = qb + lane;
         bool pass = qq < ncand;
-        uint32_t off = 0u;
-        if (pass) {
-            int cell = qq / S;
-            const int s = qq - cell * S;
-            if (cell >= centre_rank) ++cell;              // rpf.cpp:565: skip the centre pixel
-            const int ix = cell / nyv, iy = cell - ix * nyv; // xn outer, yn inner ascending (rpf.cpp:562-563)
-            off = (uint32_t)(((uint64_t)(y0 + iy) * W + (x0 + ix)) * S + s);
-        }
-        // a rejected candidate stays rejected: the later features are read only while some lane still passes
-        for (int k = 0; k < nF; ++k) {
-            if (!__any(pass)) break;
-            const double m = p.pmean[(uint64_t)k * HW + pix];
-            const double lim = p.pstd[(uint64_t)k * HW + pix] * 3.0;  // multiplyArray(std, 3), rpf.cpp:579
-            if (pass) {
-                const double a = fabs((double)wc_ldp<T>(p, colF + k, off) - m);
-                if (a >= lim) pass = false;           // allLessThan: fails iff a >= b (ops.h:101-104): a NaN never rejects
-            }
-        }
+        const uint32_t off = pass ? candidate_offset(win, W, S, qq) : 0u;
+        pass = passes_3sigma_wave<T>(p, colF, nF, off, HW, pix, pass);
         const unsigned long long mask = __ballot(pass);
         if (pass) {
             const int at = acc + __popcll(mask & ((1ull << lane) - 1ull));

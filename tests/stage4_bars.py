@@ -43,8 +43,9 @@ Which form a kernel uses, read from its source (csrc/):
              and rpf_packed_impl.inc (the packed small-neighbourhood kernels of the same routes): both form the own rows
              u_i | A_i once and run one FMA per column and pair.
   direct     generic::filter_pixel_kernel (rpf_generic.hip: route 3, the streaming size class N > 3136 and the REF_ABORT redo
-             list of every route), generic::filter_packed_kernel (rpf_generic_packed.hip), generic::filter_wave_kernel
-             (rpf_generic_wave.hip) and generic::filter_wide_kernel (rpf_generic_wide.hip): routes 4, 5, 6, 7.  All four run
+             list of every route) and generic::filter_wide_kernel (rpf_generic_wide.hip), whose stage 4 is one text,
+             rpf_generic_stream_stages.inc; generic::filter_packed_kernel (rpf_generic_packed.hip) and
+             generic::filter_wave_kernel (rpf_generic_wave.hip): routes 4, 5, 6, 7.  All four run
              sp / sc / sf term by term, (z_i - z_j)^2 * weight, as rpf.cpp:646-670.
 
 Values: direct at nwt = 17, Nmax = 3136: 8e-12 cmax.  Expanded at seed 0.5: 5e-11 (Nmax 392) ... 4e-10 (Nmax 3136); at seed

@@ -1,6 +1,6 @@
 """Every route's filtered colours, sample by sample: stage 4 (the S x N pair weights and the blend) of every kernel that has a
-stage-4 body of its own -- rpf_filter_impl.inc, rpf_packed_impl.inc, rpf_generic.hip, rpf_generic_packed.hip,
-rpf_generic_wave.hip, rpf_generic_wide.hip -- against the fp64 numpy restatement of tests/fast_weights_ref.py evaluated on the
+stage-4 body of its own -- rpf_filter_impl.inc, rpf_packed_impl.inc, rpf_generic_stream_stages.inc (the one text of
+rpf_generic.hip and rpf_generic_wide.hip), rpf_generic_packed.hip, rpf_generic_wave.hip -- against the fp64 numpy restatement of tests/fast_weights_ref.py evaluated on the
 DEVICE's own stage 1 to 3 outputs.  check_pass holds those outputs to the oracle (bit for bit, 1e-11, 1e-9); what is left
 between got["colour"] and stage4(planes, got) is the device's pair arithmetic and blend alone, and it is held to the
 worst-case rounding bound of tests/stage4_bars.py on EVERY finite sample of the checked pixels: the whole target row of a
