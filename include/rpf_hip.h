@@ -138,7 +138,7 @@ enum {
                                   the flag.  It needs neither RPF_FLAG_GENERIC_PACKED nor RPF_FLAG_GENERIC_WAVE, which keep
                                   steering the non-wide passes only.  Without RPF_FLAG_WIDE_NBHD it is RPF_E_UNSUPPORTED, from
                                   every filter entry point and from rpf_layout_kernels, before any device work. */
-    RPF_FLAG_GENERIC_FAST = 256 /* opt-in, modifies RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED (with or without
+    RPF_FLAG_GENERIC_FAST = 256, /* opt-in, modifies RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED (with or without
                                   RPF_FLAG_GENERIC_WAVE): on a pass that takes route 4 or 5 the packed kernels (N <= 64) and,
                                   with the wave flag, the one-wave kernels (64 < N <= 832) evaluate the S x N pair weights of
                                   stage 4 in fp32 -- z = (x - M) / SD and the 5 + n_feat coefficients formed in fp64 and rounded
@@ -155,6 +155,29 @@ enum {
                                   together with RPF_FLAG_FAST_WEIGHTS, or together with RPF_FLAG_WIDE_NBHD (wide passes are fp64
                                   throughout) it is RPF_E_UNSUPPORTED, from every filter entry point and from
                                   rpf_layout_kernels, before any device work. */
+    RPF_FLAG_STREAM_FAST = 512 /* opt-in, modifies RPF_FLAG_GENERIC and / or RPF_FLAG_WIDE_NBHD: the two kernels that walk a
+                                  neighbourhood of any size with 256 threads -- the generic filter kernel (route 3, the rest
+                                  list N > 64 / N > 832 of routes 4 / 5) and the wide kernel (route 6, the rest list N > 832 of
+                                  route 7) -- evaluate the S x N pair weights of stage 4 in the fp32 arithmetic described for
+                                  RPF_FLAG_GENERIC_FAST above: z and the 5 + n_feat coefficients formed in fp64 and rounded
+                                  once, differences, squares and the weighted sum in fp32, ONE hardware exponential, the
+                                  weights widened to fp64, both sums and the quotient in fp64.  On a wide pass dealt by size
+                                  class (route 7) the packed and one-wave class kernels run their fp32 instantiations as well:
+                                  under this flag every pixel of a wide pass is fp32.  On routes 4 / 5 the packed and one-wave
+                                  classes stay steered by RPF_FLAG_GENERIC_FAST alone; with both flags every pixel of the pass
+                                  is fp32.  Any layout the kernels take, fp32 or fp16 planes.  Membership, bins, statistics,
+                                  MI, alpha, beta and W_r_c are the bits of the same flags without this one; the colours move
+                                  by ~1e-8 relative (bar 1e-4).  It pays where neighbourhoods are large -- wide passes, large
+                                  boxes -- and is slower than fp64 on a box-7 pass (the fp32 instantiations hold one workgroup per
+                                  CU).  Filtered in fp64 under the flag as well, bit for bit as
+                                  without it: under RPF_DEGEN_REF_ABORT a pixel on the redo list (routes 4, 5 and 7); every
+                                  pass that runs the compiled, fused kernels (routes 0, 1, 2 -- the non-wide passes of a
+                                  RPF_FLAG_WIDE_NBHD call without RPF_FLAG_GENERIC), their streaming class N > 3136 included.
+                                  rpf_query_route, filter_kernel_launches, redo_pixels, sum_nbhd and max_nbhd are those of the
+                                  same flags without this one.  Without both RPF_FLAG_GENERIC and RPF_FLAG_WIDE_NBHD it is
+                                  RPF_E_UNSUPPORTED; together with RPF_FLAG_FAST_WEIGHTS one of that flag's refusals fires;
+                                  every older refusal stands (RPF_FLAG_GENERIC_FAST with RPF_FLAG_WIDE_NBHD among them) -- from
+                                  every filter entry point and from rpf_layout_kernels, before any device work. */
 };
 
 typedef struct rpf_desc {
@@ -391,8 +414,9 @@ int32_t rpf_multi_halo_plan(int32_t H, int32_t n_slabs, int32_t depth, int32_t *
  * RPF_FLAG_GENERIC_PACKED without RPF_FLAG_GENERIC or with RPF_FLAG_FAST_WEIGHTS; RPF_FLAG_GENERIC_WAVE without both of
  * those flags or with RPF_FLAG_FAST_WEIGHTS; RPF_FLAG_WIDE_NBHD with RPF_FLAG_FAST_WEIGHTS; RPF_FLAG_WIDE_CLASSES without
  * RPF_FLAG_WIDE_NBHD; RPF_FLAG_GENERIC_FAST without both RPF_FLAG_GENERIC and RPF_FLAG_GENERIC_PACKED, with
- * RPF_FLAG_FAST_WEIGHTS or with RPF_FLAG_WIDE_NBHD (where it is accepted, *generic_out is 1 as without it); RPF_E_BADARG for a
- * NULL desc.
+ * RPF_FLAG_FAST_WEIGHTS or with RPF_FLAG_WIDE_NBHD (where it is accepted, *generic_out is 1 as without it);
+ * RPF_FLAG_STREAM_FAST without both RPF_FLAG_GENERIC and RPF_FLAG_WIDE_NBHD (where it is accepted, *generic_out is that of the
+ * same flags without it; with RPF_FLAG_FAST_WEIGHTS one of that flag's refusals above fires); RPF_E_BADARG for a NULL desc.
  * Only n_random, n_feat, plane_dtype and flags are read.  Needs no context and no device.  generic_out may be NULL. */
 int32_t rpf_layout_kernels(const rpf_desc *desc, int32_t *generic_out);
 

@@ -42,7 +42,9 @@ SampleLayout layout_of(const rpf_desc *d) {
 // answer (the wide kernel is layout-generic: both compiled layouts take the flag as they are); with RPF_FLAG_FAST_WEIGHTS it
 // is refused.  RPF_FLAG_WIDE_CLASSES modifies the wide flag and is refused without it.  RPF_FLAG_GENERIC_FAST (fp32 pair
 // weights on the packed and one-wave layout-generic kernels) changes no answer either; it is refused without both
-// RPF_FLAG_GENERIC and RPF_FLAG_GENERIC_PACKED, with RPF_FLAG_FAST_WEIGHTS and with RPF_FLAG_WIDE_NBHD.
+// RPF_FLAG_GENERIC and RPF_FLAG_GENERIC_PACKED, with RPF_FLAG_FAST_WEIGHTS and with RPF_FLAG_WIDE_NBHD.  RPF_FLAG_STREAM_FAST (fp32
+// pair weights on the streaming and wide layout-generic kernels, and on every kernel of a wide pass) changes no answer; it is
+// refused without both RPF_FLAG_GENERIC and RPF_FLAG_WIDE_NBHD, and with RPF_FLAG_FAST_WEIGHTS one of the older refusals fires.
 int32_t layout_kernels(const rpf_desc *d, int32_t *generic_out, std::string *why) {
     if (!d) return RPF_E_BADARG;
     const SampleLayout lay = layout_of(d);
@@ -56,6 +58,8 @@ int32_t layout_kernels(const rpf_desc *d, int32_t *generic_out, std::string *why
         msg = "RPF_FLAG_GENERIC_FAST with RPF_FLAG_FAST_WEIGHTS: that flag selects the fused fp32 kernels of the 19-dim layout, this one the layout-generic ones";
     } else if ((d->flags & RPF_FLAG_GENERIC_FAST) && (d->flags & RPF_FLAG_WIDE_NBHD)) {
         msg = "RPF_FLAG_GENERIC_FAST with RPF_FLAG_WIDE_NBHD: wide passes are fp64 throughout";
+    } else if ((d->flags & RPF_FLAG_STREAM_FAST) && !(d->flags & (RPF_FLAG_GENERIC | RPF_FLAG_WIDE_NBHD))) {
+        msg = "RPF_FLAG_STREAM_FAST without RPF_FLAG_GENERIC or RPF_FLAG_WIDE_NBHD: the flag modifies the streaming and wide layout-generic kernels";
     } else if ((d->flags & RPF_FLAG_WIDE_NBHD) && (d->flags & RPF_FLAG_FAST_WEIGHTS)) {
         msg = "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_WIDE_NBHD: the wide layout-generic kernel is fp64 throughout";
     } else if ((d->flags & RPF_FLAG_GENERIC_WAVE) && (d->flags & (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) != (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) {
@@ -201,6 +205,9 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     if (wide) p.generic |= 8;
     // ... counted first and dealt by size class under RPF_FLAG_WIDE_CLASSES (above 832 spp no class can hold a pixel)
     if (wide && (d->flags & RPF_FLAG_WIDE_CLASSES) && d->S <= 832) p.generic |= 16;
+    // fp32 pair weights on the streaming / wide kernels: only a pass that runs layout-generic kernels carries the bit (a fused pass
+    // of a WIDE_NBHD | STREAM_FAST call keeps generic == 0 and runs exactly as without the flag)
+    if ((d->flags & RPF_FLAG_STREAM_FAST) && (p.generic & (1 | 8))) p.generic |= 64;
     // the fused kernels address a window's samples by 32-bit byte offsets from its first sample (Window, rpf_filter_impl.inc)
     if (rpf_check_window_span(d->W, d->S, box) != RPF_OK)
         return fail(ctx, RPF_E_UNSUPPORTED, "box*W*S*8 >= 2^32: a window's span in bytes of an fp64 plane must fit 32 bits (narrower slabs or a smaller box)");
@@ -234,9 +241,9 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     p.flat = ctx->d_flat; p.nan_flag = ctx->d_nan_flag;
     if (dbg_dev) p.dbg = *dbg_dev;
     if (wide) { // the wide kernel's carve-up: what 160 KiB leave of the joint table is one band of it
-        out.lds = generic_wide_carve(p.lay, p.nmax).total;
+        out.lds = generic_wide_carve(p.lay, p.nmax, (p.generic & 64) != 0).total;
     } else if (p.generic) { // the generic kernel's own carve-up (one kernel for every neighbourhood size of the pass)
-        out.lds = generic_carve(p.lay, p.nmax).total;
+        out.lds = generic_carve(p.lay, p.nmax, (p.generic & 64) != 0).total;
     } else { // LDS of the largest resident kernel this pass can launch (larger neighbourhoods stream: generic::filter_pixel_kernel)
         const int nres = std::min(p.nmax, kMaxResident), bres = bmax_of(nres);
         out.lds = lds_layout(p.S, nres, bres, table_in_lds(p.S, nres, bres, ctx->tun, p.lay), ctx->tun, p.lay).total;
@@ -269,9 +276,10 @@ constexpr SlotRule kPassSlots = {2048, 64, 1024, (size_t)1 << 30};           // 
 constexpr SlotRule kRedoSlots = {kSameWhenResident, 8, 128, (size_t)64 << 20}; // a fixed small grid: ordinary frames leave the list empty
 
 // One launch of the streaming kernel over p's rows or pixel list (`pixels` of them; kCountOnDevice with count_dev: the list size
-// is read on the device and the grid is the rule's slots): the slots by `rule`, the scratch, the launch
+// is read on the device and the grid is the rule's slots): the slots by `rule`, the scratch, the launch.  fast: the fp32 stage 4
+// of RPF_FLAG_STREAM_FAST
 int32_t launch_streaming(rpf_ctx *ctx, const PassParams &p, uint64_t pixels, const SlotRule &rule, const uint32_t *count_dev,
-                         hipStream_t s, int *launches) {
+                         hipStream_t s, int *launches, bool fast) {
     uint64_t slots = rule.resident;
     if (rule.resident == kSameWhenResident || !generic_carve(p.lay, p.nmax).resident) {
         const size_t per_slot = (size_t)p.nmax * (4 + (size_t)p.lay.ndim());
@@ -280,7 +288,7 @@ int32_t launch_streaming(rpf_ctx *ctx, const PassParams &p, uint64_t pixels, con
     slots = std::min<uint64_t>(pixels, slots);
     int32_t st;
     if ((st = ensure_big_scratch(ctx, p, (uint32_t)slots))) return st;
-    HIP_TRY(generic::launch_filter(p, ctx->d_big_list, ctx->d_big_bins, (uint32_t)slots, count_dev, s));
+    HIP_TRY(generic::launch_filter(p, ctx->d_big_list, ctx->d_big_bins, (uint32_t)slots, count_dev, s, fast));
     if (launches) ++*launches;
     return RPF_OK;
 }
@@ -295,7 +303,7 @@ int32_t launch_redo(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *launc
     PassParams q = p;
     q.pix_list = p.redo_list;
     q.list_count = 0;
-    return launch_streaming(ctx, q, kCountOnDevice, kRedoSlots, p.redo_count, s, launches);
+    return launch_streaming(ctx, q, kCountOnDevice, kRedoSlots, p.redo_count, s, launches, false); // a redone pixel is fp64 under every flag
 }
 
 // u64 acceptance masks per pixel: one bit per candidate of the window (the pixel's own samples are members without a test)
@@ -459,7 +467,7 @@ int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream_t
         if (c == kNumClasses - 1) { // neighbourhoods beyond the LDS-resident kernels: stream through global scratch
             const uint32_t slots = std::min<uint32_t>(counts[c], 1024u);
             if ((st = ensure_big_scratch(ctx, q, slots))) return st;
-            HIP_TRY(generic::launch_filter(q, ctx->d_big_list, ctx->d_big_bins, slots, nullptr, s));
+            HIP_TRY(generic::launch_filter(q, ctx->d_big_list, ctx->d_big_bins, slots, nullptr, s, false)); // (fp64 under every flag)
         } else if (c < kNumPacked && packed) {
             HIP_TRY(launch_filter_packed(q, class_capacity(c), nullptr, s));
         } else {
@@ -478,12 +486,12 @@ int32_t route_generic(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *lau
     ctx->last_route = 3;
     if (p.policy == RPF_DEGEN_REF_ABORT) HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
     if (p.row_end <= p.row_begin) return RPF_OK;
-    return launch_streaming(ctx, p, (uint64_t)(p.row_end - p.row_begin) * p.W, kPassSlots, nullptr, s, launches);
+    return launch_streaming(ctx, p, (uint64_t)(p.row_end - p.row_begin) * p.W, kPassSlots, nullptr, s, launches, (p.generic & 64) != 0);
 }
 
 // One launch of the wide kernel, over the slab's rows or over p.pix_list (p.list_count entries, or *count_dev of them), for at
-// most max_pixels pixels at a time: the slots and the table of route_generic_wide's comment.
-int32_t launch_wide(rpf_ctx *ctx, const PassParams &p, uint64_t max_pixels, const uint32_t *count_dev, hipStream_t s) {
+// most max_pixels pixels at a time: the slots and the table of route_generic_wide's comment.  fast: as for launch_streaming.
+int32_t launch_wide(rpf_ctx *ctx, const PassParams &p, uint64_t max_pixels, const uint32_t *count_dev, hipStream_t s, bool fast) {
     const size_t per_slot = (size_t)p.nmax * (4 + 2 * (size_t)p.lay.ndim());
     const uint32_t slots = (uint32_t)std::min<uint64_t>(max_pixels, std::max<size_t>(1, std::min<size_t>(1024, ((size_t)1 << 30) / per_slot)));
     int32_t st;
@@ -492,7 +500,7 @@ int32_t launch_wide(rpf_ctx *ctx, const PassParams &p, uint64_t max_pixels, cons
     const bool fine = p.nmax <= kTFixExact;
     if (!fine && (!ctx->d_twide || ctx->twide_n < p.nmax + 1)) return fail(ctx, RPF_E_BADARG, "wide pass without its table (setup_pass builds it)");
     HIP_TRY(generic::launch_filter_wide(p, ctx->d_big_list, ctx->d_big_bins, slots, fine ? ctx->d_tfix.ptr : ctx->d_twide.ptr,
-                                        fine ? 44 : kTWideBits, count_dev, s));
+                                        fine ? 44 : kTWideBits, count_dev, s, fast));
     return RPF_OK;
 }
 
@@ -507,7 +515,7 @@ int32_t route_generic_wide(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int
     if (p.policy == RPF_DEGEN_REF_ABORT) HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
     if (p.row_end <= p.row_begin) return RPF_OK;
     int32_t st;
-    if ((st = launch_wide(ctx, p, (uint64_t)(p.row_end - p.row_begin) * p.W, nullptr, s))) return st;
+    if ((st = launch_wide(ctx, p, (uint64_t)(p.row_end - p.row_begin) * p.W, nullptr, s, (p.generic & 64) != 0))) return st;
     if (launches) ++*launches;
     return RPF_OK;
 }
@@ -564,8 +572,8 @@ int32_t route_generic_wide_classes(rpf_ctx *ctx, const PassParams &p_in, hipStre
         PassParams q = p;
         q.pix_list = ctx->d_lists + (size_t)c * HW;
         q.list_count = counts[c];
-        if (c < kNumPacked) { HIP_TRY(generic::launch_filter_packed(q, class_capacity(c), s)); }
-        else { HIP_TRY(generic::launch_filter_wave(q, class_capacity(c), s)); }
+        if (c < kNumPacked) { HIP_TRY(generic::launch_filter_packed(q, class_capacity(c), s, (p.generic & 64) != 0)); }
+        else { HIP_TRY(generic::launch_filter_wave(q, class_capacity(c), s, (p.generic & 64) != 0)); }
         if (launches) ++*launches;
     }
     PassParams w = p_in; // the wide kernel: as on route 6, over a list
@@ -573,7 +581,7 @@ int32_t route_generic_wide_classes(rpf_ctx *ctx, const PassParams &p_in, hipStre
         Range rg("rpf:wide filter kernel (N > 832)");
         w.pix_list = ctx->d_lists + (size_t)rest_class * HW;
         w.list_count = counts[rest_class];
-        if ((st = launch_wide(ctx, w, w.list_count, nullptr, s))) return st;
+        if ((st = launch_wide(ctx, w, w.list_count, nullptr, s, (p.generic & 64) != 0))) return st;
         if (launches) ++*launches;
     }
     if (p.redo_list != nullptr) {
@@ -583,7 +591,7 @@ int32_t route_generic_wide_classes(rpf_ctx *ctx, const PassParams &p_in, hipStre
         // (a fixed small grid whose workgroups find the list empty on ordinary frames, as launch_redo's: within 256 MiB of slots)
         const size_t per_slot = (size_t)w.nmax * (4 + 2 * (size_t)w.lay.ndim());
         const uint32_t grid = (uint32_t)std::max<size_t>(8, std::min<size_t>(64, ((size_t)256 << 20) / per_slot));
-        if ((st = launch_wide(ctx, w, grid, p.redo_count, s))) return st;
+        if ((st = launch_wide(ctx, w, grid, p.redo_count, s, false))) return st; // a redone pixel is fp64 under every flag
         if (launches) ++*launches;
     }
     return RPF_OK;
@@ -635,7 +643,7 @@ int32_t route_generic_packed(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s
         PassParams q = p;
         q.pix_list = ctx->d_lists + (size_t)rest_class * HW;
         q.list_count = counts[rest_class];
-        if ((st = launch_streaming(ctx, q, q.list_count, kPassSlots, nullptr, s, launches))) return st;
+        if ((st = launch_streaming(ctx, q, q.list_count, kPassSlots, nullptr, s, launches, (p.generic & 64) != 0))) return st;
     }
     return launch_redo(ctx, p, s, launches);
 }
@@ -688,7 +696,7 @@ int32_t route_generic_wave(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, 
         PassParams q = p;
         q.pix_list = ctx->d_lists + (size_t)rest_class * HW;
         q.list_count = counts[rest_class];
-        if ((st = launch_streaming(ctx, q, q.list_count, kPassSlots, nullptr, s, launches))) return st;
+        if ((st = launch_streaming(ctx, q, q.list_count, kPassSlots, nullptr, s, launches, (p.generic & 64) != 0))) return st;
     }
     return launch_redo(ctx, p, s, launches);
 }

@@ -35,14 +35,18 @@ constexpr uint32_t kHistParBytes = 32u << 10;  // one histogram per wave while t
 //            (each wave then builds the tables of its own pairs, no workgroup barrier), else one for the workgroup
 //   red4:    stage 4's reduction scratch [4][256] doubles: behind the own rows, over the dead rest of chunk and hist
 //   list | bins: u32 member list [nmax] and bin ids [ndim][nmax], when resident
-GenericCarve generic_carve(const SampleLayout &lay, int nmax) {
+// fast: the launch of filter_pixel_kernel<T, true>, whose own rows are kStreamFastOwn floats per weighted column, read 16 bytes
+// at a time: they start at up16(off_chunk) (off_chunk is a multiple of 8 only: npair may be odd)
+GenericCarve generic_carve(const SampleLayout &lay, int nmax, bool fast) {
     const GenericDims D = generic_dims(lay);
     GenericCarve c{};
     uint32_t o = (generic_f64_doubles(D) + generic::kThreads) * 8u;
     c.off_chunk = o;
     uint32_t chunk = (uint32_t)D.ndim * (generic::kChunk + 1) * 8u;
     chunk = std::max(chunk, 2048u + (uint32_t)D.npair * 4u);      // sMargX | sMargY | sNeed
-    chunk = std::max(chunk, (uint32_t)generic::kOwn * (uint32_t)D.nwt * 8u);           // own rows of a sweep
+    const uint32_t own_at = fast ? up16(o) : o;                   // where the own rows of a sweep start
+    const uint32_t own = fast ? (uint32_t)generic::kStreamFastOwn * (uint32_t)D.nwt * 4u : (uint32_t)generic::kOwn * (uint32_t)D.nwt * 8u;
+    chunk = std::max(chunk, own_at - o + own);
     chunk = std::max(chunk, (8u + 2u * (uint32_t)D.nF) * 8u);     // stage 1b: wave counts, feature means, 3 sigma
     o = up16(o + chunk);
     c.off_hist = o;
@@ -51,7 +55,7 @@ GenericCarve generic_carve(const SampleLayout &lay, int nmax) {
     c.hist_par = 4u * hist <= generic::kHistParBytes ? 4u : 1u;
     c.hist_words = hist / 4u;
     o += c.hist_par * hist;
-    c.off_red4 = c.off_chunk + up16((uint32_t)generic::kOwn * (uint32_t)D.nwt * 8u);
+    c.off_red4 = own_at + up16(own);
     o = std::max(o, c.off_red4 + 4u * generic::kThreads * 8u);
     const uint64_t members = (uint64_t)nmax * (4u + (uint32_t)D.ndim);
     c.resident = members <= generic::kResidentBytes ? 1u : 0u;
@@ -98,7 +102,8 @@ __global__ __launch_bounds__(256) void pixel_stats_kernel(PassParams p, uint64_t
 
 // One workgroup filters one pixel at a time and walks the pixels of rows [row_begin, row_end) or, when p.pix_list is given,
 // the entries of that list (*gs.count_dev of them when that is given, else p.list_count).
-template <class T>
+// FAST (RPF_FLAG_STREAM_FAST): stage 4 alone in the fp32 arithmetic of DESIGN.md section 11f; every other statement is shared.
+template <class T, bool FAST = false>
 __global__ __launch_bounds__(256) void filter_pixel_kernel(PassParams p, GenericCarve cv, Scratch gs) {
     extern __shared__ __align__(16) unsigned char smem[];
     const GenericDims D = generic_dims(p.lay);
@@ -261,17 +266,24 @@ __global__ __launch_bounds__(256) void filter_pixel_kernel(PassParams p, Generic
             __syncthreads();
         }
 
-        // ---- stages 3c, 4: alpha, beta, W_r_c; weights and blend; the status report ----------------------------------------
+        // ---- stages 3c, 4: alpha, beta, W_r_c; weights and blend (fp64, or the fp32 pair arithmetic of FAST); the status report
 #define RPF_STREAM_PART 2
 #include "rpf_generic_stream_stages.inc"
+        if constexpr (FAST) {
+#define RPF_STREAM_PART 4
+#include "rpf_generic_stream_stages.inc"
+        } else {
+#define RPF_STREAM_PART 3
+#include "rpf_generic_stream_stages.inc"
+        }
     }
 }
 
-template <class T>
+template <class T, bool FAST>
 hipError_t launch_filter_t(const PassParams &p, const GenericCarve &cv, const Scratch &gs, unsigned grid, hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute((const void *)filter_pixel_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
+    hipError_t e = hipFuncSetAttribute((const void *)filter_pixel_kernel<T, FAST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(filter_pixel_kernel<T>, dim3(grid), dim3(kThreads), cv.total, s, p, cv, gs);
+    hipLaunchKernelGGL((filter_pixel_kernel<T, FAST>), dim3(grid), dim3(kThreads), cv.total, s, p, cv, gs);
     return hipGetLastError();
 }
 
@@ -287,8 +299,8 @@ hipError_t launch_pixel_stats(const PassParams &p, uint64_t pix0, uint64_t pix1,
 
 // list / bins: the HBM slots of the spilled mode ([slots][nmax] u32, [slots][ndim][nmax] u8), unused when the carve-up is
 // resident; the grid never exceeds `slots`: min(pixels, slots), or `slots` when the list size is on the device
-hipError_t launch_filter(const PassParams &p, void *list, void *bins, uint32_t slots, const uint32_t *count_dev, hipStream_t s) {
-    const GenericCarve cv = generic_carve(p.lay, p.nmax);
+hipError_t launch_filter(const PassParams &p, void *list, void *bins, uint32_t slots, const uint32_t *count_dev, hipStream_t s, bool fast) {
+    const GenericCarve cv = generic_carve(p.lay, p.nmax, fast);
     if ((int)cv.total > max_lds_per_block()) return hipErrorInvalidValue;
     if (p.row_end <= p.row_begin) return hipSuccess;
     const uint64_t npix = p.pix_list == nullptr ? (uint64_t)(p.row_end - p.row_begin) * p.W : p.list_count;
@@ -297,7 +309,8 @@ hipError_t launch_filter(const PassParams &p, void *list, void *bins, uint32_t s
     if (grid == 0) return hipSuccess;
     Scratch gs;
     gs.list = (uint32_t *)list; gs.bins = (uint8_t *)bins; gs.count_dev = count_dev;
-    return p.lay.f16 ? launch_filter_t<__half>(p, cv, gs, grid, s) : launch_filter_t<float>(p, cv, gs, grid, s);
+    if (fast) return p.lay.f16 ? launch_filter_t<__half, true>(p, cv, gs, grid, s) : launch_filter_t<float, true>(p, cv, gs, grid, s);
+    return p.lay.f16 ? launch_filter_t<__half, false>(p, cv, gs, grid, s) : launch_filter_t<float, false>(p, cv, gs, grid, s);
 }
 
 } // namespace generic

@@ -24,6 +24,12 @@
 #ifndef RPF_GENERIC_OWN
 #define RPF_GENERIC_OWN 4 // own samples per sweep of stage 4 (their accumulators are registers; same bits at any value)
 #endif
+// ... under RPF_FLAG_STREAM_FAST (a multiple of 4: two own samples share a packed fp32 instruction and the sweep's own rows, floats,
+// are read 16 bytes at a time).  A member's columns are gathered and normalised once per sweep, so the wider sweep wins where N is
+// large, which is what the flag is for; DESIGN.md section 11f has 8 against 16 and their registers
+#ifndef RPF_STREAM_FAST_OWN
+#define RPF_STREAM_FAST_OWN 16
+#endif
 
 namespace rpf {
 
@@ -56,6 +62,11 @@ namespace {
 
 constexpr int kThreads = 256, kChunk = 64; // the streaming kernels: threads of a workgroup, members staged per step of stage 2
 constexpr int kOwn = RPF_GENERIC_OWN;      // ... and own samples per sweep of stage 4
+constexpr int kStreamFastOwn = RPF_STREAM_FAST_OWN; // ... of the fp32 stage 4 (rpf_generic_stream_stages.inc part 4)
+constexpr int kStreamGather = 4;           // ... whose feature columns are gathered this many at a time
+static_assert(kStreamFastOwn % 4 == 0 && kStreamFastOwn >= 4, "the fp32 own rows of a sweep are read 16 bytes at a time");
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4a __attribute__((ext_vector_type(4), may_alias));
 
 template <class T>
 __device__ __forceinline__ float ldp(const PassParams &p, int col, uint32_t off) {

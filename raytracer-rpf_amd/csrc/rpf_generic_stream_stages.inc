@@ -1,7 +1,9 @@
 // rpf_generic_stream_stages.inc -- the stages that generic::filter_pixel_kernel (rpf_generic.hip) and generic::filter_wide_kernel
 // (rpf_generic_wide.hip) run with the same statements on the same thread mapping (256 threads, one pixel): one copy, included
-// into the pixel loop of both kernels.  RPF_STREAM_PART 1: stages 1b, 2 and 3a and the debug hashes; 2: stages 3c and 4 and the
-// status report.  Between the two each kernel has its own stage 3b (16-bit cells in LDS | 32-bit cells in bands).
+// into the pixel loop of both kernels.  RPF_STREAM_PART 1: stages 1b, 2 and 3a and the debug hashes; 2: stage 3c; 3: stage 4 in
+// fp64 and the status report; 4: stage 4 in the fp32 arithmetic of RPF_FLAG_STREAM_FAST (DESIGN.md section 11f) and the status
+// report -- the kernels' FAST instantiations include part 4 where the others include part 3, and nothing else differs between
+// them.  Between parts 1 and 2 each kernel has its own stage 3b (16-bit cells in LDS | 32-bit cells in bands).
 //
 // Text, not functions, and the statements spelled out rather than calls of rpf_generic_common.h's small functions: both forms
 // were built and measured (profiles/generic_refactor_parent_vs_new.txt, sections 3 and 4).  Same bits, same waves per SIMD, no
@@ -11,7 +13,8 @@
 // this text because it is one text with filter_pixel_kernel's.  As it stands both kernels' assembly is the parent's.
 //
 // Names the including kernel provides: p, D and ndim, nF, nR, nAnc, npair, nwt, colF; tid, lane, wv; W, H, S, b, HW; pix, x, y;
-// e_eps; list, bins and the type Bin of a bin id; sStat, sZ, sMI, sW, sRedD, sChunk, sRed4, sCnt.  Part 1 leaves n, B and dn.
+// e_eps; list, bins and the type Bin of a bin id; sStat, sZ, sMI, sW, sRedD, sChunk, sRed4, sCnt; for part 4 also smem and cv (the
+// start of the dynamic LDS and the carve-up, whose off_chunk it rounds up).  Part 1 leaves n, B and dn.
 #if RPF_STREAM_PART == 1
         // ---- stage 1b: the 3-sigma test and the member list, reference order (rpf.cpp:556-586) -------------------
         const int x0 = max(x - b, 0), x1 = min(x + b, W - 1), y0 = max(y - b, 0), y1 = min(y + b, H - 1);
@@ -178,6 +181,7 @@
             __syncthreads();
         }
 
+#elif RPF_STREAM_PART == 3
         // ---- stage 4: weights and blend, term by term as rpf.cpp:646-717; kOwn own samples per sweep.  The column loop is
         // outermost: a neighbour's value of column k is loaded and normalised once, then the kOwn own samples' sp / sc / sf
         // take its term -- each accumulator still receives its terms in ascending k (the reference's order).
@@ -264,7 +268,132 @@
                 atomicMin(&p.status[1], (int)pix);
             }
         }
+#elif RPF_STREAM_PART == 4
+        // ---- stage 4 under RPF_FLAG_STREAM_FAST: the pair arithmetic in fp32 (DESIGN.md section 11f), kStreamFastOwn own samples
+        // per sweep.  Once per pixel: 1 / SD per column (fp64; the slots of the column minima and maxima are dead), which columns
+        // have SD == 0 (z = 0 there) as one wave-uniform mask, and the coefficients of the summed exponent with log2 e folded in,
+        // formed in fp64 and rounded once (the sums of stage 3c they overwrite are dead).  A member's z = (x - M) * (1 / SD) is
+        // formed in fp64 and rounded once; d = z_i - z_j, d * d and E += (d * d) * coef are fp32 with one accumulator per own
+        // sample, two own samples to a packed instruction; one hardware exponential; the weight widened to fp64.  The four sums,
+        // the halving tree, the quotient, the padding rule and the status report are part 3's statements.
+        {
+            constexpr int kFO = kStreamFastOwn;
+            const double wrc = sWrc[0];
+            const double sigma_c2 = p.seed * p.seed / (1 - wrc) / (1 - wrc);                                  // rpf.cpp:662
+            const double sigma_p2 = p.sigma_p * p.sigma_p;
+            const double kLog2e = 1.4426950408889634;
+            double *sInv = sStat + 2 * ndim;
+            float *sCoef = reinterpret_cast<float *>(sDrf);
+            const double sdl = sStat[ndim + min(lane, ndim - 1)];
+            const unsigned long long sd0mask = __ballot(lane < ndim && sdl == 0.0); // (every wave forms the same mask)
+            if (tid < ndim) sInv[tid] = 1.0 / sdl;
+            if (tid < nwt)
+                sCoef[tid] = (float)((tid < 2 ? 1.0 / (2 * sigma_p2) : (tid < 5 ? sAlpha[tid - 2] : sBeta[tid - 5]) / (2 * sigma_c2)) * kLog2e);
+            auto zfast = [&](int c, double xv) { return ((sd0mask >> c) & 1ull) ? 0.f : (float)((xv - sStat[c]) * sInv[c]); };
+            // [nwt][kFO] normalised own samples of the sweep, in the dead staging chunk from its first 16-byte boundary on (the
+            // carve-ups leave the room): term() reads them as 16-byte vectors
+            float *sOwnZ = reinterpret_cast<float *>(smem + up16(cv.off_chunk));
+            bool bad = false;
+            for (int i0 = 0; i0 < S; i0 += kFO) {
+                __syncthreads();
+                for (int t = tid; t < kFO * nwt; t += kThreads) {
+                    const int k = t / kFO, ii = t % kFO, i = min(i0 + ii, S - 1);
+                    const int col = k < 5 ? k : k + nR;
+                    sOwnZ[t] = zfast(col, load_col<T>(p, col, (uint32_t)(pix * S + i)));
+                }
+                __syncthreads();
+                double sw[kFO], s0[kFO], s1[kFO], s2[kFO];
+#pragma unroll
+                for (int ii = 0; ii < kFO; ++ii) { sw[ii] = 0.0; s0[ii] = 0.0; s1[ii] = 0.0; s2[ii] = 0.0; }
+                for (int j = tid; j < n; j += kThreads) {
+                    const uint32_t off = list[j];
+                    f32x2 E[kFO / 2];
+#pragma unroll
+                    for (int q = 0; q < kFO / 2; ++q) E[q] = f32x2{0.f, 0.f};
+                    double cj[3];
+                    // one accumulator per own sample takes the column's term, two own samples to a packed instruction
+                    auto term = [&](int k, float zj) {
+                        const float ck = sCoef[k];
+                        const f32x2 zj2 = f32x2{zj, zj}, ck2 = f32x2{ck, ck};
+#pragma unroll
+                        for (int q4 = 0; q4 < kFO / 4; ++q4) {
+                            const f32x4a zo = *reinterpret_cast<const f32x4a *>(sOwnZ + k * kFO + 4 * q4);
+                            const f32x2 da = f32x2{zo[0], zo[1]} - zj2, db = f32x2{zo[2], zo[3]} - zj2;
+                            E[2 * q4] = __builtin_elementwise_fma(da * da, ck2, E[2 * q4]);
+                            E[2 * q4 + 1] = __builtin_elementwise_fma(db * db, ck2, E[2 * q4 + 1]);
+                        }
+                    };
+                    // every gather of the member that needs no loop is issued here, the features kStreamGather at a time with
+                    // the next group in flight while this one is weighed
+                    const float pf0 = ldp<T>(p, 0, off), pf1 = ldp<T>(p, 1, off);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) cj[k] = p.col_in[(uint64_t)k * p.plane_stride + off];
+                    float fv[kStreamGather];
+#pragma unroll
+                    for (int u = 0; u < kStreamGather; ++u) fv[u] = ldp<T>(p, colF + min(u, nF - 1), off);
+                    term(0, zfast(0, (double)pf0));
+                    term(1, zfast(1, (double)pf1));
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) term(2 + k, zfast(2 + k, cj[k]));
+                    for (int k0 = 0; k0 < nF; k0 += kStreamGather) {
+                        float cur[kStreamGather];
+#pragma unroll
+                        for (int u = 0; u < kStreamGather; ++u) cur[u] = fv[u];
+                        if (k0 + kStreamGather < nF) {
+#pragma unroll
+                            for (int u = 0; u < kStreamGather; ++u) fv[u] = ldp<T>(p, colF + min(k0 + kStreamGather + u, nF - 1), off);
+                        }
+#pragma unroll
+                        for (int u = 0; u < kStreamGather; ++u) {
+                            const int k = k0 + u;
+                            if (k >= nF) break;
+                            term(5 + k, zfast(colF + k, (double)cur[u]));
+                        }
+                    }
+#pragma unroll
+                    for (int ii = 0; ii < kFO; ++ii) {
+                        double w = (double)__builtin_amdgcn_exp2f(-E[ii >> 1][ii & 1]);
+                        w = (i0 + ii < S) ? w : 0.0;
+                        sw[ii] += w; s0[ii] += w * cj[0]; s1[ii] += w * cj[1]; s2[ii] += w * cj[2];   // rpf.cpp:691-692
+                    }
+                }
+                // the four sums of an own sample are reduced in the pairing of a halving tree over the 256 threads:
+                // v[t] + v[t + 128], + 64 across the waves, then 32 ... 1 inside wave 0
+#pragma unroll
+                for (int ii = 0; ii < kFO; ++ii) {
+                    if (i0 + ii >= S) break; // workgroup-uniform: a padding sample stores nothing
+                    __syncthreads();
+                    sRed4[tid] = sw[ii]; sRed4[kThreads + tid] = s0[ii];
+                    sRed4[2 * kThreads + tid] = s1[ii]; sRed4[3 * kThreads + tid] = s2[ii];
+                    __syncthreads();
+                    if (wv == 0) {
+                        double v[4];
+#pragma unroll
+                        for (int q = 0; q < 4; ++q) {
+                            const double *r = sRed4 + q * kThreads + lane;
+                            double a = (r[0] + r[128]) + (r[64] + r[192]);
+                            for (int s = 32; s > 0; s >>= 1) a = a + __shfl_down(a, s, 64);
+                            v[q] = __shfl(a, 0, 64);
+                        }
+                        const int i = i0 + ii;
+                        if (lane < 3 && i < S) {
+                            double prime = (lane == 0 ? v[1] : (lane == 1 ? v[2] : v[3])) / v[0];                 // rpf.cpp:700
+                            if (isnan(prime)) {                                                                    // rpf.cpp:702
+                                bad = true;
+                                if (p.policy == RPF_DEGEN_EPS) prime = p.col_in[(uint64_t)lane * p.plane_stride + pix * S + i];
+                            }
+                            p.col_out[(uint64_t)lane * p.plane_stride + pix * S + i] = prime;
+                        }
+                    }
+                }
+            }
+            const int anybad = __syncthreads_or(bad ? 1 : 0);
+            if (tid == 0 && anybad) {
+                atomicAdd(&p.status[0], 1);
+                atomicMin(&p.status[1], (int)pix);
+            }
+        }
 #else
-#error "RPF_STREAM_PART must be 1 or 2"
+#error "RPF_STREAM_PART must be 1, 2, 3 or 4"
 #endif
 #undef RPF_STREAM_PART

@@ -36,15 +36,17 @@ constexpr uint32_t kLdsBudget = (160u << 10) - 1024u; // dynamic LDS: the kernel
 
 // The LDS carve-up of the wide kernel (rpf_internal.h): generic_carve's fp64 block and chunk (marginals of kMargMax entries),
 // then the band of the joint histogram -- the whole table where it fits, else what the budget leaves -- and red4 over the
-// dead chunk and band.
-GenericWideCarve generic_wide_carve(const SampleLayout &lay, int nmax) {
+// dead chunk and band.  fast: the launch of filter_wide_kernel<T, true> (own rows of kStreamFastOwn floats per weighted column).
+GenericWideCarve generic_wide_carve(const SampleLayout &lay, int nmax, bool fast) {
     const GenericDims D = generic_dims(lay);
     GenericWideCarve c{};
     uint32_t o = (generic_f64_doubles(D) + generic::kThreads) * 8u;
     c.off_chunk = o;
     uint32_t chunk = (uint32_t)D.ndim * (generic::kChunk + 1) * 8u;
     chunk = std::max(chunk, 2u * generic::kMargMax * 4u + (uint32_t)D.npair * 4u); // sMargX | sMargY | sNeed
-    chunk = std::max(chunk, (uint32_t)generic::kOwn * (uint32_t)D.nwt * 8u);          // own rows of a sweep
+    const uint32_t own_at = fast ? up16(o) : o;                                        // where the own rows of a sweep start (as generic_carve)
+    const uint32_t own = fast ? (uint32_t)generic::kStreamFastOwn * (uint32_t)D.nwt * 4u : (uint32_t)generic::kOwn * (uint32_t)D.nwt * 8u;
+    chunk = std::max(chunk, own_at - o + own);
     chunk = std::max(chunk, (8u + 2u * (uint32_t)D.nF) * 8u);                         // stage 1b: wave counts, feature means, 3 sigma
     o = up16(o + chunk);
     c.off_hist = o;
@@ -54,7 +56,7 @@ GenericWideCarve generic_wide_carve(const SampleLayout &lay, int nmax) {
     if (band < row) band = up16(row); // does not fit: total says so
     c.band_words = band / 4u;
     o += band;
-    c.off_red4 = c.off_chunk + up16((uint32_t)generic::kOwn * (uint32_t)D.nwt * 8u);
+    c.off_red4 = own_at + up16(own);
     c.total = std::max(o, c.off_red4 + 4u * generic::kThreads * 8u);
     return c;
 }
@@ -71,7 +73,8 @@ struct WideScratch {
 };
 
 // One workgroup filters one pixel at a time and walks the pixels of rows [row_begin, row_end), or those of p.pix_list.
-template <class T>
+// FAST (RPF_FLAG_STREAM_FAST): stage 4 alone in the fp32 arithmetic of DESIGN.md section 11f; every other statement is shared.
+template <class T, bool FAST = false>
 __global__ __launch_bounds__(256) void filter_wide_kernel(PassParams p, GenericWideCarve cv, WideScratch gs) {
     extern __shared__ __align__(16) unsigned char smem[];
     const GenericDims D = generic_dims(p.lay);
@@ -241,25 +244,32 @@ __global__ __launch_bounds__(256) void filter_wide_kernel(PassParams p, GenericW
             __syncthreads();
         }
 
-        // ---- stages 3c, 4: alpha, beta, W_r_c; weights and blend; the status report ----------------------------------------
+        // ---- stages 3c, 4: alpha, beta, W_r_c; weights and blend (fp64, or the fp32 pair arithmetic of FAST); the status report
 #define RPF_STREAM_PART 2
 #include "rpf_generic_stream_stages.inc"
+        if constexpr (FAST) {
+#define RPF_STREAM_PART 4
+#include "rpf_generic_stream_stages.inc"
+        } else {
+#define RPF_STREAM_PART 3
+#include "rpf_generic_stream_stages.inc"
+        }
     }
 }
 
-template <class T>
+template <class T, bool FAST>
 hipError_t launch_filter_wide_t(const PassParams &p, const GenericWideCarve &cv, const WideScratch &gs, unsigned grid, hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute((const void *)filter_wide_kernel<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
+    hipError_t e = hipFuncSetAttribute((const void *)filter_wide_kernel<T, FAST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(filter_wide_kernel<T>, dim3(grid), dim3(kThreads), cv.total, s, p, cv, gs);
+    hipLaunchKernelGGL((filter_wide_kernel<T, FAST>), dim3(grid), dim3(kThreads), cv.total, s, p, cv, gs);
     return hipGetLastError();
 }
 
 } // namespace
 
 hipError_t launch_filter_wide(const PassParams &p, void *list, void *bins, uint32_t slots, const uint64_t *table, int table_bits,
-                              const uint32_t *count_dev, hipStream_t s) {
-    const GenericWideCarve cv = generic_wide_carve(p.lay, p.nmax);
+                              const uint32_t *count_dev, hipStream_t s, bool fast) {
+    const GenericWideCarve cv = generic_wide_carve(p.lay, p.nmax, fast);
     if ((int)cv.total > max_lds_per_block() || cv.total > kLdsBudget) return hipErrorInvalidValue;
     if (p.nmax < 1 || p.nmax > kMaxWideNbhd || (count_dev != nullptr && p.pix_list == nullptr)) return hipErrorInvalidValue;
     if (cv.band_words < (uint32_t)std::max(1.0, std::floor(std::sqrt((double)p.nmax)))) return hipErrorInvalidValue; // a band holds a row of the widest table
@@ -270,7 +280,8 @@ hipError_t launch_filter_wide(const PassParams &p, void *list, void *bins, uint3
     const unsigned grid = (unsigned)std::min<uint64_t>(npix, slots);
     WideScratch gs;
     gs.list = (uint32_t *)list; gs.bins = (uint16_t *)bins; gs.table = table; gs.bits = table_bits; gs.count_dev = count_dev;
-    return p.lay.f16 ? launch_filter_wide_t<__half>(p, cv, gs, grid, s) : launch_filter_wide_t<float>(p, cv, gs, grid, s);
+    if (fast) return p.lay.f16 ? launch_filter_wide_t<__half, true>(p, cv, gs, grid, s) : launch_filter_wide_t<float, true>(p, cv, gs, grid, s);
+    return p.lay.f16 ? launch_filter_wide_t<__half, false>(p, cv, gs, grid, s) : launch_filter_wide_t<float, false>(p, cv, gs, grid, s);
 }
 
 } // namespace generic

@@ -42,6 +42,9 @@ struct PassParams {
                            //          (route_generic_wide_classes); only N > 832 stays on the wide kernel
                            //   bit 5: RPF_FLAG_GENERIC_FAST: routes 4 and 5 launch the fp32-weight instantiations of their packed and
                            //          one-wave kernels (host-side only: no kernel reads the bit, and fast_weights stays 0)
+                           //   bit 6: RPF_FLAG_STREAM_FAST on a pass that runs layout-generic kernels (bit 0 or bit 3; never set on a
+                           //          fused pass): route 3, the rest lists of routes 4 / 5, route 6 and every class and the rest
+                           //          list of route 7 launch the fp32-weight instantiations; redo launches never do (host-side only)
     int32_t stage_mask;    // diagnostics only (rpf_set_option "stage_mask"): bit0 stats chain, bit1 bins, bit2 MI, bit3 weights; -1 = all
     int32_t screen;        // far-pair screen of the four-wave kernels: 0 off, 1 on
     int32_t strip_w;       // pixels per XCD strip of the pixel walk (slab_pixel)
@@ -182,14 +185,17 @@ struct GenericCarve {
     uint32_t off_chunk, off_hist, off_red4, off_list, off_bins, total, resident;
     uint32_t hist_par, hist_words; // histograms in the hist region (4: one per wave, 1) and the 32-bit words of one
 };
-GenericCarve generic_carve(const SampleLayout &lay, int nmax);
+GenericCarve generic_carve(const SampleLayout &lay, int nmax, bool fast = false); // fast: the carve-up of a launch_filter(..., fast = true)
 namespace generic {
 hipError_t launch_pixel_stats(const PassParams &p, uint64_t pix0, uint64_t pix1, hipStream_t s);
 // the streaming kernel: one launch filters rows [p.row_begin, p.row_end), or the pixels of p.pix_list when that is given
 // (the last size class of the binned route; the redo list).  list / bins: global scratch of `slots` workgroups, [slots][nmax]
 // u32 and [slots][ndim][nmax] u8 (needed when the carve-up is not resident); the grid is min(pixels, slots).
-// count_dev != null: the size of p.pix_list is read from device memory (redo list: no host read-back), grid = slots
-hipError_t launch_filter(const PassParams &p, void *list, void *bins, uint32_t slots, const uint32_t *count_dev, hipStream_t s);
+// count_dev != null: the size of p.pix_list is read from device memory (redo list: no host read-back), grid = slots.
+// fast: stage 4 in the fp32 arithmetic of RPF_FLAG_STREAM_FAST (route 3 and the rest lists of routes 4 / 5 pass it; the redo
+// list and the streaming class of the fused routes never do)
+hipError_t launch_filter(const PassParams &p, void *list, void *bins, uint32_t slots, const uint32_t *count_dev, hipStream_t s,
+                         bool fast = false);
 } // namespace generic
 
 // ---- the packed layout-generic kernels (rpf_generic_packed.hip, RPF_FLAG_GENERIC_PACKED): N <= 64, several pixels per wave --
@@ -253,14 +259,15 @@ constexpr int kTWideBits = 41;        // the wide table: round(k ln k * 2^41), b
 struct GenericWideCarve {
     uint32_t off_chunk, off_hist, off_red4, band_words, total;
 };
-GenericWideCarve generic_wide_carve(const SampleLayout &lay, int nmax);
+GenericWideCarve generic_wide_carve(const SampleLayout &lay, int nmax, bool fast = false);
 namespace generic {
 // one launch filters rows [p.row_begin, p.row_end), or the pixels of p.pix_list when that is given (the rest class and the
 // redo list of route 7).  list / bins: global scratch of `slots` workgroups, [slots][nmax] u32 and [slots][ndim][nmax] u16; the
 // grid is min(pixels, slots).  table: round(k ln k * 2^table_bits), k = 0 .. p.nmax (p.tfix is not read).  count_dev != null:
-// the size of p.pix_list is read from device memory (redo list: no host read-back), grid = slots
+// the size of p.pix_list is read from device memory (redo list: no host read-back), grid = slots.  fast: as for launch_filter
+// (route 6 and the rest list of route 7 pass it, route 7's redo launch never does)
 hipError_t launch_filter_wide(const PassParams &p, void *list, void *bins, uint32_t slots, const uint64_t *table, int table_bits,
-                              const uint32_t *count_dev, hipStream_t s);
+                              const uint32_t *count_dev, hipStream_t s, bool fast = false);
 // the count pass of route 7 (rpf_generic_wide_count.hip, S <= 832): for every pixel of rows [p.row_begin, p.row_end) N into
 // p.nbhd -- 833 for any N > 832 -- and, for S < N <= 832, the N - S members behind the own samples into pool[base[pix] ..];
 // *cursor ends at the sum of those N - S, whether or not `capacity` entries held them (a pool too small loses writes only:

@@ -30,6 +30,11 @@ FLAG_WIDE_CLASSES = 128  # with FLAG_WIDE_NBHD: a wide pass counted first and de
 # one-wave generic kernels (routes 4 / 5 as without it; the rest list, the redo list and a route-3 pass stay fp64, same bits);
 # refused without both flags, with FLAG_FAST_WEIGHTS (which keeps its meaning: the fused 19-dim kernels) and with FLAG_WIDE_NBHD
 FLAG_GENERIC_FAST = 256
+# with FLAG_GENERIC and / or FLAG_WIDE_NBHD: the pair weights of stage 4 in fp32 on the streaming generic kernel (route 3, the rest
+# lists of routes 4 / 5) and on every kernel of a wide pass (routes 6 / 7); routes, launches and counters as without it; the redo
+# list and every pass on the fused kernels stay fp64, same bits; refused without both flags (and, with FLAG_FAST_WEIGHTS, by one of
+# that flag's refusals)
+FLAG_STREAM_FAST = 512
 FLAG_WIDE_NBHD = 64  # passes with 65535 < box*box*S <= 262144 on the wide layout-generic kernel (route 6); max_nbhd() tells the bound
 MAX_NDIM = 40     # the layout-generic kernels take 5 + n_random + n_feat up to this
 PLANES_F32, PLANES_F16 = 0, 1
@@ -118,7 +123,8 @@ def layout_kernels(desc):
     """rpf_layout_kernels (no GPU needed): (status, generic) for the layout and flags of `desc` -- (OK, 0) the compiled fused
     kernels, (OK, 1) the layout-generic kernels (FLAG_GENERIC; FLAG_GENERIC_FAST does not change the answer),
     (E_UNSUPPORTED, None) where the filter entry points refuse it -- FLAG_GENERIC_FAST without FLAG_GENERIC | FLAG_GENERIC_PACKED,
-    with FLAG_FAST_WEIGHTS or with FLAG_WIDE_NBHD among them; desc None: (E_BADARG, None)"""
+    with FLAG_FAST_WEIGHTS or with FLAG_WIDE_NBHD, and FLAG_STREAM_FAST without both FLAG_GENERIC and FLAG_WIDE_NBHD, among them
+    (where FLAG_STREAM_FAST is accepted the answer is that of the same flags without it); desc None: (E_BADARG, None)"""
     g = C.c_int32(-1)
     st = load().rpf_layout_kernels(None if desc is None else C.byref(desc), C.byref(g))
     return st, (g.value if st == OK else None)
@@ -323,7 +329,7 @@ class Context:
         (FLAG_GENERIC), 4 the same with small neighbourhoods packed (FLAG_GENERIC_PACKED), 5 the same with
         64 < N <= 832 on the one-wave generic kernels (FLAG_GENERIC_WAVE; 3 for a pass with S > 832), 6 the wide kernel
         (FLAG_WIDE_NBHD on a pass with box*box*S > 65535), 7 such a pass dealt by size class (FLAG_WIDE_CLASSES); -1 before
-        any pass.  FLAG_GENERIC_FAST changes no route: 4 / 5 (or 3) as without it
+        any pass.  FLAG_GENERIC_FAST and FLAG_STREAM_FAST change no route
         (rpf_query_route)"""
         r = C.c_int32(-1)
         self._check(self._L.rpf_query_route(self._h, C.byref(r)))

@@ -22,6 +22,9 @@ the launches and the mean neighbourhood size.  Cases (--case to pick by name):
 smooth8, flat8, lay3_12, lay4_18 and lay4_18_f16 end with the legs of RPF_FLAG_GENERIC_FAST (`generic` = 12: route 4 with the
 flag, 13: route 5 with it; skipped on a library from before the flag): such a record carries ratio_to_fp64, its time over the
 same route's without the flag.
+smooth8 and flat8 (routes 3 and 5), wide57 (routes 3, 6 and 7) and flat57 (routes 6 and 7) then run the legs of
+RPF_FLAG_STREAM_FAST (`generic` + 20: 21 route 3, 23 route 5, 33 route 5 with RPF_FLAG_GENERIC_FAST as well, 26 route 6, 27 route
+7; skipped on a library from before the flag), with ratio_to_fp64 and "stream_fast": 1 in the record.
 A record of a wide pass carries the class census of its N plane (pixels with N <= 8, 16, ... 832, and the rest).
 Each case's variants run in one process on one context and on the same generated buffer; a route-4 or route-5 record
 carries ratio_to_route3 next to ratio_to_fused, a route-5 record ratio_to_route4 as well.
@@ -43,14 +46,16 @@ from raytracer_rpf_amd import hip  # noqa: E402
 
 # name: (W, H, S, box, flat_frac, [(n_random, n_feat, generic[, S of this variant: the first samples of the buffer]), ...])
 CASES = {
-    "smooth8": (1920, 270, 8, 7, 0.0, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3), (2, 12, 12), (2, 12, 13)]),
-    "flat8": (1920, 270, 8, 7, 0.94, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3), (2, 12, 12), (2, 12, 13)]),
+    "smooth8": (1920, 270, 8, 7, 0.0, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3), (2, 12, 12), (2, 12, 13), (2, 12, 21), (2, 12, 23),
+                                       (2, 12, 33)]),
+    "flat8": (1920, 270, 8, 7, 0.94, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3), (2, 12, 12), (2, 12, 13), (2, 12, 21), (2, 12, 23),
+                                      (2, 12, 33)]),
     "lay3_12": (1920, 270, 8, 7, 0.0, [(3, 12, 1), (3, 12, 2), (3, 12, 3), (3, 12, 12), (3, 12, 13)]),
     "lay4_18": (1920, 270, 8, 7, 0.0, [(4, 18, 1), (4, 18, 2), (4, 18, 3), (4, 18, 12), (4, 18, 13)]),
     "lay4_18_f16": (1920, 270, 8, 7, 0.0, [(4, 18, 1), (4, 18, 2), (4, 18, 3), (4, 18, 12), (4, 18, 13)]),
     "box17": (256, 64, 16, 17, 0.0, [(2, 12, 0), (2, 12, 1), (2, 12, 2), (2, 12, 3)]),
-    "wide57": (256, 57, 21, 57, 0.0, [(2, 12, 1, 14), (2, 12, 6, 21), (2, 12, 7, 21)]),
-    "flat57": (256, 57, 21, 57, 0.94, [(2, 12, 6, 21), (2, 12, 7, 21)]),
+    "wide57": (256, 57, 21, 57, 0.0, [(2, 12, 1, 14), (2, 12, 6, 21), (2, 12, 7, 21), (2, 12, 21, 14), (2, 12, 26, 21), (2, 12, 27, 21)]),
+    "flat57": (256, 57, 21, 57, 0.94, [(2, 12, 6, 21), (2, 12, 7, 21), (2, 12, 26, 21), (2, 12, 27, 21)]),
     "flat55": (1920, 64, 32, 55, 0.94, [(2, 12, 6, 32), (2, 12, 7, 32)]),
 }
 F16_CASES = ("lay4_18_f16",)  # planes stored as fp16 halves
@@ -62,6 +67,10 @@ def has_generic_fast():
     return hasattr(hip, "FLAG_GENERIC_FAST") and hip.layout_kernels(hip.make_desc(8, 8, 4, flags=hip.FLAG_GENERIC_FAST))[0] == hip.E_UNSUPPORTED
 
 
+def has_stream_fast():
+    return hasattr(hip, "FLAG_STREAM_FAST") and hip.layout_kernels(hip.make_desc(8, 8, 4, flags=hip.FLAG_STREAM_FAST))[0] == hip.E_UNSUPPORTED
+
+
 def run(ctx, name, steps):
     W, H, S_buf, box, flat, legs = CASES[name]
     dev = torch.device("cuda", 0)
@@ -71,6 +80,10 @@ def run(ctx, name, steps):
     f16 = name in F16_CASES
     for leg in legs:
         nr, nf, generic = leg[:3]
+        stream_fast = generic >= 20  # RPF_FLAG_STREAM_FAST
+        if stream_fast and not has_stream_fast():
+            continue
+        generic = generic - 20 if stream_fast else generic
         fast = generic in (12, 13)   # RPF_FLAG_GENERIC_FAST on route 4 / 5
         if fast and not has_generic_fast():
             continue
@@ -87,6 +100,7 @@ def run(ctx, name, steps):
         flags |= hip.FLAG_WIDE_NBHD if generic in (6, 7) else 0
         flags |= hip.FLAG_WIDE_CLASSES if generic == 7 else 0
         flags |= hip.FLAG_GENERIC_FAST if fast else 0
+        flags |= hip.FLAG_STREAM_FAST if stream_fast else 0
         desc = hip.make_desc(W, H, S, boxes=(box,), policy=hip.DEGEN_EPS, flags=flags, n_random=nr, n_feat=nf,
                              **({"plane_dtype": hip.PLANES_F16} if f16 else {}))
         ms = []
@@ -97,7 +111,7 @@ def run(ctx, name, steps):
                 ms.append(ctx.counters().filter_kernel_ms)
         c = ctx.counters()
         rec = {"case": name, "shape": "%dx%dx%d box %d" % (W, H, S, box), "flat_frac": flat, "layout": [nr, nf, "f16" if f16 else "f32"],
-               "generic": generic, "fp32_weights": int(fast), "route": ctx.route(), "launches": c.filter_kernel_launches,
+               "generic": generic, "fp32_weights": int(fast), "stream_fast": int(stream_fast), "route": ctx.route(), "launches": c.filter_kernel_launches,
                "mean_nbhd": round(c.sum_nbhd / (W * H), 1), "max_nbhd": c.max_nbhd,
                "filter_ms_min": round(min(ms), 3), "filter_ms_max": round(max(ms), 3), "stats_ms": round(c.stats_kernel_ms, 3),
                "colour_mean": float(colour.mean())}
@@ -110,7 +124,7 @@ def run(ctx, name, steps):
             rec["ratio_to_route6"] = round(rec["filter_ms_min"] / r6["filter_ms_min"], 4)
         if len(leg) > 3:
             rec["ns_per_pixel_sample"] = round(rec["filter_ms_min"] * 1e6 / max(c.sum_nbhd, 1), 4)
-        if fast:  # the same route without the flag, measured a moment ago on the same buffer
+        if fast or stream_fast:  # the same route without the flag, measured a moment ago on the same buffer
             rec["ratio_to_fp64"] = round(rec["filter_ms_min"] / out[(nr, nf, generic)]["filter_ms_min"], 3)
             print(json.dumps(rec), flush=True)
             del colour
