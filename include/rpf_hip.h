@@ -155,6 +155,19 @@ enum {
                                   together with RPF_FLAG_FAST_WEIGHTS, or together with RPF_FLAG_WIDE_NBHD (wide passes are fp64
                                   throughout) it is RPF_E_UNSUPPORTED, from every filter entry point and from
                                   rpf_layout_kernels, before any device work. */
+    RPF_FLAG_SPIKE_CLAMP = 1024, /* opt-in: after the LAST pass of the call the spike pass runs on the fp64 colours of the filtered
+                                  rows -- a sample further than `threshold` standard deviations from its pixel's mean on any
+                                  channel is replaced by the mean of the pixel's other samples, and (preserve_energy) the removed
+                                  energy is handed back to every sample of the filtered rows as one constant per channel; the
+                                  definition is DESIGN.md section 12, the parameters rpf_set_spike below.  It runs before the
+                                  reduce, before every download (fp32 samples, colour64_out, pixel means) and before the film
+                                  step, from rpf_filter, rpf_filter_ex, rpf_filter_device, rpf_filter_film, rpf_multi_filter and
+                                  rpf_multi_filter_film.  A caller who makes one call per pass sets it on the last call only.
+                                  Independent of every route flag: rpf_layout_kernels, rpf_max_nbhd, rpf_query_route,
+                                  rpf_counters and the launch counts answer as without it.  In rpf_filter it implies the serial
+                                  download of RPF_FLAG_NO_OVERLAP (no band may leave before delta is known).
+                                  RPF_E_NONFINITE is returned as before, and the spike pass still runs.
+                                  rpf_filter_pass_debug refuses the flag (RPF_E_UNSUPPORTED) before any device work. */
     RPF_FLAG_STREAM_FAST = 512 /* opt-in, modifies RPF_FLAG_GENERIC and / or RPF_FLAG_WIDE_NBHD: the two kernels that walk a
                                   neighbourhood of any size with 256 threads -- the generic filter kernel (route 3, the rest
                                   list N > 64 / N > 832 of routes 4 / 5) and the wide kernel (route 6, the rest list N > 832 of
@@ -509,6 +522,53 @@ int32_t rpf_film_window(const rpf_desc *desc, const rpf_film *film, int32_t *hal
 int32_t rpf_multi_filter_film(rpf_multi *m, const rpf_desc *desc, const rpf_film *film, const void *planes,
                               const float *ray_weight, float *sample_rgb_out, float *tile_rgb_out, float *tile_weight_out,
                               float *image_rgb_out);
+
+/* ---- the spike pass: spike clamp and energy preservation after the last filter pass (RPF_FLAG_SPIKE_CLAMP) --------------
+ * The reference leaves the HDR clamp and the energy-preservation step of the published algorithm out (commented,
+ * rpf.cpp:707-713); a firefly that survives the passes goes straight into FilmTile::AddSample.  This pass is defined in
+ * DESIGN.md section 12, in IEEE fp64 with every sum a serial chain in a stated order.  In short, on the filtered rows only:
+ *   per pixel and channel k   m_k = mean of the S colours, sd_k = sqrt(sum (c - m_k)^2 / S);
+ *   sample s is a spike       when |c_sk - m_k| > threshold * sd_k on ANY channel (strict; false against NaN: a pixel that
+ *                             holds a NaN or an infinite colour has a NaN sd_k, flags nothing and is left as it is);
+ *   n spikes of S             n == 0: untouched; n == S: untouched, counted as skipped; else every spike's three channels
+ *                             become m'_k, the mean of the samples that passed, and e_k = sum over spikes of (c_sk - m'_k);
+ *   energy                    E_k = sum over rows of (sum over x of e_k); delta_k = E_k / (rows * W * S); with
+ *                             preserve_energy every sample of the filtered rows gets c += delta_k (all three channels, unless
+ *                             all three delta_k are 0).  rayWeight plays no part.  Rows outside the slab keep their bits. */
+typedef struct rpf_spike_stats {
+    int64_t spike_samples;   /* samples replaced                                                      */
+    int64_t spike_pixels;    /* pixels with 0 < n < S                                                 */
+    int64_t skipped_pixels;  /* pixels with n == S                                                    */
+    double energy[3];        /* E_k                                                                   */
+    double delta[3];         /* delta_k as folded from E_k, whether or not preserve_energy added it  */
+    float spike_ms;          /* RPF_FLAG_TIMING: the spike pass, first launch to the end of the add   */
+    int32_t applied;         /* 1 when the most recent call ran the pass; 0 (and zeros above) otherwise */
+} rpf_spike_stats;
+
+/* threshold: finite, > 0 (default 1.0); preserve_energy: 0 or 1 (default 1); anything else is RPF_E_BADARG */
+int32_t rpf_set_spike(rpf_ctx *ctx, double threshold, int32_t preserve_energy);
+int32_t rpf_multi_set_spike(rpf_multi *m, double threshold, int32_t preserve_energy);
+/* the spike pass of the most recent rpf_filter / _ex / _device / _film call (rpf_multi_*: merged over the slabs, the same
+ * numbers as one context) */
+int32_t rpf_query_spike(rpf_ctx *ctx, rpf_spike_stats *out);
+int32_t rpf_multi_query_spike(rpf_multi *m, rpf_spike_stats *out);
+
+/* The two halves, for a caller who owns the slabs (one context per process: the row sums of every slab are gathered in
+ * image-row order, folded with rpf_spike_delta, and the same delta added on every slab).  d_colour: device, 3 fp64 planes
+ * [3][H][W][S]; rows [row_begin, row_end) of desc are worked on.  Stream-ordered on `stream` like rpf_reduce_device; both
+ * return after the stream has drained.
+ *   rpf_spike_clamp_device   replaces the spikes; row_sums_out: HOST, [(row_end - row_begin)][3] doubles, the per-row sums of the
+ *                            removed energy; stats_out (may be NULL): the three counts of these rows, applied = 1, energy and
+ *                            delta as rpf_spike_delta folds these rows alone
+ *   rpf_colour_add_device    c += delta[k] on every sample of the rows; delta: HOST, three doubles */
+int32_t rpf_spike_clamp_device(rpf_ctx *ctx, const rpf_desc *desc, double *d_colour, double threshold, double *row_sums_out,
+                               rpf_spike_stats *stats_out, void *stream);
+int32_t rpf_colour_add_device(rpf_ctx *ctx, const rpf_desc *desc, double *d_colour, const double *delta, void *stream);
+
+/* The fold every path uses: energy_out[k] = row_sums[0][k] + row_sums[1][k] + ... in row order, delta_out[k] = energy_out[k] /
+ * (double)n_samples.  row_sums: [n_rows][3]; n_samples: the number of samples of those rows, rows * W * S.  Needs no context
+ * and no device.  RPF_E_BADARG for a NULL pointer or a non-positive count. */
+int32_t rpf_spike_delta(const double *row_sums, int64_t n_rows, int64_t n_samples, double *energy_out, double *delta_out);
 
 #ifdef __cplusplus
 }

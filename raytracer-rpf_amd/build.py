@@ -17,9 +17,10 @@ KERNEL_TUS += ["rpf_generic.hip"]  # the layout-generic kernel pair (RPF_FLAG_GE
 KERNEL_TUS += ["rpf_generic_packed.hip"]  # ... its count pass and packed kernels for N <= 64 (RPF_FLAG_GENERIC_PACKED)
 KERNEL_TUS += ["rpf_generic_wave.hip"]  # ... and its one-wave kernels for 64 < N <= 832 (RPF_FLAG_GENERIC_WAVE)
 KERNEL_TUS += ["rpf_generic_wide.hip"]  # the wide layout-generic kernel: 65535 < box*box*S <= 262144 (RPF_FLAG_WIDE_NBHD)
+KERNEL_TUS += ["rpf_spike.hip"]  # the spike pass after the last filter pass: clamp, row sums, energy add (RPF_FLAG_SPIKE_CLAMP)
 KERNEL_TUS += ["rpf_generic_wide_count.hip"]  # ... and the count pass that deals a wide pass by size class (RPF_FLAG_WIDE_CLASSES)
-# the C ABI (host code only; rpf_api.h is what they share): context, validation, routes and pass loops | film step | multi-GPU
-API_TUS = ["rpf_api.hip", "rpf_api_film.hip", "rpf_api_multi.hip"]
+# the C ABI (host code only; rpf_api.h is what they share): context, validation, routes and pass loops | film step | multi-GPU | spike pass
+API_TUS = ["rpf_api.hip", "rpf_api_film.hip", "rpf_api_multi.hip", "rpf_api_spike.hip"]
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in KERNEL_TUS + API_TUS]
 HEADERS = [os.path.join(_HERE, "csrc", "rpf_internal.h"), os.path.join(_HERE, "csrc", "rpf_api.h"), os.path.join(_HERE, "csrc", "rpf_xlane.h"),
            os.path.join(_HERE, "csrc", "rpf_filter_impl.inc"), os.path.join(_HERE, "csrc", "rpf_packed_impl.inc"),

@@ -97,6 +97,13 @@ struct rpf_ctx {
     rpf::DevBuf<float> d_film_out;              // host entry: tile rgb | tile weight | image rgb
     rpf::DevBuf<float> d_film_table;            // [16*16]
     rpf::DevBuf<unsigned long long> d_film_bad; // first sample whose pFilm lies outside its pixel
+    // the spike pass (RPF_FLAG_SPIKE_CLAMP; rpf_api_spike.hip)
+    double spike_threshold = 1.0;               // rpf_set_spike
+    int32_t spike_energy = 1;
+    rpf_spike_stats spike{};                    // of the most recent call (begin_call zeroes it)
+    rpf::DevBuf<double> d_spike_e;              // [rows][W][3] removed energy per pixel
+    rpf::DevBuf<double> d_spike_rows;           // [rows][3] its row sums
+    rpf::DevBuf<unsigned long long> d_spike_cnt; // [3] replaced samples, clamped pixels, skipped pixels
 };
 
 namespace rpf {
@@ -172,5 +179,12 @@ int32_t film_first_offender(rpf_ctx *ctx, const FilmParams &f, const float *d_pl
 std::string film_offender_message(const FilmParams &f, int x, int y, int smp, float pfilm_x, float pfilm_y);
 int32_t film_splat(rpf_ctx *ctx, const FilmParams &f, const rpf_film *film, const float *d_planes, const double *d_colour,
                    const float *d_ray_weight, float *d_tile_rgb, float *d_tile_w, float *d_image, hipStream_t s);
+
+// defined in rpf_api_spike.hip, where each is described; the multi-GPU driver runs the two halves on every slab
+int32_t spike_check_params(double threshold, int32_t preserve_energy, std::string &why);
+int32_t spike_clamp(rpf_ctx *ctx, const rpf_desc *d, double *d_colour, double threshold, double *row_sums, rpf_spike_stats *stats,
+                    hipStream_t s);
+int32_t spike_add(rpf_ctx *ctx, const rpf_desc *d, double *d_colour, const double delta[3], hipStream_t s);
+int32_t spike_pass(rpf_ctx *ctx, const rpf_desc *d, double *d_colour, hipStream_t s);
 
 } // namespace rpf

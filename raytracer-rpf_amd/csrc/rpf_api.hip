@@ -747,6 +747,7 @@ int32_t begin_call(rpf_ctx *ctx, hipStream_t s) {
     ctx->bin_valid = false;
     ctx->counters = rpf_counters{};
     ctx->counters.first_bad_pixel = -1;
+    ctx->spike = rpf_spike_stats{}; // applied = 0 until this call's spike pass has run
     return RPF_OK;
 }
 
@@ -897,6 +898,9 @@ int32_t run_passes(rpf_ctx *ctx, const rpf_desc *d, const void *d_planes, double
     }
     c.filter_kernel_ms = ms_filter;
     c.stats_kernel_ms = ms_stats;
+    // the spike pass: after the last pass, before every reduce / download / film step of the callers; it runs whatever
+    // finish_counters is about to say (RPF_E_NONFINITE included)
+    if ((d->flags & RPF_FLAG_SPIKE_CLAMP) && (st = spike_pass(ctx, d, d_colour, s))) return st;
     return finish_counters(ctx, d, d->n_box, s);
 }
 
@@ -1202,7 +1206,8 @@ int32_t rpf_filter_ex(rpf_ctx *ctx, const rpf_desc *d, const void *planes, const
         if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
         return a.type == hipMemoryTypeHost;
     };
-    if (!(d->flags & (RPF_FLAG_TIMING | RPF_FLAG_NO_OVERLAP)) && !colour64_in && !colour64_out && pinned(planes) &&
+    // (RPF_FLAG_SPIKE_CLAMP: no band may leave before delta is known)
+    if (!(d->flags & (RPF_FLAG_TIMING | RPF_FLAG_NO_OVERLAP | RPF_FLAG_SPIKE_CLAMP)) && !colour64_in && !colour64_out && pinned(planes) &&
         pinned(ray_weight) && pinned(sample_rgb_out) && pinned(pixel_rgb_out))
         return run_host_pipeline(ctx, d, planes, ray_weight, sample_rgb_out, pixel_rgb_out);
     // serial variant (per-kernel event timing needs it): upload, passes, download
@@ -1266,6 +1271,9 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *d, int32_t box, cons
     int32_t st = enter(ctx, d, false);
     if (st) return st;
     if (!planes || !colour_out) return fail(ctx, RPF_E_BADARG, "NULL pointer");
+    if (d->flags & RPF_FLAG_SPIKE_CLAMP)
+        return fail(ctx, RPF_E_UNSUPPORTED, "RPF_FLAG_SPIKE_CLAMP with rpf_filter_pass_debug: the spike pass follows the last pass of "
+                                            "a whole call (rpf_filter / _ex / _device / _film); this entry point returns one pass's raw colours");
     hipStream_t s = ctx->stream;
     const size_t ps = (size_t)d->W * d->H * d->S, HW = (size_t)d->W * d->H;
     const SampleLayout lay = layout_of(d);

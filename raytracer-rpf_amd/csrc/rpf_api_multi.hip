@@ -12,6 +12,7 @@
 // its own.  One planner (plan_halo = rpf_multi_halo_plan) gives the slabs and every halo copy.
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstring>
 #include <string>
 #include <thread>
@@ -26,6 +27,9 @@ struct rpf_multi {
     std::vector<int> dev;
     std::string err;
     rpf_counters counters{};
+    double spike_threshold = 1.0; // rpf_multi_set_spike
+    int32_t spike_energy = 1;
+    rpf_spike_stats spike{};      // the spike pass of the most recent call, merged over the slabs
 };
 
 namespace {
@@ -72,6 +76,7 @@ struct MFilm {
 int32_t multi_run(rpf_multi *m, const rpf_desc *d, const void *planes_v, const float *ray_weight, float *sample_rgb_out,
                   float *pixel_rgb_out, const MFilm *mf) {
     if (!m || m->ctx.empty()) return RPF_E_BADARG;
+    m->spike = rpf_spike_stats{};
     {
         const int32_t st = validate(m->ctx[0], d, true);
         if (st != RPF_OK) return mfail(m, st, m->ctx[0]->err);
@@ -237,6 +242,43 @@ int32_t multi_run(rpf_multi *m, const rpf_desc *d, const void *planes_v, const f
         for (int g = 0; g < G; ++g) { mx = std::max(mx, ms[g]); launches += nl[g]; std::swap(cin[g], cout[g]); }
         ms_filter += mx;
     }
+    // ---- the spike pass (RPF_FLAG_SPIKE_CLAMP): every slab clamps the rows it owns, the host concatenates the row sums in
+    // image-row order and folds them with the one-context path's function, every slab adds delta to its owned rows; the same
+    // chains in the same order as one context, so the same bits.  Only then the film step's halo refresh below.
+    m->spike = rpf_spike_stats{};
+    if (d->flags & RPF_FLAG_SPIKE_CLAMP) {
+        const bool timing = (d->flags & RPF_FLAG_TIMING) != 0;
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<double> row_sums((size_t)H * 3);
+        std::vector<rpf_spike_stats> ss(G);
+        st = per_slab([&](int g) -> int32_t {
+            rpf_ctx *ctx = m->ctx[g];
+            HIP_TRY(hipSetDevice(ctx->device));
+            return spike_clamp(ctx, &sd[g], cin[g], m->spike_threshold, row_sums.data() + (size_t)sl[g].a * 3, &ss[g], ctx->stream);
+        });
+        if (st != RPF_OK) return st;
+        rpf_spike_stats tot_s{};
+        tot_s.applied = 1;
+        for (int g = 0; g < G; ++g) {
+            tot_s.spike_samples += ss[g].spike_samples;
+            tot_s.spike_pixels += ss[g].spike_pixels;
+            tot_s.skipped_pixels += ss[g].skipped_pixels;
+        }
+        (void)rpf_spike_delta(row_sums.data(), H, (int64_t)H * W * S, tot_s.energy, tot_s.delta);
+        if (m->spike_energy) {
+            st = per_slab([&](int g) -> int32_t {
+                rpf_ctx *ctx = m->ctx[g];
+                HIP_TRY(hipSetDevice(ctx->device));
+                int32_t e;
+                if ((e = spike_add(ctx, &sd[g], cin[g], tot_s.delta, ctx->stream))) return e;
+                HIP_TRY(hipStreamSynchronize(ctx->stream)); // the film step's refresh reads these rows from another slab's stream
+                return RPF_OK;
+            });
+            if (st != RPF_OK) return st;
+        }
+        if (timing) tot_s.spike_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        m->spike = tot_s;
+    }
     // the film step reads the neighbours' FILTERED colours in its halo rows (the refresh moves `depth` >= fimg.hy rows)
     if (film_out && G > 1 && (st = refresh()) != RPF_OK) return st;
 
@@ -353,6 +395,22 @@ int32_t rpf_multi_set_option(rpf_multi *m, const char *name, int64_t value) {
 int32_t rpf_multi_query_counters(rpf_multi *m, rpf_counters *out) {
     if (!m || !out) return RPF_E_BADARG;
     *out = m->counters;
+    return RPF_OK;
+}
+
+int32_t rpf_multi_set_spike(rpf_multi *m, double threshold, int32_t preserve_energy) {
+    if (!m) return RPF_E_BADARG;
+    std::string why;
+    const int32_t st = spike_check_params(threshold, preserve_energy, why);
+    if (st) return mfail(m, st, why);
+    m->spike_threshold = threshold;
+    m->spike_energy = preserve_energy;
+    return RPF_OK;
+}
+
+int32_t rpf_multi_query_spike(rpf_multi *m, rpf_spike_stats *out) {
+    if (!m || !out) return RPF_E_BADARG;
+    *out = m->spike;
     return RPF_OK;
 }
 

@@ -277,6 +277,23 @@ hipError_t launch_wide_count(const PassParams &p, uint32_t *pool, uint64_t capac
                              int32_t *nan_flag, hipStream_t s);
 } // namespace generic
 
+// ---- the spike pass (rpf_spike.hip, RPF_FLAG_SPIKE_CLAMP) -----------------------------------------------
+constexpr int kSpikeTileMaxS = 1024;       // above it 24 * S bytes per pixel leave no useful tile: one thread per pixel on global memory
+constexpr int kSpikeLdsBudget = 64 * 1024; // LDS of one tile (one wavefront): two pixels at S = 1024, 64 pixels up to S = 41
+// LDS image of the clamp kernel's tile, [3][tile][stride] doubles; tile == 0: the direct form (S > kSpikeTileMaxS)
+struct SpikeCarve {
+    uint32_t stride, tile, bytes;
+};
+SpikeCarve spike_carve(int S);
+// rows [row_begin, row_end) of the three fp64 planes [3][H][W][S]: spikes replaced in place, e [(row_end-row_begin)*W][3] the
+// per-pixel removed energy (every entry written), counts [3] += replaced samples, clamped pixels, skipped pixels
+hipError_t launch_spike_clamp(double *colour, int W, int H, int S, int row_begin, int row_end, double t, double *e,
+                              unsigned long long *counts, hipStream_t s);
+// row_sums [rows][3] = the x chain over e [rows][W][3]
+hipError_t launch_spike_row_sums(const double *e, int rows, int W, double *row_sums, hipStream_t s);
+// c += delta[k] for every sample of rows [row_begin, row_end) of plane k
+hipError_t launch_spike_add(double *colour, int W, int H, int S, int row_begin, int row_end, const double delta[3], hipStream_t s);
+
 int max_lds_per_block();
 hipError_t launch_udiv_selftest(uint64_t n, uint64_t seed, int mode, unsigned long long *d_mismatch, hipStream_t s);
 

@@ -35,6 +35,10 @@ FLAG_GENERIC_FAST = 256
 # list and every pass on the fused kernels stay fp64, same bits; refused without both flags (and, with FLAG_FAST_WEIGHTS, by one of
 # that flag's refusals)
 FLAG_STREAM_FAST = 512
+# after the last pass of the call: the spike pass on the fp64 colours (spike clamp + energy preservation, DESIGN.md section 12;
+# Context.set_spike / spike_stats), before the reduce, every download and the film step; independent of every route flag;
+# filter_pass_debug refuses it
+FLAG_SPIKE_CLAMP = 1024
 FLAG_WIDE_NBHD = 64  # passes with 65535 < box*box*S <= 262144 on the wide layout-generic kernel (route 6); max_nbhd() tells the bound
 MAX_NDIM = 40     # the layout-generic kernels take 5 + n_random + n_feat up to this
 PLANES_F32, PLANES_F16 = 0, 1
@@ -46,7 +50,8 @@ EXPORTS = ["rpf_version", "rpf_status_string", "rpf_create", "rpf_destroy", "rpf
            "rpf_multi_last_error", "rpf_multi_device_count", "rpf_multi_set_option", "rpf_multi_filter",
            "rpf_multi_query_counters", "rpf_query_nbhd", "rpf_query_route", "rpf_film_filter_table", "rpf_filter_film",
            "rpf_film_splat_device", "rpf_film_window", "rpf_multi_halo_plan", "rpf_multi_filter_film", "rpf_layout_kernels",
-           "rpf_max_nbhd", "rpf_wide_table"]
+           "rpf_max_nbhd", "rpf_wide_table", "rpf_set_spike", "rpf_multi_set_spike", "rpf_query_spike", "rpf_multi_query_spike",
+           "rpf_spike_clamp_device", "rpf_colour_add_device", "rpf_spike_delta"]
 
 # the film step: pbrt's PixelFilters (include/rpf_hip.h, rpf_film)
 PIXFILTER_BOX, PIXFILTER_TRIANGLE, PIXFILTER_GAUSSIAN, PIXFILTER_MITCHELL, PIXFILTER_SINC = range(5)
@@ -81,6 +86,24 @@ class Counters(C.Structure):
                 ("stats_kernel_ms", C.c_float), ("device_total_ms", C.c_float), ("h2d_ms", C.c_float),
                 ("d2h_ms", C.c_float), ("filter_kernel_launches", C.c_int32), ("options_active", C.c_int32),
                 ("redo_pixels", C.c_int32)]
+
+
+class SpikeStats(C.Structure):
+    """rpf_spike_stats: the spike pass of the most recent call (applied = 0 and zeros when FLAG_SPIKE_CLAMP was off)"""
+    _fields_ = [("spike_samples", C.c_int64), ("spike_pixels", C.c_int64), ("skipped_pixels", C.c_int64),
+                ("energy", C.c_double * 3), ("delta", C.c_double * 3), ("spike_ms", C.c_float), ("applied", C.c_int32)]
+
+
+def spike_delta(row_sums, n_samples):
+    """rpf_spike_delta (no GPU needed): (energy[3], delta[3]) -- the serial fold of row_sums [n_rows][3] in row order and its
+    quotient by n_samples = rows * W * S; the one fold Context and MultiContext use"""
+    rs = np.ascontiguousarray(row_sums, np.float64)
+    assert rs.ndim == 2 and rs.shape[1] == 3, rs.shape
+    e, d = np.empty(3), np.empty(3)
+    st = load().rpf_spike_delta(_p(rs), rs.shape[0], int(n_samples), _p(e), _p(d))
+    if st != OK:
+        raise RpfError(st, "rpf_spike_delta(n_rows=%r, n_samples=%r): a non-positive count" % (rs.shape[0], n_samples))
+    return e, d
 
 
 class Film(C.Structure):
@@ -248,6 +271,15 @@ def load():
         if hasattr(L, "rpf_max_nbhd"):  # (absent from a build of before the wide route, loaded through RPF_HIP_LIB)
             L.rpf_max_nbhd.argtypes = [C.POINTER(Desc), C.POINTER(C.c_int32)]
             L.rpf_wide_table.argtypes = [C.c_int32, C.c_void_p]
+        if hasattr(L, "rpf_set_spike"):  # (absent from a build of before the spike pass, loaded through RPF_HIP_LIB)
+            L.rpf_set_spike.argtypes = [C.c_void_p, C.c_double, C.c_int32]
+            L.rpf_multi_set_spike.argtypes = [C.c_void_p, C.c_double, C.c_int32]
+            L.rpf_query_spike.argtypes = [C.c_void_p, C.POINTER(SpikeStats)]
+            L.rpf_multi_query_spike.argtypes = [C.c_void_p, C.POINTER(SpikeStats)]
+            L.rpf_spike_clamp_device.argtypes = [C.c_void_p, C.POINTER(Desc), C.c_void_p, C.c_double, C.c_void_p,
+                                                 C.POINTER(SpikeStats), C.c_void_p]
+            L.rpf_colour_add_device.argtypes = [C.c_void_p, C.POINTER(Desc), C.c_void_p, C.c_void_p, C.c_void_p]
+            L.rpf_spike_delta.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
         L.rpf_host_alloc.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
         L.rpf_host_free.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
@@ -334,6 +366,31 @@ class Context:
         r = C.c_int32(-1)
         self._check(self._L.rpf_query_route(self._h, C.byref(r)))
         return r.value
+
+    # ---- the spike pass (FLAG_SPIKE_CLAMP) --------------------------------------------------------------
+    def set_spike(self, threshold=1.0, preserve_energy=True):
+        """rpf_set_spike: threshold in standard deviations (finite, > 0), preserve_energy False / True (0 / 1)"""
+        self._check(self._L.rpf_set_spike(self._h, float(threshold), int(preserve_energy)))
+
+    def spike_stats(self):
+        """rpf_query_spike: SpikeStats of the most recent call"""
+        s = SpikeStats()
+        self._check(self._L.rpf_query_spike(self._h, C.byref(s)))
+        return s
+
+    def spike_clamp_device(self, desc, d_colour, threshold=1.0, stream=None):
+        """rpf_spike_clamp_device: the clamp half on rows [row_begin, row_end) of device colours (raw pointer, 3 fp64 planes);
+        returns (row_sums float64 [rows][3] on the host, SpikeStats of these rows)"""
+        rows = np.empty((max(desc.row_end - desc.row_begin, 0), 3))
+        s = SpikeStats()
+        self._check(self._L.rpf_spike_clamp_device(self._h, C.byref(desc), d_colour, float(threshold), _p(rows), C.byref(s), stream))
+        return rows, s
+
+    def colour_add_device(self, desc, d_colour, delta, stream=None):
+        """rpf_colour_add_device: c += delta[k] on rows [row_begin, row_end) of device colours; delta: three host doubles"""
+        dl = np.ascontiguousarray(delta, np.float64)
+        assert dl.shape == (3,), dl.shape
+        self._check(self._L.rpf_colour_add_device(self._h, C.byref(desc), d_colour, _p(dl), stream))
 
     # ---- host-buffer entry points ------------------------------------------------------------------
     def host_empty(self, shape, dtype=np.float32):
@@ -478,6 +535,18 @@ class MultiContext:
         c = Counters()
         self._L.rpf_multi_query_counters(self._h, C.byref(c))
         return c
+
+    def set_spike(self, threshold=1.0, preserve_energy=True):
+        """rpf_multi_set_spike: the spike pass's parameters for every slab (Context.set_spike)"""
+        st = self._L.rpf_multi_set_spike(self._h, float(threshold), int(preserve_energy))
+        if st != OK:
+            raise RpfError(st, self._L.rpf_multi_last_error(self._h).decode())
+
+    def spike_stats(self):
+        """rpf_multi_query_spike: SpikeStats of the most recent call, merged over the slabs"""
+        s = SpikeStats()
+        self._L.rpf_multi_query_spike(self._h, C.byref(s))
+        return s
 
     def filter(self, planes, desc, ray_weight=None, allow_nonfinite=False):
         nd, _, _, pdt = dims(desc)

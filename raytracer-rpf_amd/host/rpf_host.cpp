@@ -2,6 +2,7 @@
 #include "rpf_host.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 
@@ -51,6 +52,15 @@ bool PlaneFilm::complete() const {
     return !count_.empty();
 }
 
+int RPFFilter::spike_flag(bool last_pass) {
+    if (!spikeclamp || !last_pass) return 0;
+    if (rpf_set_spike(ctx_, spikethreshold, spikeenergy ? 1 : 0) != RPF_OK) {
+        err_ = std::string("RPF_E_BADARG: ") + rpf_last_error(ctx_);
+        return -1;
+    }
+    return RPF_FLAG_SPIKE_CLAMP;
+}
+
 int RPFFilter::plane_desc(const PlaneFilm &film, const std::vector<int> &boxes, rpf_desc *out) {
     if (!ctx_) return RPF_E_NODEVICE;
     if (!film.ok()) { err_ = "PlaneFilm allocation failed"; return RPF_E_NOMEM; }
@@ -64,6 +74,9 @@ int RPFFilter::plane_desc(const PlaneFilm &film, const std::vector<int> &boxes, 
     for (size_t i = 0; i < boxes.size(); ++i) d.box_sizes[i] = boxes[i];
     d.beta_map = beta_map; d.degenerate_policy = degenerate_policy;
     d.eps = eps; d.sigma_seed = sigma_seed;
+    const int sf = spike_flag(true); // these calls run the whole box list: the spike pass follows its last entry
+    if (sf < 0) return RPF_E_BADARG;
+    d.flags |= sf;
     return RPF_OK;
 }
 
@@ -98,15 +111,15 @@ int RPFFilter::FilterAndReduce(PlaneFilm &film, const std::vector<int> &boxes, s
     return st;
 }
 
-int RPFFilter::ApplyRPFFilter(SamplingFilm &film, const int /*tileSize*/, int box_size) {
-    return run(film, std::vector<int>{box_size}, nullptr);
+int RPFFilter::ApplyRPFFilter(SamplingFilm &film, const int /*tileSize*/, int box_size, bool last_pass) {
+    return run(film, std::vector<int>{box_size}, nullptr, last_pass);
 }
 
 int RPFFilter::FilterAndReduce(SamplingFilm &film, const std::vector<int> &boxes, std::vector<float> *pixel_rgb) {
-    return run(film, boxes, pixel_rgb);
+    return run(film, boxes, pixel_rgb, true);
 }
 
-int RPFFilter::run(SamplingFilm &film, const std::vector<int> &boxes, std::vector<float> *pixel_rgb) {
+int RPFFilter::run(SamplingFilm &film, const std::vector<int> &boxes, std::vector<float> *pixel_rgb, bool spike) {
     if (!ctx_) return RPF_E_NODEVICE; // constructor failed; err_ says why.  There is no CPU fallback.
     const int W = film.getWidth(), H = film.getHeight();
     if (W <= 0 || H <= 0) { err_ = "empty SamplingFilm"; return RPF_E_BADARG; }
@@ -153,6 +166,9 @@ int RPFFilter::run(SamplingFilm &film, const std::vector<int> &boxes, std::vecto
     for (size_t i = 0; i < boxes.size(); ++i) d.box_sizes[i] = boxes[i];
     d.beta_map = beta_map; d.degenerate_policy = degenerate_policy;
     d.eps = eps; d.sigma_seed = sigma_seed;
+    const int sf = spike_flag(spike);
+    if (sf < 0) return RPF_E_BADARG;
+    d.flags |= sf;
     if (pixel_rgb) pixel_rgb->resize((size_t)W * H * 3);
     const int32_t st = rpf_filter_ex(ctx_, &d, planes_.data(), col64_.data(), rayw_.data(), nullptr,
                                      pixel_rgb ? pixel_rgb->data() : nullptr, col64_.data());
@@ -190,7 +206,32 @@ std::string RPFParams::Parse(const int *boxsizes, int n_boxsizes, const char *ba
     return std::string();
 }
 
+std::string RPFParams::ParseSpike(bool spikeclamp, double spikethreshold, bool spikeenergy, RPFParams *inout) {
+    if (!std::isfinite(spikethreshold) || !(spikethreshold > 0.0))
+        return "\"spikethreshold\" must be a finite number of standard deviations > 0";
+    if (inout) {
+        inout->spikeclamp = spikeclamp;
+        inout->spikethreshold = spikethreshold;
+        inout->spikeenergy = spikeenergy;
+    }
+    return std::string();
+}
+
 } // namespace rpf_host
+
+extern "C" int32_t rpf_host_parse_spike_params(int32_t spikeclamp, double spikethreshold, int32_t spikeenergy, int32_t *clamp_out,
+                                               double *threshold_out, int32_t *energy_out, char *err, int32_t err_len) {
+    rpf_host::RPFParams prm;
+    const std::string e = rpf_host::RPFParams::ParseSpike(spikeclamp != 0, spikethreshold, spikeenergy != 0, &prm);
+    if (!e.empty()) {
+        if (err && err_len > 0) std::snprintf(err, err_len, "%s", e.c_str());
+        return -1;
+    }
+    if (clamp_out) *clamp_out = prm.spikeclamp ? 1 : 0;
+    if (threshold_out) *threshold_out = prm.spikethreshold;
+    if (energy_out) *energy_out = prm.spikeenergy ? 1 : 0;
+    return 0;
+}
 
 extern "C" int32_t rpf_host_parse_params(const int32_t *boxsizes, int32_t n_boxsizes, const char *backend, int32_t *boxes_out,
                                          int32_t *n_out, int32_t *backend_out, char *err, int32_t err_len) {
@@ -225,12 +266,14 @@ extern "C" int32_t rpf_host_apply_filter_aos(double *aos, const float *ray_weigh
     RPFFilter f(device);
     f.beta_map = beta_map & 0xff;
     f.degenerate_policy = policy;
+    f.spikeclamp = (beta_map & RPF_HOST_SPIKE_CLAMP) != 0; // default threshold and energy preservation
     std::vector<float> pix;
     int st = RPF_OK;
     if (beta_map & RPF_HOST_PER_BOX_CALLS) {
-        // the reference's own call shape (rpf.cpp:767-775): one ApplyRPFFilter per box size on the same film
-        for (int i = 0; i < n_box && (st == RPF_OK); ++i) st = f.ApplyRPFFilter(film, 16, box_sizes[i]);
-    } else if (n_box == 1 && !pixel_rgb_out) st = f.ApplyRPFFilter(film, 16, box_sizes[0]);
+        // the reference's own call shape (rpf.cpp:767-775): one ApplyRPFFilter per box size on the same film; the spike pass
+        // follows the last of them only
+        for (int i = 0; i < n_box && (st == RPF_OK); ++i) st = f.ApplyRPFFilter(film, 16, box_sizes[i], i == n_box - 1);
+    } else if (n_box == 1 && !pixel_rgb_out) st = f.ApplyRPFFilter(film, 16, box_sizes[0], true);
     else st = f.FilterAndReduce(film, std::vector<int>(box_sizes, box_sizes + n_box), pixel_rgb_out ? &pix : nullptr);
     if (err && err_len > 0) std::snprintf(err, err_len, "%s", f.last_error().c_str());
     if (st != RPF_OK && st != RPF_E_NONFINITE) return st;

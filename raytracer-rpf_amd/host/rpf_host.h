@@ -51,11 +51,22 @@ class RPFFilter;
 //                                   (nothing of this library runs -- there is no CPU path inside it)
 // Parse() takes what pbrt's ParamSet hands out -- FindInt("boxsizes", &n) and FindOneString("backend", "hip") -- and
 // returns "" or a message for pbrt's Error().
+// Three more keys switch on the spike pass after the last filter pass (RPF_FLAG_SPIKE_CLAMP, DESIGN.md section 12: the HDR clamp
+// and energy preservation the reference leaves commented out, rpf.cpp:707-713); a file without them renders exactly as before:
+//     "bool spikeclamp"      "false"   run the spike pass after the last box size
+//     "float spikethreshold" 1         a sample further than this many standard deviations from its pixel's mean is replaced
+//     "bool spikeenergy"     "true"    hand the removed energy back to every sample as one constant per channel
+// ParseSpike() takes FindOneBool("spikeclamp", false), FindOneFloat("spikethreshold", 1.f), FindOneBool("spikeenergy", true)
+// and fills the three fields of *inout (the others are left alone); "" or a message for pbrt's Error().
 struct RPFParams {
     enum Backend { HIP = 0, REFERENCE = 1 };
     std::vector<int> boxsizes{7};
     Backend backend = HIP;
+    bool spikeclamp = false;
+    double spikethreshold = 1.0;
+    bool spikeenergy = true;
     static std::string Parse(const int *boxsizes, int n_boxsizes, const char *backend, RPFParams *out);
+    static std::string ParseSpike(bool spikeclamp, double spikethreshold, bool spikeenergy, RPFParams *inout);
 };
 
 // Page-locked array handed out by the filter's context (rpf_host_alloc); grow-only, released with its owner.
@@ -123,13 +134,20 @@ class RPFFilter {
     int beta_map = RPF_BETA_REF_GCC11_O3;
     int degenerate_policy = RPF_DEGEN_REF_ABORT;
     double eps = 1e-10, sigma_seed = 0.002;
+    // the spike pass (RPFParams::spikeclamp / spikethreshold / spikeenergy; SetSpike copies them): off by default.  It follows
+    // the LAST pass: FilterAndReduce and FilterAndSplat run it after their last box size; a caller who keeps the reference's
+    // call shape, one ApplyRPFFilter per box size, passes last_pass = true on the last call only.
+    bool spikeclamp = false;
+    double spikethreshold = 1.0;
+    bool spikeenergy = true;
+    void SetSpike(const RPFParams &p) { spikeclamp = p.spikeclamp; spikethreshold = p.spikethreshold; spikeenergy = p.spikeenergy; }
 
     // Drop-in for RPFIntegrator::ApplyRPFFilter (rpf.cpp:497-733): on return the colour columns (data[2..4]) of
     // every sample hold the filtered colours, everything else is untouched (rpf.cpp:715, 732).  tileSize is
     // accepted for signature compatibility (the GPU path does not tile on the host).  Returns an rpf_status;
     // where the reference prints "PRIME ERROR" and calls exit(1) (rpf.cpp:702-705) this returns
     // RPF_E_NONFINITE and leaves the NaNs in place for the caller to report.
-    int ApplyRPFFilter(SamplingFilm &samplingFilm, const int tileSize, int box_size);
+    int ApplyRPFFilter(SamplingFilm &samplingFilm, const int tileSize, int box_size, bool last_pass = false);
 
     // The whole post-sampling part of Render(): every box size (rpf.cpp:767-775) and the film reduction with
     // the default box reconstruction filter (rpf.cpp:779-794): pixel_rgb[(y*W+x)*3+c], may be NULL.
@@ -150,7 +168,8 @@ class RPFFilter {
     const rpf_counters &counters() const { return counters_; }
 
   private:
-    int run(SamplingFilm &film, const std::vector<int> &boxes, std::vector<float> *pixel_rgb);
+    int run(SamplingFilm &film, const std::vector<int> &boxes, std::vector<float> *pixel_rgb, bool spike);
+    int spike_flag(bool last_pass); // RPF_FLAG_SPIKE_CLAMP (the parameters handed to the context) or 0; < 0: refused, err_ says why
     int plane_desc(const PlaneFilm &film, const std::vector<int> &boxes, rpf_desc *d); // checks film and boxes
     rpf_ctx *ctx_ = nullptr;
     std::string err_;
@@ -164,6 +183,8 @@ class RPFFilter {
 // OR-ed into the beta_map argument of rpf_host_apply_filter_aos: run the box list as the reference's Render loop does,
 // one RPFFilter::ApplyRPFFilter(film, 16, box) call per box size on the same film (rpf.cpp:767-775)
 #define RPF_HOST_PER_BOX_CALLS 0x100
+// OR-ed into the same argument: RPFFilter::spikeclamp = true (the spike pass after the last box size, default parameters)
+#define RPF_HOST_SPIKE_CLAMP 0x200
 
 extern "C" {
 // test / FFI doorway: aos is double [W][H][S][19] in SamplingFilm order, ray_weight float [W][H][S] (may be NULL);
@@ -176,6 +197,9 @@ int32_t rpf_host_apply_filter_aos(double *aos, const float *ray_weight, int32_t 
 // RPFParams::Parse through a C doorway: boxes_out[RPF_MAX_BOXES]; returns 0 or -1 with the message in err
 int32_t rpf_host_parse_params(const int32_t *boxsizes, int32_t n_boxsizes, const char *backend, int32_t *boxes_out,
                               int32_t *n_out, int32_t *backend_out, char *err, int32_t err_len);
+// RPFParams::ParseSpike through a C doorway; returns 0 or -1 with the message in err
+int32_t rpf_host_parse_spike_params(int32_t spikeclamp, double spikethreshold, int32_t spikeenergy, int32_t *clamp_out,
+                                    double *threshold_out, int32_t *energy_out, char *err, int32_t err_len);
 // PlaneFilm(x0, y0) filled as above (sample (x, y) of aos lands in raster pixel (x0 + x, y0 + y)), then
 // RPFFilter::FilterAndSplat with `film` (its sample origin is replaced by (x0, y0)); outputs as rpf_filter_film's.
 int32_t rpf_host_planefilm_film(const double *aos, const float *ray_weight, int32_t W, int32_t H, int32_t S, int32_t x0,
