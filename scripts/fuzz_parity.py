@@ -7,16 +7,21 @@ flat-quad pixels (zero-variance normals: the stage-1a shortcut, the prelist, the
 on the one-wave route (option packed = 0) with bit-identical stage outputs demanded between the two routes; the packed run
 takes the probe's route, the fused route and the count-first route in turn (option count_first).  72 spp (flat pixels whose
 N = S fits no packed class), and one case in three with a NaN or +-inf sample, a +-inf pixel or +inf and -inf in one pixel.
+One 19-dim case in four is mapped to scene-scale magnitudes by a profile of tests/scene_scale.py (far at its three scales,
+far_n, neg_big, hdr in turn; chosen from the case number, so every other case draws what it always drew).
 usage: fuzz_parity.py [cases] [seed]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle")); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import torch  # noqa: F401
 import rpf_pkg
 rpf_pkg.load()
 from raytracer_rpf_amd import feature_buffer as fb, hip
 import pyoracle as O
+import scene_scale as SS
+
+PROFILES = [("far", s) for s in SS.SCALES] + [("far_n", None), ("neg_big", None), ("hdr", None)]
 
 O.build()
 cases = int(sys.argv[1]) if len(sys.argv) > 1 else 40
@@ -43,6 +48,9 @@ for i in range(cases):
     if os.environ.get("FUZZ_ONLY") and int(os.environ["FUZZ_ONLY"]) != i:
         continue
     planes = fb.synth_planes(W, H, S, seed=seed, sigma_f=sf, sigma_c=0.01, mode=mode, dtype="f16" if wide else "f32", flat_frac=flat, **L)
+    profile, scale = PROFILES[(i // 4) % len(PROFILES)] if i % 4 == 3 and not wide else (None, None)
+    if profile:
+        planes = np.array(SS.apply(planes, **dict(SS.PROFILES[profile], **({"scale": scale} if scale else {})))[0])
     f0 = 9 if wide else 7
     if inject == 1:
         planes[f0 + ik, iy, ix, isamp] = np.nan
@@ -96,8 +104,9 @@ for i in range(cases):
                 for k in ("nbhd_size", "alpha", "beta", "wrc"):
                     print(k, "gpu", got[k][y, x], "oracle", want[k][y, x])
                 print("mi diff max", np.nanmax(np.abs(got["mi"][y, x] - want["mi"][y, x])))
-    print("%3d %s  %2dx%2dx%2d box %2d %s %-9s sf %-6g flat %-4g policy %d beta %d  maxN %4d small %3d%% bad %d  %s" % (
-        i, "ok  " if ok else "FAIL", W, H, S, box, "d27" if wide else "d19", mode, sf, flat, policy, beta, int(want["nbhd_size"].max()),
+    print("%3d %s  %2dx%2dx%2d box %2d %s %-9s sf %-6g flat %-4g policy %d beta %d %-12s maxN %4d small %3d%% bad %d  %s" % (
+        i, "ok  " if ok else "FAIL", W, H, S, box, "d27" if wide else "d19", mode, sf, flat, policy, beta,
+        "-" if not profile else profile + ("" if not scale else " %g" % scale), int(want["nbhd_size"].max()),
         int(100 * (want["nbhd_size"] <= 64).mean()), want["nonfinite_pixels"], why), flush=True)
 print("fuzz_parity: %d cases, %d failures" % (cases, fails))
 sys.exit(1 if fails else 0)

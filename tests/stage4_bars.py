@@ -26,7 +26,10 @@ over the neighbourhood it enters:
   expanded      the fused kernels evaluate E = A_i + B_j + sum_k u_ik z_jk, which cancels between
                 A_i + B_j and the dot product: each of the nwt terms carries about 4 u cz_k (|z_ik| + |z_jk|)^2 <=
                 16 u cz_k max z^2, and z^2 < N for a sample of a population of N (no sample lies more than sqrt(N - 1)
-                standard deviations from its population's mean).
+                standard deviations from its population's mean).  That holds for the exact SD of the population.  An SD
+                taken from a variance E[x^2] - mean^2 that has cancelled (scene-scale magnitudes: tests/scene_scale.py) does
+                not have to obey it, so the bound on z^2 is an argument, z2max: by default N, on such frames the largest z^2
+                measured over the checked members from the oracle's mean and SD (tests/test_scene_scale_cpu.py).
                 The fused kernels also form z as (x - M) * (1 / SD), two roundings more than the division: a relative 2 u on
                 z_i and z_j moves cz_k (z_ik - z_jk)^2 by up to 4 u cz_k (|z_ik| + |z_jk|)^2, a second term of the same form.
                 It is not budgeted separately: z^2 < N is attained by one sample of a population at most (z is of order one
@@ -61,8 +64,9 @@ RESIDENT = 3136             # fused routes: neighbourhoods above it run on gener
 ROUTE_FORM = {0: "expanded", 1: "expanded", 2: "expanded", 3: "direct", 4: "direct", 5: "direct", 6: "direct", 7: "direct"}
 
 
-def delta(form, nwt, nmax, sigma_seed, box):
-    """relative error bound of the pair weights and their sums"""
+def delta(form, nwt, nmax, sigma_seed, box, z2max=None):
+    """relative error bound of the pair weights and their sums; z2max: a bound on z^2 over the checked members for the expanded
+    form (None: nmax, from z^2 < N)"""
     d = U * (MAX_EXPONENT * (nwt + 3) + 2 + nmax)
     if form == "direct":
         return d
@@ -72,12 +76,12 @@ def delta(form, nwt, nmax, sigma_seed, box):
     czmax = 1.0 / (2 * sigma_seed * sigma_seed)
     if sigma_p > 0:
         czmax = max(czmax, 1.0 / (2 * sigma_p * sigma_p))
-    return d + U * 16 * nwt * czmax * nmax
+    return d + U * 16 * nwt * czmax * (nmax if z2max is None else z2max)
 
 
-def sample_bar(form, n_feat, nmax, sigma_seed, box):
+def sample_bar(form, n_feat, nmax, sigma_seed, box, z2max=None):
     """the per-sample bar relative to cmax: |colour - restatement| <= sample_bar(...) * cmax"""
-    return 4 * delta(form, 5 + n_feat, int(nmax), sigma_seed, box)
+    return 4 * delta(form, 5 + n_feat, int(nmax), sigma_seed, box, z2max)
 
 
 def cmax_of(colour_in):
