@@ -45,6 +45,19 @@ struct DevBuf {
     }
 };
 
+// Which kernel route a pass took: what rpf_query_route returns (include/rpf_hip.h documents the values)
+enum Route : int {
+    kRouteNone = -1,         // no pass yet
+    kRouteFused = 0,         // filter_pixel_kernel runs stage 1b itself
+    kRouteCountFirst = 1,    // stage 1b as its own launch ahead of the fused and packed kernels
+    kRouteBinned = 2,        // size-binned (box*box*S > 512)
+    kRouteGeneric = 3,       // the layout-generic filter kernel, one launch
+    kRouteGenericPacked = 4, // ... with small neighbourhoods (N <= 64) on the packed layout-generic kernels
+    kRouteGenericWave = 5,   // ... and 64 < N <= 832 on the one-wave layout-generic kernels
+    kRouteWide = 6,          // the wide kernel, one launch
+    kRouteWideClasses = 7,   // a wide pass counted first and dealt by size class
+};
+
 } // namespace rpf
 
 struct rpf_ctx {
@@ -65,7 +78,7 @@ struct rpf_ctx {
     rpf::DevBuf<int32_t> d_status;              // [0] bad count [1] first bad
     rpf::DevBuf<unsigned long long> d_nred;     // [0] sum N [1] max N
     rpf::DevBuf<uint32_t> d_lists;              // size binning: [kNumClasses][H*W] pixel lists
-    int last_route = -1;                        // last pass: 1 = count first, 0 = fused, 2 = size-binned, 3 = layout-generic, 4 = layout-generic with small neighbourhoods packed, 5 = ... and 64 < N <= 832 on the one-wave kernels, 6 = the wide kernel, 7 = a wide pass dealt by size class (rpf_query_route)
+    int last_route = rpf::kRouteNone;           // the rpf::Route of the last pass (rpf_query_route)
     rpf::DevBuf<uint32_t> d_class_counts;       // [kNumClasses] list sizes + [2] the route probe's counts
     rpf::DevBuf<uint64_t> d_masks;              // size binning: stage-1b acceptance masks [H*W][stride]
     rpf::DevBuf<char> d_big_list;               // streaming kernel: member lists [slots][nmax] u32
@@ -156,7 +169,7 @@ struct PassSetup {
 };
 int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_planes, const double *col_in,
                    double *col_out, const rpf_debug *dbg_dev, PassSetup &out);
-int32_t launch_filter_binned(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches);
+int32_t route_pass(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches);
 
 int32_t begin_call(rpf_ctx *ctx, hipStream_t s);
 std::string nonfinite_message(int x, int y, long long count);

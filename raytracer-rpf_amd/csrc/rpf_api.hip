@@ -36,55 +36,64 @@ SampleLayout layout_of(const rpf_desc *d) {
     return l;
 }
 
+namespace {
+
+// One refusal of layout_kernels: a descriptor with every flag of `when` is refused with `msg` unless it has all of `all_of`, one of
+// `one_of` (0: nothing asked) and none of `none_of`.  The first failing row in this order answers.
+struct FlagRule {
+    uint32_t when, all_of, one_of, none_of;
+    const char *msg;
+};
+constexpr uint32_t kPackedRoute = RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED;
+constexpr FlagRule kFlagRules[] = {
+    {RPF_FLAG_WIDE_CLASSES, RPF_FLAG_WIDE_NBHD, 0, 0, "RPF_FLAG_WIDE_CLASSES without RPF_FLAG_WIDE_NBHD: the flag modifies the wide route"},
+    {RPF_FLAG_GENERIC_FAST, kPackedRoute, 0, 0, "RPF_FLAG_GENERIC_FAST without RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED: the flag modifies the packed layout-generic route"},
+    {RPF_FLAG_GENERIC_FAST, 0, 0, RPF_FLAG_FAST_WEIGHTS, "RPF_FLAG_GENERIC_FAST with RPF_FLAG_FAST_WEIGHTS: that flag selects the fused fp32 kernels of the 19-dim layout, this one the layout-generic ones"},
+    {RPF_FLAG_GENERIC_FAST, 0, 0, RPF_FLAG_WIDE_NBHD, "RPF_FLAG_GENERIC_FAST with RPF_FLAG_WIDE_NBHD: wide passes are fp64 throughout"},
+    {RPF_FLAG_STREAM_FAST, 0, RPF_FLAG_GENERIC | RPF_FLAG_WIDE_NBHD, 0, "RPF_FLAG_STREAM_FAST without RPF_FLAG_GENERIC or RPF_FLAG_WIDE_NBHD: the flag modifies the streaming and wide layout-generic kernels"},
+    {RPF_FLAG_WIDE_NBHD, 0, 0, RPF_FLAG_FAST_WEIGHTS, "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_WIDE_NBHD: the wide layout-generic kernel is fp64 throughout"},
+    {RPF_FLAG_GENERIC_WAVE, kPackedRoute, 0, 0, "RPF_FLAG_GENERIC_WAVE without RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED: the flag modifies the packed layout-generic route"},
+    {RPF_FLAG_GENERIC_WAVE, 0, 0, RPF_FLAG_FAST_WEIGHTS, "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_GENERIC_WAVE: the layout-generic kernels are fp64 throughout"},
+    {RPF_FLAG_GENERIC_PACKED, RPF_FLAG_GENERIC, 0, 0, "RPF_FLAG_GENERIC_PACKED without RPF_FLAG_GENERIC: the flag modifies the layout-generic route"},
+    {RPF_FLAG_GENERIC_PACKED, 0, 0, RPF_FLAG_FAST_WEIGHTS, "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_GENERIC_PACKED: the layout-generic kernels are fp64 throughout"},
+    {RPF_FLAG_GENERIC, 0, 0, RPF_FLAG_FAST_WEIGHTS, "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_GENERIC: the layout-generic kernels are fp64 throughout"},
+};
+
+// ... and, for flags no row refuses, the layout against the kernels they select: the refusal's text, or null
+const char *layout_refusal(const SampleLayout &lay, uint32_t flags) {
+    if (flags & RPF_FLAG_GENERIC)
+        return lay.generic_ok() ? nullptr
+                                : "sample layout: the layout-generic kernels take n_random >= 1, n_feat >= 1, 5 + n_random + n_feat <= "
+                                  "RPF_MAX_NDIM (40), fp32 or fp16 planes";
+    if (!lay.supported())
+        return "sample layout: kernels exist for n_random=2, n_feat=12, fp32 planes (the reference's 19 dims) and n_random=4, "
+               "n_feat=18, fp16 planes (27 dims); any other layout needs RPF_FLAG_GENERIC (the layout-generic kernels)";
+    // (launch_filter_w, rpf_filter_impl.inc: the FAST instantiations are built for the reference layout alone)
+    if ((flags & RPF_FLAG_FAST_WEIGHTS) && !lay.is_ref19())
+        return "RPF_FLAG_FAST_WEIGHTS: the fp32 pair-weight kernels exist for n_random=2, n_feat=12, fp32 planes (the reference's "
+               "19 dims) only";
+    return nullptr;
+}
+
+} // namespace
+
 // Which kernels the filter entry points run for the layout and flags of d (rpf_layout_kernels; needs no device): RPF_OK with
-// *generic_out = 0 (the compiled, fused kernels) or 1 (the layout-generic kernels, RPF_FLAG_GENERIC, with or without
-// RPF_FLAG_GENERIC_PACKED / RPF_FLAG_GENERIC_WAVE), else the refusal and its text in *why.  RPF_FLAG_WIDE_NBHD changes neither
-// answer (the wide kernel is layout-generic: both compiled layouts take the flag as they are); with RPF_FLAG_FAST_WEIGHTS it
-// is refused.  RPF_FLAG_WIDE_CLASSES modifies the wide flag and is refused without it.  RPF_FLAG_GENERIC_FAST (fp32 pair
-// weights on the packed and one-wave layout-generic kernels) changes no answer either; it is refused without both
-// RPF_FLAG_GENERIC and RPF_FLAG_GENERIC_PACKED, with RPF_FLAG_FAST_WEIGHTS and with RPF_FLAG_WIDE_NBHD.  RPF_FLAG_STREAM_FAST (fp32
-// pair weights on the streaming and wide layout-generic kernels, and on every kernel of a wide pass) changes no answer; it is
-// refused without both RPF_FLAG_GENERIC and RPF_FLAG_WIDE_NBHD, and with RPF_FLAG_FAST_WEIGHTS one of the older refusals fires.
+// *generic_out = 0 (the compiled, fused kernels) or 1 (the layout-generic kernels: RPF_FLAG_GENERIC, and no other flag changes
+// that answer), else the refusal and its text in *why -- the first failing row of kFlagRules, then the layout against the
+// kernels the flags select.  RPF_FLAG_STREAM_FAST is refused only without either of RPF_FLAG_GENERIC and RPF_FLAG_WIDE_NBHD; with
+// RPF_FLAG_FAST_WEIGHTS one of the older rows fires.  Both compiled layouts take RPF_FLAG_WIDE_NBHD as they are (the wide kernel is
+// layout-generic).
 int32_t layout_kernels(const rpf_desc *d, int32_t *generic_out, std::string *why) {
     if (!d) return RPF_E_BADARG;
     const SampleLayout lay = layout_of(d);
-    int32_t generic = 0;
+    const uint32_t flags = (uint32_t)d->flags;
+    const int32_t generic = (flags & RPF_FLAG_GENERIC) ? 1 : 0;
     const char *msg = nullptr;
-    if ((d->flags & RPF_FLAG_WIDE_CLASSES) && !(d->flags & RPF_FLAG_WIDE_NBHD)) {
-        msg = "RPF_FLAG_WIDE_CLASSES without RPF_FLAG_WIDE_NBHD: the flag modifies the wide route";
-    } else if ((d->flags & RPF_FLAG_GENERIC_FAST) && (d->flags & (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) != (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) {
-        msg = "RPF_FLAG_GENERIC_FAST without RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED: the flag modifies the packed layout-generic route";
-    } else if ((d->flags & RPF_FLAG_GENERIC_FAST) && (d->flags & RPF_FLAG_FAST_WEIGHTS)) {
-        msg = "RPF_FLAG_GENERIC_FAST with RPF_FLAG_FAST_WEIGHTS: that flag selects the fused fp32 kernels of the 19-dim layout, this one the layout-generic ones";
-    } else if ((d->flags & RPF_FLAG_GENERIC_FAST) && (d->flags & RPF_FLAG_WIDE_NBHD)) {
-        msg = "RPF_FLAG_GENERIC_FAST with RPF_FLAG_WIDE_NBHD: wide passes are fp64 throughout";
-    } else if ((d->flags & RPF_FLAG_STREAM_FAST) && !(d->flags & (RPF_FLAG_GENERIC | RPF_FLAG_WIDE_NBHD))) {
-        msg = "RPF_FLAG_STREAM_FAST without RPF_FLAG_GENERIC or RPF_FLAG_WIDE_NBHD: the flag modifies the streaming and wide layout-generic kernels";
-    } else if ((d->flags & RPF_FLAG_WIDE_NBHD) && (d->flags & RPF_FLAG_FAST_WEIGHTS)) {
-        msg = "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_WIDE_NBHD: the wide layout-generic kernel is fp64 throughout";
-    } else if ((d->flags & RPF_FLAG_GENERIC_WAVE) && (d->flags & (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) != (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED)) {
-        msg = "RPF_FLAG_GENERIC_WAVE without RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED: the flag modifies the packed layout-generic route";
-    } else if ((d->flags & RPF_FLAG_GENERIC_WAVE) && (d->flags & RPF_FLAG_FAST_WEIGHTS)) {
-        msg = "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_GENERIC_WAVE: the layout-generic kernels are fp64 throughout";
-    } else if ((d->flags & RPF_FLAG_GENERIC_PACKED) && !(d->flags & RPF_FLAG_GENERIC)) {
-        msg = "RPF_FLAG_GENERIC_PACKED without RPF_FLAG_GENERIC: the flag modifies the layout-generic route";
-    } else if ((d->flags & RPF_FLAG_GENERIC_PACKED) && (d->flags & RPF_FLAG_FAST_WEIGHTS)) {
-        msg = "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_GENERIC_PACKED: the layout-generic kernels are fp64 throughout";
-    } else if (d->flags & RPF_FLAG_GENERIC) {
-        generic = 1;
-        if (d->flags & RPF_FLAG_FAST_WEIGHTS)
-            msg = "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_GENERIC: the layout-generic kernels are fp64 throughout";
-        else if (!lay.generic_ok())
-            msg = "sample layout: the layout-generic kernels take n_random >= 1, n_feat >= 1, 5 + n_random + n_feat <= "
-                  "RPF_MAX_NDIM (40), fp32 or fp16 planes";
-    } else if (!lay.supported()) {
-        msg = "sample layout: kernels exist for n_random=2, n_feat=12, fp32 planes (the reference's 19 dims) and n_random=4, "
-              "n_feat=18, fp16 planes (27 dims); any other layout needs RPF_FLAG_GENERIC (the layout-generic kernels)";
-    } else if ((d->flags & RPF_FLAG_FAST_WEIGHTS) && !lay.is_ref19()) {
-        // (launch_filter_w, rpf_filter_impl.inc: the FAST instantiations are built for the reference layout alone)
-        msg = "RPF_FLAG_FAST_WEIGHTS: the fp32 pair-weight kernels exist for n_random=2, n_feat=12, fp32 planes (the reference's "
-              "19 dims) only";
+    for (const FlagRule &r : kFlagRules) {
+        const bool refused = (flags & r.all_of) != r.all_of || (r.one_of && !(flags & r.one_of)) || (flags & r.none_of);
+        if ((flags & r.when) == r.when && refused) { msg = r.msg; break; }
     }
+    if (!msg) msg = layout_refusal(lay, flags);
     if (msg) {
         if (why) *why = msg;
         return RPF_E_UNSUPPORTED;
@@ -188,8 +197,12 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     p.box = box; p.b = (box - 1) / 2;
     p.beta_map = d->beta_map; p.policy = d->degenerate_policy;
     p.fast_weights = (d->flags & RPF_FLAG_FAST_WEIGHTS) ? 1 : 0;
-    p.generic = (d->flags & RPF_FLAG_GENERIC) ? (1 | ((d->flags & RPF_FLAG_GENERIC_PACKED) ? 2 : 0) | ((d->flags & RPF_FLAG_GENERIC_WAVE) ? 4 : 0)) : 0;
-    if (d->flags & RPF_FLAG_GENERIC_FAST) p.generic |= 32; // (validate: only with G | P; read by routes 4 and 5, never by the fused code)
+    if (d->flags & RPF_FLAG_GENERIC) {
+        p.generic = kGenericOn;
+        if (d->flags & RPF_FLAG_GENERIC_PACKED) p.generic |= kGenericPacked;
+        if (d->flags & RPF_FLAG_GENERIC_WAVE) p.generic |= kGenericWave;
+    }
+    if (d->flags & RPF_FLAG_GENERIC_FAST) p.generic |= kGenericClassFast; // (validate: only with G | P; read by routes 4 and 5, never by the fused code)
     p.stage_mask = ctx->tun.stage_mask; // timing ablation knob (rpf_set_option); results are wrong unless -1
     p.screen = ctx->tun.screen;
     const int64_t nmax64 = (int64_t)box * box * d->S;
@@ -202,12 +215,12 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     p.nmax = (int)nmax64;
     // a wide pass: every pixel on generic::filter_wide_kernel (option "wide" = 1: every pass of a call with the flag)
     const bool wide = (d->flags & RPF_FLAG_WIDE_NBHD) && (p.nmax > kMaxNbhd || ctx->tun.wide == 1);
-    if (wide) p.generic |= 8;
+    if (wide) p.generic |= kGenericWide;
     // ... counted first and dealt by size class under RPF_FLAG_WIDE_CLASSES (above 832 spp no class can hold a pixel)
-    if (wide && (d->flags & RPF_FLAG_WIDE_CLASSES) && d->S <= 832) p.generic |= 16;
+    if (wide && (d->flags & RPF_FLAG_WIDE_CLASSES) && d->S <= 832) p.generic |= kGenericWideClasses;
     // fp32 pair weights on the streaming / wide kernels: only a pass that runs layout-generic kernels carries the bit (a fused pass
     // of a WIDE_NBHD | STREAM_FAST call keeps generic == 0 and runs exactly as without the flag)
-    if ((d->flags & RPF_FLAG_STREAM_FAST) && (p.generic & (1 | 8))) p.generic |= 64;
+    if ((d->flags & RPF_FLAG_STREAM_FAST) && (p.generic & (kGenericOn | kGenericWide))) p.generic |= kGenericStreamFast;
     // the fused kernels address a window's samples by 32-bit byte offsets from its first sample (Window, rpf_filter_impl.inc)
     if (rpf_check_window_span(d->W, d->S, box) != RPF_OK)
         return fail(ctx, RPF_E_UNSUPPORTED, "box*W*S*8 >= 2^32: a window's span in bytes of an fp64 plane must fit 32 bits (narrower slabs or a smaller box)");
@@ -232,7 +245,7 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     if ((st = ctx->d_pmean.ensure(ctx, HW * kNFeat * sizeof(double)))) return st;
     if ((st = ctx->d_pstd.ensure(ctx, HW * kNFeat * sizeof(double)))) return st;
     if ((st = ctx->d_nbhd.ensure(ctx, HW * sizeof(int32_t)))) return st;
-    // (the 2^-44 tables stop at the old cap: a wide pass reads them only where they are exact, launch_filter_binned)
+    // (the 2^-44 tables stop at the old cap: a wide pass reads them only where they are exact, launch_wide)
     if ((st = ensure_tables(ctx, std::min(p.nmax, kMaxNbhd)))) return st;
     if (wide && (st = ensure_wide_table(ctx, p.nmax))) return st;
     p.pmean = ctx->d_pmean; p.pstd = ctx->d_pstd; p.tfix = ctx->d_tfix; p.dfix = ctx->d_dfix;
@@ -241,9 +254,9 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     p.flat = ctx->d_flat; p.nan_flag = ctx->d_nan_flag;
     if (dbg_dev) p.dbg = *dbg_dev;
     if (wide) { // the wide kernel's carve-up: what 160 KiB leave of the joint table is one band of it
-        out.lds = generic_wide_carve(p.lay, p.nmax, (p.generic & 64) != 0).total;
+        out.lds = generic_wide_carve(p.lay, p.nmax, stream_fast(p)).total;
     } else if (p.generic) { // the generic kernel's own carve-up (one kernel for every neighbourhood size of the pass)
-        out.lds = generic_carve(p.lay, p.nmax, (p.generic & 64) != 0).total;
+        out.lds = generic_carve(p.lay, p.nmax, stream_fast(p)).total;
     } else { // LDS of the largest resident kernel this pass can launch (larger neighbourhoods stream: generic::filter_pixel_kernel)
         const int nres = std::min(p.nmax, kMaxResident), bres = bmax_of(nres);
         out.lds = lds_layout(p.S, nres, bres, table_in_lds(p.S, nres, bres, ctx->tun, p.lay), ctx->tun, p.lay).total;
@@ -255,40 +268,64 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
 
 namespace {
 
-// the streaming kernel's scratch in HBM: member lists [slots][nmax] u32 and bin ids [slots][ndim][nmax] u8; none when its
-// carve-up holds them in LDS
-int32_t ensure_big_scratch(rpf_ctx *ctx, const PassParams &p, uint32_t slots) {
-    if (generic_carve(p.lay, p.nmax).resident) return RPF_OK;
-    int32_t st;
-    if ((st = ctx->d_big_list.ensure(ctx, (size_t)slots * p.nmax * 4))) return st;
-    return ctx->d_big_bins.ensure(ctx, (size_t)slots * p.nmax * p.lay.ndim());
-}
-
-// How many workgroups (= scratch slots) a launch of the streaming kernel gets: min(pixels, resident) when its carve-up keeps
-// member list and bin ids in LDS, else -- and always under kSameWhenResident -- min(pixels, max(lo, min(hi, budget / bytes of a slot)))
+// How many workgroups (= scratch slots) a launch of the streaming or the wide kernel gets, for a slot of nmax members at
+// 4 + bin_bytes * ndim bytes each (a u32 list entry and one bin id per column: one byte on the streaming kernel, two on the wide
+// one): min(pixels, max(lo, min(hi, budget / bytes of a slot))) -- or min(pixels, resident) where the streaming kernel's carve-up
+// keeps member list and bin ids in LDS and the rule names a count for that (kSameWhenResident: it does not)
 struct SlotRule {
-    uint32_t resident, lo, hi;
+    uint32_t resident, lo, hi, bin_bytes;
     size_t budget;
 };
 constexpr uint32_t kSameWhenResident = 0;        // SlotRule::resident: the carve-up does not change the rule
-constexpr uint64_t kCountOnDevice = UINT64_MAX;  // launch_streaming's `pixels`: the list size is on the device, nothing to clamp to
-constexpr SlotRule kPassSlots = {2048, 64, 1024, (size_t)1 << 30};           // resident: eight workgroups on each of 256 CUs
-constexpr SlotRule kRedoSlots = {kSameWhenResident, 8, 128, (size_t)64 << 20}; // a fixed small grid: ordinary frames leave the list empty
+constexpr uint64_t kCountOnDevice = UINT64_MAX;  // `pixels` of a launch: the list size is on the device, nothing to clamp to
+constexpr SlotRule kPassSlots = {2048, 64, 1024, 1, (size_t)1 << 30};           // resident: eight workgroups on each of 256 CUs
+constexpr SlotRule kRedoSlots = {kSameWhenResident, 8, 128, 1, (size_t)64 << 20}; // a fixed small grid: ordinary frames leave the list empty
+constexpr SlotRule kBinnedSlots = {kSameWhenResident, 1024, 1024, 1, 0};        // the streaming class of the size-binned route: 1024, no budget
+constexpr SlotRule kWideSlots = {kSameWhenResident, 1, 1024, 2, (size_t)1 << 30};    // kPassSlots without its floor
+constexpr SlotRule kWideRedoSlots = {kSameWhenResident, 8, 64, 2, (size_t)256 << 20}; // as kRedoSlots, for slots of up to 21 MiB
 
-// One launch of the streaming kernel over p's rows or pixel list (`pixels` of them; kCountOnDevice with count_dev: the list size
-// is read on the device and the grid is the rule's slots): the slots by `rule`, the scratch, the launch.  fast: the fp32 stage 4
-// of RPF_FLAG_STREAM_FAST
-int32_t launch_streaming(rpf_ctx *ctx, const PassParams &p, uint64_t pixels, const SlotRule &rule, const uint32_t *count_dev,
-                         hipStream_t s, int *launches, bool fast) {
+uint32_t slot_count(const SlotRule &rule, const PassParams &p, uint64_t pixels) {
     uint64_t slots = rule.resident;
     if (rule.resident == kSameWhenResident || !generic_carve(p.lay, p.nmax).resident) {
-        const size_t per_slot = (size_t)p.nmax * (4 + (size_t)p.lay.ndim());
+        const size_t per_slot = (size_t)p.nmax * (4 + (size_t)rule.bin_bytes * p.lay.ndim());
         slots = std::max<size_t>(rule.lo, std::min<size_t>(rule.hi, rule.budget / per_slot));
     }
-    slots = std::min<uint64_t>(pixels, slots);
+    return (uint32_t)std::min<uint64_t>(pixels, slots);
+}
+
+// the slots' scratch in HBM: member lists [slots][nmax] u32 and bin ids [slots][ndim][nmax] of bin_bytes each; none when the
+// streaming kernel's carve-up holds them in LDS (the wide kernel's never does)
+int32_t ensure_slot_scratch(rpf_ctx *ctx, const PassParams &p, uint32_t slots, uint32_t bin_bytes) {
+    if (bin_bytes == 1 && generic_carve(p.lay, p.nmax).resident) return RPF_OK;
     int32_t st;
-    if ((st = ensure_big_scratch(ctx, p, (uint32_t)slots))) return st;
-    HIP_TRY(generic::launch_filter(p, ctx->d_big_list, ctx->d_big_bins, (uint32_t)slots, count_dev, s, fast));
+    if ((st = ctx->d_big_list.ensure(ctx, (size_t)slots * p.nmax * 4))) return st;
+    return ctx->d_big_bins.ensure(ctx, (size_t)slots * p.nmax * p.lay.ndim() * bin_bytes);
+}
+
+// One launch of the streaming kernel over p's rows or pixel list (`pixels` of them; kCountOnDevice with count_dev: the list size
+// is read on the device and the grid is the rule's slots): the slots by `rule`, the scratch, the launch, counted in *launches.
+// fast: the fp32 stage 4 of RPF_FLAG_STREAM_FAST
+int32_t launch_streaming(rpf_ctx *ctx, const PassParams &p, uint64_t pixels, const SlotRule &rule, const uint32_t *count_dev,
+                         hipStream_t s, int *launches, bool fast) {
+    const uint32_t slots = slot_count(rule, p, pixels);
+    int32_t st;
+    if ((st = ensure_slot_scratch(ctx, p, slots, rule.bin_bytes))) return st;
+    HIP_TRY(generic::launch_filter(p, ctx->d_big_list, ctx->d_big_bins, slots, count_dev, s, fast));
+    if (launches) ++*launches;
+    return RPF_OK;
+}
+
+// The same for the wide kernel.  The table: T_w (2^-41), or -- a forced pass below 48586 samples, where that one is exact and
+// three bits finer -- the 2^-44 table of the other kernels, so that such a pass gives route 3's bits.
+int32_t launch_wide(rpf_ctx *ctx, const PassParams &p, uint64_t pixels, const SlotRule &rule, const uint32_t *count_dev,
+                    hipStream_t s, int *launches, bool fast) {
+    const uint32_t slots = slot_count(rule, p, pixels);
+    int32_t st;
+    if ((st = ensure_slot_scratch(ctx, p, slots, rule.bin_bytes))) return st;
+    const bool fine = p.nmax <= kTFixExact;
+    if (!fine && (!ctx->d_twide || ctx->twide_n < p.nmax + 1)) return fail(ctx, RPF_E_BADARG, "wide pass without its table (setup_pass builds it)");
+    HIP_TRY(generic::launch_filter_wide(p, ctx->d_big_list, ctx->d_big_bins, slots, fine ? ctx->d_tfix.ptr : ctx->d_twide.ptr,
+                                        fine ? 44 : kTWideBits, count_dev, s, fast));
     if (launches) ++*launches;
     return RPF_OK;
 }
@@ -304,6 +341,19 @@ int32_t launch_redo(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *launc
     q.pix_list = p.redo_list;
     q.list_count = 0;
     return launch_streaming(ctx, q, kCountOnDevice, kRedoSlots, p.redo_count, s, launches, false); // a redone pixel is fp64 under every flag
+}
+
+// A pass begins under p's policy.  REF_ABORT: the redo count is zeroed, whether or not the pass keeps a list (finish_counters
+// reads it back after every REF_ABORT call); a route that keeps one gets d_redo_list and p pointed at it.  Otherwise p names none.
+int32_t begin_redo(rpf_ctx *ctx, PassParams &p, bool keeps_list, hipStream_t s) {
+    p.redo_list = nullptr; p.redo_count = nullptr;
+    if (p.policy != RPF_DEGEN_REF_ABORT) return RPF_OK;
+    HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
+    if (!keeps_list) return RPF_OK;
+    int32_t st;
+    if ((st = ctx->d_redo_list.ensure(ctx, (size_t)p.W * p.H * sizeof(uint32_t)))) return st;
+    p.redo_list = ctx->d_redo_list; p.redo_count = ctx->d_redo_count;
+    return RPF_OK;
 }
 
 // u64 acceptance masks per pixel: one bit per candidate of the window (the pixel's own samples are members without a test)
@@ -380,7 +430,7 @@ int32_t route_unbinned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream
             count_first = (n_probe_general != 0 && 2u * probe[0] >= n_probe_general) ? 1 : 0; // (only flat pixels: nothing to count)
         }
     }
-    ctx->last_route = count_first;
+    ctx->last_route = count_first == 1 ? kRouteCountFirst : kRouteFused;
     if (count_first == 1 && n_general != 0) {
         Range rg("rpf:stage 1b + classify");
         uint32_t *rlist = ctx->d_lists + (size_t)(kNumClasses - 2) * HW, *rcount = ctx->d_class_counts + (kNumClasses - 2);
@@ -424,7 +474,7 @@ int32_t route_unbinned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream
 int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream_t s, int *launches) {
     const size_t HW = (size_t)p.W * p.H;
     int32_t st;
-    ctx->last_route = 2;
+    ctx->last_route = kRouteBinned;
     if ((st = ctx->d_lists.ensure(ctx, (size_t)kNumClasses * HW * sizeof(uint32_t)))) return st;
     // the count pass keeps its acceptance masks (one u64 per 64 candidates) so the filter kernels only rebuild the list
     PassParams pc = p;
@@ -464,15 +514,12 @@ int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream_t
             "rpf:filter class N<=832", "rpf:filter class N<=1600", "rpf:filter class N<=3136", "rpf:filter class streaming"};
         Range rg(kClassName[c]);
         const PassParams q = class_params(ctx, pc, c, counts[c]);
-        if (c == kNumClasses - 1) { // neighbourhoods beyond the LDS-resident kernels: stream through global scratch
-            const uint32_t slots = std::min<uint32_t>(counts[c], 1024u);
-            if ((st = ensure_big_scratch(ctx, q, slots))) return st;
-            HIP_TRY(generic::launch_filter(q, ctx->d_big_list, ctx->d_big_bins, slots, nullptr, s, false)); // (fp64 under every flag)
-        } else if (c < kNumPacked && packed) {
-            HIP_TRY(launch_filter_packed(q, class_capacity(c), nullptr, s));
-        } else {
-            HIP_TRY(launch_filter_pass(q, tun, s, nullptr));
+        if (c == kNumClasses - 1) { // neighbourhoods beyond the LDS-resident kernels: stream through global scratch (fp64 under every flag)
+            if ((st = launch_streaming(ctx, q, counts[c], kBinnedSlots, nullptr, s, launches, false))) return st;
+            continue;
         }
+        if (c < kNumPacked && packed) { HIP_TRY(launch_filter_packed(q, class_capacity(c), nullptr, s)); }
+        else { HIP_TRY(launch_filter_pass(q, tun, s, nullptr)); }
         if (launches) ++*launches;
     }
     return launch_redo(ctx, pc, s, launches);
@@ -483,72 +530,62 @@ int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream_t
 // list: the kernel evaluates the reference's MI expression in place.  None of the rpf_set_option names applies here.
 int32_t route_generic(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *launches) {
     Range rg("rpf:generic filter kernel");
-    ctx->last_route = 3;
-    if (p.policy == RPF_DEGEN_REF_ABORT) HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
+    ctx->last_route = kRouteGeneric;
     if (p.row_end <= p.row_begin) return RPF_OK;
-    return launch_streaming(ctx, p, (uint64_t)(p.row_end - p.row_begin) * p.W, kPassSlots, nullptr, s, launches, (p.generic & 64) != 0);
-}
-
-// One launch of the wide kernel, over the slab's rows or over p.pix_list (p.list_count entries, or *count_dev of them), for at
-// most max_pixels pixels at a time: the slots and the table of route_generic_wide's comment.  fast: as for launch_streaming.
-int32_t launch_wide(rpf_ctx *ctx, const PassParams &p, uint64_t max_pixels, const uint32_t *count_dev, hipStream_t s, bool fast) {
-    const size_t per_slot = (size_t)p.nmax * (4 + 2 * (size_t)p.lay.ndim());
-    const uint32_t slots = (uint32_t)std::min<uint64_t>(max_pixels, std::max<size_t>(1, std::min<size_t>(1024, ((size_t)1 << 30) / per_slot)));
-    int32_t st;
-    if ((st = ctx->d_big_list.ensure(ctx, (size_t)slots * p.nmax * 4))) return st;
-    if ((st = ctx->d_big_bins.ensure(ctx, (size_t)slots * p.nmax * p.lay.ndim() * 2))) return st;
-    const bool fine = p.nmax <= kTFixExact;
-    if (!fine && (!ctx->d_twide || ctx->twide_n < p.nmax + 1)) return fail(ctx, RPF_E_BADARG, "wide pass without its table (setup_pass builds it)");
-    HIP_TRY(generic::launch_filter_wide(p, ctx->d_big_list, ctx->d_big_bins, slots, fine ? ctx->d_tfix.ptr : ctx->d_twide.ptr,
-                                        fine ? 44 : kTWideBits, count_dev, s, fast));
-    return RPF_OK;
+    return launch_streaming(ctx, p, (uint64_t)(p.row_end - p.row_begin) * p.W, kPassSlots, nullptr, s, launches, stream_fast(p));
 }
 
 // The wide route (RPF_FLAG_WIDE_NBHD on a pass with box*box*S > 65535, or option "wide" = 1): one launch per pass, every pixel
 // on generic::filter_wide_kernel; no count pass, no classes, no redo list (the kernel evaluates the reference's MI expression
-// in place).  Member lists (u32) and bin ids (u16) in HBM slots sized by route_generic's rule without its floor: at most 1024,
-// within 1 GiB, never more than pixels.  The table: T_w (2^-41), or -- a forced pass below 48586 samples, where that one is
-// exact and three bits finer -- the 2^-44 table of the other kernels, so that such a pass gives route 3's bits.
-int32_t route_generic_wide(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *launches) {
+// in place).  Member lists (u32) and bin ids (u16) in HBM slots by kWideSlots: at most 1024, within 1 GiB, never more than pixels.
+int32_t route_wide(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *launches) {
     Range rg("rpf:wide filter kernel");
-    ctx->last_route = 6;
-    if (p.policy == RPF_DEGEN_REF_ABORT) HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
+    ctx->last_route = kRouteWide;
     if (p.row_end <= p.row_begin) return RPF_OK;
-    int32_t st;
-    if ((st = launch_wide(ctx, p, (uint64_t)(p.row_end - p.row_begin) * p.W, nullptr, s, (p.generic & 64) != 0))) return st;
-    if (launches) ++*launches;
+    return launch_wide(ctx, p, (uint64_t)(p.row_end - p.row_begin) * p.W, kWideSlots, nullptr, s, launches, stream_fast(p));
+}
+
+constexpr int kNumWave = 8;                   // classes 0 .. 3 packed, 4 .. 7 one wave per pixel (capacities 128, 256, 448, 832)
+constexpr int kRestClass = kNumClasses - 1;   // the list of the pixels no class kernel of a generic route takes
+
+// One launch per non-empty list of the classes 0 .. n_classes - 1 of p's pass: generic::filter_packed_kernel below kNumPacked,
+// else generic::filter_wave_kernel.  fast: their fp32 stage 4 -- class_fast on routes 4 / 5, stream_fast on route 7
+int32_t launch_classes(rpf_ctx *ctx, const PassParams &p, const uint32_t *counts, int n_classes, bool fast, const char *packed_label,
+                       const char *wave_label, hipStream_t s, int *launches) {
+    for (int c = 0; c < n_classes; ++c) {
+        if (counts[c] == 0) continue;
+        Range rg(c < kNumPacked ? packed_label : wave_label);
+        PassParams q = p;
+        q.pix_list = ctx->d_lists + (size_t)c * p.W * p.H;
+        q.list_count = counts[c];
+        if (c < kNumPacked) { HIP_TRY(generic::launch_filter_packed(q, class_capacity(c), s, fast)); }
+        else { HIP_TRY(generic::launch_filter_wave(q, class_capacity(c), s, fast)); }
+        if (launches) ++*launches;
+    }
     return RPF_OK;
 }
 
 // A wide pass dealt by size class (RPF_FLAG_WIDE_NBHD | RPF_FLAG_WIDE_CLASSES, S <= 832): stage 1b as
 // its own launch (generic::wide_count_kernel: N, and the members of every pixel with N <= 832 in a member pool), the pixels
-// dealt into the eight classes of route_generic_wave and a rest class, one read-back (the list sizes and the pool cursor),
+// dealt into the eight classes of route 5 and a rest class, one read-back (the list sizes and the pool cursor),
 // then one launch per non-empty class -- generic::filter_packed_kernel / filter_wave_kernel reading the listed members, with
 // the 2^-44 table, exact for N <= 832 -- and the wide kernel over the rest list (N > 832; its own stage 1b, route 6's table).
 // REF_ABORT: the class kernels' redo list goes to the wide kernel as well (generic::filter_pixel_kernel cannot hold the
 // window), its size read on the device.  The pool holds `wide_pool` entries (option; default 8 per pixel of the slab); when
 // the cursor says the data needed more, the pool is grown to exactly that and the count and the classification are repeated:
 // which kernel filters a pixel never depends on the capacity.
-int32_t route_generic_wide_classes(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
+int32_t route_wide_classes(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
     const size_t HW = (size_t)p_in.W * p_in.H;
     int32_t st;
-    ctx->last_route = 7;
+    ctx->last_route = kRouteWideClasses;
     PassParams p = p_in;
-    p.redo_list = nullptr; p.redo_count = nullptr;
     p.masks = nullptr; p.mask_stride = 0;
-    if (p.policy == RPF_DEGEN_REF_ABORT) {
-        HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
-        if ((st = ctx->d_redo_list.ensure(ctx, HW * sizeof(uint32_t)))) return st;
-        p.redo_list = ctx->d_redo_list; p.redo_count = ctx->d_redo_count;
-    }
     if (p.row_end <= p.row_begin) return RPF_OK;
     const uint64_t npix = (uint64_t)(p.row_end - p.row_begin) * p.W;
     if ((st = ctx->d_lists.ensure(ctx, (size_t)kNumClasses * HW * sizeof(uint32_t)))) return st;
     if ((st = ctx->d_wc_base.ensure(ctx, HW * sizeof(uint64_t)))) return st;
     if ((st = ctx->d_wc_cursor.ensure(ctx, 2 * sizeof(unsigned long long)))) return st;
     uint64_t capacity = ctx->tun.wide_pool >= 0 ? (uint64_t)ctx->tun.wide_pool : 8 * npix;
-    constexpr int kNumWave = 8; // classes 0 .. 3 packed, 4 .. 7 one wave per pixel (capacities 128, 256, 448, 832)
-    const int rest_class = kNumClasses - 1;
     uint32_t counts[kNumClasses];
     for (int attempt = 0;; ++attempt) {
         Range rg("rpf:wide count + classify (stage 1b test, listed members, lane and wave classes)");
@@ -557,7 +594,7 @@ int32_t route_generic_wide_classes(rpf_ctx *ctx, const PassParams &p_in, hipStre
         HIP_TRY(hipMemsetAsync(ctx->d_class_counts, 0, kNumClasses * sizeof(uint32_t), s));
         HIP_TRY(generic::launch_wide_count(p, ctx->d_wc_pool, capacity, ctx->d_wc_base, ctx->d_wc_cursor,
                                            reinterpret_cast<int32_t *>(ctx->d_wc_cursor.ptr + 1), s));
-        HIP_TRY(launch_classify(p, ctx->d_lists, ctx->d_class_counts, kNumWave, rest_class, s));
+        HIP_TRY(launch_classify(p, ctx->d_lists, ctx->d_class_counts, kNumWave, kRestClass, s));
         HIP_TRY(hipMemcpyAsync(counts, ctx->d_class_counts, sizeof(counts), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(&used, ctx->d_wc_cursor, sizeof(used), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -566,167 +603,99 @@ int32_t route_generic_wide_classes(rpf_ctx *ctx, const PassParams &p_in, hipStre
         capacity = used; // the sum of N - S over the listed pixels: the same whatever the capacity was
     }
     p.members = ctx->d_wc_pool; p.member_base = ctx->d_wc_base;
-    for (int c = 0; c < kNumWave; ++c) {
-        if (counts[c] == 0) continue;
-        Range rg(c < kNumPacked ? "rpf:wide pass, packed class" : "rpf:wide pass, wave class");
-        PassParams q = p;
-        q.pix_list = ctx->d_lists + (size_t)c * HW;
-        q.list_count = counts[c];
-        if (c < kNumPacked) { HIP_TRY(generic::launch_filter_packed(q, class_capacity(c), s, (p.generic & 64) != 0)); }
-        else { HIP_TRY(generic::launch_filter_wave(q, class_capacity(c), s, (p.generic & 64) != 0)); }
-        if (launches) ++*launches;
-    }
-    PassParams w = p_in; // the wide kernel: as on route 6, over a list
-    if (counts[rest_class] != 0) {
+    if ((st = launch_classes(ctx, p, counts, kNumWave, stream_fast(p), "rpf:wide pass, packed class", "rpf:wide pass, wave class", s, launches))) return st;
+    PassParams w = p_in; // the wide kernel: as on route 6, over a list; it keeps no redo list of its own
+    w.redo_list = nullptr; w.redo_count = nullptr;
+    if (counts[kRestClass] != 0) {
         Range rg("rpf:wide filter kernel (N > 832)");
-        w.pix_list = ctx->d_lists + (size_t)rest_class * HW;
-        w.list_count = counts[rest_class];
-        if ((st = launch_wide(ctx, w, w.list_count, nullptr, s, (p.generic & 64) != 0))) return st;
-        if (launches) ++*launches;
+        w.pix_list = ctx->d_lists + (size_t)kRestClass * HW;
+        w.list_count = counts[kRestClass];
+        if ((st = launch_wide(ctx, w, w.list_count, kWideSlots, nullptr, s, launches, stream_fast(p)))) return st;
     }
     if (p.redo_list != nullptr) {
         Range rg("rpf:redo (wide kernel)");
         w.pix_list = p.redo_list;
         w.list_count = 0;
-        // (a fixed small grid whose workgroups find the list empty on ordinary frames, as launch_redo's: within 256 MiB of slots)
-        const size_t per_slot = (size_t)w.nmax * (4 + 2 * (size_t)w.lay.ndim());
-        const uint32_t grid = (uint32_t)std::max<size_t>(8, std::min<size_t>(64, ((size_t)256 << 20) / per_slot));
-        if ((st = launch_wide(ctx, w, grid, p.redo_count, s, false))) return st; // a redone pixel is fp64 under every flag
-        if (launches) ++*launches;
+        // (a fixed small grid whose workgroups find the list empty on ordinary frames, as launch_redo's; a redone pixel is fp64 under every flag)
+        if ((st = launch_wide(ctx, w, kCountOnDevice, kWideRedoSlots, p.redo_count, s, launches, false))) return st;
     }
     return RPF_OK;
 }
 
-// The layout-generic route with small neighbourhoods packed (RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED, S <= 64): stage 1b
-// as its own launch (generic::nbhd_count_kernel: N and the acceptance masks), the pixels dealt by N -- the four lane classes
-// of generic::filter_packed_kernel, and the rest (N > 64) into the list generic::filter_pixel_kernel walks (it runs its own
-// 3-sigma test) -- then one launch per non-empty list.  One read-back per pass (the list sizes).  REF_ABORT: the packed
-// kernels put the pixels with an in-band table on the redo list, which launch_redo filters again.  None of the
-// rpf_set_option names applies here.
-int32_t route_generic_packed(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
+// Routes 4 and 5, the layout-generic route with its small neighbourhoods on class kernels (RPF_FLAG_GENERIC |
+// RPF_FLAG_GENERIC_PACKED on a pass with S <= 64; ... | RPF_FLAG_GENERIC_WAVE on one with S <= 832): stage 1b as its own launch
+// (generic::nbhd_count_kernel: N and the acceptance masks), the pixels dealt by N into n_classes classes -- four lane classes
+// N <= 8, 16, 32, 64 of generic::filter_packed_kernel and, on route 5, N <= 128, 256, 448, 832 for generic::filter_wave_kernel
+// (one wave per pixel, member list from the acceptance masks, LDS sized for the class) -- and the rest into the list
+// generic::filter_pixel_kernel walks (it runs its own 3-sigma test); then one launch per non-empty list.  One read-back per pass
+// (the list sizes).  REF_ABORT: the class kernels put the pixels with an in-band table on the redo list, which launch_redo
+// filters again.  None of the rpf_set_option names applies here.
+int32_t route_generic_classes(rpf_ctx *ctx, const PassParams &p_in, int n_classes, Route route, hipStream_t s, int *launches) {
     const size_t HW = (size_t)p_in.W * p_in.H;
+    const bool wave = route == kRouteGenericWave;
     int32_t st;
-    ctx->last_route = 4;
+    ctx->last_route = route;
     PassParams p = p_in;
-    p.redo_list = nullptr; p.redo_count = nullptr;
-    if (p.policy == RPF_DEGEN_REF_ABORT) {
-        HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
-        if ((st = ctx->d_redo_list.ensure(ctx, HW * sizeof(uint32_t)))) return st;
-        p.redo_list = ctx->d_redo_list; p.redo_count = ctx->d_redo_count;
-    }
     if (p.row_end <= p.row_begin) return RPF_OK;
     if ((st = ctx->d_lists.ensure(ctx, (size_t)kNumClasses * HW * sizeof(uint32_t)))) return st;
     p.mask_stride = mask_stride(p);
     if ((st = ctx->d_masks.ensure(ctx, HW * p.mask_stride * sizeof(uint64_t)))) return st;
     p.masks = ctx->d_masks;
-    const int rest_class = kNumClasses - 1;
     uint32_t counts[kNumClasses];
     {
-        Range rg("rpf:generic count + classify (stage 1b test, lane classes)");
+        Range rg(wave ? "rpf:generic count + classify (stage 1b test, lane and wave classes)"
+                      : "rpf:generic count + classify (stage 1b test, lane classes)");
         HIP_TRY(hipMemsetAsync(ctx->d_class_counts, 0, kNumClasses * sizeof(uint32_t), s));
         HIP_TRY(generic::launch_nbhd_count(p, s));
-        HIP_TRY(launch_classify(p, ctx->d_lists, ctx->d_class_counts, kNumPacked, rest_class, s));
+        HIP_TRY(launch_classify(p, ctx->d_lists, ctx->d_class_counts, n_classes, kRestClass, s));
         HIP_TRY(hipMemcpyAsync(counts, ctx->d_class_counts, sizeof(counts), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     }
-    for (int c = 0; c < kNumPacked; ++c) {
-        if (counts[c] == 0) continue;
-        Range rg("rpf:generic packed class");
+    if ((st = launch_classes(ctx, p, counts, n_classes, class_fast(p), "rpf:generic packed class", "rpf:generic wave class", s, launches))) return st;
+    if (counts[kRestClass] != 0) {
+        Range rg(wave ? "rpf:generic filter kernel (N > 832)" : "rpf:generic filter kernel (N > 64)");
         PassParams q = p;
-        q.pix_list = ctx->d_lists + (size_t)c * HW;
-        q.list_count = counts[c];
-        HIP_TRY(generic::launch_filter_packed(q, class_capacity(c), s, (p.generic & 32) != 0));
-        if (launches) ++*launches;
-    }
-    if (counts[rest_class] != 0) {
-        Range rg("rpf:generic filter kernel (N > 64)");
-        PassParams q = p;
-        q.pix_list = ctx->d_lists + (size_t)rest_class * HW;
-        q.list_count = counts[rest_class];
-        if ((st = launch_streaming(ctx, q, q.list_count, kPassSlots, nullptr, s, launches, (p.generic & 64) != 0))) return st;
+        q.pix_list = ctx->d_lists + (size_t)kRestClass * HW;
+        q.list_count = counts[kRestClass];
+        if ((st = launch_streaming(ctx, q, q.list_count, kPassSlots, nullptr, s, launches, stream_fast(p)))) return st;
     }
     return launch_redo(ctx, p, s, launches);
 }
 
-// The packed layout-generic route with the one-wave kernels behind it (... | RPF_FLAG_GENERIC_WAVE, S <= 832): the count pass
-// and the read-back of route_generic_packed, the pixels dealt into eight classes -- N <= 8, 16, 32, 64 for
-// generic::filter_packed_kernel, N <= 128, 256, 448, 832 for generic::filter_wave_kernel (one wave per pixel, member list
-// from the acceptance masks, LDS sized for the class) -- and the rest (N > 832) into the list generic::filter_pixel_kernel
-// walks; then one launch per non-empty list.  REF_ABORT: both kernel families put the pixels with an in-band table on the redo
-// list, which launch_redo filters again.  None of the rpf_set_option names applies here.
-int32_t route_generic_wave(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
-    const size_t HW = (size_t)p_in.W * p_in.H;
-    int32_t st;
-    ctx->last_route = 5;
-    PassParams p = p_in;
-    p.redo_list = nullptr; p.redo_count = nullptr;
-    if (p.policy == RPF_DEGEN_REF_ABORT) {
-        HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
-        if ((st = ctx->d_redo_list.ensure(ctx, HW * sizeof(uint32_t)))) return st;
-        p.redo_list = ctx->d_redo_list; p.redo_count = ctx->d_redo_count;
-    }
-    if (p.row_end <= p.row_begin) return RPF_OK;
-    if ((st = ctx->d_lists.ensure(ctx, (size_t)kNumClasses * HW * sizeof(uint32_t)))) return st;
-    p.mask_stride = mask_stride(p);
-    if ((st = ctx->d_masks.ensure(ctx, HW * p.mask_stride * sizeof(uint64_t)))) return st;
-    p.masks = ctx->d_masks;
-    constexpr int kNumWave = 8; // classes 0 .. 3 packed, 4 .. 7 one wave per pixel (capacities 128, 256, 448, 832)
-    const int rest_class = kNumClasses - 1;
-    uint32_t counts[kNumClasses];
-    {
-        Range rg("rpf:generic count + classify (stage 1b test, lane and wave classes)");
-        HIP_TRY(hipMemsetAsync(ctx->d_class_counts, 0, kNumClasses * sizeof(uint32_t), s));
-        HIP_TRY(generic::launch_nbhd_count(p, s));
-        HIP_TRY(launch_classify(p, ctx->d_lists, ctx->d_class_counts, kNumWave, rest_class, s));
-        HIP_TRY(hipMemcpyAsync(counts, ctx->d_class_counts, sizeof(counts), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    for (int c = 0; c < kNumWave; ++c) {
-        if (counts[c] == 0) continue;
-        Range rg(c < kNumPacked ? "rpf:generic packed class" : "rpf:generic wave class");
-        PassParams q = p;
-        q.pix_list = ctx->d_lists + (size_t)c * HW;
-        q.list_count = counts[c];
-        if (c < kNumPacked) { HIP_TRY(generic::launch_filter_packed(q, class_capacity(c), s, (p.generic & 32) != 0)); }
-        else { HIP_TRY(generic::launch_filter_wave(q, class_capacity(c), s, (p.generic & 32) != 0)); }
-        if (launches) ++*launches;
-    }
-    if (counts[rest_class] != 0) {
-        Range rg("rpf:generic filter kernel (N > 832)");
-        PassParams q = p;
-        q.pix_list = ctx->d_lists + (size_t)rest_class * HW;
-        q.list_count = counts[rest_class];
-        if ((st = launch_streaming(ctx, q, q.list_count, kPassSlots, nullptr, s, launches, (p.generic & 64) != 0))) return st;
-    }
-    return launch_redo(ctx, p, s, launches);
+// Which layout-generic route a pass takes (kRouteNone: none, a pass on the compiled kernels).  Above 64 spp N >= S fits no
+// packed class, above 832 spp no one-wave class: such a pass runs as route 3 does.
+Route generic_route(const PassParams &p) {
+    if (p.generic & kGenericWide) return (p.generic & kGenericWideClasses) ? kRouteWideClasses : kRouteWide; // (setup_pass marked it)
+    if (!p.generic) return kRouteNone;
+    if ((p.generic & kGenericWave) && p.S <= class_capacity(kNumWave - 1)) return kRouteGenericWave;
+    if ((p.generic & kGenericPacked) && p.S <= class_capacity(kNumPacked - 1)) return kRouteGenericPacked;
+    return kRouteGeneric;
 }
 
 } // namespace
 
-// One fused-filter pass over rows [p.row_begin, p.row_end).  When box*box*S is above what the one-wave kernels hold
-// (512 samples), the neighbourhood sizes are counted first and every kernel family filters its own pixel list with
-// LDS sized for its capacity (rpf_kernels.hip, "neighbourhood-size binning"); option "binning" = 0/1 overrides.
+// One filter pass over rows [p.row_begin, p.row_end), on the route its flags, its sizes and the options pick.  A layout-generic
+// or wide pass: generic_route.  A pass on the compiled kernels: when box*box*S is above what the one-wave kernels hold (512
+// samples), the neighbourhood sizes are counted first and every kernel family filters its own pixel list with LDS sized for its
+// capacity (rpf_kernels.hip, "neighbourhood-size binning"); option "binning" = 0/1 overrides.
 // Needs stage 1a's planes (pmean / pstd) for those rows.  Synchronises the stream when it bins (list sizes).
-int32_t launch_filter_binned(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
-    if ((p_in.generic & 24) == 24) return route_generic_wide_classes(ctx, p_in, s, launches); // a wide pass dealt by size class
-    if (p_in.generic & 8) return route_generic_wide(ctx, p_in, s, launches); // a wide pass (setup_pass marked it)
-    // (above 64 spp N >= S fits no packed class, above 832 spp no one-wave class: the pass runs as route 3 does)
-    if ((p_in.generic & 4) && p_in.S <= 832) return route_generic_wave(ctx, p_in, s, launches);
-    if (p_in.generic) return (p_in.generic & 2) && p_in.S <= class_capacity(kNumPacked - 1) ? route_generic_packed(ctx, p_in, s, launches)
-                                                                                            : route_generic(ctx, p_in, s, launches);
+int32_t route_pass(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
+    const Route route = generic_route(p_in);
     PassParams p = p_in;
-    p.redo_list = nullptr; p.redo_count = nullptr;
-    if (p.policy == RPF_DEGEN_REF_ABORT) {
-        // finish_counters reads the count back after every REF_ABORT call: cleared whether or not this pass keeps a list
-        HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
-        // RPF_FLAG_FAST_WEIGHTS keeps the list too: MI, alpha, beta and W_r_c are the reference's under the flag as well, and a
-        // redone pixel is filtered whole, in fp64, by the reference-expression kernel (the FAST instantiations test
-        // p.redo_list at run time like the others, stage 3b)
-        if (ctx->tun.stage_mask == -1) {
-            int32_t e;
-            if ((e = ctx->d_redo_list.ensure(ctx, (size_t)p.W * p.H * sizeof(uint32_t)))) return e;
-            p.redo_list = ctx->d_redo_list; p.redo_count = ctx->d_redo_count;
-        }
+    int32_t st;
+    // Who keeps a redo list: routes 4, 5 and 7; routes 3 and 6 never (their kernels evaluate the reference's expression in
+    // place); a fused pass unless stages are skipped.  RPF_FLAG_FAST_WEIGHTS keeps the list too: MI, alpha, beta and W_r_c are the
+    // reference's under the flag as well, and a redone pixel is filtered whole, in fp64, by the reference-expression kernel (the
+    // FAST instantiations test p.redo_list at run time like the others, stage 3b)
+    const bool keeps_list = route == kRouteNone ? ctx->tun.stage_mask == -1 : route != kRouteGeneric && route != kRouteWide;
+    if ((st = begin_redo(ctx, p, keeps_list, s))) return st;
+    switch (route) {
+    case kRouteWideClasses: return route_wide_classes(ctx, p, s, launches);
+    case kRouteWide: return route_wide(ctx, p, s, launches);
+    case kRouteGenericWave: return route_generic_classes(ctx, p, kNumWave, route, s, launches);
+    case kRouteGenericPacked: return route_generic_classes(ctx, p, kNumPacked, route, s, launches);
+    case kRouteGeneric: return route_generic(ctx, p, s, launches);
+    default: break;
     }
     bool bin = p.nmax > 512;
     if (ctx->tun.binning >= 0) bin = ctx->tun.binning != 0;
@@ -876,7 +845,7 @@ int32_t run_passes(rpf_ctx *ctx, const rpf_desc *d, const void *d_planes, double
             HIP_TRY(launch_pixel_stats(ps_.p, s));
         }
         if (timing) HIP_TRY(hipEventRecord(ctx->ev[2], s));
-        if ((st = launch_filter_binned(ctx, ps_.p, s, &c.filter_kernel_launches))) return st;
+        if ((st = route_pass(ctx, ps_.p, s, &c.filter_kernel_launches))) return st;
         if (timing) {
             HIP_TRY(hipEventRecord(ctx->ev[3], s));
             HIP_TRY(hipEventSynchronize(ctx->ev[3]));
@@ -967,7 +936,7 @@ int32_t run_host_pipeline(rpf_ctx *ctx, const rpf_desc *d, const void *planes_v,
             q.row_begin = std::max(r0, d->row_begin);
             q.row_end = std::min(r1, d->row_end);
             if ((st = pass_through(ctx, d, cin, cout, r0, r1, s))) return st;
-            if (q.row_end > q.row_begin) return launch_filter_binned(ctx, q, s, &c.filter_kernel_launches);
+            if (q.row_end > q.row_begin) return route_pass(ctx, q, s, &c.filter_kernel_launches);
             return RPF_OK;
         };
         auto emit_rows = [&](int j) -> int32_t { // last pass: reduce + download band j
@@ -1250,7 +1219,7 @@ int32_t rpf_stage_pixel_stats(rpf_ctx *ctx, const rpf_desc *d, const void *plane
     if ((st = upload_frame(ctx, d, planes, nullptr, false, nullptr, s))) return st;
     PassParams p{};
     p.lay = lay;
-    p.generic = (d->flags & RPF_FLAG_GENERIC) ? 1 : 0; // (stage 1a is the same kernel with and without RPF_FLAG_GENERIC_PACKED / _WAVE)
+    p.generic = (d->flags & RPF_FLAG_GENERIC) ? kGenericOn : 0; // (stage 1a is the same kernel with and without RPF_FLAG_GENERIC_PACKED / _WAVE)
     p.W = d->W; p.H = d->H; p.S = d->S; p.policy = d->degenerate_policy;
     p.plane_stride = ps; p.planes = ctx->d_planes; p.pmean = ctx->d_pmean; p.pstd = ctx->d_pstd;
     HIP_TRY(launch_pixel_stats(p, s));
@@ -1307,7 +1276,7 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *d, int32_t box, cons
     HIP_TRY(launch_pixel_stats(ps_.p, s));
     if (timing) HIP_TRY(hipEventRecord(ctx->ev[0], s));
     rpf_counters &c = ctx->counters;
-    if ((st = launch_filter_binned(ctx, ps_.p, s, &c.filter_kernel_launches))) return st;
+    if ((st = route_pass(ctx, ps_.p, s, &c.filter_kernel_launches))) return st;
     if (timing) HIP_TRY(hipEventRecord(ctx->ev[1], s));
     HIP_TRY(hipMemcpyAsync(colour_out, ctx->d_colB, 3 * ps * sizeof(double), hipMemcpyDeviceToHost, s));
     if (dbg && dbg->nbhd_size) // N is always produced in the context's own plane

@@ -231,7 +231,7 @@ int32_t multi_run(rpf_multi *m, const rpf_desc *d, const void *planes_v, const f
             if ((e = pass_through(ctx, &sd[g], cin[g], cout[g], 0, sd[g].H, s))) return e;
             if (i == 0) HIP_TRY(launch_pixel_stats(pp.p, s)); // stage 1a depends on the features only
             HIP_TRY(hipEventRecord(ctx->ev[0], s));
-            if ((e = launch_filter_binned(ctx, pp.p, s, &nl[g]))) return e;
+            if ((e = route_pass(ctx, pp.p, s, &nl[g]))) return e;
             HIP_TRY(hipEventRecord(ctx->ev[1], s));
             HIP_TRY(hipEventSynchronize(ctx->ev[1]));
             HIP_TRY(hipEventElapsedTime(&ms[g], ctx->ev[0], ctx->ev[1]));

@@ -1,6 +1,7 @@
 // rpf_internal.h -- shared between the kernel TUs (rpf_kernels.hip, rpf_film.hip, rpf_impl_*.hip) and the C-ABI TUs (rpf_api*.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "rpf_hip.h"
@@ -26,6 +27,24 @@ struct SampleLayout {
 constexpr int kStageChunk = 64; // samples gathered per step of the in-order (reference-order) sums
 constexpr int kStageHalf = 32;  // ... and staged through LDS this many at a time
 
+// The bits of PassParams::generic (setup_pass writes them, route_pass and the routes read them; 0 = a pass on the compiled, fused
+// kernels).  Only kGenericOn reaches device-side decisions (stage 1a's kernel); the two fast bits are host-side only: no kernel
+// reads them, and PassParams::fast_weights stays 0.
+enum GenericBits : int32_t {
+    kGenericOn = 1,           // RPF_FLAG_GENERIC: stage 1a and the filter pass run on the layout-generic kernels (rpf_generic.hip)
+    kGenericPacked = 2,       // RPF_FLAG_GENERIC_PACKED: small neighbourhoods on the packed generic kernels (rpf_generic_packed.hip)
+    kGenericWave = 4,         // RPF_FLAG_GENERIC_WAVE: 64 < N <= 832 on the one-wave generic kernels (rpf_generic_wave.hip)
+    kGenericWide = 8,         // a wide pass (RPF_FLAG_WIDE_NBHD and box*box*S > 65535, or option "wide" = 1): every pixel on
+                              //   generic::filter_wide_kernel (rpf_generic_wide.hip), whatever the bits above say; stage 1a is not affected
+    kGenericWideClasses = 16, // with kGenericWide, RPF_FLAG_WIDE_CLASSES and S <= 832: the wide pass is counted first and dealt by size
+                              //   class (route_wide_classes); only N > 832 stays on the wide kernel
+    kGenericClassFast = 32,   // RPF_FLAG_GENERIC_FAST: routes 4 and 5 launch the fp32-weight instantiations of their packed and
+                              //   one-wave class kernels (class_fast below); their rest lists and route 7 do not read it
+    kGenericStreamFast = 64,  // RPF_FLAG_STREAM_FAST on a pass that runs layout-generic kernels (kGenericOn or kGenericWide; never set on
+                              //   a fused pass): route 3, the rest lists of routes 4 / 5, route 6 and every class and the rest list
+                              //   of route 7 launch the fp32-weight instantiations (stream_fast below); redo launches never do
+};
+
 // everything one pass needs, passed by value to the kernels
 struct PassParams {
     int32_t W, H, S;
@@ -33,18 +52,7 @@ struct PassParams {
     int32_t box, b;        // b = (box-1)/2, rpf.cpp:561
     int32_t beta_map, policy;
     int32_t fast_weights;  // RPF_FLAG_FAST_WEIGHTS: fp32 pair arithmetic in stage 4
-    int32_t generic;       // RPF_FLAG_GENERIC: stage 1a and the filter pass run on the layout-generic kernels (rpf_generic.hip);
-                           //   bit 1: RPF_FLAG_GENERIC_PACKED, small neighbourhoods on the packed generic kernels (rpf_generic_packed.hip)
-                           //   bit 2: RPF_FLAG_GENERIC_WAVE, 64 < N <= 832 on the one-wave generic kernels (rpf_generic_wave.hip)
-                           //   bit 3: a wide pass (RPF_FLAG_WIDE_NBHD and box*box*S > 65535, or option "wide" = 1): every pixel on
-                           //          generic::filter_wide_kernel (rpf_generic_wide.hip), whatever the other bits say; stage 1a is not affected
-                           //   bit 4: with bit 3, RPF_FLAG_WIDE_CLASSES and S <= 832: the wide pass is counted first and dealt by size class
-                           //          (route_generic_wide_classes); only N > 832 stays on the wide kernel
-                           //   bit 5: RPF_FLAG_GENERIC_FAST: routes 4 and 5 launch the fp32-weight instantiations of their packed and
-                           //          one-wave kernels (host-side only: no kernel reads the bit, and fast_weights stays 0)
-                           //   bit 6: RPF_FLAG_STREAM_FAST on a pass that runs layout-generic kernels (bit 0 or bit 3; never set on a
-                           //          fused pass): route 3, the rest lists of routes 4 / 5, route 6 and every class and the rest
-                           //          list of route 7 launch the fp32-weight instantiations; redo launches never do (host-side only)
+    int32_t generic;       // GenericBits below: which layout-generic kernels the pass runs (0: the compiled, fused ones)
     int32_t stage_mask;    // diagnostics only (rpf_set_option "stage_mask"): bit0 stats chain, bit1 bins, bit2 MI, bit3 weights; -1 = all
     int32_t screen;        // far-pair screen of the four-wave kernels: 0 off, 1 on
     int32_t strip_w;       // pixels per XCD strip of the pixel walk (slab_pixel)
@@ -88,6 +96,11 @@ struct PassParams {
     const uint32_t *members;
     const uint64_t *member_base; // [H*W]
 };
+// the kernel argument block: a field that moves or grows moves it under every kernel at once
+static_assert(sizeof(PassParams) == 352 && offsetof(PassParams, generic) == 40, "PassParams is the kernel argument block");
+// the two fp32 pair-weight selections: the class kernels of routes 4 / 5 | the streaming and wide kernels, and every kernel of a wide pass
+inline bool class_fast(const PassParams &p) { return (p.generic & kGenericClassFast) != 0; }
+inline bool stream_fast(const PassParams &p) { return (p.generic & kGenericStreamFast) != 0; }
 
 // Per-context tuning / diagnostic overrides (rpf_set_option).  Defaults = the library's own choices; nothing here is
 // read from the environment.  stage_mask != -1 skips stages (timing ablation: results are wrong) and is reported in

@@ -381,7 +381,7 @@ hipError_t launch_udiv_selftest(uint64_t n, uint64_t seed, int mode, unsigned lo
 hipError_t launch_pixel_stats_rows(const PassParams &p, int r0, int r1, hipStream_t s) {
     if (r1 <= r0) return hipSuccess;
     const uint64_t pix0 = (uint64_t)r0 * p.W, pix1 = (uint64_t)r1 * p.W;
-    if (p.generic & 7) return generic::launch_pixel_stats(p, pix0, pix1, s); // (bit 3, a wide pass, says nothing about stage 1a)
+    if (p.generic & (kGenericOn | kGenericPacked | kGenericWave)) return generic::launch_pixel_stats(p, pix0, pix1, s); // (kGenericWide, a wide pass, says nothing about stage 1a)
     return p.lay.is_ref19() ? d19::impl_pixel_stats(p, pix0, pix1, s) : d27::impl_pixel_stats(p, pix0, pix1, s);
 }
 

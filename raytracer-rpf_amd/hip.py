@@ -146,7 +146,7 @@ def layout_kernels(desc):
     """rpf_layout_kernels (no GPU needed): (status, generic) for the layout and flags of `desc` -- (OK, 0) the compiled fused
     kernels, (OK, 1) the layout-generic kernels (FLAG_GENERIC; FLAG_GENERIC_FAST does not change the answer),
     (E_UNSUPPORTED, None) where the filter entry points refuse it -- FLAG_GENERIC_FAST without FLAG_GENERIC | FLAG_GENERIC_PACKED,
-    with FLAG_FAST_WEIGHTS or with FLAG_WIDE_NBHD, and FLAG_STREAM_FAST without both FLAG_GENERIC and FLAG_WIDE_NBHD, among them
+    with FLAG_FAST_WEIGHTS or with FLAG_WIDE_NBHD, and FLAG_STREAM_FAST without either of FLAG_GENERIC and FLAG_WIDE_NBHD, among them
     (where FLAG_STREAM_FAST is accepted the answer is that of the same flags without it); desc None: (E_BADARG, None)"""
     g = C.c_int32(-1)
     st = load().rpf_layout_kernels(None if desc is None else C.byref(desc), C.byref(g))

@@ -32,7 +32,7 @@ def test_every_class_edge_is_planted():
     for cap in P.CAPACITIES[1:]:          # (16 spp is the fewest samples the size-binned route starts at: N >= 16)
         assert cap in binned and cap + 1 in binned, cap
     for fid, (_, S, box, targets, _, is_binned) in P.FRAMES.items():
-        assert (box * box * S > 512) == is_binned, fid   # the route launch_filter_binned picks by default
+        assert (box * box * S > 512) == is_binned, fid   # the route route_pass picks by default
 
 
 @pytest.mark.parametrize("fid", [f for f, v in P.FRAMES.items() if not v[5] and v[1] in (8, 2)])
