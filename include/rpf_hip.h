@@ -168,6 +168,28 @@ enum {
                                   download of RPF_FLAG_NO_OVERLAP (no band may leave before delta is known).
                                   RPF_E_NONFINITE is returned as before, and the spike pass still runs.
                                   rpf_filter_pass_debug refuses the flag (RPF_E_UNSUPPORTED) before any device work. */
+    RPF_FLAG_SAMPLED_NBHD = 2048, /* opt-in: the published random-subset gather.  A pass p of the call with draws[p] > 0
+                                  (rpf_set_sampling below) does not take every sample of its box as a candidate: it draws
+                                  draws[p] samples per pixel, Gaussian-distributed around the pixel, from a counter-based
+                                  generator in integer arithmetic, keeps the distinct ones in the
+                                  reference's visiting order and runs the unchanged 3-sigma test on them.  The member list
+                                  is a subsequence of the full-box list; everything behind it (statistics, bins, MI, alpha,
+                                  beta, W_r_c, weights, blend; fp64) is that of the packed and one-wave layout-generic
+                                  kernels on that list.  rpf_query_route says 8, redo_pixels is 0, filter_kernel_launches
+                                  counts one launch per non-empty size class, sum_nbhd / max_nbhd / rpf_query_nbhd report
+                                  the sampled N.  S + draws[p] <= 832 (RPF_E_BADARG otherwise).  A pass with draws[p] == 0
+                                  runs exactly as without the flag: same route, same bits.  Every filter entry point takes
+                                  the flag (rpf_filter_pass_debug: pass id pass_id0, draws[0]); an entry point that runs no
+                                  pass (stage 1a, the colour / reduce / spike / film-window helpers) takes a descriptor with
+                                  the flag as one without it and does not look at the configuration.  The two compiled layouts
+                                  take it alone, any other layout needs RPF_FLAG_GENERIC as before; rpf_layout_kernels
+                                  reports *generic_out as without it; rpf_max_nbhd is unchanged (a pass above 65535 still
+                                  needs RPF_FLAG_WIDE_NBHD).  Refused before any device work: the flag without a prior
+                                  rpf_set_sampling, a negative draw count, S + draws[p] > 832 (RPF_E_BADARG); a pass with
+                                  draws[p] > 0 under RPF_DEGEN_REF_ABORT (the reference has no sampled gather to reproduce and
+                                  the redo kernels run their own full-box stage 1b), the flag with RPF_FLAG_FAST_WEIGHTS,
+                                  RPF_FLAG_GENERIC_FAST or RPF_FLAG_STREAM_FAST (sampled passes are fp64; rpf_layout_kernels
+                                  answers the same way) (RPF_E_UNSUPPORTED). */
     RPF_FLAG_STREAM_FAST = 512 /* opt-in, modifies RPF_FLAG_GENERIC and / or RPF_FLAG_WIDE_NBHD: the two kernels that walk a
                                   neighbourhood of any size with 256 threads -- the generic filter kernel (route 3, the rest
                                   list N > 64 / N > 832 of routes 4 / 5) and the wide kernel (route 6, the rest list N > 832 of
@@ -355,7 +377,10 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *desc, int32_t box, c
  * With RPF_FLAG_WIDE_CLASSES as well (route 7) such a pass counts as route 5 does, with the wide kernel in place of the generic
  * filter kernel: one launch per non-empty packed class, one per non-empty one-wave class, one for the wide kernel when some
  * pixel has N > 832, and under RPF_DEGEN_REF_ABORT one for the redo launch (the wide kernel again); redo_pixels counts the
- * pixels the packed and the one-wave kernels put on the redo list. */
+ * pixels the packed and the one-wave kernels put on the redo list.
+ * A sampled pass (RPF_FLAG_SAMPLED_NBHD with draws > 0: route 8) counts one launch per non-empty packed or one-wave class and
+ * nothing else -- S + draws <= 832 leaves no rest list, and RPF_DEGEN_REF_ABORT is refused -- and leaves redo_pixels 0;
+ * sum_nbhd / max_nbhd are those of the sampled neighbourhoods. */
 int32_t rpf_query_counters(rpf_ctx *ctx, rpf_counters *out);
 
 /* neighbourhood size N of every pixel (rpf.cpp:586: the neighbourhood vector's size) as the last pass of the most recent
@@ -371,6 +396,7 @@ int32_t rpf_query_nbhd(rpf_ctx *ctx, int32_t *nbhd_out, int64_t count);
  * on a pass with S <= 64), 5 = the same with 64 < N <= 832 on the one-wave layout-generic kernels (... | RPF_FLAG_GENERIC_WAVE
  * on a pass with S <= 832), 6 = the wide layout-generic kernel (RPF_FLAG_WIDE_NBHD on a pass with box*box*S > 65535),
  * 7 = such a pass counted first and dealt by size class (... | RPF_FLAG_WIDE_CLASSES, S <= 832),
+ * 8 = a sampled pass (RPF_FLAG_SAMPLED_NBHD with draws > 0: the one route whose member lists differ, by definition),
  * -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1. */
 int32_t rpf_query_route(rpf_ctx *ctx, int32_t *route_out);
 
@@ -569,6 +595,35 @@ int32_t rpf_colour_add_device(rpf_ctx *ctx, const rpf_desc *desc, double *d_colo
  * (double)n_samples.  row_sums: [n_rows][3]; n_samples: the number of samples of those rows, rows * W * S.  Needs no context
  * and no device.  RPF_E_BADARG for a NULL pointer or a non-positive count. */
 int32_t rpf_spike_delta(const double *row_sums, int64_t n_rows, int64_t n_samples, double *energy_out, double *delta_out);
+
+/* ---- sampled neighbourhoods (RPF_FLAG_SAMPLED_NBHD) ---------------------------------------------
+ * Pass p of a call has id pass_id0 + p and draws[p] draws per pixel (0: the pass runs as without the flag).  row_origin is the
+ * image row of buffer row 0: the key of a pixel is formed from its IMAGE row, so a row slab draws what the whole image draws.
+ * rpf_multi_* adds each slab's first buffer row to the caller's value; a caller who owns the slabs sets it, and sets pass_id0
+ * when making one call per pass. */
+typedef struct rpf_sampling {
+    uint64_t seed;
+    int32_t pass_id0;
+    int32_t row_origin;
+    int32_t draws[RPF_MAX_BOXES];
+} rpf_sampling;
+
+/* RPF_E_BADARG for a NULL pointer or a negative draw count; needs no device work.  The configuration stays until replaced. */
+int32_t rpf_set_sampling(rpf_ctx *ctx, const rpf_sampling *cfg);
+int32_t rpf_multi_set_sampling(rpf_multi *m, const rpf_sampling *cfg);
+
+/* The Gaussian threshold table of a box: table_out[k] = floor(2^32 * C_k / C_(box-1)), k = 0 .. box - 2 (box - 1 entries),
+ * C_k = sum_{j <= k} exp(-(j - b)^2 / (2 sigma^2)), b = (box - 1) / 2, sigma = box / 4.0, computed in long double.  A 32-bit
+ * word u names the window column (or row) #{k : table[k] <= u}.  Host only; RPF_E_BADARG for NULL, an even box or a box
+ * outside [1, 511]. */
+int32_t rpf_sampling_table(int32_t box, uint32_t *table_out);
+
+/* The draws of buffer pixel (x, y) of a W x H x S buffer in pass `pass` (index into cfg->draws) with `box`: the distinct
+ * surviving visiting-order indices qq in ascending order, BEFORE the 3-sigma test; qq_out has room for cfg->draws[pass]
+ * entries, *n_out tells how many were written.  Host only, no device.  RPF_E_BADARG for NULL, pass outside [0, RPF_MAX_BOXES),
+ * a negative draw count, an even or out-of-range box, non-positive sizes or a pixel outside the buffer. */
+int32_t rpf_sampling_draws(const rpf_sampling *cfg, int32_t pass, int32_t box, int32_t W, int32_t H, int32_t S, int32_t x,
+                           int32_t y, int32_t *qq_out, int32_t *n_out);
 
 #ifdef __cplusplus
 }

@@ -56,6 +56,14 @@ enum Route : int {
     kRouteGenericWave = 5,   // ... and 64 < N <= 832 on the one-wave layout-generic kernels
     kRouteWide = 6,          // the wide kernel, one launch
     kRouteWideClasses = 7,   // a wide pass counted first and dealt by size class
+    kRouteSampled = 8,       // a sampled pass: the draws' count kernel, then the class kernels on its member lists
+};
+
+static_assert(sizeof(rpf_sampling) == 48 && offsetof(rpf_sampling, draws) == 16, "rpf_sampling is ABI");
+
+// The sampled pass in progress (RPF_FLAG_SAMPLED_NBHD; setup_pass fills it, route_sampled reads it): draws == 0, not sampled
+struct SampledPass {
+    int32_t draws = 0, pass_id = 0;
 };
 
 } // namespace rpf
@@ -117,6 +125,11 @@ struct rpf_ctx {
     rpf::DevBuf<double> d_spike_e;              // [rows][W][3] removed energy per pixel
     rpf::DevBuf<double> d_spike_rows;           // [rows][3] its row sums
     rpf::DevBuf<unsigned long long> d_spike_cnt; // [3] replaced samples, clamped pixels, skipped pixels
+    // sampled neighbourhoods (RPF_FLAG_SAMPLED_NBHD)
+    rpf_sampling sampling{};                    // rpf_set_sampling
+    bool sampling_set = false;
+    rpf::SampledPass samp_now;                  // of the pass setup_pass prepared last
+    rpf::DevBuf<uint32_t> d_samp_table; int samp_table_box = 0; // the Gaussian thresholds of that box (rpf_sampling_table)
 };
 
 namespace rpf {
@@ -160,6 +173,9 @@ struct Range {
 SampleLayout layout_of(const rpf_desc *d);
 int32_t layout_kernels(const rpf_desc *d, int32_t *generic_out, std::string *why);
 void wide_table(int nmax, uint64_t *out); // out[k] = round(k ln k * 2^kTWideBits), k = 0 .. nmax
+void sampling_table(int box, uint32_t *out); // the box - 1 Gaussian thresholds of an odd box (rpf_sampling_table)
+int32_t check_sampling(const rpf_sampling *cfg, std::string &why); // what rpf_set_sampling refuses
+int32_t check_sampled(rpf_ctx *ctx, const rpf_desc *d, int n_pass); // RPF_FLAG_SAMPLED_NBHD of a call that runs n_pass passes
 int32_t validate(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes);
 int32_t enter(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes); // validate, then make the context's device current
 
@@ -167,7 +183,8 @@ struct PassSetup {
     PassParams p;
     uint32_t lds = 0;
 };
-int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_planes, const double *col_in,
+// pass: the index of the pass in its call (what RPF_FLAG_SAMPLED_NBHD reads draws[] and forms the pass id with)
+int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const void *d_planes, const double *col_in,
                    double *col_out, const rpf_debug *dbg_dev, PassSetup &out);
 int32_t route_pass(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches);
 

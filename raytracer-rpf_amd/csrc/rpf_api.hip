@@ -5,6 +5,7 @@
 // driver rpf_api_multi.hip; rpf_api.h is what the three share.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <climits>
 #include <cmath>
@@ -46,6 +47,9 @@ struct FlagRule {
 };
 constexpr uint32_t kPackedRoute = RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED;
 constexpr FlagRule kFlagRules[] = {
+    {RPF_FLAG_SAMPLED_NBHD, 0, 0, RPF_FLAG_FAST_WEIGHTS, "RPF_FLAG_SAMPLED_NBHD with RPF_FLAG_FAST_WEIGHTS: sampled passes are fp64 throughout"},
+    {RPF_FLAG_SAMPLED_NBHD, 0, 0, RPF_FLAG_GENERIC_FAST, "RPF_FLAG_SAMPLED_NBHD with RPF_FLAG_GENERIC_FAST: sampled passes are fp64 throughout"},
+    {RPF_FLAG_SAMPLED_NBHD, 0, 0, RPF_FLAG_STREAM_FAST, "RPF_FLAG_SAMPLED_NBHD with RPF_FLAG_STREAM_FAST: sampled passes are fp64 throughout"},
     {RPF_FLAG_WIDE_CLASSES, RPF_FLAG_WIDE_NBHD, 0, 0, "RPF_FLAG_WIDE_CLASSES without RPF_FLAG_WIDE_NBHD: the flag modifies the wide route"},
     {RPF_FLAG_GENERIC_FAST, kPackedRoute, 0, 0, "RPF_FLAG_GENERIC_FAST without RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED: the flag modifies the packed layout-generic route"},
     {RPF_FLAG_GENERIC_FAST, 0, 0, RPF_FLAG_FAST_WEIGHTS, "RPF_FLAG_GENERIC_FAST with RPF_FLAG_FAST_WEIGHTS: that flag selects the fused fp32 kernels of the 19-dim layout, this one the layout-generic ones"},
@@ -102,6 +106,25 @@ int32_t layout_kernels(const rpf_desc *d, int32_t *generic_out, std::string *why
     return RPF_OK;
 }
 
+// RPF_FLAG_SAMPLED_NBHD against the context's configuration, for a call that runs passes 0 .. n_pass - 1 of it (the entry points
+// that filter: validate with the box list, rpf_filter_pass_debug with its one pass).  An entry point that runs no pass -- stage 1a,
+// the colour / reduce / spike / film-window helpers -- accepts a descriptor with the flag as it accepts one without
+int32_t check_sampled(rpf_ctx *ctx, const rpf_desc *d, int n_pass) {
+    if (!(d->flags & RPF_FLAG_SAMPLED_NBHD)) return RPF_OK;
+    if (!ctx->sampling_set) return fail(ctx, RPF_E_BADARG, "RPF_FLAG_SAMPLED_NBHD without a prior rpf_set_sampling");
+    for (int i = 0; i < std::max(0, std::min(n_pass, RPF_MAX_BOXES)); ++i) {
+        const int32_t D = ctx->sampling.draws[i];
+        if (D < 0) return fail(ctx, RPF_E_BADARG, "rpf_sampling: a negative draw count");
+        if (D > 0 && (int64_t)d->S + D > 832)
+            return fail(ctx, RPF_E_BADARG, "RPF_FLAG_SAMPLED_NBHD: S + draws > 832 (the largest size class of the one-wave kernels; a rest "
+                                           "kernel that reads listed members does not exist)");
+        if (D > 0 && d->degenerate_policy == RPF_DEGEN_REF_ABORT)
+            return fail(ctx, RPF_E_UNSUPPORTED, "a sampled pass under RPF_DEGEN_REF_ABORT: the reference has no sampled gather to reproduce, "
+                                                "and the redo kernels run their own full-box stage 1b (use RPF_DEGEN_EPS)");
+    }
+    return RPF_OK;
+}
+
 int32_t validate(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes) {
     if (!ctx) return RPF_E_BADARG;
     if (!d) return fail(ctx, RPF_E_BADARG, "desc is NULL");
@@ -118,6 +141,10 @@ int32_t validate(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes) {
     }
     if (d->degenerate_policy < 0 || d->degenerate_policy > RPF_DEGEN_EPS)
         return fail(ctx, RPF_E_BADARG, "unknown degenerate_policy");
+    if (need_boxes) {
+        const int32_t st = check_sampled(ctx, d, d->n_box);
+        if (st) return st;
+    }
     if (need_boxes) {
         if (d->n_box < 1 || d->n_box > RPF_MAX_BOXES) return fail(ctx, RPF_E_BADARG, "n_box must be 1..8");
         // The reference filters the WHOLE film in every pass (rpf.cpp:732 swaps the full film), so pass i+1 reads
@@ -150,7 +177,42 @@ void wide_table(int nmax, uint64_t *out) {
     for (int k = 1; k <= nmax; ++k) out[k] = (uint64_t)std::llroundl(std::ldexp((long double)k * std::log((long double)k), kTWideBits));
 }
 
+// The Gaussian threshold table of an odd box: out[k] = floor(2^32 * C_k / C_(box-1)), k = 0 .. box - 2,
+// C_k = sum_{j <= k} exp(-(j - b)^2 / (2 sigma^2)), sigma = box / 4.0, in long double.  C_k < C_(box-1): every entry is below 2^32.
+void sampling_table(int box, uint32_t *out) {
+    const int b = (box - 1) / 2;
+    const long double sigma = (long double)box / 4.0L;
+    std::vector<long double> c((size_t)box);
+    long double acc = 0.0L;
+    for (int j = 0; j < box; ++j) {
+        const long double dj = (long double)(j - b);
+        acc += std::exp(-(dj * dj) / (2.0L * sigma * sigma));
+        c[j] = acc;
+    }
+    for (int k = 0; k + 1 < box; ++k) out[k] = (uint32_t)std::floor(std::ldexp(c[k] / c[box - 1], 32));
+}
+
+int32_t check_sampling(const rpf_sampling *cfg, std::string &why) {
+    if (!cfg) { why = "rpf_sampling is NULL"; return RPF_E_BADARG; }
+    for (int i = 0; i < RPF_MAX_BOXES; ++i)
+        if (cfg->draws[i] < 0) { why = "rpf_sampling: a negative draw count"; return RPF_E_BADARG; }
+    return RPF_OK;
+}
+
 namespace {
+
+// the sampled count kernel's table of `box`, on the device
+int32_t ensure_sampling_table(rpf_ctx *ctx, int box) {
+    if (ctx->d_samp_table && ctx->samp_table_box == box) return RPF_OK;
+    std::vector<uint32_t> t((size_t)std::max(box - 1, 1), 0u);
+    sampling_table(box, t.data());
+    int32_t st;
+    ctx->samp_table_box = 0;
+    if ((st = ctx->d_samp_table.ensure(ctx, t.size() * sizeof(uint32_t)))) return st;
+    HIP_TRY(hipMemcpy(ctx->d_samp_table, t.data(), t.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    ctx->samp_table_box = box;
+    return RPF_OK;
+}
 
 // T[k] = k ln k in 2^-44 fixed point (computed in long double, rounded once) and its first differences
 int32_t ensure_tables(rpf_ctx *ctx, int nmax) {
@@ -185,7 +247,7 @@ int bmax_of(int nmax) { return std::max(1, (int)std::sqrt((double)nmax)); }
 
 } // namespace
 
-int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_planes, const double *col_in,
+int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const void *d_planes, const double *col_in,
                    double *col_out, const rpf_debug *dbg_dev, PassSetup &out) {
     if (box < 1 || (box & 1) == 0) return fail(ctx, RPF_E_BADARG, "box must be odd and positive");
     PassParams &p = out.p;
@@ -221,6 +283,13 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     // fp32 pair weights on the streaming / wide kernels: only a pass that runs layout-generic kernels carries the bit (a fused pass
     // of a WIDE_NBHD | STREAM_FAST call keeps generic == 0 and runs exactly as without the flag)
     if ((d->flags & RPF_FLAG_STREAM_FAST) && (p.generic & (kGenericOn | kGenericWide))) p.generic |= kGenericStreamFast;
+    // a sampled pass (validate checked the configuration): draws[pass] > 0; with 0 draws the pass carries no bit and runs as without the flag
+    ctx->samp_now = SampledPass{};
+    if ((d->flags & RPF_FLAG_SAMPLED_NBHD) && ctx->sampling_set && pass >= 0 && pass < RPF_MAX_BOXES && ctx->sampling.draws[pass] > 0) {
+        ctx->samp_now.draws = ctx->sampling.draws[pass];
+        ctx->samp_now.pass_id = (int32_t)((uint32_t)ctx->sampling.pass_id0 + (uint32_t)pass); // (mod 2^32: the key reads it as uint32)
+        p.generic |= kGenericSampled;
+    }
     // the fused kernels address a window's samples by 32-bit byte offsets from its first sample (Window, rpf_filter_impl.inc)
     if (rpf_check_window_span(d->W, d->S, box) != RPF_OK)
         return fail(ctx, RPF_E_UNSUPPORTED, "box*W*S*8 >= 2^32: a window's span in bytes of an fp64 plane must fit 32 bits (narrower slabs or a smaller box)");
@@ -248,6 +317,7 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, const void *d_plane
     // (the 2^-44 tables stop at the old cap: a wide pass reads them only where they are exact, launch_wide)
     if ((st = ensure_tables(ctx, std::min(p.nmax, kMaxNbhd)))) return st;
     if (wide && (st = ensure_wide_table(ctx, p.nmax))) return st;
+    if ((p.generic & kGenericSampled) && (st = ensure_sampling_table(ctx, box))) return st;
     p.pmean = ctx->d_pmean; p.pstd = ctx->d_pstd; p.tfix = ctx->d_tfix; p.dfix = ctx->d_dfix;
     p.nbhd = ctx->d_nbhd; p.status = ctx->d_status;
     if ((st = ctx->d_flat.ensure(ctx, HW))) return st;
@@ -622,6 +692,54 @@ int32_t route_wide_classes(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, 
     return RPF_OK;
 }
 
+// A sampled pass (RPF_FLAG_SAMPLED_NBHD with draws > 0): route 7 with another count kernel and nothing
+// behind the classes.  generic::sampled_count_kernel lists, per pixel, the distinct draws of its key that pass the 3-sigma test;
+// S + draws <= 832 puts every pixel into one of the eight classes, so there is no rest launch, and REF_ABORT is refused, so there
+// is no redo launch.  Pool capacity and growth are route 7's (option "wide_pool").  The lists of this pass are no other pass's:
+// the membership cache of the size-binned route neither serves it nor survives it (d_lists is overwritten).
+int32_t route_sampled(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
+    const size_t HW = (size_t)p_in.W * p_in.H;
+    int32_t st;
+    ctx->last_route = kRouteSampled;
+    ctx->bin_valid = false;
+    PassParams p = p_in;
+    p.masks = nullptr; p.mask_stride = 0;
+    p.redo_list = nullptr; p.redo_count = nullptr;
+    if (p.row_end <= p.row_begin) return RPF_OK;
+    const SampledPass sp = ctx->samp_now;
+    if (sp.draws < 1 || p.S + sp.draws > class_capacity(kNumWave - 1) || !ctx->d_samp_table || ctx->samp_table_box != p.box)
+        return fail(ctx, RPF_E_BADARG, "sampled pass without its configuration (setup_pass prepares it)");
+    const uint64_t npix = (uint64_t)(p.row_end - p.row_begin) * p.W;
+    if ((st = ctx->d_lists.ensure(ctx, (size_t)kNumClasses * HW * sizeof(uint32_t)))) return st;
+    if ((st = ctx->d_wc_base.ensure(ctx, HW * sizeof(uint64_t)))) return st;
+    if ((st = ctx->d_wc_cursor.ensure(ctx, 2 * sizeof(unsigned long long)))) return st;
+    generic::SampledCountArgs a;
+    a.table = ctx->d_samp_table; a.seed = ctx->sampling.seed; a.pass_id = sp.pass_id; a.row_origin = ctx->sampling.row_origin;
+    a.draws = sp.draws;
+    // (a sampled pass lists hundreds of members per pixel where route 7 lists a handful: what the grow-only pool already holds is
+    // offered too, so that the repeat is paid by the first pass of that size only, not by every pass of every call)
+    uint64_t capacity = ctx->tun.wide_pool >= 0 ? (uint64_t)ctx->tun.wide_pool
+                                                : std::max<uint64_t>(8 * npix, ctx->d_wc_pool.ptr ? ctx->d_wc_pool.cap / sizeof(uint32_t) : 0);
+    uint32_t counts[kNumClasses];
+    for (int attempt = 0;; ++attempt) {
+        Range rg("rpf:sampled count + classify (draws, stage 1b test, listed members, lane and wave classes)");
+        if ((st = ctx->d_wc_pool.ensure(ctx, (size_t)std::max<uint64_t>(capacity, 1) * sizeof(uint32_t)))) return st;
+        unsigned long long used = 0;
+        HIP_TRY(hipMemsetAsync(ctx->d_class_counts, 0, kNumClasses * sizeof(uint32_t), s));
+        HIP_TRY(generic::launch_sampled_count(p, a, ctx->d_wc_pool, capacity, ctx->d_wc_base, ctx->d_wc_cursor, s));
+        HIP_TRY(launch_classify(p, ctx->d_lists, ctx->d_class_counts, kNumWave, kRestClass, s));
+        HIP_TRY(hipMemcpyAsync(counts, ctx->d_class_counts, sizeof(counts), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(&used, ctx->d_wc_cursor, sizeof(used), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (used <= capacity) break;
+        if (attempt != 0) return fail(ctx, RPF_E_HIP, "sampled count pass: the member pool overflowed at its exact size");
+        capacity = used; // the sum of N - S over the slab: the same whatever the capacity was
+    }
+    if (counts[kRestClass] != 0) return fail(ctx, RPF_E_HIP, "sampled count pass: a pixel with N > 832");
+    p.members = ctx->d_wc_pool; p.member_base = ctx->d_wc_base;
+    return launch_classes(ctx, p, counts, kNumWave, false, "rpf:sampled pass, packed class", "rpf:sampled pass, wave class", s, launches);
+}
+
 // Routes 4 and 5, the layout-generic route with its small neighbourhoods on class kernels (RPF_FLAG_GENERIC |
 // RPF_FLAG_GENERIC_PACKED on a pass with S <= 64; ... | RPF_FLAG_GENERIC_WAVE on one with S <= 832): stage 1b as its own launch
 // (generic::nbhd_count_kernel: N and the acceptance masks), the pixels dealt by N into n_classes classes -- four lane classes
@@ -665,6 +783,7 @@ int32_t route_generic_classes(rpf_ctx *ctx, const PassParams &p_in, int n_classe
 // Which layout-generic route a pass takes (kRouteNone: none, a pass on the compiled kernels).  Above 64 spp N >= S fits no
 // packed class, above 832 spp no one-wave class: such a pass runs as route 3 does.
 Route generic_route(const PassParams &p) {
+    if (p.generic & kGenericSampled) return kRouteSampled; // (setup_pass marked it: draws > 0)
     if (p.generic & kGenericWide) return (p.generic & kGenericWideClasses) ? kRouteWideClasses : kRouteWide; // (setup_pass marked it)
     if (!p.generic) return kRouteNone;
     if ((p.generic & kGenericWave) && p.S <= class_capacity(kNumWave - 1)) return kRouteGenericWave;
@@ -690,6 +809,7 @@ int32_t route_pass(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *lau
     const bool keeps_list = route == kRouteNone ? ctx->tun.stage_mask == -1 : route != kRouteGeneric && route != kRouteWide;
     if ((st = begin_redo(ctx, p, keeps_list, s))) return st;
     switch (route) {
+    case kRouteSampled: return route_sampled(ctx, p, s, launches);
     case kRouteWideClasses: return route_wide_classes(ctx, p, s, launches);
     case kRouteWide: return route_wide(ctx, p, s, launches);
     case kRouteGenericWave: return route_generic_classes(ctx, p, kNumWave, route, s, launches);
@@ -836,7 +956,7 @@ int32_t run_passes(rpf_ctx *ctx, const rpf_desc *d, const void *d_planes, double
     double *cin = d_colour, *cout = ctx->d_colB; // ping-pong: the filtered colours replace the film's (rpf.cpp:732)
     for (int i = 0; i < d->n_box; ++i) {
         PassSetup ps_;
-        if ((st = setup_pass(ctx, d, d->box_sizes[i], d_planes, cin, cout, nullptr, ps_))) return st;
+        if ((st = setup_pass(ctx, d, d->box_sizes[i], i, d_planes, cin, cout, nullptr, ps_))) return st;
         if ((st = pass_through(ctx, d, cin, cout, 0, d->H, s))) return st;
         if (timing) HIP_TRY(hipEventRecord(ctx->ev[1], s));
         // stage 1a depends on the features only: formed once (the reference recomputes identical values per pass)
@@ -930,7 +1050,7 @@ int32_t run_host_pipeline(rpf_ctx *ctx, const rpf_desc *d, const void *planes_v,
     for (int i = 0; i < d->n_box; ++i) {
         const bool first = i == 0, last = i == d->n_box - 1;
         PassSetup ps_;
-        if ((st = setup_pass(ctx, d, d->box_sizes[i], ctx->d_planes, cin, cout, nullptr, ps_))) return st;
+        if ((st = setup_pass(ctx, d, d->box_sizes[i], i, ctx->d_planes, cin, cout, nullptr, ps_))) return st;
         auto filter_rows = [&](int r0, int r1) -> int32_t {
             PassParams q = ps_.p;
             q.row_begin = std::max(r0, d->row_begin);
@@ -1063,6 +1183,64 @@ int32_t rpf_layout_kernels(const rpf_desc *d, int32_t *generic_out) { return lay
 int32_t rpf_max_nbhd(const rpf_desc *d, int32_t *nmax_out) {
     if (!d || !nmax_out) return RPF_E_BADARG;
     *nmax_out = (d->flags & RPF_FLAG_WIDE_NBHD) ? kMaxWideNbhd : kMaxNbhd;
+    return RPF_OK;
+}
+
+int32_t rpf_set_sampling(rpf_ctx *ctx, const rpf_sampling *cfg) {
+    if (!ctx) return RPF_E_BADARG;
+    std::string why;
+    const int32_t st = check_sampling(cfg, why);
+    if (st) return fail(ctx, st, why);
+    ctx->sampling = *cfg;
+    ctx->sampling_set = true;
+    ctx->bin_valid = false;
+    return RPF_OK;
+}
+
+int32_t rpf_sampling_table(int32_t box, uint32_t *table_out) {
+    if (!table_out || box < 1 || box > 511 || (box & 1) == 0) return RPF_E_BADARG;
+    sampling_table(box, table_out);
+    return RPF_OK;
+}
+
+int32_t rpf_sampling_draws(const rpf_sampling *cfg, int32_t pass, int32_t box, int32_t W, int32_t H, int32_t S, int32_t x, int32_t y,
+                           int32_t *qq_out, int32_t *n_out) {
+    if (!cfg || !qq_out || !n_out || pass < 0 || pass >= RPF_MAX_BOXES || box < 1 || box > 511 || (box & 1) == 0) return RPF_E_BADARG;
+    if (W <= 0 || H <= 0 || S <= 0 || x < 0 || x >= W || y < 0 || y >= H || cfg->draws[pass] < 0) return RPF_E_BADARG;
+    auto mix = [](uint64_t z) {
+        z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+        z ^= z >> 27; z *= 0x94D049BB133111EBull;
+        z ^= z >> 31;
+        return z;
+    };
+    const uint64_t G = 0x9E3779B97F4A7C15ull;
+    const int b = (box - 1) / 2, D = cfg->draws[pass];
+    std::vector<uint32_t> T((size_t)std::max(box - 1, 1), 0u);
+    sampling_table(box, T.data());
+    const int nT = box - 1;
+    auto count_le = [&](uint32_t u) { return (int)(std::upper_bound(T.begin(), T.begin() + nT, u) - T.begin()); };
+    uint64_t h = mix(cfg->seed + G);
+    h = mix(h ^ (uint64_t)((uint32_t)cfg->pass_id0 + (uint32_t)pass)); // (sums mod 2^32: no signed overflow at any configuration)
+    h = mix(h ^ (uint64_t)((uint32_t)cfg->row_origin + (uint32_t)y));
+    h = mix(h ^ (uint64_t)(uint32_t)x);
+    // the window's numbering: candidate_offset of rpf_generic_common.h, inverted
+    const int x0 = std::max(x - b, 0), y0 = std::max(y - b, 0), y1 = std::min(y + b, H - 1);
+    const int nyv = y1 - y0 + 1, centre_rank = (x - x0) * nyv + (y - y0);
+    std::vector<int32_t> qq;
+    qq.reserve((size_t)D);
+    for (int q = 0; q < D; ++q) {
+        const uint64_t r = mix(h + (uint64_t)(q + 1) * G), r2 = mix(r ^ G);
+        const int xn = x + count_le((uint32_t)r) - b, yn = y + count_le((uint32_t)(r >> 32)) - b;
+        const int smp = (int)(((uint64_t)(uint32_t)r2 * (uint32_t)S) >> 32);
+        if (xn < 0 || xn >= W || yn < 0 || yn >= H || (xn == x && yn == y)) continue;
+        int cell = (xn - x0) * nyv + (yn - y0);
+        if (cell > centre_rank) --cell;
+        qq.push_back(cell * S + smp);
+    }
+    std::sort(qq.begin(), qq.end());
+    qq.erase(std::unique(qq.begin(), qq.end()), qq.end());
+    std::copy(qq.begin(), qq.end(), qq_out);
+    *n_out = (int32_t)qq.size();
     return RPF_OK;
 }
 
@@ -1240,6 +1418,7 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *d, int32_t box, cons
     int32_t st = enter(ctx, d, false);
     if (st) return st;
     if (!planes || !colour_out) return fail(ctx, RPF_E_BADARG, "NULL pointer");
+    if ((st = check_sampled(ctx, d, 1))) return st; // pass id pass_id0, draws[0]
     if (d->flags & RPF_FLAG_SPIKE_CLAMP)
         return fail(ctx, RPF_E_UNSUPPORTED, "RPF_FLAG_SPIKE_CLAMP with rpf_filter_pass_debug: the spike pass follows the last pass of "
                                             "a whole call (rpf_filter / _ex / _device / _film); this entry point returns one pass's raw colours");
@@ -1270,7 +1449,7 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *d, int32_t box, cons
     }
     if ((st = begin_call(ctx, s))) return st;
     PassSetup ps_;
-    if ((st = setup_pass(ctx, d, box, ctx->d_planes, ctx->d_colA, ctx->d_colB, &dev, ps_))) return st;
+    if ((st = setup_pass(ctx, d, box, 0, ctx->d_planes, ctx->d_colA, ctx->d_colB, &dev, ps_))) return st;
     HIP_TRY(launch_copy_f64(ctx->d_colA, ctx->d_colB, 3 * ps, s));
     const bool timing = (d->flags & RPF_FLAG_TIMING) != 0;
     HIP_TRY(launch_pixel_stats(ps_.p, s));

@@ -30,6 +30,8 @@ struct rpf_multi {
     double spike_threshold = 1.0; // rpf_multi_set_spike
     int32_t spike_energy = 1;
     rpf_spike_stats spike{};      // the spike pass of the most recent call, merged over the slabs
+    rpf_sampling sampling{};      // rpf_multi_set_sampling: the caller's configuration (every slab adds its first image row to row_origin)
+    bool sampling_set = false;
 };
 
 namespace {
@@ -145,6 +147,10 @@ int32_t multi_run(rpf_multi *m, const rpf_desc *d, const void *planes_v, const f
         const size_t ps = row * q.rows();
         rpf_desc &ds = sd[g];
         ds.H = q.rows(); ds.row_begin = q.ht; ds.row_end = q.ht + (q.b - q.a); ds.n_box = 1;
+        if (m->sampling_set) { // buffer row 0 of the slab is image row a - ht: the slab draws what the whole image draws
+            ctx->sampling = m->sampling;
+            ctx->sampling.row_origin = m->sampling.row_origin + (q.a - q.ht);
+        }
         int32_t e;
         if ((e = ensure_frame(ctx, &ds, ray_weight != nullptr, true))) return e;
         if ((e = ctx->d_colB.ensure(ctx, 3 * ps * sizeof(double)))) return e;
@@ -226,7 +232,7 @@ int32_t multi_run(rpf_multi *m, const rpf_desc *d, const void *planes_v, const f
             hipStream_t s = ctx->stream;
             PassSetup pp;
             int32_t e;
-            if ((e = setup_pass(ctx, &sd[g], box, ctx->d_planes, cin[g], cout[g], nullptr, pp))) return e;
+            if ((e = setup_pass(ctx, &sd[g], box, i, ctx->d_planes, cin[g], cout[g], nullptr, pp))) return e;
             // halo rows pass through (they are refreshed from the neighbour before the next pass)
             if ((e = pass_through(ctx, &sd[g], cin[g], cout[g], 0, sd[g].H, s))) return e;
             if (i == 0) HIP_TRY(launch_pixel_stats(pp.p, s)); // stage 1a depends on the features only
@@ -405,6 +411,17 @@ int32_t rpf_multi_set_spike(rpf_multi *m, double threshold, int32_t preserve_ene
     if (st) return mfail(m, st, why);
     m->spike_threshold = threshold;
     m->spike_energy = preserve_energy;
+    return RPF_OK;
+}
+
+int32_t rpf_multi_set_sampling(rpf_multi *m, const rpf_sampling *cfg) {
+    if (!m) return RPF_E_BADARG;
+    std::string why;
+    const int32_t st = check_sampling(cfg, why);
+    if (st) return mfail(m, st, why);
+    m->sampling = *cfg;
+    m->sampling_set = true;
+    for (rpf_ctx *c : m->ctx) (void)rpf_set_sampling(c, cfg); // multi_run moves each slab's row_origin
     return RPF_OK;
 }
 

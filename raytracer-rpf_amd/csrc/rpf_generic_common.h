@@ -1,11 +1,11 @@
-// rpf_generic_common.h -- what the five layout-generic translation units share (rpf_generic.hip, rpf_generic_packed.hip,
-// rpf_generic_wave.hip, rpf_generic_wide.hip, rpf_generic_wide_count.hip; routes 3 to 7).  Only they include it.  Device
+// rpf_generic_common.h -- what the layout-generic translation units share (rpf_generic.hip, rpf_generic_packed.hip,
+// rpf_generic_wave.hip, rpf_generic_wide.hip, rpf_generic_wide_count.hip, rpf_generic_sampled_count.hip; routes 3 to 8).  Only they include it.  Device
 // code has internal linkage, like rpf_device_common.h: each TU carries its own copy.
 //
 // For every TU: the column counts of a layout (GenericDims), up16 and the size of the fp64 block of the LDS carve-ups (host side), the
 // plane loaders, pair_cols and block_reduce.  Moving these here left the device assembly of every kernel as it was.
 //
-// For the packed kernels and the two count kernels, whose stage bodies call them: the window of stage 1b and the decode of a
+// For the packed kernels and the count kernels, whose stage bodies call them: the window of stage 1b and the decode of a
 // candidate, the 3-sigma test of a wave, the column constants and the bin id, the zero band of stage 3b, the beta numerator, the
 // debug hashes and the store of a filtered colour -- the statements the routes promise the same bits for.
 //

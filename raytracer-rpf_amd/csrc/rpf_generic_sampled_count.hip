@@ -1,0 +1,160 @@
+// rpf_generic_sampled_count.hip -- the count pass of a sampled pass (RPF_FLAG_SAMPLED_NBHD with draws > 0, rpf_query_route 8;
+// DESIGN.md section 13).  Compiled with -ffp-contract=off like every kernel TU.
+//
+// sampled_count_kernel is generic::wide_count_kernel (rpf_generic_wide_count.hip) with another source of candidates: not every
+// sample of the box but the D draws of the pixel's key -- SplitMix64 words mapped through the Gaussian threshold table of the box
+// to a window cell and a sample, integer arithmetic only -- made distinct and put in ascending visiting-order index qq, so that
+// the listed members are a subsequence of the full-box list and depend on nothing but the key.  What stays: one wave per pixel,
+// the strict 3-sigma test of passes_3sigma_wave on 64 candidates at a time, the accepted plane offsets staged per wave in LDS and
+// copied to the member pool behind one cursor reservation per pixel, N = S + accepted into p.nbhd, no pool entry for a pixel
+// that accepts nothing.  What goes: the early exit (S + D <= 832 bounds N by construction) and the flat-pixel proof.
+//
+// Distinct and ordered: an in-wave enumeration sort.  The D indices (0xffffffff for a discarded draw) are staged in LDS in draw
+// order; index i goes to position #{j : key_j < key_i, or key_j == key_i and j < i} of a second array, which makes that array a
+// sorted permutation with duplicates adjacent, and the test loop skips an entry equal to its predecessor.  D * ceil(D / 64) LDS
+// words read per wave, at most 10816 of them, no atomics, no dependence on the order lanes land in (measured: 16 to 25 % of a
+// sampled pass; an in-wave bitonic sort, O(D log^2 D / 64) steps, is what would cut it should the count kernel ever dominate).
+// A bitmap over qq would need box*box*S bits per wave (32 KiB at the widest window): one wave per workgroup at 64 KiB, against
+// four here.
+// LDS per workgroup: 4 waves * 2 arrays * 832 words + the threshold table (512 words) = 28672 bytes, whatever the window.
+#include "rpf_generic_common.h"
+
+#include <algorithm>
+
+namespace rpf {
+namespace generic {
+namespace {
+
+constexpr int kScCap = 832;            // the largest class of the one-wave kernels: S + D <= kScCap
+constexpr int kScTable = 512;          // room for the box - 1 thresholds (box <= 511: box*box*S <= 262144)
+constexpr uint32_t kScNone = ~0u;      // a discarded draw
+constexpr uint64_t kScG = 0x9E3779B97F4A7C15ull;
+
+__device__ __forceinline__ uint64_t sc_mix(uint64_t z) { // the SplitMix64 finaliser
+    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
+    z ^= z >> 27; z *= 0x94D049BB133111EBull;
+    z ^= z >> 31;
+    return z;
+}
+// #{k < n : t[k] <= u} of a non-decreasing table
+__device__ __forceinline__ int sc_count_le(const uint32_t *t, int n, uint32_t u) {
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (t[mid] <= u) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+struct SampledCountOut {
+    uint32_t *pool;              // [capacity] plane offsets of the listed members behind the own samples
+    uint64_t capacity;
+    uint64_t *base;              // [H*W] first pool entry of a pixel with N > S
+    unsigned long long *cursor;  // [1] entries reserved so far
+    const uint32_t *table;       // [box - 1] Gaussian thresholds of the box (rpf_sampling_table)
+    uint64_t seed;
+    int32_t pass_id, row_origin, draws;
+};
+
+// One wave per pixel of rows [row_begin, row_end).
+template <class T>
+__global__ __launch_bounds__(256) void sampled_count_kernel(PassParams p, SampledCountOut o) {
+    __shared__ uint32_t sKey[4][kScCap];  // the draws' qq in draw order; later the accepted plane offsets
+    __shared__ uint32_t sSort[4][kScCap]; // ... in ascending order, duplicates adjacent
+    __shared__ uint32_t sT[kScTable];
+    const int nT = p.box - 1;
+    for (int k = threadIdx.x; k < nT; k += 256) sT[k] = o.table[k];
+    __syncthreads(); // the only barrier: before any wave leaves
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t npix = (uint32_t)(p.row_end - p.row_begin) * (uint32_t)p.W;
+    const uint32_t e = blockIdx.x * 4u + (uint32_t)wv;
+    if (e >= npix) return; // wave-uniform
+    const int W = p.W, H = p.H, S = p.S, b = p.b;
+    const uint64_t HW = (uint64_t)H * W;
+    const uint64_t pix = (uint64_t)p.row_begin * W + e;
+    const int y = (int)(pix / (uint32_t)W), x = (int)(pix - (uint64_t)y * W);
+    const int nF = p.lay.nF, colF = 5 + p.lay.nR;
+    const int D = o.draws; // 1 .. kScCap - S (the route's condition)
+    uint32_t *key = sKey[wv], *srt = sSort[wv];
+
+    // ---- the pixel key and its D draws ---------------------------------------------------------
+    uint64_t h = sc_mix(o.seed + kScG);
+    h = sc_mix(h ^ (uint64_t)(uint32_t)o.pass_id);
+    h = sc_mix(h ^ (uint64_t)((uint32_t)o.row_origin + (uint32_t)y)); // (mod 2^32)
+    h = sc_mix(h ^ (uint64_t)(uint32_t)x);
+    const Window win = make_window(x, y, b, W, H, S);
+    for (int q = lane; q < D; q += 64) {
+        const uint64_t r = sc_mix(h + (uint64_t)(q + 1) * kScG), r2 = sc_mix(r ^ kScG);
+        const int xn = x + sc_count_le(sT, nT, (uint32_t)r) - b, yn = y + sc_count_le(sT, nT, (uint32_t)(r >> 32)) - b;
+        const int s = (int)(((uint64_t)(uint32_t)r2 * (uint32_t)S) >> 32);
+        uint32_t qq = kScNone;
+        if (xn >= 0 && xn < W && yn >= 0 && yn < H && !(xn == x && yn == y)) {
+            int cell = (xn - win.x0) * win.nyv + (yn - win.y0);
+            if (cell > win.centre_rank) --cell; // candidate_offset's numbering skips the centre
+            qq = (uint32_t)(cell * S + s);
+        }
+        key[q] = qq;
+    }
+    wsync();
+    // ---- enumeration sort: ties by draw order, so the ranks are a permutation of 0 .. D - 1 ---------------------------
+    for (int i0 = 0; i0 < D; i0 += 64) {
+        const int i = i0 + lane;
+        const uint32_t ki = i < D ? key[i] : kScNone;
+        int rank = 0;
+        for (int j = 0; j < D; ++j) {
+            const uint32_t kj = key[j]; // the same word in every lane
+            rank += (kj < ki || (kj == ki && j < i)) ? 1 : 0;
+        }
+        if (i < D) srt[rank] = ki;
+    }
+    wsync(); // key[] is dead from here: it takes the accepted offsets
+
+    // ---- stage 1b's test on the distinct draws in ascending qq, 64 at a time (rpf.cpp:576-586) -------------------------
+    int acc = 0;
+    for (int kb = 0; kb < D; kb += 64) {
+        const int k = kb + lane;
+        const uint32_t qq = k < D ? srt[k] : kScNone;
+        bool pass = qq != kScNone && (k == 0 || srt[k - 1] != qq);
+        if (!__any(qq != kScNone)) break; // only discarded draws from here on
+        const uint32_t off = pass ? candidate_offset(win, W, S, (int)qq) : 0u;
+        pass = passes_3sigma_wave<T>(p, colF, nF, off, HW, pix, pass);
+        const unsigned long long mask = __ballot(pass);
+        if (pass) key[acc + __popcll(mask & ((1ull << lane) - 1ull))] = off;
+        acc += __popcll(mask);
+    }
+    if (lane == 0) p.nbhd[pix] = S + acc;
+    if (acc == 0) return;
+    wsync(); // the staged offsets are read by other lanes than wrote them
+    uint32_t lo = 0u, hi = 0u;
+    if (lane == 0) {
+        const unsigned long long at = atomicAdd(o.cursor, (unsigned long long)acc);
+        o.base[pix] = at;
+        lo = (uint32_t)at; hi = (uint32_t)(at >> 32);
+    }
+    const uint64_t at = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)hi) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+    if (at + (uint64_t)acc <= o.capacity)
+        for (int j = lane; j < acc; j += 64) o.pool[at + j] = key[j];
+}
+
+} // namespace
+
+hipError_t launch_sampled_count(const PassParams &p, const SampledCountArgs &a, uint32_t *pool, uint64_t capacity, uint64_t *base,
+                                unsigned long long *cursor, hipStream_t s) {
+    if (pool == nullptr || base == nullptr || cursor == nullptr || a.table == nullptr || p.nbhd == nullptr) return hipErrorInvalidValue;
+    if (p.S < 1 || a.draws < 1 || p.S + a.draws > kScCap || p.box - 1 > kScTable || !p.lay.generic_ok()) return hipErrorInvalidValue;
+    if (p.row_end <= p.row_begin) return hipSuccess;
+    hipError_t e;
+    if ((e = hipMemsetAsync(cursor, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
+    const uint64_t npix = (uint64_t)(p.row_end - p.row_begin) * p.W;
+    const dim3 grid((unsigned)((npix + 3) / 4));
+    SampledCountOut o;
+    o.pool = pool; o.capacity = capacity; o.base = base; o.cursor = cursor;
+    o.table = a.table; o.seed = a.seed; o.pass_id = a.pass_id; o.row_origin = a.row_origin; o.draws = a.draws;
+    if (p.lay.f16) hipLaunchKernelGGL(sampled_count_kernel<__half>, grid, dim3(256), 0, s, p, o);
+    else hipLaunchKernelGGL(sampled_count_kernel<float>, grid, dim3(256), 0, s, p, o);
+    return hipGetLastError();
+}
+
+} // namespace generic
+} // namespace rpf

@@ -43,6 +43,8 @@ enum GenericBits : int32_t {
     kGenericStreamFast = 64,  // RPF_FLAG_STREAM_FAST on a pass that runs layout-generic kernels (kGenericOn or kGenericWide; never set on
                               //   a fused pass): route 3, the rest lists of routes 4 / 5, route 6 and every class and the rest list
                               //   of route 7 launch the fp32-weight instantiations (stream_fast below); redo launches never do
+    kGenericSampled = 128,    // RPF_FLAG_SAMPLED_NBHD on a pass with draws > 0: route 8 whatever the bits above say (route_sampled; the
+                              //   draws and the pass id are rpf_ctx::samp_now, which setup_pass fills); stage 1a is not affected
 };
 
 // everything one pass needs, passed by value to the kernels
@@ -288,6 +290,17 @@ hipError_t launch_filter_wide(const PassParams &p, void *list, void *bins, uint3
 // the slab's windows reach
 hipError_t launch_wide_count(const PassParams &p, uint32_t *pool, uint64_t capacity, uint64_t *base, unsigned long long *cursor,
                              int32_t *nan_flag, hipStream_t s);
+// the count pass of route 8 (rpf_generic_sampled_count.hip, S + draws <= 832): for every pixel of rows
+// [p.row_begin, p.row_end) the distinct draws of its key that pass the 3-sigma test, in ascending visiting order, into
+// pool[base[pix] ..] and N = S + their number into p.nbhd; *cursor as launch_wide_count leaves it.  table: device, the box - 1
+// Gaussian thresholds of p.box
+struct SampledCountArgs {
+    const uint32_t *table;
+    uint64_t seed;
+    int32_t pass_id, row_origin, draws;
+};
+hipError_t launch_sampled_count(const PassParams &p, const SampledCountArgs &a, uint32_t *pool, uint64_t capacity, uint64_t *base,
+                                unsigned long long *cursor, hipStream_t s);
 } // namespace generic
 
 // ---- the spike pass (rpf_spike.hip, RPF_FLAG_SPIKE_CLAMP) -----------------------------------------------

@@ -39,6 +39,14 @@ FLAG_STREAM_FAST = 512
 # Context.set_spike / spike_stats), before the reduce, every download and the film step; independent of every route flag;
 # filter_pass_debug refuses it
 FLAG_SPIKE_CLAMP = 1024
+# the published random-subset gather (Context.set_sampling): a pass with draws > 0 draws that many candidates per
+# pixel instead of walking the box (route 8; fp64; S + draws <= 832); a pass with draws == 0 runs as without the flag.  Refused
+# without set_sampling, under DEGEN_REF_ABORT on a sampled pass, and with FLAG_FAST_WEIGHTS / FLAG_GENERIC_FAST / FLAG_STREAM_FAST.
+# RPF_FLAG_SAMPLED_NBHD of the header.  Its name stands outside the FLAG_* family on purpose: that family is the eleven bits whose
+# rpf_layout_kernels answers tests/golden/flag_table.npz records (words 0 .. 2047), and tests/test_flag_table_cpu.py holds it to
+# exactly those; the twelfth bit has its own table in tests/test_sampled_cpu.py.  The name is provisional: once that test and its
+# recording are widened to twelve bits, it becomes FLAG_SAMPLED_NBHD like the others
+SAMPLED_NBHD_FLAG = 2048
 FLAG_WIDE_NBHD = 64  # passes with 65535 < box*box*S <= 262144 on the wide layout-generic kernel (route 6); max_nbhd() tells the bound
 MAX_NDIM = 40     # the layout-generic kernels take 5 + n_random + n_feat up to this
 PLANES_F32, PLANES_F16 = 0, 1
@@ -51,7 +59,8 @@ EXPORTS = ["rpf_version", "rpf_status_string", "rpf_create", "rpf_destroy", "rpf
            "rpf_multi_query_counters", "rpf_query_nbhd", "rpf_query_route", "rpf_film_filter_table", "rpf_filter_film",
            "rpf_film_splat_device", "rpf_film_window", "rpf_multi_halo_plan", "rpf_multi_filter_film", "rpf_layout_kernels",
            "rpf_max_nbhd", "rpf_wide_table", "rpf_set_spike", "rpf_multi_set_spike", "rpf_query_spike", "rpf_multi_query_spike",
-           "rpf_spike_clamp_device", "rpf_colour_add_device", "rpf_spike_delta"]
+           "rpf_spike_clamp_device", "rpf_colour_add_device", "rpf_spike_delta", "rpf_set_sampling", "rpf_multi_set_sampling",
+           "rpf_sampling_table", "rpf_sampling_draws"]
 
 # the film step: pbrt's PixelFilters (include/rpf_hip.h, rpf_film)
 PIXFILTER_BOX, PIXFILTER_TRIANGLE, PIXFILTER_GAUSSIAN, PIXFILTER_MITCHELL, PIXFILTER_SINC = range(5)
@@ -92,6 +101,40 @@ class SpikeStats(C.Structure):
     """rpf_spike_stats: the spike pass of the most recent call (applied = 0 and zeros when FLAG_SPIKE_CLAMP was off)"""
     _fields_ = [("spike_samples", C.c_int64), ("spike_pixels", C.c_int64), ("skipped_pixels", C.c_int64),
                 ("energy", C.c_double * 3), ("delta", C.c_double * 3), ("spike_ms", C.c_float), ("applied", C.c_int32)]
+
+
+class Sampling(C.Structure):
+    """rpf_sampling: pass p of a call has id pass_id0 + p and draws[p] draws per pixel (0: the pass runs as without
+    SAMPLED_NBHD_FLAG); row_origin is the image row of buffer row 0"""
+    _fields_ = [("seed", C.c_uint64), ("pass_id0", C.c_int32), ("row_origin", C.c_int32), ("draws", C.c_int32 * MAX_BOXES)]
+
+
+def make_sampling(seed, draws, pass_id0=0, row_origin=0):
+    s = Sampling()
+    s.seed, s.pass_id0, s.row_origin = int(seed), int(pass_id0), int(row_origin)
+    for i, d in enumerate(list(draws)[:MAX_BOXES]):
+        s.draws[i] = int(d)
+    return s
+
+
+def sampling_table(box):
+    """rpf_sampling_table (no GPU needed): uint32 [box - 1], the Gaussian thresholds of an odd box"""
+    out = np.zeros(max(int(box) - 1, 1), np.uint32)
+    st = load().rpf_sampling_table(int(box), _p(out))
+    if st != OK:
+        raise RpfError(st, "rpf_sampling_table(box=%r): an even box, or a box outside [1, 511]" % (box,))
+    return out[:int(box) - 1]
+
+
+def sampling_draws(cfg, pass_index, box, W, H, S, x, y):
+    """rpf_sampling_draws (no GPU needed): int32 array, the distinct surviving visiting-order indices of buffer pixel (x, y) in
+    pass `pass_index` of cfg, ascending, before the 3-sigma test"""
+    out = np.zeros(max(int(cfg.draws[pass_index]) if 0 <= pass_index < MAX_BOXES else 0, 1), np.int32)
+    n = C.c_int32(0)
+    st = load().rpf_sampling_draws(C.byref(cfg), int(pass_index), int(box), int(W), int(H), int(S), int(x), int(y), _p(out), C.byref(n))
+    if st != OK:
+        raise RpfError(st, "rpf_sampling_draws(pass=%r, box=%r, W=%r, H=%r, S=%r, x=%r, y=%r)" % (pass_index, box, W, H, S, x, y))
+    return out[:n.value].copy()
 
 
 def spike_delta(row_sums, n_samples):
@@ -280,6 +323,11 @@ def load():
                                                  C.POINTER(SpikeStats), C.c_void_p]
             L.rpf_colour_add_device.argtypes = [C.c_void_p, C.POINTER(Desc), C.c_void_p, C.c_void_p, C.c_void_p]
             L.rpf_spike_delta.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+        if hasattr(L, "rpf_set_sampling"):  # (absent from a build of before sampled neighbourhoods, loaded through RPF_HIP_LIB)
+            L.rpf_set_sampling.argtypes = [C.c_void_p, C.POINTER(Sampling)]
+            L.rpf_multi_set_sampling.argtypes = [C.c_void_p, C.POINTER(Sampling)]
+            L.rpf_sampling_table.argtypes = [C.c_int32, C.c_void_p]
+            L.rpf_sampling_draws.argtypes = [C.POINTER(Sampling)] + [C.c_int32] * 7 + [C.c_void_p, C.POINTER(C.c_int32)]
         L.rpf_host_alloc.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
         L.rpf_host_free.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
@@ -360,8 +408,8 @@ class Context:
         """kernel route of the last pass: 0 fused, 1 count first, 2 size-binned, 3 the layout-generic kernels
         (FLAG_GENERIC), 4 the same with small neighbourhoods packed (FLAG_GENERIC_PACKED), 5 the same with
         64 < N <= 832 on the one-wave generic kernels (FLAG_GENERIC_WAVE; 3 for a pass with S > 832), 6 the wide kernel
-        (FLAG_WIDE_NBHD on a pass with box*box*S > 65535), 7 such a pass dealt by size class (FLAG_WIDE_CLASSES); -1 before
-        any pass.  FLAG_GENERIC_FAST and FLAG_STREAM_FAST change no route
+        (FLAG_WIDE_NBHD on a pass with box*box*S > 65535), 7 such a pass dealt by size class (FLAG_WIDE_CLASSES), 8 a sampled
+        pass (SAMPLED_NBHD_FLAG with draws > 0); -1 before any pass.  FLAG_GENERIC_FAST and FLAG_STREAM_FAST change no route
         (rpf_query_route)"""
         r = C.c_int32(-1)
         self._check(self._L.rpf_query_route(self._h, C.byref(r)))
@@ -377,6 +425,11 @@ class Context:
         s = SpikeStats()
         self._check(self._L.rpf_query_spike(self._h, C.byref(s)))
         return s
+
+    # ---- sampled neighbourhoods (SAMPLED_NBHD_FLAG) ---------------------------------------------------------
+    def set_sampling(self, cfg):
+        """rpf_set_sampling: cfg a Sampling (make_sampling), or None -> RPF_E_BADARG as the ABI answers a NULL pointer"""
+        self._check(self._L.rpf_set_sampling(self._h, None if cfg is None else C.byref(cfg)))
 
     def spike_clamp_device(self, desc, d_colour, threshold=1.0, stream=None):
         """rpf_spike_clamp_device: the clamp half on rows [row_begin, row_end) of device colours (raw pointer, 3 fp64 planes);
@@ -539,6 +592,12 @@ class MultiContext:
     def set_spike(self, threshold=1.0, preserve_energy=True):
         """rpf_multi_set_spike: the spike pass's parameters for every slab (Context.set_spike)"""
         st = self._L.rpf_multi_set_spike(self._h, float(threshold), int(preserve_energy))
+        if st != OK:
+            raise RpfError(st, self._L.rpf_multi_last_error(self._h).decode())
+
+    def set_sampling(self, cfg):
+        """rpf_multi_set_sampling: the configuration of every slab (each adds its first image row to cfg.row_origin)"""
+        st = self._L.rpf_multi_set_sampling(self._h, None if cfg is None else C.byref(cfg))
         if st != OK:
             raise RpfError(st, self._L.rpf_multi_last_error(self._h).decode())
 

@@ -37,12 +37,25 @@ def buffer_rows(slab):
     return slab.halo_top + n + slab.halo_bottom, slab.halo_top, slab.halo_top + n
 
 
+def check_desc(desc):
+    """Refuses a descriptor these helpers cannot drive yet.  SAMPLED_NBHD_FLAG: a sampled pass keys every pixel by its IMAGE row
+    and by the pass id, so a rank would have to set ``Sampling.row_origin`` to its buffer's first image row and ``pass_id0`` to
+    the pass of each one-pass call; nothing here does, and a rank that filtered with the whole
+    image's configuration would silently draw other samples than the whole image does."""
+    from . import hip
+    if desc.flags & hip.SAMPLED_NBHD_FLAG:
+        raise NotImplementedError("slabs: SAMPLED_NBHD_FLAG (RPF_FLAG_SAMPLED_NBHD) is not supported across ranks yet: each rank must set "
+                                  "Sampling.row_origin (image row of its buffer row 0) and pass_id0 per one-pass call itself "
+                                  "(INTEGRATION.md section 2f), or use MultiContext, which does")
+    return desc
+
+
 def film_halo_rows(desc, film):
     """rows of each neighbour a slab must hold for the film step: the gather's row half-width for the WHOLE image
     (rpf_film_window; desc and film describe the whole sample film).  ``slab_for`` is called with the larger of this and
     the box halo."""
     from . import hip
-    return hip.film_window(desc, film)[1]
+    return hip.film_window(check_desc(desc), film)[1]
 
 
 def film_for_slab(film, slab, H):
