@@ -190,6 +190,29 @@ enum {
                                   the redo kernels run their own full-box stage 1b), the flag with RPF_FLAG_FAST_WEIGHTS,
                                   RPF_FLAG_GENERIC_FAST or RPF_FLAG_STREAM_FAST (sampled passes are fp64; rpf_layout_kernels
                                   answers the same way) (RPF_E_UNSUPPORTED). */
+    RPF_FLAG_MEMBER_TEST = 4096,  /* opt-in: the published membership test.  Stage 1b's test takes a multiple of sigma and an
+                                  absolute floor per feature (rpf_set_membership below): a candidate is
+                                  rejected on feature k iff |f_k - m_k| >= sd_k * mult_k AND |f_k - m_k| > fl_k, fl_k = -inf when
+                                  sd_k > floor_k, else floor_k -- so a flat pixel (sd_k = 0) accepts its flat neighbours instead
+                                  of rejecting everything.  mult 3 and a negative floor on every feature is the reference's test
+                                  on every input.  Own samples first, the visiting order and every stage behind the list are
+                                  unchanged.  The flag covers every pass of a call.  A full-box pass takes route 9
+                                  (rpf_query_route): a count kernel lists the members of every pixel with N <= 832, the packed
+                                  and one-wave layout-generic kernels filter them by size class, the wide kernel takes the
+                                  pixels with N > 832 under the same test; redo_pixels is 0, filter_kernel_launches counts one
+                                  launch per non-empty class plus one for a non-empty rest list, sum_nbhd / max_nbhd /
+                                  rpf_query_nbhd report the new N.  The member pool grows to the sum of N - S over the listed
+                                  pixels (option "wide_pool" sets its first size): about pixels * 384 * 4 bytes, 3 GB, on a
+                                  flat 1080p frame of 8 spp at box 7.  A sampled pass (RPF_FLAG_SAMPLED_NBHD, draws > 0) stays
+                                  route 8 and applies the test to its draws.  A call without the flag is not affected.  The two
+                                  compiled layouts take the flag alone, any other layout needs RPF_FLAG_GENERIC;
+                                  rpf_layout_kernels reports *generic_out as without it; rpf_max_nbhd is unchanged.  Every
+                                  filter entry point takes the flag; one that runs no pass ignores it.  Refused before any
+                                  device work: the flag without a prior rpf_set_membership (RPF_E_BADARG); under
+                                  RPF_DEGEN_REF_ABORT (the reference has no such test, and the redo kernels run their own
+                                  stage 1b), with RPF_FLAG_FAST_WEIGHTS, RPF_FLAG_GENERIC_FAST or RPF_FLAG_STREAM_FAST (fp64
+                                  only; rpf_layout_kernels answers the same way), a full-box pass with S > 832
+                                  (RPF_E_UNSUPPORTED). */
     RPF_FLAG_STREAM_FAST = 512 /* opt-in, modifies RPF_FLAG_GENERIC and / or RPF_FLAG_WIDE_NBHD: the two kernels that walk a
                                   neighbourhood of any size with 256 threads -- the generic filter kernel (route 3, the rest
                                   list N > 64 / N > 832 of routes 4 / 5) and the wide kernel (route 6, the rest list N > 832 of
@@ -380,7 +403,10 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *desc, int32_t box, c
  * pixels the packed and the one-wave kernels put on the redo list.
  * A sampled pass (RPF_FLAG_SAMPLED_NBHD with draws > 0: route 8) counts one launch per non-empty packed or one-wave class and
  * nothing else -- S + draws <= 832 leaves no rest list, and RPF_DEGEN_REF_ABORT is refused -- and leaves redo_pixels 0;
- * sum_nbhd / max_nbhd are those of the sampled neighbourhoods. */
+ * sum_nbhd / max_nbhd are those of the sampled neighbourhoods.
+ * A full-box pass under RPF_FLAG_MEMBER_TEST (route 9) counts one launch per non-empty packed or one-wave class and one for the
+ * wide kernel when some pixel has N > 832; RPF_DEGEN_REF_ABORT is refused, so redo_pixels is 0; sum_nbhd / max_nbhd are those
+ * of the neighbourhoods the configured test leaves. */
 int32_t rpf_query_counters(rpf_ctx *ctx, rpf_counters *out);
 
 /* neighbourhood size N of every pixel (rpf.cpp:586: the neighbourhood vector's size) as the last pass of the most recent
@@ -396,7 +422,9 @@ int32_t rpf_query_nbhd(rpf_ctx *ctx, int32_t *nbhd_out, int64_t count);
  * on a pass with S <= 64), 5 = the same with 64 < N <= 832 on the one-wave layout-generic kernels (... | RPF_FLAG_GENERIC_WAVE
  * on a pass with S <= 832), 6 = the wide layout-generic kernel (RPF_FLAG_WIDE_NBHD on a pass with box*box*S > 65535),
  * 7 = such a pass counted first and dealt by size class (... | RPF_FLAG_WIDE_CLASSES, S <= 832),
- * 8 = a sampled pass (RPF_FLAG_SAMPLED_NBHD with draws > 0: the one route whose member lists differ, by definition),
+ * 8 = a sampled pass (RPF_FLAG_SAMPLED_NBHD with draws > 0: its member lists differ, by definition),
+ * 9 = a full-box pass under RPF_FLAG_MEMBER_TEST (count kernel with the configured membership test, size classes, the wide
+ * kernel for N > 832; its member lists are the reference's only under the reference's multiples and floors),
  * -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1. */
 int32_t rpf_query_route(rpf_ctx *ctx, int32_t *route_out);
 
@@ -624,6 +652,32 @@ int32_t rpf_sampling_table(int32_t box, uint32_t *table_out);
  * a negative draw count, an even or out-of-range box, non-positive sizes or a pixel outside the buffer. */
 int32_t rpf_sampling_draws(const rpf_sampling *cfg, int32_t pass, int32_t box, int32_t W, int32_t H, int32_t S, int32_t x,
                            int32_t y, int32_t *qq_out, int32_t *n_out);
+
+/* ---- the membership test of stage 1b (RPF_FLAG_MEMBER_TEST) ----------------------------------------
+ * Feature k < n_feat of the descriptor has a multiple mult[k] of the pixel's sigma and an absolute floor floor[k]; with
+ * a = |(double)f_k - m_k|, lim = sd_k * mult[k] (one rounding) and fl = sd_k > floor[k] ? -inf : floor[k], a candidate is
+ * rejected on k iff a >= lim && a > fl, and is a member iff no feature rejects it.  Every comparison with a NaN is false: a
+ * NaN never rejects.  mult 3 with a negative floor on every feature is the reference's test on every input. */
+typedef struct rpf_membership {
+    double mult[RPF_MAX_NDIM];
+    double floor[RPF_MAX_NDIM];
+} rpf_membership;
+
+/* RPF_E_BADARG for a NULL pointer, a mult that is not finite and > 0, or a floor that is NaN or +inf, in ANY of the
+ * RPF_MAX_NDIM entries (so that a later descriptor with any n_feat is covered); needs no device work.  The configuration
+ * stays until replaced. */
+int32_t rpf_set_membership(rpf_ctx *ctx, const rpf_membership *cfg);
+int32_t rpf_multi_set_membership(rpf_multi *m, const rpf_membership *cfg);
+
+/* Fills all RPF_MAX_NDIM entries of *out (those from n_feat on as kind 0 has them).  Host only, no device.
+ * kind 0, the reference: every multiple 3, every floor -1 (any 1 <= n_feat <= RPF_MAX_NDIM).
+ * kind 1, "published, 19-dim layout": multiples 3, and 30 on features 3..5 and 9..11 (the world positions p0 and p1); floors
+ * 0.1; needs n_feat == 12.  These constants are written down FROM MEMORY of the paper's Algorithm 2 (3 sigma generally, 30
+ * sigma for world position, floor 0.1): the paper was not at hand, and nothing in the library depends on them.  A floor on a
+ * world position is scene-scale dependent (positions span +-10^3): a caller is expected to set those floors for
+ * the scene, the preset is a convenience.
+ * RPF_E_BADARG for NULL, an unknown kind, n_feat outside [1, RPF_MAX_NDIM], or kind 1 with n_feat != 12. */
+int32_t rpf_membership_preset(int32_t kind, int32_t n_feat, rpf_membership *out);
 
 #ifdef __cplusplus
 }

@@ -57,9 +57,12 @@ enum Route : int {
     kRouteWide = 6,          // the wide kernel, one launch
     kRouteWideClasses = 7,   // a wide pass counted first and dealt by size class
     kRouteSampled = 8,       // a sampled pass: the draws' count kernel, then the class kernels on its member lists
+    kRouteMemberTest = 9,    // a full-box pass under RPF_FLAG_MEMBER_TEST: route 7's structure with the configured test
 };
 
 static_assert(sizeof(rpf_sampling) == 48 && offsetof(rpf_sampling, draws) == 16, "rpf_sampling is ABI");
+static_assert(sizeof(rpf_membership) == 2 * RPF_MAX_NDIM * sizeof(double) && offsetof(rpf_membership, floor) == RPF_MAX_NDIM * sizeof(double),
+              "rpf_membership is ABI, and the image of the device table: mult[RPF_MAX_NDIM] | floor[RPF_MAX_NDIM]");
 
 // The sampled pass in progress (RPF_FLAG_SAMPLED_NBHD; setup_pass fills it, route_sampled reads it): draws == 0, not sampled
 struct SampledPass {
@@ -130,6 +133,10 @@ struct rpf_ctx {
     bool sampling_set = false;
     rpf::SampledPass samp_now;                  // of the pass setup_pass prepared last
     rpf::DevBuf<uint32_t> d_samp_table; int samp_table_box = 0; // the Gaussian thresholds of that box (rpf_sampling_table)
+    // the membership test (RPF_FLAG_MEMBER_TEST)
+    rpf_membership membership{};                // rpf_set_membership
+    bool membership_set = false;
+    rpf::DevBuf<double> d_member; bool member_fresh = false; // its device image, which setup_pass uploads when it is stale
 };
 
 namespace rpf {
@@ -176,6 +183,8 @@ void wide_table(int nmax, uint64_t *out); // out[k] = round(k ln k * 2^kTWideBit
 void sampling_table(int box, uint32_t *out); // the box - 1 Gaussian thresholds of an odd box (rpf_sampling_table)
 int32_t check_sampling(const rpf_sampling *cfg, std::string &why); // what rpf_set_sampling refuses
 int32_t check_sampled(rpf_ctx *ctx, const rpf_desc *d, int n_pass); // RPF_FLAG_SAMPLED_NBHD of a call that runs n_pass passes
+int32_t check_membership(const rpf_membership *cfg, std::string &why); // what rpf_set_membership refuses
+int32_t check_member_test(rpf_ctx *ctx, const rpf_desc *d, int n_pass); // RPF_FLAG_MEMBER_TEST of a call that runs n_pass passes
 int32_t validate(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes);
 int32_t enter(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes); // validate, then make the context's device current
 

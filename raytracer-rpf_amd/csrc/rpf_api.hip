@@ -47,6 +47,9 @@ struct FlagRule {
 };
 constexpr uint32_t kPackedRoute = RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED;
 constexpr FlagRule kFlagRules[] = {
+    {RPF_FLAG_MEMBER_TEST, 0, 0, RPF_FLAG_FAST_WEIGHTS, "RPF_FLAG_MEMBER_TEST with RPF_FLAG_FAST_WEIGHTS: passes under the membership test are fp64 throughout"},
+    {RPF_FLAG_MEMBER_TEST, 0, 0, RPF_FLAG_GENERIC_FAST, "RPF_FLAG_MEMBER_TEST with RPF_FLAG_GENERIC_FAST: passes under the membership test are fp64 throughout"},
+    {RPF_FLAG_MEMBER_TEST, 0, 0, RPF_FLAG_STREAM_FAST, "RPF_FLAG_MEMBER_TEST with RPF_FLAG_STREAM_FAST: passes under the membership test are fp64 throughout"},
     {RPF_FLAG_SAMPLED_NBHD, 0, 0, RPF_FLAG_FAST_WEIGHTS, "RPF_FLAG_SAMPLED_NBHD with RPF_FLAG_FAST_WEIGHTS: sampled passes are fp64 throughout"},
     {RPF_FLAG_SAMPLED_NBHD, 0, 0, RPF_FLAG_GENERIC_FAST, "RPF_FLAG_SAMPLED_NBHD with RPF_FLAG_GENERIC_FAST: sampled passes are fp64 throughout"},
     {RPF_FLAG_SAMPLED_NBHD, 0, 0, RPF_FLAG_STREAM_FAST, "RPF_FLAG_SAMPLED_NBHD with RPF_FLAG_STREAM_FAST: sampled passes are fp64 throughout"},
@@ -125,6 +128,22 @@ int32_t check_sampled(rpf_ctx *ctx, const rpf_desc *d, int n_pass) {
     return RPF_OK;
 }
 
+// RPF_FLAG_MEMBER_TEST on the same terms, after check_sampled: the configuration, the policy, and S of every full-box pass -- one
+// without draws of its own -- against the largest size class (a pixel's own samples are members of a class kernel's list)
+int32_t check_member_test(rpf_ctx *ctx, const rpf_desc *d, int n_pass) {
+    if (!(d->flags & RPF_FLAG_MEMBER_TEST)) return RPF_OK;
+    if (!ctx->membership_set) return fail(ctx, RPF_E_BADARG, "RPF_FLAG_MEMBER_TEST without a prior rpf_set_membership");
+    if (d->degenerate_policy == RPF_DEGEN_REF_ABORT)
+        return fail(ctx, RPF_E_UNSUPPORTED, "RPF_FLAG_MEMBER_TEST under RPF_DEGEN_REF_ABORT: the reference has no such test to reproduce, and "
+                                            "the redo kernels run their own stage 1b (use RPF_DEGEN_EPS)");
+    const bool draws = (d->flags & RPF_FLAG_SAMPLED_NBHD) && ctx->sampling_set;
+    for (int i = 0; i < std::max(0, std::min(n_pass, RPF_MAX_BOXES)); ++i)
+        if (!(draws && ctx->sampling.draws[i] > 0) && d->S > 832)
+            return fail(ctx, RPF_E_UNSUPPORTED, "RPF_FLAG_MEMBER_TEST: a full-box pass with S > 832 (the largest size class of the one-wave "
+                                                "kernels; the count kernel deals every pixel by N >= S)");
+    return RPF_OK;
+}
+
 int32_t validate(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes) {
     if (!ctx) return RPF_E_BADARG;
     if (!d) return fail(ctx, RPF_E_BADARG, "desc is NULL");
@@ -142,8 +161,9 @@ int32_t validate(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes) {
     if (d->degenerate_policy < 0 || d->degenerate_policy > RPF_DEGEN_EPS)
         return fail(ctx, RPF_E_BADARG, "unknown degenerate_policy");
     if (need_boxes) {
-        const int32_t st = check_sampled(ctx, d, d->n_box);
+        int32_t st = check_sampled(ctx, d, d->n_box);
         if (st) return st;
+        if ((st = check_member_test(ctx, d, d->n_box))) return st;
     }
     if (need_boxes) {
         if (d->n_box < 1 || d->n_box > RPF_MAX_BOXES) return fail(ctx, RPF_E_BADARG, "n_box must be 1..8");
@@ -199,7 +219,27 @@ int32_t check_sampling(const rpf_sampling *cfg, std::string &why) {
     return RPF_OK;
 }
 
+int32_t check_membership(const rpf_membership *cfg, std::string &why) {
+    if (!cfg) { why = "rpf_membership is NULL"; return RPF_E_BADARG; }
+    for (int k = 0; k < RPF_MAX_NDIM; ++k) {
+        if (!(std::isfinite(cfg->mult[k]) && cfg->mult[k] > 0.0)) { why = "rpf_membership: a multiple that is not finite and > 0"; return RPF_E_BADARG; }
+        if (std::isnan(cfg->floor[k]) || (std::isinf(cfg->floor[k]) && cfg->floor[k] > 0.0)) { why = "rpf_membership: a floor that is NaN or +inf"; return RPF_E_BADARG; }
+    }
+    return RPF_OK;
+}
+
 namespace {
+
+// the multiples and floors of RPF_FLAG_MEMBER_TEST on the device: mult[RPF_MAX_NDIM] | floor[RPF_MAX_NDIM]
+int32_t ensure_member_table(rpf_ctx *ctx) {
+    if (ctx->d_member && ctx->member_fresh) return RPF_OK;
+    int32_t st;
+    ctx->member_fresh = false;
+    if ((st = ctx->d_member.ensure(ctx, sizeof(rpf_membership)))) return st;
+    HIP_TRY(hipMemcpy(ctx->d_member, &ctx->membership, sizeof(rpf_membership), hipMemcpyHostToDevice));
+    ctx->member_fresh = true;
+    return RPF_OK;
+}
 
 // the sampled count kernel's table of `box`, on the device
 int32_t ensure_sampling_table(rpf_ctx *ctx, int box) {
@@ -290,6 +330,9 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
         ctx->samp_now.pass_id = (int32_t)((uint32_t)ctx->sampling.pass_id0 + (uint32_t)pass); // (mod 2^32: the key reads it as uint32)
         p.generic |= kGenericSampled;
     }
+    // the membership test (validate checked the configuration and refused every fp32 flag): every pass of the call carries the bit
+    const bool member = (d->flags & RPF_FLAG_MEMBER_TEST) && ctx->membership_set;
+    if (member) p.generic |= kGenericMemberTest;
     // the fused kernels address a window's samples by 32-bit byte offsets from its first sample (Window, rpf_filter_impl.inc)
     if (rpf_check_window_span(d->W, d->S, box) != RPF_OK)
         return fail(ctx, RPF_E_UNSUPPORTED, "box*W*S*8 >= 2^32: a window's span in bytes of an fp64 plane must fit 32 bits (narrower slabs or a smaller box)");
@@ -317,13 +360,16 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
     // (the 2^-44 tables stop at the old cap: a wide pass reads them only where they are exact, launch_wide)
     if ((st = ensure_tables(ctx, std::min(p.nmax, kMaxNbhd)))) return st;
     if (wide && (st = ensure_wide_table(ctx, p.nmax))) return st;
+    // (route 9's rest launch reads the 2^-44 table where that is exact, as a forced wide pass does, and route 6's table above)
+    if (member && !wide && p.nmax > kTFixExact && (st = ensure_wide_table(ctx, p.nmax))) return st;
+    if (member && (st = ensure_member_table(ctx))) return st;
     if ((p.generic & kGenericSampled) && (st = ensure_sampling_table(ctx, box))) return st;
     p.pmean = ctx->d_pmean; p.pstd = ctx->d_pstd; p.tfix = ctx->d_tfix; p.dfix = ctx->d_dfix;
     p.nbhd = ctx->d_nbhd; p.status = ctx->d_status;
     if ((st = ctx->d_flat.ensure(ctx, HW))) return st;
     p.flat = ctx->d_flat; p.nan_flag = ctx->d_nan_flag;
     if (dbg_dev) p.dbg = *dbg_dev;
-    if (wide) { // the wide kernel's carve-up: what 160 KiB leave of the joint table is one band of it
+    if (wide || (member && !(p.generic & kGenericSampled))) { // the wide kernel's carve-up: what 160 KiB leave of the joint table is one band of it
         out.lds = generic_wide_carve(p.lay, p.nmax, stream_fast(p)).total;
     } else if (p.generic) { // the generic kernel's own carve-up (one kernel for every neighbourhood size of the pass)
         out.lds = generic_carve(p.lay, p.nmax, stream_fast(p)).total;
@@ -388,14 +434,14 @@ int32_t launch_streaming(rpf_ctx *ctx, const PassParams &p, uint64_t pixels, con
 // The same for the wide kernel.  The table: T_w (2^-41), or -- a forced pass below 48586 samples, where that one is exact and
 // three bits finer -- the 2^-44 table of the other kernels, so that such a pass gives route 3's bits.
 int32_t launch_wide(rpf_ctx *ctx, const PassParams &p, uint64_t pixels, const SlotRule &rule, const uint32_t *count_dev,
-                    hipStream_t s, int *launches, bool fast) {
+                    hipStream_t s, int *launches, bool fast, const double *member = nullptr) {
     const uint32_t slots = slot_count(rule, p, pixels);
     int32_t st;
     if ((st = ensure_slot_scratch(ctx, p, slots, rule.bin_bytes))) return st;
     const bool fine = p.nmax <= kTFixExact;
     if (!fine && (!ctx->d_twide || ctx->twide_n < p.nmax + 1)) return fail(ctx, RPF_E_BADARG, "wide pass without its table (setup_pass builds it)");
     HIP_TRY(generic::launch_filter_wide(p, ctx->d_big_list, ctx->d_big_bins, slots, fine ? ctx->d_tfix.ptr : ctx->d_twide.ptr,
-                                        fine ? 44 : kTWideBits, count_dev, s, fast));
+                                        fine ? 44 : kTWideBits, count_dev, s, fast, member));
     if (launches) ++*launches;
     return RPF_OK;
 }
@@ -644,10 +690,12 @@ int32_t launch_classes(rpf_ctx *ctx, const PassParams &p, const uint32_t *counts
 // window), its size read on the device.  The pool holds `wide_pool` entries (option; default 8 per pixel of the slab); when
 // the cursor says the data needed more, the pool is grown to exactly that and the count and the classification are repeated:
 // which kernel filters a pixel never depends on the capacity.
-int32_t route_wide_classes(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
+// member != null: route 9 (route_member_test below), the same structure with the count kernel's and the wide kernel's MEMBER
+// instantiations; null: route 7, which runs as it always did.
+int32_t route_wide_classes(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches, const double *member = nullptr) {
     const size_t HW = (size_t)p_in.W * p_in.H;
     int32_t st;
-    ctx->last_route = kRouteWideClasses;
+    ctx->last_route = member ? kRouteMemberTest : kRouteWideClasses;
     PassParams p = p_in;
     p.masks = nullptr; p.mask_stride = 0;
     if (p.row_end <= p.row_begin) return RPF_OK;
@@ -656,6 +704,8 @@ int32_t route_wide_classes(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, 
     if ((st = ctx->d_wc_base.ensure(ctx, HW * sizeof(uint64_t)))) return st;
     if ((st = ctx->d_wc_cursor.ensure(ctx, 2 * sizeof(unsigned long long)))) return st;
     uint64_t capacity = ctx->tun.wide_pool >= 0 ? (uint64_t)ctx->tun.wide_pool : 8 * npix;
+    // (route 9 lists hundreds of members per pixel, as route 8 does: what the grow-only pool already holds is offered too)
+    if (member && ctx->tun.wide_pool < 0 && ctx->d_wc_pool.ptr) capacity = std::max<uint64_t>(capacity, ctx->d_wc_pool.cap / sizeof(uint32_t));
     uint32_t counts[kNumClasses];
     for (int attempt = 0;; ++attempt) {
         Range rg("rpf:wide count + classify (stage 1b test, listed members, lane and wave classes)");
@@ -663,7 +713,7 @@ int32_t route_wide_classes(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, 
         unsigned long long used = 0;
         HIP_TRY(hipMemsetAsync(ctx->d_class_counts, 0, kNumClasses * sizeof(uint32_t), s));
         HIP_TRY(generic::launch_wide_count(p, ctx->d_wc_pool, capacity, ctx->d_wc_base, ctx->d_wc_cursor,
-                                           reinterpret_cast<int32_t *>(ctx->d_wc_cursor.ptr + 1), s));
+                                           reinterpret_cast<int32_t *>(ctx->d_wc_cursor.ptr + 1), s, member));
         HIP_TRY(launch_classify(p, ctx->d_lists, ctx->d_class_counts, kNumWave, kRestClass, s));
         HIP_TRY(hipMemcpyAsync(counts, ctx->d_class_counts, sizeof(counts), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(&used, ctx->d_wc_cursor, sizeof(used), hipMemcpyDeviceToHost, s));
@@ -680,7 +730,7 @@ int32_t route_wide_classes(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, 
         Range rg("rpf:wide filter kernel (N > 832)");
         w.pix_list = ctx->d_lists + (size_t)kRestClass * HW;
         w.list_count = counts[kRestClass];
-        if ((st = launch_wide(ctx, w, w.list_count, kWideSlots, nullptr, s, launches, stream_fast(p)))) return st;
+        if ((st = launch_wide(ctx, w, w.list_count, kWideSlots, nullptr, s, launches, stream_fast(p), member))) return st;
     }
     if (p.redo_list != nullptr) {
         Range rg("rpf:redo (wide kernel)");
@@ -690,6 +740,17 @@ int32_t route_wide_classes(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, 
         if ((st = launch_wide(ctx, w, kCountOnDevice, kWideRedoSlots, p.redo_count, s, launches, false))) return st;
     }
     return RPF_OK;
+}
+
+// A full-box pass under RPF_FLAG_MEMBER_TEST (route 9): route 7's structure, whatever the window's size, with
+// the configured test in the count kernel and in the wide kernel's own stage 1b.  The class kernels read the listed members as
+// they are.  REF_ABORT is refused, so there is no redo list; the lists of this pass are no other pass's (the membership cache of
+// the size-binned route neither serves it nor survives it).
+int32_t route_member_test(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *launches) {
+    ctx->bin_valid = false;
+    if (!ctx->d_member || !ctx->member_fresh || p.S > class_capacity(kNumWave - 1) || p.redo_list != nullptr)
+        return fail(ctx, RPF_E_BADARG, "pass under the membership test without its configuration (setup_pass prepares it)");
+    return route_wide_classes(ctx, p, s, launches, ctx->d_member);
 }
 
 // A sampled pass (RPF_FLAG_SAMPLED_NBHD with draws > 0): route 7 with another count kernel and nothing
@@ -716,6 +777,10 @@ int32_t route_sampled(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *
     generic::SampledCountArgs a;
     a.table = ctx->d_samp_table; a.seed = ctx->sampling.seed; a.pass_id = sp.pass_id; a.row_origin = ctx->sampling.row_origin;
     a.draws = sp.draws;
+    if (p.generic & kGenericMemberTest) { // with RPF_FLAG_MEMBER_TEST the draws meet the configured test
+        if (!ctx->d_member || !ctx->member_fresh) return fail(ctx, RPF_E_BADARG, "pass under the membership test without its configuration (setup_pass prepares it)");
+        a.member = ctx->d_member;
+    }
     // (a sampled pass lists hundreds of members per pixel where route 7 lists a handful: what the grow-only pool already holds is
     // offered too, so that the repeat is paid by the first pass of that size only, not by every pass of every call)
     uint64_t capacity = ctx->tun.wide_pool >= 0 ? (uint64_t)ctx->tun.wide_pool
@@ -784,6 +849,7 @@ int32_t route_generic_classes(rpf_ctx *ctx, const PassParams &p_in, int n_classe
 // packed class, above 832 spp no one-wave class: such a pass runs as route 3 does.
 Route generic_route(const PassParams &p) {
     if (p.generic & kGenericSampled) return kRouteSampled; // (setup_pass marked it: draws > 0)
+    if (p.generic & kGenericMemberTest) return kRouteMemberTest; // (... a full-box pass of a call under RPF_FLAG_MEMBER_TEST)
     if (p.generic & kGenericWide) return (p.generic & kGenericWideClasses) ? kRouteWideClasses : kRouteWide; // (setup_pass marked it)
     if (!p.generic) return kRouteNone;
     if ((p.generic & kGenericWave) && p.S <= class_capacity(kNumWave - 1)) return kRouteGenericWave;
@@ -810,6 +876,7 @@ int32_t route_pass(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *lau
     if ((st = begin_redo(ctx, p, keeps_list, s))) return st;
     switch (route) {
     case kRouteSampled: return route_sampled(ctx, p, s, launches);
+    case kRouteMemberTest: return route_member_test(ctx, p, s, launches);
     case kRouteWideClasses: return route_wide_classes(ctx, p, s, launches);
     case kRouteWide: return route_wide(ctx, p, s, launches);
     case kRouteGenericWave: return route_generic_classes(ctx, p, kNumWave, route, s, launches);
@@ -1197,6 +1264,30 @@ int32_t rpf_set_sampling(rpf_ctx *ctx, const rpf_sampling *cfg) {
     return RPF_OK;
 }
 
+int32_t rpf_set_membership(rpf_ctx *ctx, const rpf_membership *cfg) {
+    if (!ctx) return RPF_E_BADARG;
+    std::string why;
+    const int32_t st = check_membership(cfg, why);
+    if (st) return fail(ctx, st, why);
+    ctx->membership = *cfg;
+    ctx->membership_set = true;
+    ctx->member_fresh = false; // setup_pass uploads it
+    ctx->bin_valid = false;
+    return RPF_OK;
+}
+
+int32_t rpf_membership_preset(int32_t kind, int32_t n_feat, rpf_membership *out) {
+    if (!out || kind < 0 || kind > 1 || n_feat < 1 || n_feat > RPF_MAX_NDIM) return RPF_E_BADARG;
+    if (kind == 1 && n_feat != 12) return RPF_E_BADARG; // the 19-dim layout: n0 | p0 | n1 | p1, three features each
+    for (int k = 0; k < RPF_MAX_NDIM; ++k) { out->mult[k] = 3.0; out->floor[k] = -1.0; }
+    if (kind == 1)
+        for (int k = 0; k < 12; ++k) {
+            out->mult[k] = ((k >= 3 && k < 6) || k >= 9) ? 30.0 : 3.0;
+            out->floor[k] = 0.1;
+        }
+    return RPF_OK;
+}
+
 int32_t rpf_sampling_table(int32_t box, uint32_t *table_out) {
     if (!table_out || box < 1 || box > 511 || (box & 1) == 0) return RPF_E_BADARG;
     sampling_table(box, table_out);
@@ -1419,6 +1510,7 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *d, int32_t box, cons
     if (st) return st;
     if (!planes || !colour_out) return fail(ctx, RPF_E_BADARG, "NULL pointer");
     if ((st = check_sampled(ctx, d, 1))) return st; // pass id pass_id0, draws[0]
+    if ((st = check_member_test(ctx, d, 1))) return st;
     if (d->flags & RPF_FLAG_SPIKE_CLAMP)
         return fail(ctx, RPF_E_UNSUPPORTED, "RPF_FLAG_SPIKE_CLAMP with rpf_filter_pass_debug: the spike pass follows the last pass of "
                                             "a whole call (rpf_filter / _ex / _device / _film); this entry point returns one pass's raw colours");

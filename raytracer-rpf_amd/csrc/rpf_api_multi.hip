@@ -425,6 +425,15 @@ int32_t rpf_multi_set_sampling(rpf_multi *m, const rpf_sampling *cfg) {
     return RPF_OK;
 }
 
+int32_t rpf_multi_set_membership(rpf_multi *m, const rpf_membership *cfg) {
+    if (!m) return RPF_E_BADARG;
+    std::string why;
+    const int32_t st = check_membership(cfg, why);
+    if (st) return mfail(m, st, why);
+    for (rpf_ctx *c : m->ctx) (void)rpf_set_membership(c, cfg); // a function of the pixel alone: every slab takes it as it is
+    return RPF_OK;
+}
+
 int32_t rpf_multi_query_spike(rpf_multi *m, rpf_spike_stats *out) {
     if (!m || !out) return RPF_E_BADARG;
     *out = m->spike;

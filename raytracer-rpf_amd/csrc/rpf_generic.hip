@@ -127,6 +127,8 @@ __global__ __launch_bounds__(256) void filter_pixel_kernel(PassParams p, Generic
     using Bin = uint8_t;
     Bin *bins = cv.resident ? smem + cv.off_bins : gs.bins + (uint64_t)blockIdx.x * ndim * p.nmax;
     const double e_eps = (p.policy == RPF_DEGEN_EPS) ? p.eps : 0.0;
+    constexpr bool kMemberTest = false;         // (RPF_FLAG_MEMBER_TEST never reaches this kernel: the stage text's statements
+    constexpr const double *mtab = nullptr;     //  under it are discarded, and the assembly is what it was)
 
     const uint32_t npix = p.pix_list == nullptr ? (uint32_t)(p.row_end - p.row_begin) * (uint32_t)W
                                                 : (gs.count_dev != nullptr ? *gs.count_dev : p.list_count);

@@ -136,6 +136,27 @@ __device__ __forceinline__ bool passes_3sigma_wave(const PassParams &p, int colF
     return pass;
 }
 
+// The membership test of RPF_FLAG_MEMBER_TEST on the same terms: mt = mult[RPF_MAX_NDIM] |
+// floor[RPF_MAX_NDIM].  lim and fl are wave-uniform, formed once per feature; a candidate is rejected on k iff a >= lim && a > fl,
+// fl = -inf where the pixel's sigma is above the floor.  Every comparison with a NaN is false: a NaN never rejects.  With mult 3.0
+// and a negative floor: lim has the bits of pstd * 3.0 above and a > fl holds wherever a >= lim does -- passes_3sigma_wave
+template <class T>
+__device__ __forceinline__ bool passes_member_wave(const PassParams &p, const double *mt, int colF, int nF, uint32_t off, uint64_t HW,
+                                                   uint64_t pix, bool pass) {
+    for (int k = 0; k < nF; ++k) {
+        if (!__any(pass)) break;
+        const double m = p.pmean[(uint64_t)k * HW + pix];
+        const double sd = p.pstd[(uint64_t)k * HW + pix];
+        const double lim = sd * mt[k];
+        const double fl = sd > mt[RPF_MAX_NDIM + k] ? -__builtin_inf() : mt[RPF_MAX_NDIM + k];
+        if (pass) {
+            const double a = fabs((double)ldp<T>(p, colF + k, off) - m);
+            if (a >= lim && a > fl) pass = false;
+        }
+    }
+    return pass;
+}
+
 // ---- stage 2: the constants of a column from its in-order sums and its extrema (sd.h:229-232, mi.cpp:47-50) -----------
 __device__ __forceinline__ void column_mean_sd(double sum, double sq, double dn, int policy, double &mean, double &sd) {
     mean = sum / dn;                                    // ops.h:123

@@ -54,10 +54,12 @@ struct SampledCountOut {
     const uint32_t *table;       // [box - 1] Gaussian thresholds of the box (rpf_sampling_table)
     uint64_t seed;
     int32_t pass_id, row_origin, draws;
+    const double *member;        // MEMBER: mult[RPF_MAX_NDIM] | floor[RPF_MAX_NDIM]; the other instantiation does not read it
 };
 
-// One wave per pixel of rows [row_begin, row_end).
-template <class T>
+// One wave per pixel of rows [row_begin, row_end).  MEMBER (with RPF_FLAG_MEMBER_TEST): the draws meet
+// passes_member_wave instead of the 3-sigma test, and nothing else differs; the first instantiation is the code it was.
+template <class T, bool MEMBER = false>
 __global__ __launch_bounds__(256) void sampled_count_kernel(PassParams p, SampledCountOut o) {
     __shared__ uint32_t sKey[4][kScCap];  // the draws' qq in draw order; later the accepted plane offsets
     __shared__ uint32_t sSort[4][kScCap]; // ... in ascending order, duplicates adjacent
@@ -118,7 +120,8 @@ __global__ __launch_bounds__(256) void sampled_count_kernel(PassParams p, Sample
         bool pass = qq != kScNone && (k == 0 || srt[k - 1] != qq);
         if (!__any(qq != kScNone)) break; // only discarded draws from here on
         const uint32_t off = pass ? candidate_offset(win, W, S, (int)qq) : 0u;
-        pass = passes_3sigma_wave<T>(p, colF, nF, off, HW, pix, pass);
+        if constexpr (MEMBER) pass = passes_member_wave<T>(p, o.member, colF, nF, off, HW, pix, pass);
+        else pass = passes_3sigma_wave<T>(p, colF, nF, off, HW, pix, pass);
         const unsigned long long mask = __ballot(pass);
         if (pass) key[acc + __popcll(mask & ((1ull << lane) - 1ull))] = off;
         acc += __popcll(mask);
@@ -150,8 +153,11 @@ hipError_t launch_sampled_count(const PassParams &p, const SampledCountArgs &a, 
     const dim3 grid((unsigned)((npix + 3) / 4));
     SampledCountOut o;
     o.pool = pool; o.capacity = capacity; o.base = base; o.cursor = cursor;
-    o.table = a.table; o.seed = a.seed; o.pass_id = a.pass_id; o.row_origin = a.row_origin; o.draws = a.draws;
-    if (p.lay.f16) hipLaunchKernelGGL(sampled_count_kernel<__half>, grid, dim3(256), 0, s, p, o);
+    o.table = a.table; o.seed = a.seed; o.pass_id = a.pass_id; o.row_origin = a.row_origin; o.draws = a.draws; o.member = a.member;
+    if (a.member != nullptr) {
+        if (p.lay.f16) hipLaunchKernelGGL((sampled_count_kernel<__half, true>), grid, dim3(256), 0, s, p, o);
+        else hipLaunchKernelGGL((sampled_count_kernel<float, true>), grid, dim3(256), 0, s, p, o);
+    } else if (p.lay.f16) hipLaunchKernelGGL(sampled_count_kernel<__half>, grid, dim3(256), 0, s, p, o);
     else hipLaunchKernelGGL(sampled_count_kernel<float>, grid, dim3(256), 0, s, p, o);
     return hipGetLastError();
 }

@@ -14,7 +14,9 @@
 //
 // Names the including kernel provides: p, D and ndim, nF, nR, nAnc, npair, nwt, colF; tid, lane, wv; W, H, S, b, HW; pix, x, y;
 // e_eps; list, bins and the type Bin of a bin id; sStat, sZ, sMI, sW, sRedD, sChunk, sRed4, sCnt; for part 4 also smem and cv (the
-// start of the dynamic LDS and the carve-up, whose off_chunk it rounds up).  Part 1 leaves n, B and dn.
+// start of the dynamic LDS and the carve-up, whose off_chunk it rounds up); for part 1 also the compile-time constant kMemberTest
+// and, where it is true, mtab (RPF_FLAG_MEMBER_TEST: mult[RPF_MAX_NDIM] | floor[RPF_MAX_NDIM] on the device; DESIGN.md section 14).
+// The statements under kMemberTest are discarded where it is false: such a kernel sees the text it saw.  Part 1 leaves n, B and dn.
 #if RPF_STREAM_PART == 1
         // ---- stage 1b: the 3-sigma test and the member list, reference order (rpf.cpp:556-586) -------------------
         const int x0 = max(x - b, 0), x1 = min(x + b, W - 1), y0 = max(y - b, 0), y1 = min(y + b, H - 1);
@@ -26,7 +28,13 @@
         double *sMf = sChunk + 8, *sLf = sMf + nF;
         for (int k = tid; k < nF; k += kThreads) {
             sMf[k] = p.pmean[(uint64_t)k * HW + pix];
-            sLf[k] = p.pstd[(uint64_t)k * HW + pix] * 3.0; // multiplyArray(std, 3), rpf.cpp:579
+            if constexpr (kMemberTest) { // lim_k = sd_k * mult_k, fl_k = -inf where sd_k is above the floor (behind sLf)
+                const double sd = p.pstd[(uint64_t)k * HW + pix], fk = mtab[RPF_MAX_NDIM + k];
+                sLf[k] = sd * mtab[k];
+                sLf[nF + k] = sd > fk ? -__builtin_inf() : fk;
+            } else {
+                sLf[k] = p.pstd[(uint64_t)k * HW + pix] * 3.0; // multiplyArray(std, 3), rpf.cpp:579
+            }
         }
         __syncthreads();
         for (int q0 = 0; q0 < ncand; q0 += kThreads) {
@@ -44,7 +52,11 @@
                     off = (uint32_t)(((uint64_t)(y0 + iy) * W + (x0 + ix)) * S + s);
                     for (int k = 0; k < nF; ++k) {
                         const double a = fabs((double)ldp<T>(p, colF + k, off) - sMf[k]);
-                        if (a >= sLf[k]) pass = false;     // allLessThan: fails iff a >= b (ops.h:101-104): a NaN never rejects
+                        if constexpr (kMemberTest) {
+                            if (a >= sLf[k] && a > sLf[nF + k]) pass = false; // a NaN never rejects here either
+                        } else {
+                            if (a >= sLf[k]) pass = false;     // allLessThan: fails iff a >= b (ops.h:101-104): a NaN never rejects
+                        }
                     }
                 }
                 mask = __ballot(pass);

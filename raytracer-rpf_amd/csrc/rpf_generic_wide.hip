@@ -47,7 +47,7 @@ GenericWideCarve generic_wide_carve(const SampleLayout &lay, int nmax, bool fast
     const uint32_t own_at = fast ? up16(o) : o;                                        // where the own rows of a sweep start (as generic_carve)
     const uint32_t own = fast ? (uint32_t)generic::kStreamFastOwn * (uint32_t)D.nwt * 4u : (uint32_t)generic::kOwn * (uint32_t)D.nwt * 8u;
     chunk = std::max(chunk, own_at - o + own);
-    chunk = std::max(chunk, (8u + 2u * (uint32_t)D.nF) * 8u);                         // stage 1b: wave counts, feature means, 3 sigma
+    chunk = std::max(chunk, (8u + 3u * (uint32_t)D.nF) * 8u);                         // stage 1b: wave counts, feature means, limits, floors (MEMBER)
     o = up16(o + chunk);
     c.off_hist = o;
     const uint32_t bmax = (uint32_t)std::max(1.0, std::floor(std::sqrt((double)nmax)));
@@ -70,12 +70,15 @@ struct WideScratch {
     const uint64_t *table; // round(k ln k * 2^bits), k = 0 .. nmax
     int32_t bits;
     const uint32_t *count_dev; // size of p.pix_list on the device, or null = p.list_count
+    const double *member;  // MEMBER: mult[RPF_MAX_NDIM] | floor[RPF_MAX_NDIM]; the other instantiations do not read it
 };
 
 // One workgroup filters one pixel at a time and walks the pixels of rows [row_begin, row_end), or those of p.pix_list.
 // FAST (RPF_FLAG_STREAM_FAST): stage 4 alone in the fp32 arithmetic of DESIGN.md section 11f; every other statement is shared.
-template <class T, bool FAST = false>
+// MEMBER (RPF_FLAG_MEMBER_TEST, the rest list of route 9): stage 1b alone under the two-compare test of DESIGN.md section 14.
+template <class T, bool FAST = false, bool MEMBER = false>
 __global__ __launch_bounds__(256) void filter_wide_kernel(PassParams p, GenericWideCarve cv, WideScratch gs) {
+    constexpr bool kMemberTest = MEMBER;
     extern __shared__ __align__(16) unsigned char smem[];
     const GenericDims D = generic_dims(p.lay);
     const int ndim = D.ndim, nF = D.nF, nR = D.nR, nAnc = D.nAnc, npair = D.npair, nwt = D.nwt, colF = D.colF;
@@ -98,6 +101,7 @@ __global__ __launch_bounds__(256) void filter_wide_kernel(PassParams p, GenericW
     using Bin = uint16_t;
     Bin *bins = gs.bins + (uint64_t)blockIdx.x * ndim * p.nmax;
     const uint64_t *tw = gs.table;
+    const double *mtab = gs.member;
     const double e_eps = (p.policy == RPF_DEGEN_EPS) ? p.eps : 0.0;
 
     const uint32_t npix = p.pix_list ? (gs.count_dev ? *gs.count_dev : p.list_count) : (uint32_t)(p.row_end - p.row_begin) * (uint32_t)W;
@@ -257,21 +261,22 @@ __global__ __launch_bounds__(256) void filter_wide_kernel(PassParams p, GenericW
     }
 }
 
-template <class T, bool FAST>
+template <class T, bool FAST, bool MEMBER = false>
 hipError_t launch_filter_wide_t(const PassParams &p, const GenericWideCarve &cv, const WideScratch &gs, unsigned grid, hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute((const void *)filter_wide_kernel<T, FAST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
+    hipError_t e = hipFuncSetAttribute((const void *)filter_wide_kernel<T, FAST, MEMBER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((filter_wide_kernel<T, FAST>), dim3(grid), dim3(kThreads), cv.total, s, p, cv, gs);
+    hipLaunchKernelGGL((filter_wide_kernel<T, FAST, MEMBER>), dim3(grid), dim3(kThreads), cv.total, s, p, cv, gs);
     return hipGetLastError();
 }
 
 } // namespace
 
 hipError_t launch_filter_wide(const PassParams &p, void *list, void *bins, uint32_t slots, const uint64_t *table, int table_bits,
-                              const uint32_t *count_dev, hipStream_t s, bool fast) {
+                              const uint32_t *count_dev, hipStream_t s, bool fast, const double *member) {
     const GenericWideCarve cv = generic_wide_carve(p.lay, p.nmax, fast);
     if ((int)cv.total > max_lds_per_block() || cv.total > kLdsBudget) return hipErrorInvalidValue;
     if (p.nmax < 1 || p.nmax > kMaxWideNbhd || (count_dev != nullptr && p.pix_list == nullptr)) return hipErrorInvalidValue;
+    if (member != nullptr && fast) return hipErrorInvalidValue; // (the membership test is fp64 only: no such instantiation)
     if (cv.band_words < (uint32_t)std::max(1.0, std::floor(std::sqrt((double)p.nmax)))) return hipErrorInvalidValue; // a band holds a row of the widest table
     if (p.row_end <= p.row_begin) return hipSuccess;
     if (p.pix_list != nullptr && count_dev == nullptr && p.list_count == 0) return hipSuccess;
@@ -280,6 +285,8 @@ hipError_t launch_filter_wide(const PassParams &p, void *list, void *bins, uint3
     const unsigned grid = (unsigned)std::min<uint64_t>(npix, slots);
     WideScratch gs;
     gs.list = (uint32_t *)list; gs.bins = (uint16_t *)bins; gs.table = table; gs.bits = table_bits; gs.count_dev = count_dev;
+    gs.member = member;
+    if (member != nullptr) return p.lay.f16 ? launch_filter_wide_t<__half, false, true>(p, cv, gs, grid, s) : launch_filter_wide_t<float, false, true>(p, cv, gs, grid, s);
     if (fast) return p.lay.f16 ? launch_filter_wide_t<__half, true>(p, cv, gs, grid, s) : launch_filter_wide_t<float, true>(p, cv, gs, grid, s);
     return p.lay.f16 ? launch_filter_wide_t<__half, false>(p, cv, gs, grid, s) : launch_filter_wide_t<float, false>(p, cv, gs, grid, s);
 }

@@ -15,6 +15,10 @@
 //     the strict test then rejects every finite and every infinite candidate -- and no feature mean is NaN in the rows the
 //     slab's windows reach (wide_nan_scan_kernel: a NaN sample makes its own pixel's mean NaN, and a NaN candidate is the one
 //     kind that passes a zero-width test).  A mean of +-inf proves nothing: |inf - inf| is NaN, which never rejects.
+// MEMBER (RPF_FLAG_MEMBER_TEST, route 9): the second instantiation runs passes_member_wave on the uploaded
+// multiples and floors, and its flat proof asks of feature k: pstd[k] * mult[k] == 0.0, a finite mean AND floor[k] < 0 -- under
+// a non-negative floor a zero-variance feature accepts its equals, so nothing is proven.  The first instantiation is the code it
+// was.
 #include "rpf_generic_common.h"
 
 #include <algorithm>
@@ -31,6 +35,7 @@ struct WideCountOut {
     uint64_t *base;              // [H*W] first pool entry of a pixel with S < N <= 832
     unsigned long long *cursor;  // [1] entries reserved so far
     const int32_t *nan_flag;     // [1] != 0: some feature mean in reach of the slab is NaN
+    const double *member;        // MEMBER: mult[RPF_MAX_NDIM] | floor[RPF_MAX_NDIM]; the other instantiation does not read it
 };
 
 // *flag |= 1 when a feature mean of pixels [pix0, pix1) is NaN (stage 1a's planes, [nF][H*W])
@@ -43,7 +48,7 @@ __global__ __launch_bounds__(256) void wide_nan_scan_kernel(const double *pmean,
 }
 
 // One wave per pixel of rows [row_begin, row_end).
-template <class T>
+template <class T, bool MEMBER = false>
 __global__ __launch_bounds__(256) void wide_count_kernel(PassParams p, WideCountOut o) {
     __shared__ uint32_t sOff[4][kWcCap];
     const int lane = threadIdx.x & 63;
@@ -64,7 +69,11 @@ __global__ __launch_bounds__(256) void wide_count_kernel(PassParams p, WideCount
     if (*o.nan_flag == 0) {
         for (int k = lane; k < nF; k += 64) {
             const double m = p.pmean[(uint64_t)k * HW + pix];
-            if (p.pstd[(uint64_t)k * HW + pix] * 3.0 == 0.0 && isfinite(m)) flat = true;
+            if constexpr (MEMBER) {
+                if (p.pstd[(uint64_t)k * HW + pix] * o.member[k] == 0.0 && isfinite(m) && o.member[RPF_MAX_NDIM + k] < 0.0) flat = true;
+            } else {
+                if (p.pstd[(uint64_t)k * HW + pix] * 3.0 == 0.0 && isfinite(m)) flat = true;
+            }
         }
         flat = __any(flat);
     }
@@ -77,7 +86,8 @@ __global__ __launch_bounds__(256) void wide_count_kernel(PassParams p, WideCount
         const int qq = qb + lane;
         bool pass = qq < ncand;
         const uint32_t off = pass ? candidate_offset(win, W, S, qq) : 0u;
-        pass = passes_3sigma_wave<T>(p, colF, nF, off, HW, pix, pass);
+        if constexpr (MEMBER) pass = passes_member_wave<T>(p, o.member, colF, nF, off, HW, pix, pass);
+        else pass = passes_3sigma_wave<T>(p, colF, nF, off, HW, pix, pass);
         const unsigned long long mask = __ballot(pass);
         if (pass) {
             const int at = acc + __popcll(mask & ((1ull << lane) - 1ull));
@@ -106,7 +116,7 @@ __global__ __launch_bounds__(256) void wide_count_kernel(PassParams p, WideCount
 } // namespace
 
 hipError_t launch_wide_count(const PassParams &p, uint32_t *pool, uint64_t capacity, uint64_t *base, unsigned long long *cursor,
-                             int32_t *nan_flag, hipStream_t s) {
+                             int32_t *nan_flag, hipStream_t s, const double *member) {
     if (pool == nullptr || base == nullptr || cursor == nullptr || nan_flag == nullptr || p.nbhd == nullptr) return hipErrorInvalidValue;
     if (p.S < 1 || p.S > kWcCap || !p.lay.generic_ok()) return hipErrorInvalidValue;
     if (p.row_end <= p.row_begin) return hipSuccess;
@@ -120,8 +130,11 @@ hipError_t launch_wide_count(const PassParams &p, uint32_t *pool, uint64_t capac
     const uint64_t npix = (uint64_t)(p.row_end - p.row_begin) * p.W;
     const dim3 grid((unsigned)((npix + 3) / 4));
     WideCountOut o;
-    o.pool = pool; o.capacity = capacity; o.base = base; o.cursor = cursor; o.nan_flag = nan_flag;
-    if (p.lay.f16) hipLaunchKernelGGL(wide_count_kernel<__half>, grid, dim3(256), 0, s, p, o);
+    o.pool = pool; o.capacity = capacity; o.base = base; o.cursor = cursor; o.nan_flag = nan_flag; o.member = member;
+    if (member != nullptr) {
+        if (p.lay.f16) hipLaunchKernelGGL((wide_count_kernel<__half, true>), grid, dim3(256), 0, s, p, o);
+        else hipLaunchKernelGGL((wide_count_kernel<float, true>), grid, dim3(256), 0, s, p, o);
+    } else if (p.lay.f16) hipLaunchKernelGGL(wide_count_kernel<__half>, grid, dim3(256), 0, s, p, o);
     else hipLaunchKernelGGL(wide_count_kernel<float>, grid, dim3(256), 0, s, p, o);
     return hipGetLastError();
 }

@@ -45,6 +45,9 @@ enum GenericBits : int32_t {
                               //   of route 7 launch the fp32-weight instantiations (stream_fast below); redo launches never do
     kGenericSampled = 128,    // RPF_FLAG_SAMPLED_NBHD on a pass with draws > 0: route 8 whatever the bits above say (route_sampled; the
                               //   draws and the pass id are rpf_ctx::samp_now, which setup_pass fills); stage 1a is not affected
+    kGenericMemberTest = 256, // RPF_FLAG_MEMBER_TEST: stage 1b under the configured multiples and floors (rpf_ctx::d_member, which
+                              //   setup_pass uploads).  A full-box pass: route 9 whatever the bits above say (route_member_test); a
+                              //   sampled pass stays route 8 and its count kernel runs the test; stage 1a is not affected
 };
 
 // everything one pass needs, passed by value to the kernels
@@ -281,23 +284,27 @@ namespace generic {
 // grid is min(pixels, slots).  table: round(k ln k * 2^table_bits), k = 0 .. p.nmax (p.tfix is not read).  count_dev != null:
 // the size of p.pix_list is read from device memory (redo list: no host read-back), grid = slots.  fast: as for launch_filter
 // (route 6 and the rest list of route 7 pass it, route 7's redo launch never does)
+// member != null (RPF_FLAG_MEMBER_TEST, never with fast): device, mult[RPF_MAX_NDIM] | floor[RPF_MAX_NDIM]; stage 1b runs the
+// two-compare test of DESIGN.md section 14 on them (the MEMBER instantiations; the others are the code they were)
 hipError_t launch_filter_wide(const PassParams &p, void *list, void *bins, uint32_t slots, const uint64_t *table, int table_bits,
-                              const uint32_t *count_dev, hipStream_t s, bool fast = false);
+                              const uint32_t *count_dev, hipStream_t s, bool fast = false, const double *member = nullptr);
 // the count pass of route 7 (rpf_generic_wide_count.hip, S <= 832): for every pixel of rows [p.row_begin, p.row_end) N into
 // p.nbhd -- 833 for any N > 832 -- and, for S < N <= 832, the N - S members behind the own samples into pool[base[pix] ..];
 // *cursor ends at the sum of those N - S, whether or not `capacity` entries held them (a pool too small loses writes only:
 // the caller compares and repeats).  nan_flag: [1], scratch of the flat-pixel proof.  Reads stage 1a's planes of the rows
-// the slab's windows reach
+// the slab's windows reach.  member != null (route 9): as for launch_filter_wide; the flat-pixel proof then asks for a negative
+// floor as well
 hipError_t launch_wide_count(const PassParams &p, uint32_t *pool, uint64_t capacity, uint64_t *base, unsigned long long *cursor,
-                             int32_t *nan_flag, hipStream_t s);
+                             int32_t *nan_flag, hipStream_t s, const double *member = nullptr);
 // the count pass of route 8 (rpf_generic_sampled_count.hip, S + draws <= 832): for every pixel of rows
 // [p.row_begin, p.row_end) the distinct draws of its key that pass the 3-sigma test, in ascending visiting order, into
 // pool[base[pix] ..] and N = S + their number into p.nbhd; *cursor as launch_wide_count leaves it.  table: device, the box - 1
-// Gaussian thresholds of p.box
+// Gaussian thresholds of p.box; member != null (with RPF_FLAG_MEMBER_TEST): as for launch_filter_wide, the test of the draws
 struct SampledCountArgs {
     const uint32_t *table;
     uint64_t seed;
     int32_t pass_id, row_origin, draws;
+    const double *member = nullptr;
 };
 hipError_t launch_sampled_count(const PassParams &p, const SampledCountArgs &a, uint32_t *pool, uint64_t capacity, uint64_t *base,
                                 unsigned long long *cursor, hipStream_t s);

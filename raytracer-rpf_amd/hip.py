@@ -47,6 +47,13 @@ FLAG_SPIKE_CLAMP = 1024
 # exactly those; the twelfth bit has its own table in tests/test_sampled_cpu.py.  The name is provisional: once that test and its
 # recording are widened to twelve bits, it becomes FLAG_SAMPLED_NBHD like the others
 SAMPLED_NBHD_FLAG = 2048
+# the published membership test (Context.set_membership): stage 1b takes a multiple of sigma and an absolute
+# floor per feature, so that a flat pixel accepts its flat neighbours.  Every pass of the call: a full-box pass takes route 9 (count
+# kernel, size classes, the wide kernel for N > 832; fp64), a sampled pass stays route 8 and tests its draws the same way.  Refused
+# without set_membership, under DEGEN_REF_ABORT, with FLAG_FAST_WEIGHTS / FLAG_GENERIC_FAST / FLAG_STREAM_FAST, and on a full-box pass
+# with S > 832.  RPF_FLAG_MEMBER_TEST of the header; the name stays outside the FLAG_* family for SAMPLED_NBHD_FLAG's reason (its
+# table: tests/test_member_test_cpu.py)
+MEMBER_TEST_FLAG = 4096
 FLAG_WIDE_NBHD = 64  # passes with 65535 < box*box*S <= 262144 on the wide layout-generic kernel (route 6); max_nbhd() tells the bound
 MAX_NDIM = 40     # the layout-generic kernels take 5 + n_random + n_feat up to this
 PLANES_F32, PLANES_F16 = 0, 1
@@ -60,7 +67,7 @@ EXPORTS = ["rpf_version", "rpf_status_string", "rpf_create", "rpf_destroy", "rpf
            "rpf_film_splat_device", "rpf_film_window", "rpf_multi_halo_plan", "rpf_multi_filter_film", "rpf_layout_kernels",
            "rpf_max_nbhd", "rpf_wide_table", "rpf_set_spike", "rpf_multi_set_spike", "rpf_query_spike", "rpf_multi_query_spike",
            "rpf_spike_clamp_device", "rpf_colour_add_device", "rpf_spike_delta", "rpf_set_sampling", "rpf_multi_set_sampling",
-           "rpf_sampling_table", "rpf_sampling_draws"]
+           "rpf_sampling_table", "rpf_sampling_draws", "rpf_set_membership", "rpf_multi_set_membership", "rpf_membership_preset"]
 
 # the film step: pbrt's PixelFilters (include/rpf_hip.h, rpf_film)
 PIXFILTER_BOX, PIXFILTER_TRIANGLE, PIXFILTER_GAUSSIAN, PIXFILTER_MITCHELL, PIXFILTER_SINC = range(5)
@@ -115,6 +122,40 @@ def make_sampling(seed, draws, pass_id0=0, row_origin=0):
     for i, d in enumerate(list(draws)[:MAX_BOXES]):
         s.draws[i] = int(d)
     return s
+
+
+class Membership(C.Structure):
+    """rpf_membership: feature k < n_feat is rejected iff |f_k - m_k| >= sd_k * mult[k] and |f_k - m_k| > (sd_k > floor[k] ? -inf :
+    floor[k]); all MAX_NDIM entries are validated (mult finite and > 0, floor neither NaN nor +inf)"""
+    _fields_ = [("mult", C.c_double * MAX_NDIM), ("floor", C.c_double * MAX_NDIM)]
+
+
+MEMBERSHIP_REFERENCE, MEMBERSHIP_PUBLISHED_19 = 0, 1
+
+
+def make_membership(mult, floor):
+    """a Membership from two sequences (or two scalars, for every feature); entries not given are the reference's 3 and -1"""
+    m = Membership()
+    for k in range(MAX_NDIM):
+        m.mult[k], m.floor[k] = 3.0, -1.0
+    mu = [mult] * MAX_NDIM if np.isscalar(mult) else list(mult)
+    fl = [floor] * MAX_NDIM if np.isscalar(floor) else list(floor)
+    for k, v in enumerate(mu[:MAX_NDIM]):
+        m.mult[k] = float(v)
+    for k, v in enumerate(fl[:MAX_NDIM]):
+        m.floor[k] = float(v)
+    return m
+
+
+def membership_preset(kind, n_feat=NFEAT):
+    """rpf_membership_preset (no GPU needed): kind MEMBERSHIP_REFERENCE -- multiples 3, floors -1 -- or MEMBERSHIP_PUBLISHED_19 --
+    multiples 3, 30 on the world positions (features 3..5 and 9..11), floors 0.1; n_feat must be 12.  The constants of the latter
+    are from memory of the paper, and a floor on a world position depends on the scene's scale: set those for the scene"""
+    m = Membership()
+    st = load().rpf_membership_preset(int(kind), int(n_feat), C.byref(m))
+    if st != OK:
+        raise RpfError(st, "rpf_membership_preset(kind=%r, n_feat=%r): an unknown kind, n_feat outside [1, 40], or kind 1 with n_feat != 12" % (kind, n_feat))
+    return m
 
 
 def sampling_table(box):
@@ -328,6 +369,10 @@ def load():
             L.rpf_multi_set_sampling.argtypes = [C.c_void_p, C.POINTER(Sampling)]
             L.rpf_sampling_table.argtypes = [C.c_int32, C.c_void_p]
             L.rpf_sampling_draws.argtypes = [C.POINTER(Sampling)] + [C.c_int32] * 7 + [C.c_void_p, C.POINTER(C.c_int32)]
+        if hasattr(L, "rpf_set_membership"):  # (absent from a build of before the membership test, loaded through RPF_HIP_LIB)
+            L.rpf_set_membership.argtypes = [C.c_void_p, C.POINTER(Membership)]
+            L.rpf_multi_set_membership.argtypes = [C.c_void_p, C.POINTER(Membership)]
+            L.rpf_membership_preset.argtypes = [C.c_int32, C.c_int32, C.POINTER(Membership)]
         L.rpf_host_alloc.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
         L.rpf_host_free.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
@@ -409,7 +454,7 @@ class Context:
         (FLAG_GENERIC), 4 the same with small neighbourhoods packed (FLAG_GENERIC_PACKED), 5 the same with
         64 < N <= 832 on the one-wave generic kernels (FLAG_GENERIC_WAVE; 3 for a pass with S > 832), 6 the wide kernel
         (FLAG_WIDE_NBHD on a pass with box*box*S > 65535), 7 such a pass dealt by size class (FLAG_WIDE_CLASSES), 8 a sampled
-        pass (SAMPLED_NBHD_FLAG with draws > 0); -1 before any pass.  FLAG_GENERIC_FAST and FLAG_STREAM_FAST change no route
+        pass (SAMPLED_NBHD_FLAG with draws > 0), 9 a full-box pass under MEMBER_TEST_FLAG; -1 before any pass.  FLAG_GENERIC_FAST and FLAG_STREAM_FAST change no route
         (rpf_query_route)"""
         r = C.c_int32(-1)
         self._check(self._L.rpf_query_route(self._h, C.byref(r)))
@@ -430,6 +475,11 @@ class Context:
     def set_sampling(self, cfg):
         """rpf_set_sampling: cfg a Sampling (make_sampling), or None -> RPF_E_BADARG as the ABI answers a NULL pointer"""
         self._check(self._L.rpf_set_sampling(self._h, None if cfg is None else C.byref(cfg)))
+
+    # ---- the membership test (MEMBER_TEST_FLAG) ---------------------------------------------------------------
+    def set_membership(self, cfg):
+        """rpf_set_membership: cfg a Membership (make_membership / membership_preset), or None -> RPF_E_BADARG"""
+        self._check(self._L.rpf_set_membership(self._h, None if cfg is None else C.byref(cfg)))
 
     def spike_clamp_device(self, desc, d_colour, threshold=1.0, stream=None):
         """rpf_spike_clamp_device: the clamp half on rows [row_begin, row_end) of device colours (raw pointer, 3 fp64 planes);
@@ -598,6 +648,12 @@ class MultiContext:
     def set_sampling(self, cfg):
         """rpf_multi_set_sampling: the configuration of every slab (each adds its first image row to cfg.row_origin)"""
         st = self._L.rpf_multi_set_sampling(self._h, None if cfg is None else C.byref(cfg))
+        if st != OK:
+            raise RpfError(st, self._L.rpf_multi_last_error(self._h).decode())
+
+    def set_membership(self, cfg):
+        """rpf_multi_set_membership: the membership test of every slab (a function of the pixel alone: nothing moves per slab)"""
+        st = self._L.rpf_multi_set_membership(self._h, None if cfg is None else C.byref(cfg))
         if st != OK:
             raise RpfError(st, self._L.rpf_multi_last_error(self._h).decode())
 

@@ -41,12 +41,18 @@ def check_desc(desc):
     """Refuses a descriptor these helpers cannot drive yet.  SAMPLED_NBHD_FLAG: a sampled pass keys every pixel by its IMAGE row
     and by the pass id, so a rank would have to set ``Sampling.row_origin`` to its buffer's first image row and ``pass_id0`` to
     the pass of each one-pass call; nothing here does, and a rank that filtered with the whole
-    image's configuration would silently draw other samples than the whole image does."""
+    image's configuration would silently draw other samples than the whole image does.  MEMBER_TEST_FLAG: every rank's context
+    would need the same ``set_membership`` and these helpers carry no such configuration; the test itself is a function of the
+    pixel alone, so MultiContext (or a caller that configures each rank's context) gives the whole image's bits."""
     from . import hip
     if desc.flags & hip.SAMPLED_NBHD_FLAG:
         raise NotImplementedError("slabs: SAMPLED_NBHD_FLAG (RPF_FLAG_SAMPLED_NBHD) is not supported across ranks yet: each rank must set "
                                   "Sampling.row_origin (image row of its buffer row 0) and pass_id0 per one-pass call itself "
                                   "(INTEGRATION.md section 2f), or use MultiContext, which does")
+    if desc.flags & hip.MEMBER_TEST_FLAG:
+        raise NotImplementedError("slabs: MEMBER_TEST_FLAG (RPF_FLAG_MEMBER_TEST) is not supported across ranks yet: each rank's context "
+                                  "needs the same Context.set_membership, which these helpers do not carry (INTEGRATION.md "
+                                  "section 2g), or use MultiContext, which does")
     return desc
 
 

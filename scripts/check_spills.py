@@ -201,9 +201,14 @@ def demangle_short(name):
     if k:
         s += "<K=%s,TL=%s,FAST=%s,NW=%s,PHASE=%s>" % k.groups()
     # the layout-generic kernels: the plane type, and FAST where a kernel has the fp32 stage-4 instantiation (RPF_FLAG_GENERIC_FAST)
-    t = re.search(r"3rpf7generic.*kernelI(f|6__half)(?:Lb([01])E)?E", name)
+    # ... and MEMBER where one has the membership test of RPF_FLAG_MEMBER_TEST in its stage 1b: the second flag of the wide kernel, the
+    # only flag of the two count kernels
+    t = re.search(r"3rpf7generic.*kernelI(f|6__half)(?:Lb([01])E)?(?:Lb([01])E)?E", name)
     if t:
-        s += "<%s%s>" % ("float" if t.group(1) == "f" else "__half", ",FAST" if t.group(2) == "1" else "")
+        count = re.search(r"(wide|sampled)_count_kernel", name) is not None
+        fast = t.group(2) == "1" and not count
+        member = t.group(3) == "1" or (count and t.group(2) == "1")
+        s += "<%s%s%s>" % ("float" if t.group(1) == "f" else "__half", ",FAST" if fast else "", ",MEMBER" if member else "")
     g = re.search(r"packed_kernelILi(\d+)E", name)
     if g:
         s += "<G=%s>" % g.group(1)
