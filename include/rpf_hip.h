@@ -213,7 +213,27 @@ enum {
                                   stage 1b), with RPF_FLAG_FAST_WEIGHTS, RPF_FLAG_GENERIC_FAST or RPF_FLAG_STREAM_FAST (fp64
                                   only; rpf_layout_kernels answers the same way), a full-box pass with S > 832
                                   (RPF_E_UNSUPPORTED). */
-    RPF_FLAG_STREAM_FAST = 512 /* opt-in, modifies RPF_FLAG_GENERIC and / or RPF_FLAG_WIDE_NBHD: the two kernels that walk a
+    RPF_FLAG_SCHEDULE = 8192,     /* opt-in: the per-pass schedule of the weight stage (rpf_set_schedule below; DESIGN.md section
+                                  15).  Pass p of the call reads entry e = pass0 + p of the table: seed[e] replaces
+                                  desc.sigma_seed (sigma_c^2 = sigma_f^2 = seed[e]^2 / (1 - W_r_c)^2), and stage 3c forms
+                                  alpha_k = clamp0(1 - gain_c[e] * W_r^{c,k}), beta_k = clamp0(1 - gain_f[e] * W_r^{f,k}) *
+                                  W_c^{f,k} with clamp0(v) = v < 0 ? 0 : v (a NaN stays a NaN), each product and each difference
+                                  rounded once.  W_r_c, sigma_p, stages 1 to 3b and the blend are untouched; the debug planes
+                                  alpha / beta report the scheduled values.  A pass whose two gains are exactly 1 runs the
+                                  statements of a call without the flag on the route it would take without it (the fused
+                                  routes 0 to 2 included, under either degenerate policy) with seed[e] as its seed: gains 1 are
+                                  the reference on every input by construction.  A pass with a gain other than 1 runs on the
+                                  layout-generic kernels only (routes 3 to 9: RPF_FLAG_GENERIC, a wide pass, a sampled pass or
+                                  RPF_FLAG_MEMBER_TEST), fp64 or with RPF_FLAG_GENERIC_FAST / RPF_FLAG_STREAM_FAST (the fp32
+                                  coefficients are formed from the scheduled alpha / beta).  The flag selects no route:
+                                  rpf_query_route, the counters, rpf_layout_kernels and rpf_max_nbhd answer as without it.  It
+                                  composes with RPF_FLAG_SAMPLED_NBHD, RPF_FLAG_MEMBER_TEST and RPF_FLAG_SPIKE_CLAMP.  An entry
+                                  point that runs no pass ignores it; rpf_filter_pass_debug is one pass and reads entry pass0.
+                                  Refused before any device work: the flag without a prior rpf_set_schedule, pass0 + the
+                                  number of passes > RPF_MAX_BOXES (RPF_E_BADARG); a pass with a gain other than 1 under
+                                  RPF_DEGEN_REF_ABORT (the reference has no such rule, and the redo launch would have to carry
+                                  it) or on the fused kernels (RPF_E_UNSUPPORTED). */
+    RPF_FLAG_STREAM_FAST = 512/* opt-in, modifies RPF_FLAG_GENERIC and / or RPF_FLAG_WIDE_NBHD: the two kernels that walk a
                                   neighbourhood of any size with 256 threads -- the generic filter kernel (route 3, the rest
                                   list N > 64 / N > 832 of routes 4 / 5) and the wide kernel (route 6, the rest list N > 832 of
                                   route 7) -- evaluate the S x N pair weights of stage 4 in the fp32 arithmetic described for
@@ -678,6 +698,35 @@ int32_t rpf_multi_set_membership(rpf_multi *m, const rpf_membership *cfg);
  * the scene, the preset is a convenience.
  * RPF_E_BADARG for NULL, an unknown kind, n_feat outside [1, RPF_MAX_NDIM], or kind 1 with n_feat != 12. */
 int32_t rpf_membership_preset(int32_t kind, int32_t n_feat, rpf_membership *out);
+
+/* ---- the per-pass schedule of the weight stage (RPF_FLAG_SCHEDULE) ----------------------------------
+ * Pass p of a call reads entry e = pass0 + p.  With W_r^{c,k} and W_r^{f,k} the ratios stage 3c forms today (same sums, same
+ * order, the policy's epsilon in the denominators), in IEEE fp64 without contraction:
+ *   alpha_k = clamp0(1 - gain_c[e] * W_r^{c,k}),  beta_k = clamp0(1 - gain_f[e] * W_r^{f,k}) * W_c^{f,k},
+ *   clamp0(v) = (v < 0) ? 0.0 : v  (a NaN stays a NaN), the product and the difference rounded once each,
+ * and seed[e] stands where desc.sigma_seed stood.  A pass with both gains exactly 1.0 runs the unscheduled statements. */
+typedef struct rpf_schedule {
+    int32_t pass0;                    /* pass p of a call reads entry pass0 + p (rpf_sampling.pass_id0's part for a caller who makes one call per pass) */
+    int32_t reserved;                 /* 0 */
+    double  seed[RPF_MAX_BOXES];      /* replaces desc.sigma_seed for that pass: sigma_c^2 = sigma_f^2 = seed^2 / (1 - W_r_c)^2 */
+    double  gain_c[RPF_MAX_BOXES];    /* g_c: alpha_k = clamp0(1 - g_c * W_r^{c,k}) */
+    double  gain_f[RPF_MAX_BOXES];    /* g_f: beta_k  = clamp0(1 - g_f * W_r^{f,k}) * W_c^{f,k} */
+} rpf_schedule;
+
+/* RPF_E_BADARG for a NULL pointer, pass0 outside [0, RPF_MAX_BOXES), a seed that is not finite and > 0, or a gain that is not
+ * finite and >= 0, in ANY of the RPF_MAX_BOXES entries; needs no device work.  The configuration stays until replaced. */
+int32_t rpf_set_schedule(rpf_ctx *ctx, const rpf_schedule *cfg);
+int32_t rpf_multi_set_schedule(rpf_multi *m, const rpf_schedule *cfg);
+
+/* Fills *out (pass0 = 0, reserved = 0, all RPF_MAX_BOXES entries).  Host only, no device.  S: samples per pixel.
+ * kind 0, the reference: every seed 0.002, every gain 1.
+ * kind 1, "published": seed[t] = sqrt(8.0 * v_t / (double)S) with v_0 = 0.02 and v_t = 0.002 otherwise, gain_c[t] =
+ * 2.0 * (1.0 + 0.1 * t), gain_f[t] = 1.0 + 0.1 * t, formed in C doubles in exactly these expressions.  These constants are
+ * written down FROM MEMORY of the paper (sigma^2 = 8 sigma_8^2 / spp with sigma_8^2 = 0.02 in the first iteration and 0.002
+ * afterwards; alpha = max(1 - 2 (1 + 0.1 t) W_r^c, 0), beta = W_c^f max(1 - (1 + 0.1 t) W_r^f, 0)): the paper was not at hand,
+ * and nothing in the library depends on them.
+ * RPF_E_BADARG for NULL, an unknown kind, or S <= 0. */
+int32_t rpf_schedule_preset(int32_t kind, int32_t S, rpf_schedule *out);
 
 #ifdef __cplusplus
 }

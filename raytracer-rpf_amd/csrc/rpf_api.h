@@ -63,6 +63,8 @@ enum Route : int {
 static_assert(sizeof(rpf_sampling) == 48 && offsetof(rpf_sampling, draws) == 16, "rpf_sampling is ABI");
 static_assert(sizeof(rpf_membership) == 2 * RPF_MAX_NDIM * sizeof(double) && offsetof(rpf_membership, floor) == RPF_MAX_NDIM * sizeof(double),
               "rpf_membership is ABI, and the image of the device table: mult[RPF_MAX_NDIM] | floor[RPF_MAX_NDIM]");
+static_assert(sizeof(rpf_schedule) == 8 + 3 * RPF_MAX_BOXES * sizeof(double) && offsetof(rpf_schedule, seed) == 8 &&
+                  offsetof(rpf_schedule, gain_c) == 8 + RPF_MAX_BOXES * sizeof(double), "rpf_schedule is ABI");
 
 // The sampled pass in progress (RPF_FLAG_SAMPLED_NBHD; setup_pass fills it, route_sampled reads it): draws == 0, not sampled
 struct SampledPass {
@@ -137,6 +139,9 @@ struct rpf_ctx {
     rpf_membership membership{};                // rpf_set_membership
     bool membership_set = false;
     rpf::DevBuf<double> d_member; bool member_fresh = false; // its device image, which setup_pass uploads when it is stale
+    // the per-pass schedule of the weight stage (RPF_FLAG_SCHEDULE): host only, setup_pass copies a pass's entry
+    rpf_schedule schedule{};                    // rpf_set_schedule
+    bool schedule_set = false;
 };
 
 namespace rpf {
@@ -185,6 +190,11 @@ int32_t check_sampling(const rpf_sampling *cfg, std::string &why); // what rpf_s
 int32_t check_sampled(rpf_ctx *ctx, const rpf_desc *d, int n_pass); // RPF_FLAG_SAMPLED_NBHD of a call that runs n_pass passes
 int32_t check_membership(const rpf_membership *cfg, std::string &why); // what rpf_set_membership refuses
 int32_t check_member_test(rpf_ctx *ctx, const rpf_desc *d, int n_pass); // RPF_FLAG_MEMBER_TEST of a call that runs n_pass passes
+int32_t check_schedule_table(const rpf_schedule *cfg, std::string &why); // what rpf_set_schedule refuses
+// RPF_FLAG_SCHEDULE of a call that runs n_pass passes at boxes[0 .. n_pass)
+int32_t check_schedule(rpf_ctx *ctx, const rpf_desc *d, const int32_t *boxes, int n_pass);
+// the GenericBits of pass `pass` at `box` without kGenericSchedule (0: the fused kernels): what setup_pass and check_schedule share
+int32_t pass_generic_bits(const rpf_ctx *ctx, const rpf_desc *d, int box, int pass);
 int32_t validate(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes);
 int32_t enter(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes); // validate, then make the context's device current
 

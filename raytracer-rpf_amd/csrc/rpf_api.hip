@@ -144,6 +144,57 @@ int32_t check_member_test(rpf_ctx *ctx, const rpf_desc *d, int n_pass) {
     return RPF_OK;
 }
 
+// Which layout-generic kernels pass `pass` of a call under d runs at `box`: the GenericBits of PassParams::generic, all but
+// kGenericSchedule (setup_pass adds that one from the table's entry); 0 = the compiled, fused kernels.  Reads the flags, S, option
+// "wide" and the two configurations; setup_pass and check_schedule both ask here.
+int32_t pass_generic_bits(const rpf_ctx *ctx, const rpf_desc *d, int box, int pass) {
+    int32_t g = 0;
+    if (d->flags & RPF_FLAG_GENERIC) {
+        g = kGenericOn;
+        if (d->flags & RPF_FLAG_GENERIC_PACKED) g |= kGenericPacked;
+        if (d->flags & RPF_FLAG_GENERIC_WAVE) g |= kGenericWave;
+    }
+    if (d->flags & RPF_FLAG_GENERIC_FAST) g |= kGenericClassFast; // (validate: only with G | P; read by routes 4 and 5, never by the fused code)
+    // a wide pass: every pixel on generic::filter_wide_kernel (option "wide" = 1: every pass of a call with the flag)
+    const bool wide = (d->flags & RPF_FLAG_WIDE_NBHD) && ((int64_t)box * box * d->S > kMaxNbhd || ctx->tun.wide == 1);
+    if (wide) g |= kGenericWide;
+    // ... counted first and dealt by size class under RPF_FLAG_WIDE_CLASSES (above 832 spp no class can hold a pixel)
+    if (wide && (d->flags & RPF_FLAG_WIDE_CLASSES) && d->S <= 832) g |= kGenericWideClasses;
+    // fp32 pair weights on the streaming / wide kernels: only a pass that runs layout-generic kernels carries the bit (a fused pass
+    // of a WIDE_NBHD | STREAM_FAST call keeps generic == 0 and runs exactly as without the flag)
+    if ((d->flags & RPF_FLAG_STREAM_FAST) && (g & (kGenericOn | kGenericWide))) g |= kGenericStreamFast;
+    // a sampled pass: draws[pass] > 0; with 0 draws the pass carries no bit and runs as without the flag
+    if ((d->flags & RPF_FLAG_SAMPLED_NBHD) && ctx->sampling_set && pass >= 0 && pass < RPF_MAX_BOXES && ctx->sampling.draws[pass] > 0)
+        g |= kGenericSampled;
+    // the membership test: every pass of the call carries the bit
+    if ((d->flags & RPF_FLAG_MEMBER_TEST) && ctx->membership_set) g |= kGenericMemberTest;
+    return g;
+}
+
+// RPF_FLAG_SCHEDULE on the terms of check_sampled, after it and check_member_test: the table, the entries passes 0 .. n_pass - 1
+// read, and -- for a pass whose entry has a gain other than 1 -- the policy and that the pass runs layout-generic kernels.  A pass
+// with both gains 1 is any pass with another seed and is never refused here
+int32_t check_schedule(rpf_ctx *ctx, const rpf_desc *d, const int32_t *boxes, int n_pass) {
+    if (!(d->flags & RPF_FLAG_SCHEDULE)) return RPF_OK;
+    if (!ctx->schedule_set) return fail(ctx, RPF_E_BADARG, "RPF_FLAG_SCHEDULE without a prior rpf_set_schedule");
+    const rpf_schedule &sc = ctx->schedule;
+    if (n_pass < 0 || (int64_t)sc.pass0 + n_pass > RPF_MAX_BOXES)
+        return fail(ctx, RPF_E_BADARG, "RPF_FLAG_SCHEDULE: pass0 + the number of passes > RPF_MAX_BOXES (the call would read beyond entry 7 of rpf_schedule)");
+    for (int i = 0; i < n_pass; ++i) {
+        const int e = sc.pass0 + i;
+        if (sc.gain_c[e] == 1.0 && sc.gain_f[e] == 1.0) continue;
+        if (d->degenerate_policy == RPF_DEGEN_REF_ABORT)
+            return fail(ctx, RPF_E_UNSUPPORTED, "RPF_FLAG_SCHEDULE: a pass with a gain other than 1 under RPF_DEGEN_REF_ABORT: the reference has no "
+                                                "such rule to reproduce, and the redo launch would have to carry it (use RPF_DEGEN_EPS)");
+        if (pass_generic_bits(ctx, d, boxes[i], i) == 0)
+            return fail(ctx, RPF_E_UNSUPPORTED, "RPF_FLAG_SCHEDULE: a pass with a gain other than 1 would run on the fused kernels, which do not know "
+                                                "the rule; a layout-generic route does: RPF_FLAG_GENERIC (| RPF_FLAG_GENERIC_PACKED | "
+                                                "RPF_FLAG_GENERIC_WAVE), RPF_FLAG_WIDE_NBHD on a wide pass, RPF_FLAG_SAMPLED_NBHD with draws > 0 for "
+                                                "the pass, or RPF_FLAG_MEMBER_TEST");
+    }
+    return RPF_OK;
+}
+
 int32_t validate(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes) {
     if (!ctx) return RPF_E_BADARG;
     if (!d) return fail(ctx, RPF_E_BADARG, "desc is NULL");
@@ -178,6 +229,8 @@ int32_t validate(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes) {
         for (int i = 0; i < d->n_box; ++i)
             if (d->box_sizes[i] < 1 || (d->box_sizes[i] & 1) == 0)
                 return fail(ctx, RPF_E_BADARG, "box sizes must be odd and positive (rpf.cpp:561)");
+        const int32_t st = check_schedule(ctx, d, d->box_sizes, d->n_box);
+        if (st) return st;
     }
     return RPF_OK;
 }
@@ -224,6 +277,19 @@ int32_t check_membership(const rpf_membership *cfg, std::string &why) {
     for (int k = 0; k < RPF_MAX_NDIM; ++k) {
         if (!(std::isfinite(cfg->mult[k]) && cfg->mult[k] > 0.0)) { why = "rpf_membership: a multiple that is not finite and > 0"; return RPF_E_BADARG; }
         if (std::isnan(cfg->floor[k]) || (std::isinf(cfg->floor[k]) && cfg->floor[k] > 0.0)) { why = "rpf_membership: a floor that is NaN or +inf"; return RPF_E_BADARG; }
+    }
+    return RPF_OK;
+}
+
+int32_t check_schedule_table(const rpf_schedule *cfg, std::string &why) {
+    if (!cfg) { why = "rpf_schedule is NULL"; return RPF_E_BADARG; }
+    if (cfg->pass0 < 0 || cfg->pass0 >= RPF_MAX_BOXES) { why = "rpf_schedule: pass0 outside [0, RPF_MAX_BOXES)"; return RPF_E_BADARG; }
+    for (int e = 0; e < RPF_MAX_BOXES; ++e) {
+        if (!(std::isfinite(cfg->seed[e]) && cfg->seed[e] > 0.0)) { why = "rpf_schedule: a seed that is not finite and > 0"; return RPF_E_BADARG; }
+        if (!(std::isfinite(cfg->gain_c[e]) && cfg->gain_c[e] >= 0.0) || !(std::isfinite(cfg->gain_f[e]) && cfg->gain_f[e] >= 0.0)) {
+            why = "rpf_schedule: a gain that is not finite and >= 0";
+            return RPF_E_BADARG;
+        }
     }
     return RPF_OK;
 }
@@ -299,12 +365,7 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
     p.box = box; p.b = (box - 1) / 2;
     p.beta_map = d->beta_map; p.policy = d->degenerate_policy;
     p.fast_weights = (d->flags & RPF_FLAG_FAST_WEIGHTS) ? 1 : 0;
-    if (d->flags & RPF_FLAG_GENERIC) {
-        p.generic = kGenericOn;
-        if (d->flags & RPF_FLAG_GENERIC_PACKED) p.generic |= kGenericPacked;
-        if (d->flags & RPF_FLAG_GENERIC_WAVE) p.generic |= kGenericWave;
-    }
-    if (d->flags & RPF_FLAG_GENERIC_FAST) p.generic |= kGenericClassFast; // (validate: only with G | P; read by routes 4 and 5, never by the fused code)
+    p.generic = pass_generic_bits(ctx, d, box, pass);
     p.stage_mask = ctx->tun.stage_mask; // timing ablation knob (rpf_set_option); results are wrong unless -1
     p.screen = ctx->tun.screen;
     const int64_t nmax64 = (int64_t)box * box * d->S;
@@ -315,24 +376,15 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
             ? "box*box*S > 65535: neighbourhood too large (16-bit histogram cells, one-byte bin ids) without RPF_FLAG_WIDE_NBHD"
             : "box*box*S > 262144: neighbourhood too large for the wide kernel of RPF_FLAG_WIDE_NBHD (16-bit bin ids, B <= 512)");
     p.nmax = (int)nmax64;
-    // a wide pass: every pixel on generic::filter_wide_kernel (option "wide" = 1: every pass of a call with the flag)
-    const bool wide = (d->flags & RPF_FLAG_WIDE_NBHD) && (p.nmax > kMaxNbhd || ctx->tun.wide == 1);
-    if (wide) p.generic |= kGenericWide;
-    // ... counted first and dealt by size class under RPF_FLAG_WIDE_CLASSES (above 832 spp no class can hold a pixel)
-    if (wide && (d->flags & RPF_FLAG_WIDE_CLASSES) && d->S <= 832) p.generic |= kGenericWideClasses;
-    // fp32 pair weights on the streaming / wide kernels: only a pass that runs layout-generic kernels carries the bit (a fused pass
-    // of a WIDE_NBHD | STREAM_FAST call keeps generic == 0 and runs exactly as without the flag)
-    if ((d->flags & RPF_FLAG_STREAM_FAST) && (p.generic & (kGenericOn | kGenericWide))) p.generic |= kGenericStreamFast;
+    const bool wide = (p.generic & kGenericWide) != 0;
     // a sampled pass (validate checked the configuration): draws[pass] > 0; with 0 draws the pass carries no bit and runs as without the flag
     ctx->samp_now = SampledPass{};
-    if ((d->flags & RPF_FLAG_SAMPLED_NBHD) && ctx->sampling_set && pass >= 0 && pass < RPF_MAX_BOXES && ctx->sampling.draws[pass] > 0) {
+    if (p.generic & kGenericSampled) {
         ctx->samp_now.draws = ctx->sampling.draws[pass];
         ctx->samp_now.pass_id = (int32_t)((uint32_t)ctx->sampling.pass_id0 + (uint32_t)pass); // (mod 2^32: the key reads it as uint32)
-        p.generic |= kGenericSampled;
     }
     // the membership test (validate checked the configuration and refused every fp32 flag): every pass of the call carries the bit
-    const bool member = (d->flags & RPF_FLAG_MEMBER_TEST) && ctx->membership_set;
-    if (member) p.generic |= kGenericMemberTest;
+    const bool member = (p.generic & kGenericMemberTest) != 0;
     // the fused kernels address a window's samples by 32-bit byte offsets from its first sample (Window, rpf_filter_impl.inc)
     if (rpf_check_window_span(d->W, d->S, box) != RPF_OK)
         return fail(ctx, RPF_E_UNSUPPORTED, "box*W*S*8 >= 2^32: a window's span in bytes of an fp64 plane must fit 32 bits (narrower slabs or a smaller box)");
@@ -349,6 +401,18 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
     }
     p.bmax = bmax_of(p.nmax);
     p.eps = d->eps; p.seed = d->sigma_seed;
+    // the schedule (check_schedule checked the table, the entry's range, and that a pass with a gain other than 1 is layout-generic):
+    // the entry's seed stands for the descriptor's; with both gains 1 the pass carries no bit and runs as without the flag
+    if ((d->flags & RPF_FLAG_SCHEDULE) && ctx->schedule_set) {
+        const int e = ctx->schedule.pass0 + pass;
+        if (pass < 0 || e < 0 || e >= RPF_MAX_BOXES) return fail(ctx, RPF_E_BADARG, "RPF_FLAG_SCHEDULE: the pass reads beyond the table's last entry");
+        p.seed = ctx->schedule.seed[e];
+        if (ctx->schedule.gain_c[e] != 1.0 || ctx->schedule.gain_f[e] != 1.0) {
+            if (!p.generic) return fail(ctx, RPF_E_UNSUPPORTED, "RPF_FLAG_SCHEDULE: a pass with a gain other than 1 on the fused kernels");
+            p.generic |= kGenericSchedule;
+            p.gain_c = ctx->schedule.gain_c[e]; p.gain_f = ctx->schedule.gain_f[e];
+        }
+    }
     p.sigma_p = (double)(box / 4); // rpf.cpp:531: integer division
     p.plane_stride = (uint64_t)d->W * d->H * d->S;
     p.planes = d_planes; p.col_in = col_in; p.col_out = col_out;
@@ -1288,6 +1352,32 @@ int32_t rpf_membership_preset(int32_t kind, int32_t n_feat, rpf_membership *out)
     return RPF_OK;
 }
 
+int32_t rpf_set_schedule(rpf_ctx *ctx, const rpf_schedule *cfg) {
+    if (!ctx) return RPF_E_BADARG;
+    std::string why;
+    const int32_t st = check_schedule_table(cfg, why);
+    if (st) return fail(ctx, st, why);
+    ctx->schedule = *cfg;
+    ctx->schedule_set = true; // (host only: setup_pass copies a pass's entry into its PassParams)
+    return RPF_OK;
+}
+
+int32_t rpf_schedule_preset(int32_t kind, int32_t S, rpf_schedule *out) {
+    if (!out || kind < 0 || kind > 1 || S <= 0) return RPF_E_BADARG;
+    out->pass0 = 0; out->reserved = 0;
+    for (int t = 0; t < RPF_MAX_BOXES; ++t) {
+        if (kind == 0) { // the reference: one seed (rpf.cpp:662's 0.002), alpha = 1 - W_r^c, beta = (1 - W_r^f) W_c^f
+            out->seed[t] = 0.002; out->gain_c[t] = 1.0; out->gain_f[t] = 1.0;
+        } else { // "published", from memory of the paper (include/rpf_hip.h says so): nothing in the library depends on these
+            const double v_t = t == 0 ? 0.02 : 0.002;
+            out->seed[t] = sqrt(8.0 * v_t / (double)S);
+            out->gain_c[t] = 2.0 * (1.0 + 0.1 * t);
+            out->gain_f[t] = 1.0 + 0.1 * t;
+        }
+    }
+    return RPF_OK;
+}
+
 int32_t rpf_sampling_table(int32_t box, uint32_t *table_out) {
     if (!table_out || box < 1 || box > 511 || (box & 1) == 0) return RPF_E_BADARG;
     sampling_table(box, table_out);
@@ -1511,6 +1601,7 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *d, int32_t box, cons
     if (!planes || !colour_out) return fail(ctx, RPF_E_BADARG, "NULL pointer");
     if ((st = check_sampled(ctx, d, 1))) return st; // pass id pass_id0, draws[0]
     if ((st = check_member_test(ctx, d, 1))) return st;
+    if ((st = check_schedule(ctx, d, &box, 1))) return st; // entry pass0
     if (d->flags & RPF_FLAG_SPIKE_CLAMP)
         return fail(ctx, RPF_E_UNSUPPORTED, "RPF_FLAG_SPIKE_CLAMP with rpf_filter_pass_debug: the spike pass follows the last pass of "
                                             "a whole call (rpf_filter / _ex / _device / _film); this entry point returns one pass's raw colours");

@@ -434,6 +434,15 @@ int32_t rpf_multi_set_membership(rpf_multi *m, const rpf_membership *cfg) {
     return RPF_OK;
 }
 
+int32_t rpf_multi_set_schedule(rpf_multi *m, const rpf_schedule *cfg) {
+    if (!m) return RPF_E_BADARG;
+    std::string why;
+    const int32_t st = check_schedule_table(cfg, why);
+    if (st) return mfail(m, st, why);
+    for (rpf_ctx *c : m->ctx) (void)rpf_set_schedule(c, cfg); // indexed by the pass of the call, which every slab runs: the same table
+    return RPF_OK;
+}
+
 int32_t rpf_multi_query_spike(rpf_multi *m, rpf_spike_stats *out) {
     if (!m || !out) return RPF_E_BADARG;
     *out = m->spike;

@@ -290,9 +290,12 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
             double wsum = 0.0;
             for (int i = 0; i < 3; ++i) wsum += sD9[i] / (sD9[i] + sD9[3 + i] + e_eps); // rpf.cpp:470, 485
             const double wrc = wsum / 3;                                               // rpf.cpp:487
+            const bool sched = (p.generic & kGenericSchedule) != 0; // RPF_FLAG_SCHEDULE with a gain other than 1: wave-uniform
             if (t < 3) {
                 const double Drc = sD9[t], Dpc = sD9[3 + t];
-                const double alpha_c = 1 - Drc / (Drc + Dpc + e_eps);                  // rpf.cpp:470, 475
+                double alpha_c;
+                if (sched) alpha_c = schedule_factor(p.gain_c, Drc / (Drc + Dpc + e_eps)); // clamp0(1 - g_c W_r^{c,t})
+                else alpha_c = 1 - Drc / (Drc + Dpc + e_eps);                          // rpf.cpp:470, 475
                 sAlpha[t] = alpha_c;
                 if (p.dbg.alpha && gvalid) p.dbg.alpha[pix * 3 + t] = alpha_c;
             }
@@ -306,7 +309,9 @@ __global__ __launch_bounds__(256) void filter_packed_kernel(PassParams p, Generi
                 for (int l = 0; l < 2; ++l) Dpf += mi[k * nAnc + nR + l];              // rpf.cpp:425
                 for (int cc = 0; cc < 3; ++cc) Dcf += mi[D.npairF + cc * D.npairC + nAnc + k];
                 const double num = beta_numerator(p.beta_map, k, k, Dcf, sD9, sDrf);
-                const double beta_k = (1 - Drf / (Drf + Dpf + e_eps)) * (num / den);   // rpf.cpp:464-465, 479
+                double beta_k;
+                if (sched) beta_k = schedule_factor(p.gain_f, Drf / (Drf + Dpf + e_eps)) * (num / den); // clamp0(1 - g_f W_r^{f,k}) W_c^{f,k}
+                else beta_k = (1 - Drf / (Drf + Dpf + e_eps)) * (num / den);           // rpf.cpp:464-465, 479
                 sBeta[k] = beta_k;
                 if (p.dbg.beta && gvalid) p.dbg.beta[pix * nF + k] = beta_k;
             }

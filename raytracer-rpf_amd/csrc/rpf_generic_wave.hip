@@ -354,13 +354,18 @@ __global__ __launch_bounds__(256) void filter_wave_kernel(PassParams p, GenericW
             double wsum = 0.0;
             for (int i = 0; i < 3; ++i) wsum += sD9[i] / (sD9[i] + sD9[3 + i] + e_eps);                      // rpf.cpp:470, 485
             const double wrc = wsum / 3;                                                                     // rpf.cpp:487
-            const double alpha_c = 1 - Drc / (Drc + Dpc + e_eps);                                            // rpf.cpp:470, 475
+            const bool sched = (p.generic & kGenericSchedule) != 0; // RPF_FLAG_SCHEDULE with a gain other than 1: wave-uniform
+            double alpha_c;
+            if (sched) alpha_c = schedule_factor(p.gain_c, Drc / (Drc + Dpc + e_eps));                       // clamp0(1 - g_c W_r^{c,k})
+            else alpha_c = 1 - Drc / (Drc + Dpc + e_eps);                                                    // rpf.cpp:470, 475
             // the beta presets keep the reference's stack rule for any nF: k < 3 reads D_f_ck, a gap of zeros, then D_r_fk
             double num;
             if (p.beta_map == RPF_BETA_PAPER) num = Dcf;
             else if (p.beta_map == RPF_BETA_REF_GCC11_O2) num = k < 3 ? sD9[6 + c] : (k < 8 ? 0.0 : sDrf[max(k - 8, 0)]);
             else num = k < 3 ? sD9[6 + c] : (k < 4 ? 0.0 : sDrf[max(k - 4, 0)]);
-            const double beta_k = (1 - Drf / (Drf + Dpf + e_eps)) * (num / den);                             // rpf.cpp:464-465, 479
+            double beta_k;
+            if (sched) beta_k = schedule_factor(p.gain_f, Drf / (Drf + Dpf + e_eps)) * (num / den);          // clamp0(1 - g_f W_r^{f,k}) W_c^{f,k}
+            else beta_k = (1 - Drf / (Drf + Dpf + e_eps)) * (num / den);                                     // rpf.cpp:464-465, 479
             if (lane < nF) { sBeta[lane] = beta_k; if (p.dbg.beta) p.dbg.beta[pix * nF + lane] = beta_k; }
             if (lane < 3) { sAlpha[lane] = alpha_c; if (p.dbg.alpha) p.dbg.alpha[pix * 3 + lane] = alpha_c; }
             if (lane == 0) { sWrc[0] = wrc; if (p.dbg.wrc) p.dbg.wrc[pix] = wrc; }

@@ -28,8 +28,9 @@ constexpr int kStageChunk = 64; // samples gathered per step of the in-order (re
 constexpr int kStageHalf = 32;  // ... and staged through LDS this many at a time
 
 // The bits of PassParams::generic (setup_pass writes them, route_pass and the routes read them; 0 = a pass on the compiled, fused
-// kernels).  Only kGenericOn reaches device-side decisions (stage 1a's kernel); the two fast bits are host-side only: no kernel
-// reads them, and PassParams::fast_weights stays 0.
+// kernels).  Two bits reach device-side decisions: kGenericOn (stage 1a's kernel) and kGenericSchedule (stage 3c of the layout-generic
+// filter kernels, a wave-uniform branch); the two fast bits are host-side only: no kernel reads them, and PassParams::fast_weights
+// stays 0.
 enum GenericBits : int32_t {
     kGenericOn = 1,           // RPF_FLAG_GENERIC: stage 1a and the filter pass run on the layout-generic kernels (rpf_generic.hip)
     kGenericPacked = 2,       // RPF_FLAG_GENERIC_PACKED: small neighbourhoods on the packed generic kernels (rpf_generic_packed.hip)
@@ -48,6 +49,9 @@ enum GenericBits : int32_t {
     kGenericMemberTest = 256, // RPF_FLAG_MEMBER_TEST: stage 1b under the configured multiples and floors (rpf_ctx::d_member, which
                               //   setup_pass uploads).  A full-box pass: route 9 whatever the bits above say (route_member_test); a
                               //   sampled pass stays route 8 and its count kernel runs the test; stage 1a is not affected
+    kGenericSchedule = 512,   // RPF_FLAG_SCHEDULE on a pass whose entry has a gain other than 1 (setup_pass; never on a fused pass, which
+                              //   check_schedule refuses): stage 3c of the packed, one-wave, streaming and wide layout-generic kernels
+                              //   forms alpha and beta from PassParams::gain_c / gain_f; selects no route
 };
 
 // everything one pass needs, passed by value to the kernels
@@ -100,9 +104,12 @@ struct PassParams {
     // wrote them), instead of rebuilding them from `masks`; or null
     const uint32_t *members;
     const uint64_t *member_base; // [H*W]
+    // RPF_FLAG_SCHEDULE (kGenericSchedule; read by no kernel without that bit): the gains of this pass's entry, g_c and g_f of
+    // alpha_k = clamp0(1 - g_c * W_r^{c,k}), beta_k = clamp0(1 - g_f * W_r^{f,k}) * W_c^{f,k}.  Last: no other field moves
+    double gain_c, gain_f;
 };
 // the kernel argument block: a field that moves or grows moves it under every kernel at once
-static_assert(sizeof(PassParams) == 352 && offsetof(PassParams, generic) == 40, "PassParams is the kernel argument block");
+static_assert(sizeof(PassParams) == 368 && offsetof(PassParams, generic) == 40 && offsetof(PassParams, gain_c) == 352, "PassParams is the kernel argument block");
 // the two fp32 pair-weight selections: the class kernels of routes 4 / 5 | the streaming and wide kernels, and every kernel of a wide pass
 inline bool class_fast(const PassParams &p) { return (p.generic & kGenericClassFast) != 0; }
 inline bool stream_fast(const PassParams &p) { return (p.generic & kGenericStreamFast) != 0; }

@@ -54,6 +54,13 @@ SAMPLED_NBHD_FLAG = 2048
 # with S > 832.  RPF_FLAG_MEMBER_TEST of the header; the name stays outside the FLAG_* family for SAMPLED_NBHD_FLAG's reason (its
 # table: tests/test_member_test_cpu.py)
 MEMBER_TEST_FLAG = 4096
+# the per-pass schedule of the weight stage (Context.set_schedule): pass p of a call reads entry pass0 + p of
+# a table of (seed, gain_c, gain_f); the seed stands for the descriptor's sigma_seed, and alpha_k = clamp0(1 - gain_c W_r^{c,k}),
+# beta_k = clamp0(1 - gain_f W_r^{f,k}) W_c^{f,k}.  A pass with both gains 1 runs as without the flag on any route (the fused ones
+# included) with its entry's seed; a pass with another gain needs a layout-generic route (FLAG_GENERIC, a wide pass, a sampled
+# pass, MEMBER_TEST_FLAG) and DEGEN_EPS.  Selects no route.  RPF_FLAG_SCHEDULE of the header; the name stays outside the FLAG_*
+# family for SAMPLED_NBHD_FLAG's reason (tests/test_flag_table_cpu.py holds FLAG_* to eleven bits)
+SCHEDULE_FLAG = 8192
 FLAG_WIDE_NBHD = 64  # passes with 65535 < box*box*S <= 262144 on the wide layout-generic kernel (route 6); max_nbhd() tells the bound
 MAX_NDIM = 40     # the layout-generic kernels take 5 + n_random + n_feat up to this
 PLANES_F32, PLANES_F16 = 0, 1
@@ -67,7 +74,8 @@ EXPORTS = ["rpf_version", "rpf_status_string", "rpf_create", "rpf_destroy", "rpf
            "rpf_film_splat_device", "rpf_film_window", "rpf_multi_halo_plan", "rpf_multi_filter_film", "rpf_layout_kernels",
            "rpf_max_nbhd", "rpf_wide_table", "rpf_set_spike", "rpf_multi_set_spike", "rpf_query_spike", "rpf_multi_query_spike",
            "rpf_spike_clamp_device", "rpf_colour_add_device", "rpf_spike_delta", "rpf_set_sampling", "rpf_multi_set_sampling",
-           "rpf_sampling_table", "rpf_sampling_draws", "rpf_set_membership", "rpf_multi_set_membership", "rpf_membership_preset"]
+           "rpf_sampling_table", "rpf_sampling_draws", "rpf_set_membership", "rpf_multi_set_membership", "rpf_membership_preset",
+           "rpf_set_schedule", "rpf_multi_set_schedule", "rpf_schedule_preset"]
 
 # the film step: pbrt's PixelFilters (include/rpf_hip.h, rpf_film)
 PIXFILTER_BOX, PIXFILTER_TRIANGLE, PIXFILTER_GAUSSIAN, PIXFILTER_MITCHELL, PIXFILTER_SINC = range(5)
@@ -156,6 +164,40 @@ def membership_preset(kind, n_feat=NFEAT):
     if st != OK:
         raise RpfError(st, "rpf_membership_preset(kind=%r, n_feat=%r): an unknown kind, n_feat outside [1, 40], or kind 1 with n_feat != 12" % (kind, n_feat))
     return m
+
+
+class Schedule(C.Structure):
+    """rpf_schedule: pass p of a call reads entry pass0 + p; all MAX_BOXES entries are validated (seed finite and > 0, gains finite
+    and >= 0, pass0 in [0, MAX_BOXES))"""
+    _fields_ = [("pass0", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_double * MAX_BOXES),
+                ("gain_c", C.c_double * MAX_BOXES), ("gain_f", C.c_double * MAX_BOXES)]
+
+
+SCHEDULE_REFERENCE, SCHEDULE_PUBLISHED = 0, 1
+
+
+def make_schedule(seed, gain_c, gain_f, pass0=0):
+    """a Schedule from three sequences (or scalars, for every entry); entries not given are the reference's 0.002, 1, 1"""
+    sc = Schedule()
+    sc.pass0, sc.reserved = int(pass0), 0
+    for e in range(MAX_BOXES):
+        sc.seed[e], sc.gain_c[e], sc.gain_f[e] = 0.002, 1.0, 1.0
+    for dst, src in ((sc.seed, seed), (sc.gain_c, gain_c), (sc.gain_f, gain_f)):
+        vals = [src] * MAX_BOXES if np.isscalar(src) else list(src)
+        for e, v in enumerate(vals[:MAX_BOXES]):
+            dst[e] = float(v)
+    return sc
+
+
+def schedule_preset(kind, S):
+    """rpf_schedule_preset (no GPU needed): kind SCHEDULE_REFERENCE -- seeds 0.002, gains 1 -- or SCHEDULE_PUBLISHED -- seed[t] =
+    sqrt(8 v_t / S) with v_0 = 0.02, v_t = 0.002 otherwise, gain_c[t] = 2 (1 + 0.1 t), gain_f[t] = 1 + 0.1 t.  The constants of the
+    latter are from memory of the paper; nothing in the library depends on them"""
+    sc = Schedule()
+    st = load().rpf_schedule_preset(int(kind), int(S), C.byref(sc))
+    if st != OK:
+        raise RpfError(st, "rpf_schedule_preset(kind=%r, S=%r): an unknown kind or S <= 0" % (kind, S))
+    return sc
 
 
 def sampling_table(box):
@@ -373,6 +415,10 @@ def load():
             L.rpf_set_membership.argtypes = [C.c_void_p, C.POINTER(Membership)]
             L.rpf_multi_set_membership.argtypes = [C.c_void_p, C.POINTER(Membership)]
             L.rpf_membership_preset.argtypes = [C.c_int32, C.c_int32, C.POINTER(Membership)]
+        if hasattr(L, "rpf_set_schedule"):  # (absent from a build of before the schedule, loaded through RPF_HIP_LIB)
+            L.rpf_set_schedule.argtypes = [C.c_void_p, C.POINTER(Schedule)]
+            L.rpf_multi_set_schedule.argtypes = [C.c_void_p, C.POINTER(Schedule)]
+            L.rpf_schedule_preset.argtypes = [C.c_int32, C.c_int32, C.POINTER(Schedule)]
         L.rpf_host_alloc.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
         L.rpf_host_free.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
@@ -480,6 +526,11 @@ class Context:
     def set_membership(self, cfg):
         """rpf_set_membership: cfg a Membership (make_membership / membership_preset), or None -> RPF_E_BADARG"""
         self._check(self._L.rpf_set_membership(self._h, None if cfg is None else C.byref(cfg)))
+
+    # ---- the per-pass schedule (SCHEDULE_FLAG) ----------------------------------------------------------------
+    def set_schedule(self, cfg):
+        """rpf_set_schedule: cfg a Schedule (make_schedule / schedule_preset), or None -> RPF_E_BADARG"""
+        self._check(self._L.rpf_set_schedule(self._h, None if cfg is None else C.byref(cfg)))
 
     def spike_clamp_device(self, desc, d_colour, threshold=1.0, stream=None):
         """rpf_spike_clamp_device: the clamp half on rows [row_begin, row_end) of device colours (raw pointer, 3 fp64 planes);
@@ -654,6 +705,12 @@ class MultiContext:
     def set_membership(self, cfg):
         """rpf_multi_set_membership: the membership test of every slab (a function of the pixel alone: nothing moves per slab)"""
         st = self._L.rpf_multi_set_membership(self._h, None if cfg is None else C.byref(cfg))
+        if st != OK:
+            raise RpfError(st, self._L.rpf_multi_last_error(self._h).decode())
+
+    def set_schedule(self, cfg):
+        """rpf_multi_set_schedule: the same table on every slab (the passes of the call index it, and every slab runs them all)"""
+        st = self._L.rpf_multi_set_schedule(self._h, None if cfg is None else C.byref(cfg))
         if st != OK:
             raise RpfError(st, self._L.rpf_multi_last_error(self._h).decode())
 

@@ -43,7 +43,9 @@ def check_desc(desc):
     the pass of each one-pass call; nothing here does, and a rank that filtered with the whole
     image's configuration would silently draw other samples than the whole image does.  MEMBER_TEST_FLAG: every rank's context
     would need the same ``set_membership`` and these helpers carry no such configuration; the test itself is a function of the
-    pixel alone, so MultiContext (or a caller that configures each rank's context) gives the whole image's bits."""
+    pixel alone, so MultiContext (or a caller that configures each rank's context) gives the whole image's bits.  SCHEDULE_FLAG:
+    every rank's context would need the same ``set_schedule`` and, since these helpers drive one pass per call, a ``pass0`` that
+    moves with each call; nothing here does either."""
     from . import hip
     if desc.flags & hip.SAMPLED_NBHD_FLAG:
         raise NotImplementedError("slabs: SAMPLED_NBHD_FLAG (RPF_FLAG_SAMPLED_NBHD) is not supported across ranks yet: each rank must set "
@@ -53,6 +55,10 @@ def check_desc(desc):
         raise NotImplementedError("slabs: MEMBER_TEST_FLAG (RPF_FLAG_MEMBER_TEST) is not supported across ranks yet: each rank's context "
                                   "needs the same Context.set_membership, which these helpers do not carry (INTEGRATION.md "
                                   "section 2g), or use MultiContext, which does")
+    if desc.flags & hip.SCHEDULE_FLAG:
+        raise NotImplementedError("slabs: SCHEDULE_FLAG (RPF_FLAG_SCHEDULE) is not supported across ranks yet: each rank's context needs "
+                                  "the same Context.set_schedule table and, for these one-pass calls, Schedule.pass0 set to the pass "
+                                  "of each call (INTEGRATION.md section 2h), or use MultiContext, which does")
     return desc
 
 
