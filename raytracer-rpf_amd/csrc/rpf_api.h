@@ -1,9 +1,11 @@
-// rpf_api.h -- host only: what the three TUs of the C ABI share.  rpf_api.hip holds the context, validation, pass set-up,
-// the routes and the two pass loops; rpf_api_film.hip the film step's host half; rpf_api_multi.hip the one-process
-// multi-GPU driver.
+// rpf_api.h -- host only: what the TUs of the C ABI share.  rpf_api.hip holds the context, validation, pass set-up and the
+// two pass loops; rpf_api_routes.hip the pass router (route_pass); rpf_api_film.hip the film step's host half;
+// rpf_api_multi.hip the one-process multi-GPU driver; rpf_api_spike.hip the spike pass.
 #pragma once
 #include <dlfcn.h>
 
+#include <algorithm>
+#include <cmath>
 #include <string>
 #include <utility>
 #include <vector>
@@ -181,7 +183,10 @@ struct Range {
             return rpf::fail(ctx, RPF_E_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
     } while (0)
 
-// defined in rpf_api.hip, where each is described
+// floor(sqrt(nmax)), at least 1: the most histogram bins per axis a neighbourhood of that capacity can ask for
+inline int bmax_of(int nmax) { return std::max(1, (int)std::sqrt((double)nmax)); }
+
+// defined in rpf_api.hip, where each is described (route_pass: in rpf_api_routes.hip)
 SampleLayout layout_of(const rpf_desc *d);
 int32_t layout_kernels(const rpf_desc *d, int32_t *generic_out, std::string *why);
 void wide_table(int nmax, uint64_t *out); // out[k] = round(k ln k * 2^kTWideBits), k = 0 .. nmax

@@ -1,5 +1,5 @@
 // rpf_generic_common.h -- what the layout-generic translation units share (rpf_generic.hip, rpf_generic_packed.hip,
-// rpf_generic_wave.hip, rpf_generic_wide.hip, rpf_generic_wide_count.hip, rpf_generic_sampled_count.hip; routes 3 to 8).  Only they include it.  Device
+// rpf_generic_wave.hip, rpf_generic_wide.hip, rpf_generic_wide_count.hip, rpf_generic_sampled_count.hip; routes 3 to 9).  Only they include it.  Device
 // code has internal linkage, like rpf_device_common.h: each TU carries its own copy.
 //
 // For every TU: the column counts of a layout (GenericDims), up16 and the size of the fp64 block of the LDS carve-ups (host side), the
@@ -7,7 +7,9 @@
 //
 // For the packed kernels and the count kernels, whose stage bodies call them: the window of stage 1b and the decode of a
 // candidate, the 3-sigma test of a wave, the column constants and the bin id, the zero band of stage 3b, the beta numerator, the
-// debug hashes and the store of a filtered colour -- the statements the routes promise the same bits for.
+// debug hashes and the store of a filtered colour -- the statements the routes promise the same bits for.  For the two count
+// kernels of the member pool (routes 7 to 9) alone: passes_stage1b_wave, the test their instantiation runs, publish_members, their
+// common tail behind one cursor reservation, and dispatch_count_kernel, which picks the instantiation at the launch.
 //
 // filter_pixel_kernel, filter_wide_kernel and filter_wave_kernel spell the same statements inside their stage bodies and do not
 // call these functions.  Two forms that do were built and held to the bars (profiles/generic_refactor_parent_vs_new.txt): (a)
@@ -155,6 +157,39 @@ __device__ __forceinline__ bool passes_member_wave(const PassParams &p, const do
         }
     }
     return pass;
+}
+// stage 1b's test as an instantiation of a count kernel runs it: the configured test on mt (MEMBER), else the 3-sigma test
+template <class T, bool MEMBER>
+__device__ __forceinline__ bool passes_stage1b_wave(const PassParams &p, const double *mt, int colF, int nF, uint32_t off, uint64_t HW,
+                                                    uint64_t pix, bool pass) {
+    if constexpr (MEMBER) return passes_member_wave<T>(p, mt, colF, nF, off, HW, pix, pass);
+    else return passes_3sigma_wave<T>(p, colF, nF, off, HW, pix, pass);
+}
+
+// The tail of a count kernel, a wave with acc > 0 accepted plane offsets staged in LDS: the wave reserves its entries with one
+// atomic add on the cursor, records its base and copies the offsets where the pool holds them.  A pool too small loses the
+// writes, never the reservation: the cursor ends at the sum of acc whatever the capacity was
+__device__ __forceinline__ void publish_members(const MemberPool &m, uint64_t pix, const uint32_t *staged, int acc, int lane) {
+    wsync(); // the staged offsets are read by other lanes than wrote them
+    uint32_t lo = 0u, hi = 0u;
+    if (lane == 0) {
+        const unsigned long long at = atomicAdd(m.cursor, (unsigned long long)acc);
+        m.base[pix] = at;
+        lo = (uint32_t)at; hi = (uint32_t)(at >> 32);
+    }
+    const uint64_t at = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)hi) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+    if (at + (uint64_t)acc <= m.capacity)
+        for (int j = lane; j < acc; j += 64) m.pool[at + j] = staged[j];
+}
+
+// The launch of a count kernel: f(PlaneType<T>, std::bool_constant<MEMBER>) is called for the instantiation that p's planes
+// (fp32 or fp16) and the presence of a membership table pick
+template <class T>
+struct PlaneType { using type = T; };
+template <class F>
+inline void dispatch_count_kernel(const PassParams &p, const double *member, F &&f) {
+    if (member != nullptr) p.lay.f16 ? f(PlaneType<__half>{}, std::true_type{}) : f(PlaneType<float>{}, std::true_type{});
+    else p.lay.f16 ? f(PlaneType<__half>{}, std::false_type{}) : f(PlaneType<float>{}, std::false_type{});
 }
 
 // ---- stage 2: the constants of a column from its in-order sums and its extrema (sd.h:229-232, mi.cpp:47-50) -----------

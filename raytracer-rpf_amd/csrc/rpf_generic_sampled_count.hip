@@ -5,9 +5,9 @@
 // sample of the box but the D draws of the pixel's key -- SplitMix64 words mapped through the Gaussian threshold table of the box
 // to a window cell and a sample, integer arithmetic only -- made distinct and put in ascending visiting-order index qq, so that
 // the listed members are a subsequence of the full-box list and depend on nothing but the key.  What stays: one wave per pixel,
-// the strict 3-sigma test of passes_3sigma_wave on 64 candidates at a time, the accepted plane offsets staged per wave in LDS and
-// copied to the member pool behind one cursor reservation per pixel, N = S + accepted into p.nbhd, no pool entry for a pixel
-// that accepts nothing.  What goes: the early exit (S + D <= 832 bounds N by construction) and the flat-pixel proof.
+// the strict 3-sigma test of passes_3sigma_wave on 64 candidates at a time (passes_stage1b_wave), the accepted plane offsets staged
+// per wave in LDS and copied to the member pool behind one cursor reservation per pixel (publish_members, the tail the two kernels
+// share, rpf_generic_common.h), N = S + accepted into p.nbhd, no pool entry for a pixel that accepts nothing.  What goes: the early exit (S + D <= 832 bounds N by construction) and the flat-pixel proof.
 //
 // Distinct and ordered: an in-wave enumeration sort.  The D indices (0xffffffff for a discarded draw) are staged in LDS in draw
 // order; index i goes to position #{j : key_j < key_i, or key_j == key_i and j < i} of a second array, which makes that array a
@@ -47,10 +47,7 @@ __device__ __forceinline__ int sc_count_le(const uint32_t *t, int n, uint32_t u)
 }
 
 struct SampledCountOut {
-    uint32_t *pool;              // [capacity] plane offsets of the listed members behind the own samples
-    uint64_t capacity;
-    uint64_t *base;              // [H*W] first pool entry of a pixel with N > S
-    unsigned long long *cursor;  // [1] entries reserved so far
+    MemberPool m;                // base: of a pixel with N > S
     const uint32_t *table;       // [box - 1] Gaussian thresholds of the box (rpf_sampling_table)
     uint64_t seed;
     int32_t pass_id, row_origin, draws;
@@ -120,45 +117,30 @@ __global__ __launch_bounds__(256) void sampled_count_kernel(PassParams p, Sample
         bool pass = qq != kScNone && (k == 0 || srt[k - 1] != qq);
         if (!__any(qq != kScNone)) break; // only discarded draws from here on
         const uint32_t off = pass ? candidate_offset(win, W, S, (int)qq) : 0u;
-        if constexpr (MEMBER) pass = passes_member_wave<T>(p, o.member, colF, nF, off, HW, pix, pass);
-        else pass = passes_3sigma_wave<T>(p, colF, nF, off, HW, pix, pass);
+        pass = passes_stage1b_wave<T, MEMBER>(p, o.member, colF, nF, off, HW, pix, pass);
         const unsigned long long mask = __ballot(pass);
         if (pass) key[acc + __popcll(mask & ((1ull << lane) - 1ull))] = off;
         acc += __popcll(mask);
     }
     if (lane == 0) p.nbhd[pix] = S + acc;
     if (acc == 0) return;
-    wsync(); // the staged offsets are read by other lanes than wrote them
-    uint32_t lo = 0u, hi = 0u;
-    if (lane == 0) {
-        const unsigned long long at = atomicAdd(o.cursor, (unsigned long long)acc);
-        o.base[pix] = at;
-        lo = (uint32_t)at; hi = (uint32_t)(at >> 32);
-    }
-    const uint64_t at = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)hi) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
-    if (at + (uint64_t)acc <= o.capacity)
-        for (int j = lane; j < acc; j += 64) o.pool[at + j] = key[j];
+    publish_members(o.m, pix, key, acc, lane);
 }
 
 } // namespace
 
-hipError_t launch_sampled_count(const PassParams &p, const SampledCountArgs &a, uint32_t *pool, uint64_t capacity, uint64_t *base,
-                                unsigned long long *cursor, hipStream_t s) {
-    if (pool == nullptr || base == nullptr || cursor == nullptr || a.table == nullptr || p.nbhd == nullptr) return hipErrorInvalidValue;
+hipError_t launch_sampled_count(const PassParams &p, const SampledCountArgs &a, const MemberPool &m, hipStream_t s) {
+    if (m.pool == nullptr || m.base == nullptr || m.cursor == nullptr || a.table == nullptr || p.nbhd == nullptr) return hipErrorInvalidValue;
     if (p.S < 1 || a.draws < 1 || p.S + a.draws > kScCap || p.box - 1 > kScTable || !p.lay.generic_ok()) return hipErrorInvalidValue;
     if (p.row_end <= p.row_begin) return hipSuccess;
     hipError_t e;
-    if ((e = hipMemsetAsync(cursor, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(m.cursor, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
     const uint64_t npix = (uint64_t)(p.row_end - p.row_begin) * p.W;
     const dim3 grid((unsigned)((npix + 3) / 4));
-    SampledCountOut o;
-    o.pool = pool; o.capacity = capacity; o.base = base; o.cursor = cursor;
-    o.table = a.table; o.seed = a.seed; o.pass_id = a.pass_id; o.row_origin = a.row_origin; o.draws = a.draws; o.member = a.member;
-    if (a.member != nullptr) {
-        if (p.lay.f16) hipLaunchKernelGGL((sampled_count_kernel<__half, true>), grid, dim3(256), 0, s, p, o);
-        else hipLaunchKernelGGL((sampled_count_kernel<float, true>), grid, dim3(256), 0, s, p, o);
-    } else if (p.lay.f16) hipLaunchKernelGGL(sampled_count_kernel<__half>, grid, dim3(256), 0, s, p, o);
-    else hipLaunchKernelGGL(sampled_count_kernel<float>, grid, dim3(256), 0, s, p, o);
+    const SampledCountOut o{m, a.table, a.seed, a.pass_id, a.row_origin, a.draws, a.member};
+    dispatch_count_kernel(p, a.member, [&](auto plane, auto with_member) {
+        hipLaunchKernelGGL((sampled_count_kernel<typename decltype(plane)::type, decltype(with_member)::value>), grid, dim3(256), 0, s, p, o);
+    });
     return hipGetLastError();
 }
 

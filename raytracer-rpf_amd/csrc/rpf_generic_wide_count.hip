@@ -19,6 +19,9 @@
 // multiples and floors, and its flat proof asks of feature k: pstd[k] * mult[k] == 0.0, a finite mean AND floor[k] < 0 -- under
 // a non-negative floor a zero-variance feature accepts its equals, so nothing is proven.  The first instantiation is the code it
 // was.
+// What it shares with sampled_count_kernel lives in rpf_generic_common.h: the pool (MemberPool, the first member of the kernel's
+// second argument), the test of an instantiation (passes_stage1b_wave), the tail behind the cursor (publish_members) and the
+// choice of the instantiation at the launch (dispatch_count_kernel).
 #include "rpf_generic_common.h"
 
 #include <algorithm>
@@ -30,10 +33,7 @@ namespace {
 constexpr int kWcCap = 832; // the largest class of the one-wave kernels
 
 struct WideCountOut {
-    uint32_t *pool;              // [capacity] plane offsets of the listed members behind the own samples
-    uint64_t capacity;
-    uint64_t *base;              // [H*W] first pool entry of a pixel with S < N <= 832
-    unsigned long long *cursor;  // [1] entries reserved so far
+    MemberPool m;                // base: of a pixel with S < N <= 832
     const int32_t *nan_flag;     // [1] != 0: some feature mean in reach of the slab is NaN
     const double *member;        // MEMBER: mult[RPF_MAX_NDIM] | floor[RPF_MAX_NDIM]; the other instantiation does not read it
 };
@@ -86,8 +86,7 @@ __global__ __launch_bounds__(256) void wide_count_kernel(PassParams p, WideCount
         const int qq = qb + lane;
         bool pass = qq < ncand;
         const uint32_t off = pass ? candidate_offset(win, W, S, qq) : 0u;
-        if constexpr (MEMBER) pass = passes_member_wave<T>(p, o.member, colF, nF, off, HW, pix, pass);
-        else pass = passes_3sigma_wave<T>(p, colF, nF, off, HW, pix, pass);
+        pass = passes_stage1b_wave<T, MEMBER>(p, o.member, colF, nF, off, HW, pix, pass);
         const unsigned long long mask = __ballot(pass);
         if (pass) {
             const int at = acc + __popcll(mask & ((1ull << lane) - 1ull));
@@ -101,27 +100,17 @@ __global__ __launch_bounds__(256) void wide_count_kernel(PassParams p, WideCount
     }
     if (lane == 0) p.nbhd[pix] = S + acc;
     if (acc == 0) return;
-    wsync(); // the staged offsets are read by other lanes than wrote them
-    uint32_t lo = 0u, hi = 0u;
-    if (lane == 0) {
-        const unsigned long long at = atomicAdd(o.cursor, (unsigned long long)acc);
-        o.base[pix] = at;
-        lo = (uint32_t)at; hi = (uint32_t)(at >> 32);
-    }
-    const uint64_t at = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)hi) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
-    if (at + (uint64_t)acc <= o.capacity)
-        for (int j = lane; j < acc; j += 64) o.pool[at + j] = mine[j];
+    publish_members(o.m, pix, mine, acc, lane);
 }
 
 } // namespace
 
-hipError_t launch_wide_count(const PassParams &p, uint32_t *pool, uint64_t capacity, uint64_t *base, unsigned long long *cursor,
-                             int32_t *nan_flag, hipStream_t s, const double *member) {
-    if (pool == nullptr || base == nullptr || cursor == nullptr || nan_flag == nullptr || p.nbhd == nullptr) return hipErrorInvalidValue;
+hipError_t launch_wide_count(const PassParams &p, const MemberPool &m, int32_t *nan_flag, const double *member, hipStream_t s) {
+    if (m.pool == nullptr || m.base == nullptr || m.cursor == nullptr || nan_flag == nullptr || p.nbhd == nullptr) return hipErrorInvalidValue;
     if (p.S < 1 || p.S > kWcCap || !p.lay.generic_ok()) return hipErrorInvalidValue;
     if (p.row_end <= p.row_begin) return hipSuccess;
     hipError_t e;
-    if ((e = hipMemsetAsync(cursor, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(m.cursor, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(nan_flag, 0, sizeof(int32_t), s)) != hipSuccess) return e;
     const uint64_t HW = (uint64_t)p.H * p.W;
     const uint64_t pix0 = (uint64_t)std::max(p.row_begin - p.b, 0) * p.W, pix1 = (uint64_t)std::min(p.row_end + p.b, p.H) * p.W;
@@ -129,13 +118,10 @@ hipError_t launch_wide_count(const PassParams &p, uint32_t *pool, uint64_t capac
                        p.pmean, HW, pix0, pix1, p.lay.nF, nan_flag);
     const uint64_t npix = (uint64_t)(p.row_end - p.row_begin) * p.W;
     const dim3 grid((unsigned)((npix + 3) / 4));
-    WideCountOut o;
-    o.pool = pool; o.capacity = capacity; o.base = base; o.cursor = cursor; o.nan_flag = nan_flag; o.member = member;
-    if (member != nullptr) {
-        if (p.lay.f16) hipLaunchKernelGGL((wide_count_kernel<__half, true>), grid, dim3(256), 0, s, p, o);
-        else hipLaunchKernelGGL((wide_count_kernel<float, true>), grid, dim3(256), 0, s, p, o);
-    } else if (p.lay.f16) hipLaunchKernelGGL(wide_count_kernel<__half>, grid, dim3(256), 0, s, p, o);
-    else hipLaunchKernelGGL(wide_count_kernel<float>, grid, dim3(256), 0, s, p, o);
+    const WideCountOut o{m, nan_flag, member};
+    dispatch_count_kernel(p, member, [&](auto plane, auto with_member) {
+        hipLaunchKernelGGL((wide_count_kernel<typename decltype(plane)::type, decltype(with_member)::value>), grid, dim3(256), 0, s, p, o);
+    });
     return hipGetLastError();
 }
 

@@ -295,26 +295,34 @@ namespace generic {
 // two-compare test of DESIGN.md section 14 on them (the MEMBER instantiations; the others are the code they were)
 hipError_t launch_filter_wide(const PassParams &p, void *list, void *bins, uint32_t slots, const uint64_t *table, int table_bits,
                               const uint32_t *count_dev, hipStream_t s, bool fast = false, const double *member = nullptr);
-// the count pass of route 7 (rpf_generic_wide_count.hip, S <= 832): for every pixel of rows [p.row_begin, p.row_end) N into
-// p.nbhd -- 833 for any N > 832 -- and, for S < N <= 832, the N - S members behind the own samples into pool[base[pix] ..];
-// *cursor ends at the sum of those N - S, whether or not `capacity` entries held them (a pool too small loses writes only:
-// the caller compares and repeats).  nan_flag: [1], scratch of the flat-pixel proof.  Reads stage 1a's planes of the rows
-// the slab's windows reach.  member != null (route 9): as for launch_filter_wide; the flat-pixel proof then asks for a negative
-// floor as well
-hipError_t launch_wide_count(const PassParams &p, uint32_t *pool, uint64_t capacity, uint64_t *base, unsigned long long *cursor,
-                             int32_t *nan_flag, hipStream_t s, const double *member = nullptr);
+// The member pool of routes 7, 8 and 9, all in device memory: what a count kernel fills and the class kernels read back as
+// PassParams::members / member_base.  The two count kernels take it as the first 32 bytes of their second argument
+struct MemberPool {
+    uint32_t *pool;              // [capacity] plane offsets of the listed members behind the own samples
+    uint64_t capacity;
+    uint64_t *base;              // [H*W] first pool entry of a pixel that lists members
+    unsigned long long *cursor;  // [1] entries reserved so far
+};
+static_assert(sizeof(MemberPool) == 32 && offsetof(MemberPool, capacity) == 8 && offsetof(MemberPool, base) == 16 &&
+                  offsetof(MemberPool, cursor) == 24, "the count kernels' argument offsets");
+// the count pass of routes 7 and 9 (rpf_generic_wide_count.hip, S <= 832): for every pixel of rows [p.row_begin, p.row_end) N
+// into p.nbhd -- 833 for any N > 832 -- and, for S < N <= 832, the N - S members behind the own samples into
+// m.pool[m.base[pix] ..]; *m.cursor ends at the sum of those N - S, whether or not m.capacity entries held them (a pool too small
+// loses writes only: the caller compares and repeats).  nan_flag: [1], scratch of the flat-pixel proof.  Reads stage 1a's planes
+// of the rows the slab's windows reach.  member != null (route 9): as for launch_filter_wide; the flat-pixel proof then asks for
+// a negative floor as well
+hipError_t launch_wide_count(const PassParams &p, const MemberPool &m, int32_t *nan_flag, const double *member, hipStream_t s);
 // the count pass of route 8 (rpf_generic_sampled_count.hip, S + draws <= 832): for every pixel of rows
 // [p.row_begin, p.row_end) the distinct draws of its key that pass the 3-sigma test, in ascending visiting order, into
-// pool[base[pix] ..] and N = S + their number into p.nbhd; *cursor as launch_wide_count leaves it.  table: device, the box - 1
-// Gaussian thresholds of p.box; member != null (with RPF_FLAG_MEMBER_TEST): as for launch_filter_wide, the test of the draws
+// m.pool[m.base[pix] ..] and N = S + their number into p.nbhd; *m.cursor as launch_wide_count leaves it.  table: device, the
+// box - 1 Gaussian thresholds of p.box; member != null (with RPF_FLAG_MEMBER_TEST): as for launch_filter_wide, the test of the draws
 struct SampledCountArgs {
     const uint32_t *table;
     uint64_t seed;
     int32_t pass_id, row_origin, draws;
     const double *member = nullptr;
 };
-hipError_t launch_sampled_count(const PassParams &p, const SampledCountArgs &a, uint32_t *pool, uint64_t capacity, uint64_t *base,
-                                unsigned long long *cursor, hipStream_t s);
+hipError_t launch_sampled_count(const PassParams &p, const SampledCountArgs &a, const MemberPool &m, hipStream_t s);
 } // namespace generic
 
 // ---- the spike pass (rpf_spike.hip, RPF_FLAG_SPIKE_CLAMP) -----------------------------------------------
