@@ -373,7 +373,6 @@ int32_t route_wide_classes(rpf_ctx *ctx, const PassParams &p_in, const double *m
     const ListedPass lp = {member != nullptr, "rpf:wide count + classify (stage 1b test, listed members, lane and wave classes)",
                            "wide count pass: the member pool overflowed at its exact size"};
     ctx->last_route = member ? kRouteMemberTest : kRouteWideClasses;
-    ctx->bin_valid = false;
     PassParams p = p_in;
     if (p.row_end <= p.row_begin) return RPF_OK;
     uint32_t counts[kNumClasses];
@@ -406,7 +405,6 @@ int32_t route_wide_classes(rpf_ctx *ctx, const PassParams &p_in, const double *m
 // they are.  REF_ABORT is refused, so there is no redo list; the lists of this pass are no other pass's (the membership cache of
 // the size-binned route neither serves it nor survives it).
 int32_t route_member_test(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *launches) {
-    ctx->bin_valid = false;
     if (!ctx->d_member || !ctx->member_fresh || p.S > class_capacity(kNumWave - 1) || p.redo_list != nullptr)
         return fail(ctx, RPF_E_BADARG, "pass under the membership test without its configuration (setup_pass prepares it)");
     return route_wide_classes(ctx, p, ctx->d_member, s, launches);
@@ -420,7 +418,6 @@ int32_t route_member_test(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int 
 int32_t route_sampled(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
     int32_t st;
     ctx->last_route = kRouteSampled;
-    ctx->bin_valid = false;
     PassParams p = p_in;
     p.redo_list = nullptr; p.redo_count = nullptr;
     if (p.row_end <= p.row_begin) return RPF_OK;
@@ -511,6 +508,15 @@ int32_t route_pass(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *lau
     // FAST instantiations test p.redo_list at run time like the others, stage 3b)
     const bool keeps_list = route == kRouteNone ? ctx->tun.stage_mask == -1 : route != kRouteGeneric && route != kRouteWide;
     if ((st = begin_redo(ctx, p, keeps_list, s))) return st;
+    // a pass on the compiled kernels: size-binned or not
+    bool bin = route == kRouteNone && p.nmax > 512;
+    if (route == kRouteNone && ctx->tun.binning >= 0) bin = ctx->tun.binning != 0;
+    if (route == kRouteNone && p.nmax > kMaxResident) bin = true; // the streaming kernel takes the pixels no resident kernel can hold
+    // The membership cache of the size-binned route (bin_valid: the class counts on the host, d_lists and d_masks on the device)
+    // outlives a pass only from one size-binned pass to the next: route_binned alone sets it, and every other route drops it
+    // here, before it runs -- the unbinned route with its packed lists, routes 4 and 5 and the listed-member routes 7, 8 and 9
+    // write their own lists, masks and class counts into the same buffers
+    if (!bin) ctx->bin_valid = false;
     switch (route) {
     case kRouteSampled: return route_sampled(ctx, p, s, launches);
     case kRouteMemberTest: return route_member_test(ctx, p, s, launches);
@@ -521,9 +527,6 @@ int32_t route_pass(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *lau
     case kRouteGeneric: return route_generic(ctx, p, s, launches);
     default: break;
     }
-    bool bin = p.nmax > 512;
-    if (ctx->tun.binning >= 0) bin = ctx->tun.binning != 0;
-    if (p.nmax > kMaxResident) bin = true; // the streaming kernel takes the pixels no resident kernel can hold
     // small neighbourhoods (N <= 64) run on the packed kernels, several pixels per wave (rpf_packed_impl.inc); option "packed"
     const bool packed = ctx->tun.packed != 0 && !p.fast_weights && ctx->tun.stage_mask == -1 && ctx->tun.lds_pad == 0;
     return bin ? route_binned(ctx, p, packed, s, launches) : route_unbinned(ctx, p, packed, s, launches);

@@ -469,7 +469,8 @@ def test_multi_pass_with_size_binning(ctx, hipmod, oracle):
     assert rel_l2(srgb.astype(np.float64), planes[2:5].astype(np.float64)) > 1e-3
 
 
-@pytest.mark.parametrize("boxes,rows", [((7,), None), ((7, 5), None), ((5, 7, 5), None), ((5,), (6, 140)), ((7,), (20, 41))])
+@pytest.mark.parametrize("boxes,rows", [((7,), None), ((7, 5), None), ((5, 7, 5), None), ((5,), (6, 140)), ((7,), (20, 41)),
+                                        ((9, 7, 9), None)])  # size-binned, unbinned, size-binned again (8 spp: 648 > 512 >= 392)
 def test_host_entry_band_pipeline_equals_serial(ctx, hipmod, oracle, boxes, rows):
     """rpf_filter() on page-locked buffers (rpf_host_alloc) overlaps upload / filter / download over row bands; it
     must give bit-for-bit what the serial sequence (RPF_FLAG_NO_OVERLAP, and any pageable buffer) gives"""
