@@ -312,7 +312,9 @@ typedef struct rpf_counters {
     int32_t options_active;     /* 1 when any rpf_set_option override was in force (diagnostic runs)   */
     int32_t redo_pixels;        /* RPF_DEGEN_REF_ABORT, last pass: pixels filtered a second time with the reference's own
                                    floating-point MI expression (an exactly independent histogram pair at a non-power-of-two
-                                   N: mi.cpp:79-86 returns rounding residue there, not 0)                */
+                                   N: mi.cpp:79-86 returns rounding residue there, not 0).  The total of the pass: rpf_filter's
+                                   row-band pipeline, which filters the last pass band by band, reports the sum over its
+                                   bands, the figure of the serial call                                  */
 } rpf_counters;
 
 const char *rpf_version(void);
@@ -445,7 +447,10 @@ int32_t rpf_query_nbhd(rpf_ctx *ctx, int32_t *nbhd_out, int64_t count);
  * 8 = a sampled pass (RPF_FLAG_SAMPLED_NBHD with draws > 0: its member lists differ, by definition),
  * 9 = a full-box pass under RPF_FLAG_MEMBER_TEST (count kernel with the configured membership test, size classes, the wide
  * kernel for N > 832; its member lists are the reference's only under the reference's multiples and floors),
- * -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1. */
+ * -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1.  rpf_filter's row-band
+ * pipeline runs that probe once per band, on the rows of the slab that are resident by then -- the last band of a pass on the
+ * whole slab -- so the answer after such a call is the serial call's (bands above the last may have taken the other of 0 / 1:
+ * same bits). */
 int32_t rpf_query_route(rpf_ctx *ctx, int32_t *route_out);
 
 /* visualizeSF (rpf.cpp:37-101, visualization/vis.cpp:34-51): the reference's six debug images, without the EXR

@@ -68,6 +68,10 @@ static_assert(sizeof(rpf_membership) == 2 * RPF_MAX_NDIM * sizeof(double) && off
 static_assert(sizeof(rpf_schedule) == 8 + 3 * RPF_MAX_BOXES * sizeof(double) && offsetof(rpf_schedule, seed) == 8 &&
                   offsetof(rpf_schedule, gain_c) == 8 + RPF_MAX_BOXES * sizeof(double), "rpf_schedule is ABI");
 
+// The redo counts of a pass under REF_ABORT: one per route_pass call, and rpf_filter's row-band pipeline cuts a pass into at most
+// eight bands (run_host_pipeline)
+constexpr int kRedoCounts = 8;
+
 // The sampled pass in progress (RPF_FLAG_SAMPLED_NBHD; setup_pass fills it, route_sampled reads it): draws == 0, not sampled
 struct SampledPass {
     int32_t draws = 0, pass_id = 0;
@@ -101,7 +105,12 @@ struct rpf_ctx {
     rpf::DevBuf<uint8_t> d_flat;                // stage 1a by-product: pixels with a zero-variance feature [H*W]
     rpf::DevBuf<int32_t> d_nan_flag;            // ... and whether any feature mean of the buffer is NaN
     rpf::DevBuf<uint32_t> d_redo_list;          // REF_ABORT: pixels handed to the reference-expression kernel [H*W]
-    rpf::DevBuf<uint32_t> d_redo_count;
+    rpf::DevBuf<uint32_t> d_redo_count;         // [kRedoCounts] ... and how many: one count per route_pass call of a pass (per row band)
+    // the rows the route probe of an unbinned pass reads (option "count_first" at -1), when they are not those of the route_pass call:
+    // rpf_filter's row-band pipeline names the rows of the slab that are resident, so that a band is not judged by its own few rows
+    // and the last band of a pass decides on the whole slab, as the serial call does.  Empty: the call's own rows (setup_pass)
+    int probe_r0 = 0, probe_r1 = 0;
+    int redo_used = 0;                          // the counts the pass in progress has taken (setup_pass: 0; begin_redo: the next)
     // a wide pass dealt by size class (RPF_FLAG_WIDE_CLASSES, route 7): what its count kernel leaves for the class kernels
     rpf::DevBuf<uint32_t> d_wc_pool;            // member pool: the N - S members behind the own samples of every pixel with N <= 832
     rpf::DevBuf<uint64_t> d_wc_base;            // [H*W] a pixel's first pool entry

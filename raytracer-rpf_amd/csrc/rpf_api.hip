@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <numeric>
 #include <string>
 #include <vector>
 
@@ -374,6 +375,8 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
     const bool wide = (p.generic & kGenericWide) != 0;
     // a sampled pass (validate checked the configuration): draws[pass] > 0; with 0 draws the pass carries no bit and runs as without the flag
     ctx->samp_now = SampledPass{};
+    ctx->probe_r0 = ctx->probe_r1 = 0; // ... and its route probe reads the rows of its route_pass calls unless the caller names others
+    ctx->redo_used = 0; // a pass begins: its route_pass calls take the redo counts from the first on (begin_redo)
     if (p.generic & kGenericSampled) {
         ctx->samp_now.draws = ctx->sampling.draws[pass];
         ctx->samp_now.pass_id = (int32_t)((uint32_t)ctx->sampling.pass_id0 + (uint32_t)pass); // (mod 2^32: the key reads it as uint32)
@@ -463,20 +466,21 @@ std::string nonfinite_message(int x, int y, long long count) {
     return buf;
 }
 
-// A call ends, after n_pass passes over the slab of d: reduces N, reads status, N reduction and redo count back (one
+// A call ends, after n_pass passes over the slab of d: reduces N, reads status, N reduction and the last pass's redo counts back (one
 // synchronisation of s) and fills the counters that do not depend on the entry point.
 int32_t finish_counters(rpf_ctx *ctx, const rpf_desc *d, int n_pass, hipStream_t s) {
     rpf_counters &c = ctx->counters;
     HIP_TRY(launch_nbhd_reduce(ctx->d_nbhd, d->W, d->row_begin, d->row_end, ctx->d_nred, s));
     int32_t hst[2];
     unsigned long long nred[2];
-    uint32_t redo = 0;
+    uint32_t redo[kRedoCounts] = {};
     HIP_TRY(hipMemcpyAsync(hst, ctx->d_status, sizeof(hst), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipMemcpyAsync(nred, ctx->d_nred, sizeof(nred), hipMemcpyDeviceToHost, s));
     if (d->degenerate_policy == RPF_DEGEN_REF_ABORT)
-        HIP_TRY(hipMemcpyAsync(&redo, ctx->d_redo_count, sizeof(redo), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(redo, ctx->d_redo_count, sizeof(redo), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    c.redo_pixels = (int32_t)redo;
+    // the last pass's: one count per route_pass call of it -- one, or one per row band of rpf_filter's pipeline
+    c.redo_pixels = (int32_t)std::accumulate(redo, redo + std::min(ctx->redo_used, kRedoCounts), (uint32_t)0);
     c.samples_filtered = (int64_t)(d->row_end - d->row_begin) * d->W * d->S * n_pass;
     c.options_active = ctx->tun.is_default() ? 0 : 1;
     c.sum_nbhd = (int64_t)nred[0];
@@ -672,8 +676,15 @@ int32_t run_host_pipeline(rpf_ctx *ctx, const rpf_desc *d, const void *planes_v,
             q.row_begin = std::max(r0, d->row_begin);
             q.row_end = std::min(r1, d->row_end);
             if ((st = pass_through(ctx, d, cin, cout, r0, r1, s))) return st;
-            if (q.row_end > q.row_begin) return route_pass(ctx, q, s, &c.filter_kernel_launches);
-            return RPF_OK;
+            if (q.row_end <= q.row_begin) return RPF_OK;
+            // the route probe of an unbinned pass: every row of the slab that is resident and has its stage 1a -- in the first pass
+            // those down to the band's last row (the band below it, its halo, is up), afterwards the whole slab.  The last band of
+            // a pass so decides on the serial call's lattice, and rpf_query_route answers as after the serial call
+            ctx->probe_r0 = d->row_begin;
+            ctx->probe_r1 = first ? std::min(r1, d->row_end) : d->row_end;
+            st = route_pass(ctx, q, s, &c.filter_kernel_launches);
+            ctx->probe_r0 = ctx->probe_r1 = 0;
+            return st;
         };
         auto emit_rows = [&](int j) -> int32_t { // last pass: reduce + download band j
             if (!want_out) return RPF_OK;
@@ -764,8 +775,8 @@ int32_t rpf_create(rpf_ctx **out, int32_t device) {
     if ((st = ctx->d_class_counts.ensure(ctx, (kNumClasses + 2) * sizeof(uint32_t)))) return st;
     if ((st = ctx->d_nan_flag.ensure(ctx, sizeof(int32_t)))) return st;
     HIP_TRY(hipMemset(ctx->d_nan_flag, 0, sizeof(int32_t)));
-    if ((st = ctx->d_redo_count.ensure(ctx, sizeof(uint32_t)))) return st;
-    HIP_TRY(hipMemset(ctx->d_redo_count, 0, sizeof(uint32_t)));
+    if ((st = ctx->d_redo_count.ensure(ctx, kRedoCounts * sizeof(uint32_t)))) return st;
+    HIP_TRY(hipMemset(ctx->d_redo_count, 0, kRedoCounts * sizeof(uint32_t)));
     for (auto &e : ctx->ev) HIP_TRY(hipEventCreate(&e));
     return RPF_OK;
 }

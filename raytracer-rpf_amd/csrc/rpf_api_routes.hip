@@ -88,16 +88,20 @@ int32_t launch_redo(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *launc
     return launch_streaming(ctx, q, kCountOnDevice, kRedoSlots, p.redo_count, s, launches, false); // a redone pixel is fp64 under every flag
 }
 
-// A pass begins under p's policy.  REF_ABORT: the redo count is zeroed, whether or not the pass keeps a list (finish_counters
-// reads it back after every REF_ABORT call); a route that keeps one gets d_redo_list and p pointed at it.  Otherwise p names none.
+// A route_pass call begins under p's policy.  REF_ABORT: the call takes the next of the pass's redo counts (setup_pass starts a pass
+// at the first) and zeroes it, whether or not the route keeps a list: a pass filtered band by band (rpf_filter's row-band pipeline)
+// gives every band a count of its own -- the list size its redo launch reads on the device -- and finish_counters adds up those of
+// the last pass.  A route that keeps a list gets d_redo_list and p pointed at it and at that count.  Otherwise p names none.
 int32_t begin_redo(rpf_ctx *ctx, PassParams &p, bool keeps_list, hipStream_t s) {
     p.redo_list = nullptr; p.redo_count = nullptr;
     if (p.policy != RPF_DEGEN_REF_ABORT) return RPF_OK;
-    HIP_TRY(hipMemsetAsync(ctx->d_redo_count, 0, sizeof(uint32_t), s));
+    if (ctx->redo_used >= kRedoCounts) return fail(ctx, RPF_E_BADARG, "a pass cut into more row bands than it has redo counts");
+    uint32_t *count = ctx->d_redo_count + ctx->redo_used++;
+    HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint32_t), s));
     if (!keeps_list) return RPF_OK;
     int32_t st;
     if ((st = ctx->d_redo_list.ensure(ctx, (size_t)p.W * p.H * sizeof(uint32_t)))) return st;
-    p.redo_list = ctx->d_redo_list; p.redo_count = ctx->d_redo_count;
+    p.redo_list = ctx->d_redo_list; p.redo_count = count;
     return RPF_OK;
 }
 
@@ -156,8 +160,9 @@ int32_t route_unbinned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream
         Range rg("rpf:route probe + prelist (flat quads)");
         uint32_t probe[2] = {0, 0};
         const int step = 32;
+        PassParams pr = q; // the probe's rows: the call's, or those the band pipeline names (rpf_ctx::probe_r0)
+        if (ctx->probe_r1 > ctx->probe_r0) { pr.row_begin = ctx->probe_r0; pr.row_end = ctx->probe_r1; }
         if (count_first < 0) {
-            PassParams pr = q;
             pr.masks = nullptr; pr.reroute_masks = nullptr;
             if (!ctx->flat_fresh) pr.flat = nullptr;
             HIP_TRY(hipMemsetAsync(pcount, 0, 2 * sizeof(uint32_t), s));
@@ -170,7 +175,7 @@ int32_t route_unbinned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream
         }
         HIP_TRY(hipStreamSynchronize(s)); // one read-back for both
         if (count_first < 0) {
-            const uint32_t n_probe = (uint32_t)((p.W + step - 1) / step) * (uint32_t)((p.row_end - p.row_begin + step - 1) / step);
+            const uint32_t n_probe = (uint32_t)((p.W + step - 1) / step) * (uint32_t)((pr.row_end - pr.row_begin + step - 1) / step);
             const uint32_t n_probe_general = n_probe - std::min(n_probe, probe[1]);
             count_first = (n_probe_general != 0 && 2u * probe[0] >= n_probe_general) ? 1 : 0; // (only flat pixels: nothing to count)
         }

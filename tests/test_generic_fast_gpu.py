@@ -259,7 +259,8 @@ def test_entries_filter_pinned_and_multi_context(ctx, hipmod, oracle):
     # really fp32: not the bits of the call without X
     _, _, _, c64_ref = ctx.filter(e["planes"], desc_for(hipmod, ENTRY_LAY, W, H, S, fast=False, boxes=(7, 5), policy=EPS), want_colour64=True)
     assert rel_l2(c64_ref, c) <= 1e-9 and not np.array_equal(c64_ref, e["c64"])
-    # the band pipeline from page-locked buffers
+    # page-locked buffers take the host pipeline's path; 12 rows are ONE band there (a frame below 32 rows is never cut), so this is the
+    # serial order on the pipeline's streams -- the cut into several bands is held by tests/test_host_bands_gpu.py
     pin = ctx.host_empty(e["planes"].shape, e["planes"].dtype)
     pin[...] = e["planes"]
     out_s, out_p = ctx.host_empty(e["srgb"].shape), ctx.host_empty(e["prgb"].shape)

@@ -241,7 +241,8 @@ def test_entries_stats_multi_pass_and_pinned(ctx, hipmod, oracle, lay):
                                debug=False)["colour"]
     assert rel_l2(c64, c) <= 1e-9
     assert np.array_equal(srgb, c64.astype(np.float32))
-    # the band pipeline from page-locked buffers
+    # page-locked buffers take the host pipeline's path; 11 rows are ONE band there (a frame below 32 rows is never cut), so this is the
+    # serial order on the pipeline's streams -- the cut into several bands is held by tests/test_host_bands_gpu.py
     pin = ctx.host_empty(planes.shape, planes.dtype)
     pin[...] = planes
     out_s, out_p = ctx.host_empty(srgb.shape), ctx.host_empty(prgb.shape)

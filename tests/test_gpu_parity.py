@@ -732,7 +732,8 @@ def test_layout27_multi_pass_host_entry_and_stage1a(ctx, hipmod, oracle):
     for box in (7, 5):
         c = oracle.filter_pass(p32, oracle.make_desc(W, H, S, box=box, policy=1, **L27), colour_in=c, debug=False)["colour"]
     assert rel_l2(c64, c) <= 1e-9
-    # the pinned-buffer band pipeline moves fp16 planes too
+    # the host pipeline's path (page-locked buffers) moves fp16 planes too; 11 rows are ONE band there (a frame below 32 rows is
+    # never cut): the cut into several bands, fp16 planes included, is held by tests/test_host_bands_gpu.py
     pin = ctx.host_empty(p16.shape, np.float16)
     pin[...] = p16
     out_s, out_p = ctx.host_empty(srgb.shape), ctx.host_empty(prgb.shape)

@@ -138,7 +138,8 @@ def end_to_end(ctx, hipmod, planes, boxes, flags=0, nonfinite=False, **lay):
     # rpf_filter (no fp64 colours across the boundary): the same samples and pixel means
     s3, p3, _ = ctx.filter(planes, on, allow_nonfinite=nonfinite)
     assert np.array_equal(s3, srgb, equal_nan=True) and np.array_equal(p3, prgb, equal_nan=True)
-    # ... and from page-locked buffers, where rpf_filter would otherwise download band by band before delta is known
+    # ... and from page-locked buffers: the flag takes the serial path there (no band may leave before delta is known), so no
+    # band pipeline runs in this test -- and these frames, below 32 rows, would be one band of it anyway
     pp, ps_, ppx = ctx.host_empty(planes.shape), ctx.host_empty(srgb.shape), ctx.host_empty(prgb.shape)
     pp[...] = planes
     ps_[...] = 0

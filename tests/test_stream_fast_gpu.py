@@ -406,7 +406,9 @@ def test_entries_two_passes_pinned_and_multi_context(ctx, hipmod, oracle):
     assert np.array_equal(e["srgb"], e["c64"].astype(np.float32))
     _, _, _, c64_ref = ctx.filter(e["planes"], desc_for(hipmod, ENTRY_LAY, W, H, S, "G", boxes=(7, 5), policy=EPS), want_colour64=True)
     assert rel_l2(c64_ref, c) <= 1e-9 and not np.array_equal(c64_ref, e["c64"])        # really fp32
-    pin = ctx.host_empty(e["planes"].shape, e["planes"].dtype)                           # the band pipeline
+    # page-locked buffers take the host pipeline's path; 12 rows are ONE band there (a frame below 32 rows is never cut), so this is the
+    # serial order on the pipeline's streams -- the cut into several bands is held by tests/test_host_bands_gpu.py
+    pin = ctx.host_empty(e["planes"].shape, e["planes"].dtype)
     pin[...] = e["planes"]
     out_s, out_p = ctx.host_empty(e["srgb"].shape), ctx.host_empty(e["prgb"].shape)
     ctx.filter(pin, e["d"], out_samples=out_s, out_pixels=out_p)
