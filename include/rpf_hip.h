@@ -36,6 +36,7 @@ extern "C" {
 #define RPF_NPAIR 96
 #define RPF_MAX_BOXES 8
 #define RPF_MAX_NDIM 40 /* widest sample vector of the layout-generic kernels (RPF_FLAG_GENERIC): 5 + n_random + n_feat */
+#define RPF_SAMPLED_MAX 8192 /* the most S + draws of a sampled pass under RPF_FLAG_SAMPLED_REST (832 without it); rpf_max_draws() */
 /* general layout: columns [0,2) pFilm | [2,5) colour | [5,5+nR) random parameters | [5+nR,5+nR+nF) features */
 #define RPF_NDIM_OF(nR, nF) (5 + (nR) + (nF))
 #define RPF_NPAIR_OF(nR, nF) ((nF) * ((nR) + 2) + 3 * ((nR) + 2 + (nF))) /* MI pairs, rpf.cpp:416-442 generalised */
@@ -177,7 +178,8 @@ enum {
                                   beta, W_r_c, weights, blend; fp64) is that of the packed and one-wave layout-generic
                                   kernels on that list.  rpf_query_route says 8, redo_pixels is 0, filter_kernel_launches
                                   counts one launch per non-empty size class, sum_nbhd / max_nbhd / rpf_query_nbhd report
-                                  the sampled N.  S + draws[p] <= 832 (RPF_E_BADARG otherwise).  A pass with draws[p] == 0
+                                  the sampled N.  S + draws[p] <= 832 (RPF_E_BADARG otherwise; RPF_FLAG_SAMPLED_REST lifts
+                                  the bound to 8192).  A pass with draws[p] == 0
                                   runs exactly as without the flag: same route, same bits.  Every filter entry point takes
                                   the flag (rpf_filter_pass_debug: pass id pass_id0, draws[0]); an entry point that runs no
                                   pass (stage 1a, the colour / reduce / spike / film-window helpers) takes a descriptor with
@@ -233,6 +235,27 @@ enum {
                                   number of passes > RPF_MAX_BOXES (RPF_E_BADARG); a pass with a gain other than 1 under
                                   RPF_DEGEN_REF_ABORT (the reference has no such rule, and the redo launch would have to carry
                                   it) or on the fused kernels (RPF_E_UNSUPPORTED). */
+    RPF_FLAG_SAMPLED_REST = 16384, /* opt-in, modifies RPF_FLAG_SAMPLED_NBHD: a sampled pass may have S + draws[p] <= RPF_SAMPLED_MAX
+                                  (8192) instead of 832; rpf_max_draws() tells the bound.  The definition
+                                  of a sampled neighbourhood is unchanged: the own samples, then the distinct surviving draws
+                                  that pass stage 1b's test, in ascending visiting order.  A pass with S + draws[p] <= 832 runs
+                                  exactly as without this flag: same count kernel, same launches, same bits.  Above it the draws
+                                  are counted by a kernel that sorts them a workgroup per pixel; pixels that end with N <= 832
+                                  run on the packed and one-wave class kernels as before, and pixels with N > 832 go to one rest
+                                  launch of the generic filter kernel that reads their listed members (fp64, the 2^-44 table,
+                                  LDS and scratch sized for S + draws, not for box*box*S).  S itself may exceed 832: every
+                                  pixel of such a pass is a rest pixel.  rpf_query_route keeps saying 8, redo_pixels is 0,
+                                  filter_kernel_launches counts one launch per non-empty class plus one for a non-empty rest
+                                  list, sum_nbhd / max_nbhd / rpf_query_nbhd report the sampled N.  The member pool grows to the
+                                  sum of N - S over the pixels, at most pixels * draws entries (option "wide_pool" sets its
+                                  first size).  It composes with RPF_FLAG_MEMBER_TEST, RPF_FLAG_SCHEDULE, RPF_FLAG_SPIKE_CLAMP
+                                  and RPF_FLAG_WIDE_NBHD (a pass with box*box*S > 65535 still needs that flag) as route 8 does,
+                                  from every filter entry point; rpf_layout_kernels reports *generic_out as without it and
+                                  rpf_max_nbhd is unchanged.  Refused before any device work: the flag without
+                                  RPF_FLAG_SAMPLED_NBHD (RPF_E_UNSUPPORTED; rpf_layout_kernels answers the same way);
+                                  S + draws[p] > 8192 on a pass with draws[p] > 0 (RPF_E_BADARG); every other refusal of a
+                                  sampled pass stands (RPF_DEGEN_REF_ABORT, the three fp32 flags, a missing rpf_set_sampling,
+                                  a negative draw count). */
     RPF_FLAG_STREAM_FAST = 512/* opt-in, modifies RPF_FLAG_GENERIC and / or RPF_FLAG_WIDE_NBHD: the two kernels that walk a
                                   neighbourhood of any size with 256 threads -- the generic filter kernel (route 3, the rest
                                   list N > 64 / N > 832 of routes 4 / 5) and the wide kernel (route 6, the rest list N > 832 of
@@ -424,7 +447,8 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *desc, int32_t box, c
  * pixel has N > 832, and under RPF_DEGEN_REF_ABORT one for the redo launch (the wide kernel again); redo_pixels counts the
  * pixels the packed and the one-wave kernels put on the redo list.
  * A sampled pass (RPF_FLAG_SAMPLED_NBHD with draws > 0: route 8) counts one launch per non-empty packed or one-wave class and
- * nothing else -- S + draws <= 832 leaves no rest list, and RPF_DEGEN_REF_ABORT is refused -- and leaves redo_pixels 0;
+ * nothing else -- S + draws <= 832 leaves no rest list, and RPF_DEGEN_REF_ABORT is refused -- and leaves redo_pixels 0; under
+ * RPF_FLAG_SAMPLED_REST a pass with S + draws > 832 adds one launch for a non-empty rest list (N > 832);
  * sum_nbhd / max_nbhd are those of the sampled neighbourhoods.
  * A full-box pass under RPF_FLAG_MEMBER_TEST (route 9) counts one launch per non-empty packed or one-wave class and one for the
  * wide kernel when some pixel has N > 832; RPF_DEGEN_REF_ABORT is refused, so redo_pixels is 0; sum_nbhd / max_nbhd are those
@@ -516,6 +540,12 @@ int32_t rpf_layout_kernels(const rpf_desc *desc, int32_t *generic_out);
  * larger pass is RPF_E_UNSUPPORTED from every filter entry point (the pass set-up calls this function, so the two cannot
  * drift).  Only flags is read.  Needs no context and no device.  RPF_E_BADARG for a NULL pointer. */
 int32_t rpf_max_nbhd(const rpf_desc *desc, int32_t *nmax_out);
+
+/* The most draws a sampled pass (RPF_FLAG_SAMPLED_NBHD) may have under S and the flags of desc: *dmax_out = max(0, 832 - S), or
+ * max(0, RPF_SAMPLED_MAX - S) with RPF_FLAG_SAMPLED_REST; a pass with more is RPF_E_BADARG from every filter entry point (their
+ * check calls this function, so the two cannot drift).  Only S and flags are read.  Needs no context and no device.
+ * RPF_E_BADARG for a NULL pointer or S <= 0. */
+int32_t rpf_max_draws(const rpf_desc *desc, int32_t *dmax_out);
 
 /* The table the wide kernel forms MI from: table_out[k] = round(k ln k * 2^41), k = 0 .. nmax (nmax + 1 entries), computed on
  * the host in long double.  Every entry up to nmax = 262144 is below 2^63 (the 2^-44 table of the other kernels stops being

@@ -75,6 +75,7 @@ constexpr int kRedoCounts = 8;
 // The sampled pass in progress (RPF_FLAG_SAMPLED_NBHD; setup_pass fills it, route_sampled reads it): draws == 0, not sampled
 struct SampledPass {
     int32_t draws = 0, pass_id = 0;
+    int32_t max_draws = 0; // rpf_max_draws of the call's descriptor: 832 - S, or RPF_SAMPLED_MAX - S under RPF_FLAG_SAMPLED_REST
 };
 
 } // namespace rpf

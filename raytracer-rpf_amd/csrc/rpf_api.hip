@@ -52,6 +52,7 @@ constexpr FlagRule kFlagRules[] = {
     {RPF_FLAG_SAMPLED_NBHD, 0, 0, RPF_FLAG_FAST_WEIGHTS, "RPF_FLAG_SAMPLED_NBHD with RPF_FLAG_FAST_WEIGHTS: sampled passes are fp64 throughout"},
     {RPF_FLAG_SAMPLED_NBHD, 0, 0, RPF_FLAG_GENERIC_FAST, "RPF_FLAG_SAMPLED_NBHD with RPF_FLAG_GENERIC_FAST: sampled passes are fp64 throughout"},
     {RPF_FLAG_SAMPLED_NBHD, 0, 0, RPF_FLAG_STREAM_FAST, "RPF_FLAG_SAMPLED_NBHD with RPF_FLAG_STREAM_FAST: sampled passes are fp64 throughout"},
+    {RPF_FLAG_SAMPLED_REST, RPF_FLAG_SAMPLED_NBHD, 0, 0, "RPF_FLAG_SAMPLED_REST without RPF_FLAG_SAMPLED_NBHD: the flag modifies the sampled route"},
     {RPF_FLAG_WIDE_CLASSES, RPF_FLAG_WIDE_NBHD, 0, 0, "RPF_FLAG_WIDE_CLASSES without RPF_FLAG_WIDE_NBHD: the flag modifies the wide route"},
     {RPF_FLAG_GENERIC_FAST, kPackedRoute, 0, 0, "RPF_FLAG_GENERIC_FAST without RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED: the flag modifies the packed layout-generic route"},
     {RPF_FLAG_GENERIC_FAST, 0, 0, RPF_FLAG_FAST_WEIGHTS, "RPF_FLAG_GENERIC_FAST with RPF_FLAG_FAST_WEIGHTS: that flag selects the fused fp32 kernels of the 19-dim layout, this one the layout-generic ones"},
@@ -117,9 +118,13 @@ int32_t check_sampled(rpf_ctx *ctx, const rpf_desc *d, int n_pass) {
     for (int i = 0; i < std::max(0, std::min(n_pass, RPF_MAX_BOXES)); ++i) {
         const int32_t D = ctx->sampling.draws[i];
         if (D < 0) return fail(ctx, RPF_E_BADARG, "rpf_sampling: a negative draw count");
-        if (D > 0 && (int64_t)d->S + D > 832)
-            return fail(ctx, RPF_E_BADARG, "RPF_FLAG_SAMPLED_NBHD: S + draws > 832 (the largest size class of the one-wave kernels; a rest "
-                                           "kernel that reads listed members does not exist)");
+        int32_t dmax = 0;
+        (void)rpf_max_draws(d, &dmax); // (validate refused S <= 0)
+        if (D > dmax)
+            return fail(ctx, RPF_E_BADARG, (d->flags & RPF_FLAG_SAMPLED_REST)
+                ? "RPF_FLAG_SAMPLED_NBHD | RPF_FLAG_SAMPLED_REST: S + draws > 8192 (RPF_SAMPLED_MAX: the count kernel sorts a pixel's draws in 32 KiB of LDS)"
+                : "RPF_FLAG_SAMPLED_NBHD: S + draws > 832 (the largest size class of the one-wave kernels; RPF_FLAG_SAMPLED_REST "
+                  "lifts the bound to 8192)");
         if (D > 0 && d->degenerate_policy == RPF_DEGEN_REF_ABORT)
             return fail(ctx, RPF_E_UNSUPPORTED, "a sampled pass under RPF_DEGEN_REF_ABORT: the reference has no sampled gather to reproduce, "
                                                 "and the redo kernels run their own full-box stage 1b (use RPF_DEGEN_EPS)");
@@ -380,6 +385,7 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
     if (p.generic & kGenericSampled) {
         ctx->samp_now.draws = ctx->sampling.draws[pass];
         ctx->samp_now.pass_id = (int32_t)((uint32_t)ctx->sampling.pass_id0 + (uint32_t)pass); // (mod 2^32: the key reads it as uint32)
+        (void)rpf_max_draws(d, &ctx->samp_now.max_draws);
     }
     // the membership test (validate checked the configuration and refused every fp32 flag): every pass of the call carries the bit
     const bool member = (p.generic & kGenericMemberTest) != 0;
@@ -810,6 +816,13 @@ int32_t rpf_layout_kernels(const rpf_desc *d, int32_t *generic_out) { return lay
 int32_t rpf_max_nbhd(const rpf_desc *d, int32_t *nmax_out) {
     if (!d || !nmax_out) return RPF_E_BADARG;
     *nmax_out = (d->flags & RPF_FLAG_WIDE_NBHD) ? kMaxWideNbhd : kMaxNbhd;
+    return RPF_OK;
+}
+
+int32_t rpf_max_draws(const rpf_desc *d, int32_t *dmax_out) {
+    if (!d || !dmax_out || d->S <= 0) return RPF_E_BADARG;
+    const int32_t cap = (d->flags & RPF_FLAG_SAMPLED_REST) ? RPF_SAMPLED_MAX : 832;
+    *dmax_out = std::max(0, cap - d->S);
     return RPF_OK;
 }
 

@@ -48,13 +48,13 @@ int32_t ensure_slot_scratch(rpf_ctx *ctx, const PassParams &p, uint32_t slots, u
 
 // One launch of the streaming kernel over p's rows or pixel list (`pixels` of them; kCountOnDevice with count_dev: the list size
 // is read on the device and the grid is the rule's slots): the slots by `rule`, the scratch, the launch, counted in *launches.
-// fast: the fp32 stage 4 of RPF_FLAG_STREAM_FAST
+// fast: the fp32 stage 4 of RPF_FLAG_STREAM_FAST; listed: the LISTED instantiation (the rest launch of a sampled pass)
 int32_t launch_streaming(rpf_ctx *ctx, const PassParams &p, uint64_t pixels, const SlotRule &rule, const uint32_t *count_dev,
-                         hipStream_t s, int *launches, bool fast) {
+                         hipStream_t s, int *launches, bool fast, bool listed = false) {
     const uint32_t slots = slot_count(rule, p, pixels);
     int32_t st;
     if ((st = ensure_slot_scratch(ctx, p, slots, rule.bin_bytes))) return st;
-    HIP_TRY(generic::launch_filter(p, ctx->d_big_list, ctx->d_big_bins, slots, count_dev, s, fast));
+    HIP_TRY(generic::launch_filter(p, ctx->d_big_list, ctx->d_big_bins, slots, count_dev, s, fast, listed));
     if (launches) ++*launches;
     return RPF_OK;
 }
@@ -415,11 +415,14 @@ int32_t route_member_test(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int 
     return route_wide_classes(ctx, p, ctx->d_member, s, launches);
 }
 
-// A sampled pass (RPF_FLAG_SAMPLED_NBHD with draws > 0): route 7 with another count kernel and nothing
-// behind the classes.  generic::sampled_count_kernel lists, per pixel, the distinct draws of its key that pass the 3-sigma test;
-// S + draws <= 832 puts every pixel into one of the eight classes, so there is no rest launch, and REF_ABORT is refused, so there
-// is no redo launch.  Pool capacity and growth are route 7's (option "wide_pool").  The lists of this pass are no other pass's:
-// the membership cache of the size-binned route neither serves it nor survives it (d_lists is overwritten).
+// A sampled pass (RPF_FLAG_SAMPLED_NBHD with draws > 0): route 7 with another count kernel.
+// generic::launch_sampled_count lists, per pixel, the distinct draws of its key that pass the 3-sigma test; S + draws <= 832 puts
+// every pixel into one of the eight classes, so there is no rest launch, and REF_ABORT is refused, so there is no redo launch.
+// Under RPF_FLAG_SAMPLED_REST S + draws may reach RPF_SAMPLED_MAX (section 13e): the count is then the block kernel's, and the
+// pixels with N > 832 -- the rest list -- go to one launch of generic::filter_pixel_kernel's LISTED instantiation, which reads their
+// listed members, with nmax = S + draws (never more than the window holds) for its carve-up and its HBM slots, kPassSlots' rule,
+// and the 2^-44 table.  Pool capacity and growth are route 7's (option "wide_pool"): up to pixels * draws entries.  The lists of this
+// pass are no other pass's: the membership cache of the size-binned route neither serves it nor survives it (d_lists is overwritten).
 int32_t route_sampled(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *launches) {
     int32_t st;
     ctx->last_route = kRouteSampled;
@@ -427,7 +430,7 @@ int32_t route_sampled(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *
     p.redo_list = nullptr; p.redo_count = nullptr;
     if (p.row_end <= p.row_begin) return RPF_OK;
     const SampledPass sp = ctx->samp_now;
-    if (sp.draws < 1 || p.S + sp.draws > class_capacity(kNumWave - 1) || !ctx->d_samp_table || ctx->samp_table_box != p.box)
+    if (sp.draws < 1 || sp.draws > sp.max_draws || !ctx->d_samp_table || ctx->samp_table_box != p.box)
         return fail(ctx, RPF_E_BADARG, "sampled pass without its configuration (setup_pass prepares it)");
     generic::SampledCountArgs a = {ctx->d_samp_table, ctx->sampling.seed, sp.pass_id, ctx->sampling.row_origin, sp.draws};
     if (p.generic & kGenericMemberTest) { // with RPF_FLAG_MEMBER_TEST the draws meet the configured test
@@ -440,8 +443,18 @@ int32_t route_sampled(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *
     // (launch_sampled_count zeroes the cursor itself)
     const auto count = [&](const PassParams &q, const generic::MemberPool &m, hipStream_t cs) { return generic::launch_sampled_count(q, a, m, cs); };
     if ((st = count_and_deal(ctx, p, lp, count, counts, s))) return st;
-    if (counts[kRestClass] != 0) return fail(ctx, RPF_E_HIP, "sampled count pass: a pixel with N > 832");
-    return launch_classes(ctx, p, counts, kNumWave, false, "rpf:sampled pass, packed class", "rpf:sampled pass, wave class", s, launches);
+    if (counts[kRestClass] != 0 && p.S + sp.draws <= class_capacity(kNumWave - 1)) return fail(ctx, RPF_E_HIP, "sampled count pass: a pixel with N > 832");
+    if ((st = launch_classes(ctx, p, counts, kNumWave, false, "rpf:sampled pass, packed class", "rpf:sampled pass, wave class", s, launches))) return st;
+    if (counts[kRestClass] != 0) {
+        Range rg("rpf:sampled pass, listed rest kernel (N > 832)");
+        PassParams q = p;
+        q.nmax = (int32_t)std::min<int64_t>(p.nmax, (int64_t)p.S + sp.draws);
+        q.bmax = bmax_of(q.nmax);
+        q.pix_list = ctx->d_lists + (size_t)kRestClass * p.W * p.H;
+        q.list_count = counts[kRestClass];
+        if ((st = launch_streaming(ctx, q, q.list_count, kPassSlots, nullptr, s, launches, false, true))) return st;
+    }
+    return RPF_OK;
 }
 
 // Routes 4 and 5, the layout-generic route with its small neighbourhoods on class kernels (RPF_FLAG_GENERIC |

@@ -103,7 +103,9 @@ __global__ __launch_bounds__(256) void pixel_stats_kernel(PassParams p, uint64_t
 // One workgroup filters one pixel at a time and walks the pixels of rows [row_begin, row_end) or, when p.pix_list is given,
 // the entries of that list (*gs.count_dev of them when that is given, else p.list_count).
 // FAST (RPF_FLAG_STREAM_FAST): stage 4 alone in the fp32 arithmetic of DESIGN.md section 11f; every other statement is shared.
-template <class T, bool FAST = false>
+// LISTED (the rest launch of a sampled pass, RPF_FLAG_SAMPLED_REST): stage 1b alone reads N from p.nbhd and the
+// members behind the own samples from p.members / p.member_base instead of walking the box; every other statement is shared.
+template <class T, bool FAST = false, bool LISTED = false>
 __global__ __launch_bounds__(256) void filter_pixel_kernel(PassParams p, GenericCarve cv, Scratch gs) {
     extern __shared__ __align__(16) unsigned char smem[];
     const GenericDims D = generic_dims(p.lay);
@@ -129,6 +131,7 @@ __global__ __launch_bounds__(256) void filter_pixel_kernel(PassParams p, Generic
     const double e_eps = (p.policy == RPF_DEGEN_EPS) ? p.eps : 0.0;
     constexpr bool kMemberTest = false;         // (RPF_FLAG_MEMBER_TEST never reaches this kernel: the stage text's statements
     constexpr const double *mtab = nullptr;     //  under it are discarded, and the assembly is what it was)
+    constexpr bool kListed = LISTED;
 
     const uint32_t npix = p.pix_list == nullptr ? (uint32_t)(p.row_end - p.row_begin) * (uint32_t)W
                                                 : (gs.count_dev != nullptr ? *gs.count_dev : p.list_count);
@@ -281,11 +284,11 @@ __global__ __launch_bounds__(256) void filter_pixel_kernel(PassParams p, Generic
     }
 }
 
-template <class T, bool FAST>
+template <class T, bool FAST, bool LISTED>
 hipError_t launch_filter_t(const PassParams &p, const GenericCarve &cv, const Scratch &gs, unsigned grid, hipStream_t s) {
-    hipError_t e = hipFuncSetAttribute((const void *)filter_pixel_kernel<T, FAST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
+    hipError_t e = hipFuncSetAttribute((const void *)filter_pixel_kernel<T, FAST, LISTED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)cv.total);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((filter_pixel_kernel<T, FAST>), dim3(grid), dim3(kThreads), cv.total, s, p, cv, gs);
+    hipLaunchKernelGGL((filter_pixel_kernel<T, FAST, LISTED>), dim3(grid), dim3(kThreads), cv.total, s, p, cv, gs);
     return hipGetLastError();
 }
 
@@ -300,8 +303,11 @@ hipError_t launch_pixel_stats(const PassParams &p, uint64_t pix0, uint64_t pix1,
 }
 
 // list / bins: the HBM slots of the spilled mode ([slots][nmax] u32, [slots][ndim][nmax] u8), unused when the carve-up is
-// resident; the grid never exceeds `slots`: min(pixels, slots), or `slots` when the list size is on the device
-hipError_t launch_filter(const PassParams &p, void *list, void *bins, uint32_t slots, const uint32_t *count_dev, hipStream_t s, bool fast) {
+// resident; the grid never exceeds `slots`: min(pixels, slots), or `slots` when the list size is on the device.  listed: the
+// LISTED instantiation over p.pix_list, fp64 only (p.nbhd, p.members and p.member_base as a count kernel of the member pool left them)
+hipError_t launch_filter(const PassParams &p, void *list, void *bins, uint32_t slots, const uint32_t *count_dev, hipStream_t s, bool fast,
+                         bool listed) {
+    if (listed && (fast || p.members == nullptr || p.member_base == nullptr || p.pix_list == nullptr || count_dev != nullptr)) return hipErrorInvalidValue;
     const GenericCarve cv = generic_carve(p.lay, p.nmax, fast);
     if ((int)cv.total > max_lds_per_block()) return hipErrorInvalidValue;
     if (p.row_end <= p.row_begin) return hipSuccess;
@@ -311,8 +317,9 @@ hipError_t launch_filter(const PassParams &p, void *list, void *bins, uint32_t s
     if (grid == 0) return hipSuccess;
     Scratch gs;
     gs.list = (uint32_t *)list; gs.bins = (uint8_t *)bins; gs.count_dev = count_dev;
-    if (fast) return p.lay.f16 ? launch_filter_t<__half, true>(p, cv, gs, grid, s) : launch_filter_t<float, true>(p, cv, gs, grid, s);
-    return p.lay.f16 ? launch_filter_t<__half, false>(p, cv, gs, grid, s) : launch_filter_t<float, false>(p, cv, gs, grid, s);
+    if (listed) return p.lay.f16 ? launch_filter_t<__half, false, true>(p, cv, gs, grid, s) : launch_filter_t<float, false, true>(p, cv, gs, grid, s);
+    if (fast) return p.lay.f16 ? launch_filter_t<__half, true, false>(p, cv, gs, grid, s) : launch_filter_t<float, true, false>(p, cv, gs, grid, s);
+    return p.lay.f16 ? launch_filter_t<__half, false, false>(p, cv, gs, grid, s) : launch_filter_t<float, false, false>(p, cv, gs, grid, s);
 }
 
 } // namespace generic

@@ -9,7 +9,7 @@
 // candidate, the 3-sigma test of a wave, the column constants and the bin id, the zero band of stage 3b, the beta numerator, the
 // debug hashes and the store of a filtered colour -- the statements the routes promise the same bits for.  For the two count
 // kernels of the member pool (routes 7 to 9) alone: passes_stage1b_wave, the test their instantiation runs, publish_members, their
-// common tail behind one cursor reservation, and dispatch_count_kernel, which picks the instantiation at the launch.
+// common tail behind one cursor reservation (publish_members_block: its workgroup form), and dispatch_count_kernel, which picks the instantiation at the launch.
 //
 // filter_pixel_kernel, filter_wide_kernel and filter_wave_kernel spell the same statements inside their stage bodies and do not
 // call these functions.  Two forms that do were built and held to the bars (profiles/generic_refactor_parent_vs_new.txt): (a)
@@ -180,6 +180,21 @@ __device__ __forceinline__ void publish_members(const MemberPool &m, uint64_t pi
     const uint64_t at = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)hi) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
     if (at + (uint64_t)acc <= m.capacity)
         for (int j = lane; j < acc; j += 64) m.pool[at + j] = staged[j];
+}
+
+// The same tail for a workgroup of 256 threads that counted one pixel (sampled_count_block_kernel): acc > 0 offsets staged in LDS,
+// acc workgroup-uniform; thread 0 reserves and hands the base to the others through sAt (LDS)
+__device__ __forceinline__ void publish_members_block(const MemberPool &m, uint64_t pix, const uint32_t *staged, int acc, unsigned long long *sAt) {
+    __syncthreads(); // the staged offsets are read by other threads than wrote them
+    if (threadIdx.x == 0) {
+        const unsigned long long at = atomicAdd(m.cursor, (unsigned long long)acc);
+        m.base[pix] = at;
+        *sAt = at;
+    }
+    __syncthreads();
+    const uint64_t at = *sAt;
+    if (at + (uint64_t)acc <= m.capacity)
+        for (int j = threadIdx.x; j < acc; j += 256) m.pool[at + j] = staged[j];
 }
 
 // The launch of a count kernel: f(PlaneType<T>, std::bool_constant<MEMBER>) is called for the instantiation that p's planes

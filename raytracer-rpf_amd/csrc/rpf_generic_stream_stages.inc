@@ -14,66 +14,75 @@
 //
 // Names the including kernel provides: p, D and ndim, nF, nR, nAnc, npair, nwt, colF; tid, lane, wv; W, H, S, b, HW; pix, x, y;
 // e_eps; list, bins and the type Bin of a bin id; sStat, sZ, sMI, sW, sRedD, sChunk, sRed4, sCnt; for part 4 also smem and cv (the
-// start of the dynamic LDS and the carve-up, whose off_chunk it rounds up); for part 1 also the compile-time constant kMemberTest
-// and, where it is true, mtab (RPF_FLAG_MEMBER_TEST: mult[RPF_MAX_NDIM] | floor[RPF_MAX_NDIM] on the device; DESIGN.md section 14).
-// The statements under kMemberTest are discarded where it is false: such a kernel sees the text it saw.  Part 1 leaves n, B and dn.
+// start of the dynamic LDS and the carve-up, whose off_chunk it rounds up); for part 1 also the compile-time constants kMemberTest
+// and kListed and, where kMemberTest is true, mtab (RPF_FLAG_MEMBER_TEST: mult[RPF_MAX_NDIM] | floor[RPF_MAX_NDIM] on the device; DESIGN.md section 14).
+// The statements under kMemberTest are discarded where it is false, and so is one side of kListed: such a kernel sees the text it saw.
+// Part 1 leaves n, B and dn.
 #if RPF_STREAM_PART == 1
         // ---- stage 1b: the 3-sigma test and the member list, reference order (rpf.cpp:556-586) -------------------
-        const int x0 = max(x - b, 0), x1 = min(x + b, W - 1), y0 = max(y - b, 0), y1 = min(y + b, H - 1);
-        const int nyv = y1 - y0 + 1;
-        const int centre_rank = (x - x0) * nyv + (y - y0);
-        const int ncand = ((x1 - x0 + 1) * nyv - 1) * S;
+        // kListed (the rest launch of a sampled pass; DESIGN.md section 13e): no walk of the box -- N is what the count kernel wrote, the
+        // members behind the own samples are those it listed, in its order, and p.nbhd is not rewritten
         for (int s = tid; s < S; s += kThreads) list[s] = (uint32_t)(pix * S + s); // own samples first
         int n = S;
-        double *sMf = sChunk + 8, *sLf = sMf + nF;
-        for (int k = tid; k < nF; k += kThreads) {
-            sMf[k] = p.pmean[(uint64_t)k * HW + pix];
-            if constexpr (kMemberTest) { // lim_k = sd_k * mult_k, fl_k = -inf where sd_k is above the floor (behind sLf)
-                const double sd = p.pstd[(uint64_t)k * HW + pix], fk = mtab[RPF_MAX_NDIM + k];
-                sLf[k] = sd * mtab[k];
-                sLf[nF + k] = sd > fk ? -__builtin_inf() : fk;
-            } else {
-                sLf[k] = p.pstd[(uint64_t)k * HW + pix] * 3.0; // multiplyArray(std, 3), rpf.cpp:579
+        if constexpr (kListed) {
+            n = min(p.nbhd[pix], p.nmax); // (S + draws <= p.nmax by the route's construction: the clamp never bites)
+            const uint64_t mb = n > S ? p.member_base[pix] : 0ull; // (a pixel that lists nothing has no base)
+            for (int i = tid; i < n - S; i += kThreads) list[S + i] = p.members[mb + i];
+        } else {
+            const int x0 = max(x - b, 0), x1 = min(x + b, W - 1), y0 = max(y - b, 0), y1 = min(y + b, H - 1);
+            const int nyv = y1 - y0 + 1;
+            const int centre_rank = (x - x0) * nyv + (y - y0);
+            const int ncand = ((x1 - x0 + 1) * nyv - 1) * S;
+            double *sMf = sChunk + 8, *sLf = sMf + nF;
+            for (int k = tid; k < nF; k += kThreads) {
+                sMf[k] = p.pmean[(uint64_t)k * HW + pix];
+                if constexpr (kMemberTest) { // lim_k = sd_k * mult_k, fl_k = -inf where sd_k is above the floor (behind sLf)
+                    const double sd = p.pstd[(uint64_t)k * HW + pix], fk = mtab[RPF_MAX_NDIM + k];
+                    sLf[k] = sd * mtab[k];
+                    sLf[nF + k] = sd > fk ? -__builtin_inf() : fk;
+                } else {
+                    sLf[k] = p.pstd[(uint64_t)k * HW + pix] * 3.0; // multiplyArray(std, 3), rpf.cpp:579
+                }
             }
-        }
-        __syncthreads();
-        for (int q0 = 0; q0 < ncand; q0 += kThreads) {
-            const int qb = q0 + wv * 64;                       // this wave's 64-candidate block
-            unsigned long long mask = 0ull;
-            uint32_t off = 0u;
-            if (qb < ncand) { // wave-uniform
-                const int qq = qb + lane;
-                bool pass = qq < ncand;
-                if (pass) {
-                    int cell = qq / S;
-                    const int s = qq - cell * S;
-                    if (cell >= centre_rank) ++cell;              // rpf.cpp:565: skip the centre pixel
-                    const int ix = cell / nyv, iy = cell - ix * nyv; // xn outer, yn inner ascending (rpf.cpp:562-563)
-                    off = (uint32_t)(((uint64_t)(y0 + iy) * W + (x0 + ix)) * S + s);
-                    for (int k = 0; k < nF; ++k) {
-                        const double a = fabs((double)ldp<T>(p, colF + k, off) - sMf[k]);
-                        if constexpr (kMemberTest) {
-                            if (a >= sLf[k] && a > sLf[nF + k]) pass = false; // a NaN never rejects here either
-                        } else {
-                            if (a >= sLf[k]) pass = false;     // allLessThan: fails iff a >= b (ops.h:101-104): a NaN never rejects
+            __syncthreads();
+            for (int q0 = 0; q0 < ncand; q0 += kThreads) {
+                const int qb = q0 + wv * 64;                       // this wave's 64-candidate block
+                unsigned long long mask = 0ull;
+                uint32_t off = 0u;
+                if (qb < ncand) { // wave-uniform
+                    const int qq = qb + lane;
+                    bool pass = qq < ncand;
+                    if (pass) {
+                        int cell = qq / S;
+                        const int s = qq - cell * S;
+                        if (cell >= centre_rank) ++cell;              // rpf.cpp:565: skip the centre pixel
+                        const int ix = cell / nyv, iy = cell - ix * nyv; // xn outer, yn inner ascending (rpf.cpp:562-563)
+                        off = (uint32_t)(((uint64_t)(y0 + iy) * W + (x0 + ix)) * S + s);
+                        for (int k = 0; k < nF; ++k) {
+                            const double a = fabs((double)ldp<T>(p, colF + k, off) - sMf[k]);
+                            if constexpr (kMemberTest) {
+                                if (a >= sLf[k] && a > sLf[nF + k]) pass = false; // a NaN never rejects here either
+                            } else {
+                                if (a >= sLf[k]) pass = false;     // allLessThan: fails iff a >= b (ops.h:101-104): a NaN never rejects
+                            }
                         }
                     }
+                    mask = __ballot(pass);
                 }
-                mask = __ballot(pass);
+                if (lane == 0) sCnt[wv] = __popcll(mask);
+                __syncthreads();
+                int base = n;
+                for (int w = 0; w < wv; ++w) base += sCnt[w];
+                const int tot = sCnt[0] + sCnt[1] + sCnt[2] + sCnt[3];
+                if ((mask >> lane) & 1ull) {
+                    const int at = base + __popcll(mask & ((1ull << lane) - 1ull));
+                    if (at < p.nmax) list[at] = off;
+                }
+                n += tot;
+                __syncthreads();
             }
-            if (lane == 0) sCnt[wv] = __popcll(mask);
-            __syncthreads();
-            int base = n;
-            for (int w = 0; w < wv; ++w) base += sCnt[w];
-            const int tot = sCnt[0] + sCnt[1] + sCnt[2] + sCnt[3];
-            if ((mask >> lane) & 1ull) {
-                const int at = base + __popcll(mask & ((1ull << lane) - 1ull));
-                if (at < p.nmax) list[at] = off;
-            }
-            n += tot;
-            __syncthreads();
+            if (tid == 0) p.nbhd[pix] = n;
         }
-        if (tid == 0) p.nbhd[pix] = n;
         __threadfence_block();
         __syncthreads();
         const int B = max(1, (int)sqrt((double)n));                // mi.cpp:54

@@ -79,6 +79,7 @@ struct WideScratch {
 template <class T, bool FAST = false, bool MEMBER = false>
 __global__ __launch_bounds__(256) void filter_wide_kernel(PassParams p, GenericWideCarve cv, WideScratch gs) {
     constexpr bool kMemberTest = MEMBER;
+    constexpr bool kListed = false; // (this kernel always walks the box: the listed stage 1b is generic::filter_pixel_kernel's alone)
     extern __shared__ __align__(16) unsigned char smem[];
     const GenericDims D = generic_dims(p.lay);
     const int ndim = D.ndim, nF = D.nF, nR = D.nR, nAnc = D.nAnc, npair = D.npair, nwt = D.nwt, colF = D.colF;

@@ -219,8 +219,11 @@ hipError_t launch_pixel_stats(const PassParams &p, uint64_t pix0, uint64_t pix1,
 // count_dev != null: the size of p.pix_list is read from device memory (redo list: no host read-back), grid = slots.
 // fast: stage 4 in the fp32 arithmetic of RPF_FLAG_STREAM_FAST (route 3 and the rest lists of routes 4 / 5 pass it; the redo
 // list and the streaming class of the fused routes never do)
+// listed: the rest launch of a sampled pass (route 8 under RPF_FLAG_SAMPLED_REST): stage 1b reads N from p.nbhd and the members
+// behind the own samples from p.members / p.member_base, as the count kernel left them, instead of walking the box; p.pix_list is
+// the rest list, p.nmax the listed capacity S + draws (it sizes the carve-up and the slots); fp64 only, never with count_dev
 hipError_t launch_filter(const PassParams &p, void *list, void *bins, uint32_t slots, const uint32_t *count_dev, hipStream_t s,
-                         bool fast = false);
+                         bool fast = false, bool listed = false);
 } // namespace generic
 
 // ---- the packed layout-generic kernels (rpf_generic_packed.hip, RPF_FLAG_GENERIC_PACKED): N <= 64, several pixels per wave --
@@ -312,7 +315,8 @@ static_assert(sizeof(MemberPool) == 32 && offsetof(MemberPool, capacity) == 8 &&
 // of the rows the slab's windows reach.  member != null (route 9): as for launch_filter_wide; the flat-pixel proof then asks for
 // a negative floor as well
 hipError_t launch_wide_count(const PassParams &p, const MemberPool &m, int32_t *nan_flag, const double *member, hipStream_t s);
-// the count pass of route 8 (rpf_generic_sampled_count.hip, S + draws <= 832): for every pixel of rows
+// the count pass of route 8 (rpf_generic_sampled_count.hip): sampled_count_kernel for S + draws <= 832, else
+// sampled_count_block_kernel (S + draws <= RPF_SAMPLED_MAX; section 13e), with the same result.  For every pixel of rows
 // [p.row_begin, p.row_end) the distinct draws of its key that pass the 3-sigma test, in ascending visiting order, into
 // m.pool[m.base[pix] ..] and N = S + their number into p.nbhd; *m.cursor as launch_wide_count leaves it.  table: device, the
 // box - 1 Gaussian thresholds of p.box; member != null (with RPF_FLAG_MEMBER_TEST): as for launch_filter_wide, the test of the draws

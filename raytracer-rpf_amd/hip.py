@@ -40,7 +40,7 @@ FLAG_STREAM_FAST = 512
 # filter_pass_debug refuses it
 FLAG_SPIKE_CLAMP = 1024
 # the published random-subset gather (Context.set_sampling): a pass with draws > 0 draws that many candidates per
-# pixel instead of walking the box (route 8; fp64; S + draws <= 832); a pass with draws == 0 runs as without the flag.  Refused
+# pixel instead of walking the box (route 8; fp64; S + draws <= 832, or SAMPLED_MAX with SAMPLED_REST_FLAG); a pass with draws == 0 runs as without the flag.  Refused
 # without set_sampling, under DEGEN_REF_ABORT on a sampled pass, and with FLAG_FAST_WEIGHTS / FLAG_GENERIC_FAST / FLAG_STREAM_FAST.
 # RPF_FLAG_SAMPLED_NBHD of the header.  Its name stands outside the FLAG_* family on purpose: that family is the eleven bits whose
 # rpf_layout_kernels answers tests/golden/flag_table.npz records (words 0 .. 2047), and tests/test_flag_table_cpu.py holds it to
@@ -61,6 +61,12 @@ MEMBER_TEST_FLAG = 4096
 # pass, MEMBER_TEST_FLAG) and DEGEN_EPS.  Selects no route.  RPF_FLAG_SCHEDULE of the header; the name stays outside the FLAG_*
 # family for SAMPLED_NBHD_FLAG's reason (tests/test_flag_table_cpu.py holds FLAG_* to eleven bits)
 SCHEDULE_FLAG = 8192
+# modifies SAMPLED_NBHD_FLAG: a sampled pass may have S + draws <= SAMPLED_MAX instead of 832; pixels that end
+# with N > 832 go to a rest launch that reads their listed members (route 8 still); a pass with S + draws <= 832 runs as without it;
+# max_draws() tells the bound.  Refused without SAMPLED_NBHD_FLAG.  RPF_FLAG_SAMPLED_REST of the header; the name stays outside the
+# FLAG_* family for SAMPLED_NBHD_FLAG's reason (its table: tests/test_sampled_rest_cpu.py)
+SAMPLED_REST_FLAG = 16384
+SAMPLED_MAX = 8192  # RPF_SAMPLED_MAX
 FLAG_WIDE_NBHD = 64  # passes with 65535 < box*box*S <= 262144 on the wide layout-generic kernel (route 6); max_nbhd() tells the bound
 MAX_NDIM = 40     # the layout-generic kernels take 5 + n_random + n_feat up to this
 PLANES_F32, PLANES_F16 = 0, 1
@@ -75,7 +81,7 @@ EXPORTS = ["rpf_version", "rpf_status_string", "rpf_create", "rpf_destroy", "rpf
            "rpf_max_nbhd", "rpf_wide_table", "rpf_set_spike", "rpf_multi_set_spike", "rpf_query_spike", "rpf_multi_query_spike",
            "rpf_spike_clamp_device", "rpf_colour_add_device", "rpf_spike_delta", "rpf_set_sampling", "rpf_multi_set_sampling",
            "rpf_sampling_table", "rpf_sampling_draws", "rpf_set_membership", "rpf_multi_set_membership", "rpf_membership_preset",
-           "rpf_set_schedule", "rpf_multi_set_schedule", "rpf_schedule_preset"]
+           "rpf_set_schedule", "rpf_multi_set_schedule", "rpf_schedule_preset", "rpf_max_draws"]
 
 # the film step: pbrt's PixelFilters (include/rpf_hip.h, rpf_film)
 PIXFILTER_BOX, PIXFILTER_TRIANGLE, PIXFILTER_GAUSSIAN, PIXFILTER_MITCHELL, PIXFILTER_SINC = range(5)
@@ -287,6 +293,14 @@ def max_nbhd(desc):
     return st, (n.value if st == OK else None)
 
 
+def max_draws(desc):
+    """rpf_max_draws (no GPU needed): (status, dmax) -- the most draws a sampled pass may have under S and the flags of `desc`:
+    (OK, max(0, 832 - S)), or (OK, max(0, SAMPLED_MAX - S)) with SAMPLED_REST_FLAG; desc None or S <= 0: (E_BADARG, None)"""
+    n = C.c_int32(-1)
+    st = load().rpf_max_draws(None if desc is None else C.byref(desc), C.byref(n))
+    return st, (n.value if st == OK else None)
+
+
 def wide_table(nmax):
     """rpf_wide_table (no GPU needed): uint64 [nmax + 1], round(k ln k * 2^41) -- the table the wide kernel forms MI from"""
     out = np.empty(nmax + 1, np.uint64)
@@ -419,6 +433,8 @@ def load():
             L.rpf_set_schedule.argtypes = [C.c_void_p, C.POINTER(Schedule)]
             L.rpf_multi_set_schedule.argtypes = [C.c_void_p, C.POINTER(Schedule)]
             L.rpf_schedule_preset.argtypes = [C.c_int32, C.c_int32, C.POINTER(Schedule)]
+        if hasattr(L, "rpf_max_draws"):  # (absent from a build of before the listed rest launch, loaded through RPF_HIP_LIB)
+            L.rpf_max_draws.argtypes = [C.POINTER(Desc), C.POINTER(C.c_int32)]
         L.rpf_host_alloc.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
         L.rpf_host_free.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L

@@ -202,13 +202,15 @@ def demangle_short(name):
         s += "<K=%s,TL=%s,FAST=%s,NW=%s,PHASE=%s>" % k.groups()
     # the layout-generic kernels: the plane type, and FAST where a kernel has the fp32 stage-4 instantiation (RPF_FLAG_GENERIC_FAST)
     # ... and MEMBER where one has the membership test of RPF_FLAG_MEMBER_TEST in its stage 1b: the second flag of the wide kernel, the
-    # only flag of the two count kernels
+    # only flag of the count kernels; LISTED where generic::filter_pixel_kernel reads listed members (its third parameter)
     t = re.search(r"3rpf7generic.*kernelI(f|6__half)(?:Lb([01])E)?(?:Lb([01])E)?E", name)
     if t:
-        count = re.search(r"(wide|sampled)_count_kernel", name) is not None
+        count = re.search(r"(wide|sampled)_count(_block)?_kernel", name) is not None
+        pixel = re.search(r"\d+filter_pixel_kernel", name) is not None
         fast = t.group(2) == "1" and not count
-        member = t.group(3) == "1" or (count and t.group(2) == "1")
-        s += "<%s%s%s>" % ("float" if t.group(1) == "f" else "__half", ",FAST" if fast else "", ",MEMBER" if member else "")
+        member = (t.group(3) == "1" and not pixel) or (count and t.group(2) == "1")
+        s += "<%s%s%s%s>" % ("float" if t.group(1) == "f" else "__half", ",FAST" if fast else "", ",MEMBER" if member else "",
+                             ",LISTED" if pixel and t.group(3) == "1" else "")
     g = re.search(r"packed_kernelILi(\d+)E", name)
     if g:
         s += "<G=%s>" % g.group(1)
