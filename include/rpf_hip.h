@@ -256,6 +256,17 @@ enum {
                                   S + draws[p] > 8192 on a pass with draws[p] > 0 (RPF_E_BADARG); every other refusal of a
                                   sampled pass stands (RPF_DEGEN_REF_ABORT, the three fp32 flags, a missing rpf_set_sampling,
                                   a negative draw count). */
+    RPF_FLAG_PASS_REPORT = 32768, /* opt-in: every pass of the call leaves one rpf_pass_report (below), reduced
+                                  on the device from that pass's input colours, its output colours (before the spike pass), N,
+                                  alpha, beta and W_r_c over the filtered rows.  Taken by rpf_filter, rpf_filter_ex,
+                                  rpf_filter_device, rpf_filter_film, rpf_multi_filter, rpf_multi_filter_film and
+                                  rpf_filter_pass_debug (entry 0); an entry point that runs no pass ignores it.  It changes no
+                                  result, counter, route or launch count: rpf_layout_kernels, rpf_max_nbhd, rpf_max_draws,
+                                  rpf_query_route and rpf_counters answer as without it (filter_kernel_launches counts filter
+                                  kernels, not the report's).  Each pass pays three scratch planes (alpha, beta, W_r_c), their
+                                  clearing, the report kernels and one small read-back that drains the stream.  In rpf_filter it
+                                  implies the serial order of RPF_FLAG_NO_OVERLAP.  RPF_E_NONFINITE is returned as before, and
+                                  the report is still filled. */
     RPF_FLAG_STREAM_FAST = 512/* opt-in, modifies RPF_FLAG_GENERIC and / or RPF_FLAG_WIDE_NBHD: the two kernels that walk a
                                   neighbourhood of any size with 256 threads -- the generic filter kernel (route 3, the rest
                                   list N > 64 / N > 832 of routes 4 / 5) and the wide kernel (route 6, the rest list N > 832 of
@@ -678,6 +689,59 @@ int32_t rpf_colour_add_device(rpf_ctx *ctx, const rpf_desc *desc, double *d_colo
  * (double)n_samples.  row_sums: [n_rows][3]; n_samples: the number of samples of those rows, rows * W * S.  Needs no context
  * and no device.  RPF_E_BADARG for a NULL pointer or a non-positive count. */
 int32_t rpf_spike_delta(const double *row_sums, int64_t n_rows, int64_t n_samples, double *energy_out, double *delta_out);
+
+/* ---- the per-pass activity report (RPF_FLAG_PASS_REPORT) ----------------------------------------------
+ * What one pass did to the filtered rows [row_begin, row_end), in IEEE fp64 with every sum a serial chain whose first term is
+ * its first element.  a = the pass's input colours, b = its output colours (before the spike pass), k = channel.
+ *   per pixel, chains over s   m_k = sum (b-a)*(b-a), i_k = sum a*a, pa_k = sum a, pb_k = sum b, pm_k = (pb_k - pa_k)^2,
+ *                              pi_k = pa_k^2.  A pixel with a non-finite value among its 6*S colours is BAD: it gives +0.0 to all
+ *                              twelve, counts once in nonfinite_pixels, and its samples that hold a non-finite value count in
+ *                              nonfinite_samples.  unchanged_samples: samples whose three b have the 64 bits of their a (bad
+ *                              pixels included).
+ *   per row, chains over x     the twelve pixel values, alpha_k, beta_k (k < n_feat) and W_r_c of every pixel; a weight that is
+ *                              not finite gives +0.0 and counts in weights_nonfinite; alpha_zero / beta_zero count the entries
+ *                              == 0.0.  sum / min / max of N, the pixels with N == S, the pixels per size class (N <= 8, 16, 32,
+ *                              64, 128, 256, 448, 832, and above: the classes of the routes).
+ *   per pass                   the rows folded in ascending image-row order by rpf_pass_report_fold: doubles as a chain, counts
+ *                              summed, min_nbhd / max_nbhd the minimum / maximum.
+ * Relative L2 moved per pass = sqrt(sum_k moved2[k] / sum_k in2[k]); of the pixel means, the same of pix_moved2 / pix_in2; mean
+ * alpha_k = alpha_sum[k] / pixels; share of clamped alpha = alpha_zero[k] / pixels; share of N = S = own_only_pixels / pixels. */
+#define RPF_REPORT_NCLASS 9
+typedef struct rpf_report_row {
+    double moved2[3], in2[3], pix_moved2[3], pix_in2[3];     /* sums over the row's pixels of m_k, i_k, pm_k, pi_k */
+    double alpha_sum[3], wrc_sum, beta_sum[RPF_MAX_NDIM];
+    int64_t sum_nbhd, own_only_pixels, class_pixels[RPF_REPORT_NCLASS];
+    int64_t unchanged_samples, nonfinite_samples, nonfinite_pixels, weights_nonfinite;
+    int64_t alpha_zero[3], beta_zero[RPF_MAX_NDIM];
+    int32_t min_nbhd, max_nbhd;
+} rpf_report_row;
+typedef struct rpf_pass_report {
+    int32_t applied;          /* 1 when the most recent call filled this entry, else 0 and zeros below */
+    int32_t box, draws, route, rows; /* the pass's box, its draws (0: not sampled), its rpf_query_route, row_end - row_begin */
+    int64_t pixels, samples;  /* rows*W, rows*W*S */
+    rpf_report_row total;     /* the fold of the rows */
+} rpf_pass_report;
+
+/* Pass `pass` of the most recent call on ctx: its record | its (row_end - row_begin) row records, in row order (for a caller who
+ * owns the slabs and folds them itself; n_rows must be that count, 0 rows and applied == 0 included) | merged over the slabs of a
+ * rpf_multi: the rows of every slab gathered in image-row order and folded, the same numbers as one context; `route` and `draws`
+ * are the first slab's.  An entry no pass of that call filled has applied = 0 and zeros.  RPF_E_BADARG for a NULL pointer, a
+ * pass outside [0, RPF_MAX_BOXES) or a wrong n_rows. */
+int32_t rpf_query_pass_report(rpf_ctx *ctx, int32_t pass, rpf_pass_report *out);
+int32_t rpf_query_pass_report_rows(rpf_ctx *ctx, int32_t pass, rpf_report_row *rows_out, int64_t n_rows);
+int32_t rpf_multi_query_pass_report(rpf_multi *m, int32_t pass, rpf_pass_report *out);
+
+/* The device half, for a caller who owns the passes: the row records of rows [row_begin, row_end) of desc from device buffers --
+ * d_col_in / d_col_out: 3 fp64 planes [3][H][W][S]; d_nbhd: int32 [H*W]; d_alpha [H*W][3], d_beta [H*W][n_feat], d_wrc [H*W]
+ * fp64, each may be NULL (its fields are then zero).  rows_out: HOST, row_end - row_begin records.  Stream-ordered on `stream`
+ * like rpf_spike_clamp_device; returns after the stream has drained. */
+int32_t rpf_pass_report_rows_device(rpf_ctx *ctx, const rpf_desc *desc, const double *d_col_in, const double *d_col_out,
+                                    const int32_t *d_nbhd, const double *d_alpha, const double *d_beta, const double *d_wrc,
+                                    rpf_report_row *rows_out, void *stream);
+
+/* The fold every path uses: *total_out = rows[0] folded with rows[1], rows[2], ... in that order.  Needs no context and no device.
+ * RPF_E_BADARG for a NULL pointer or n_rows <= 0. */
+int32_t rpf_pass_report_fold(const rpf_report_row *rows, int64_t n_rows, rpf_report_row *total_out);
 
 /* ---- sampled neighbourhoods (RPF_FLAG_SAMPLED_NBHD) ---------------------------------------------
  * Pass p of a call has id pass_id0 + p and draws[p] draws per pixel (0: the pass runs as without the flag).  row_origin is the

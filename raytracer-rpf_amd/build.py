@@ -20,9 +20,10 @@ KERNEL_TUS += ["rpf_generic_wide.hip"]  # the wide layout-generic kernel: 65535 
 KERNEL_TUS += ["rpf_spike.hip"]  # the spike pass after the last filter pass: clamp, row sums, energy add (RPF_FLAG_SPIKE_CLAMP)
 KERNEL_TUS += ["rpf_generic_wide_count.hip"]  # ... and the count pass that deals a wide pass by size class (RPF_FLAG_WIDE_CLASSES)
 KERNEL_TUS += ["rpf_generic_sampled_count.hip"]  # the count pass of a sampled pass: the draws of a pixel's key (RPF_FLAG_SAMPLED_NBHD)
-# the C ABI (host code only; rpf_api.h is what they share): context, validation and pass loops | pass router | film step | multi-GPU | spike pass
+KERNEL_TUS += ["rpf_report.hip"]  # the per-pass activity report: per-pixel chains, per-row chains and counts (RPF_FLAG_PASS_REPORT)
+# the C ABI (host code only; rpf_api.h is what they share): context, validation and pass loops | pass router | film step | multi-GPU | spike pass | pass report
 # (the names start with rpf_api: the spill scan below skips them by that)
-API_TUS = ["rpf_api.hip", "rpf_api_routes.hip", "rpf_api_film.hip", "rpf_api_multi.hip", "rpf_api_spike.hip"]
+API_TUS = ["rpf_api.hip", "rpf_api_routes.hip", "rpf_api_film.hip", "rpf_api_multi.hip", "rpf_api_spike.hip", "rpf_api_report.hip"]
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in KERNEL_TUS + API_TUS]
 HEADERS = [os.path.join(_HERE, "csrc", "rpf_internal.h"), os.path.join(_HERE, "csrc", "rpf_api.h"), os.path.join(_HERE, "csrc", "rpf_xlane.h"),
            os.path.join(_HERE, "csrc", "rpf_filter_impl.inc"), os.path.join(_HERE, "csrc", "rpf_packed_impl.inc"),

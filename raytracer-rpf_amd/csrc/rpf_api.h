@@ -1,6 +1,6 @@
 // rpf_api.h -- host only: what the TUs of the C ABI share.  rpf_api.hip holds the context, validation, pass set-up and the
 // two pass loops; rpf_api_routes.hip the pass router (route_pass); rpf_api_film.hip the film step's host half;
-// rpf_api_multi.hip the one-process multi-GPU driver; rpf_api_spike.hip the spike pass.
+// rpf_api_multi.hip the one-process multi-GPU driver; rpf_api_spike.hip the spike pass; rpf_api_report.hip the per-pass report.
 #pragma once
 #include <dlfcn.h>
 
@@ -142,6 +142,12 @@ struct rpf_ctx {
     rpf::DevBuf<double> d_spike_e;              // [rows][W][3] removed energy per pixel
     rpf::DevBuf<double> d_spike_rows;           // [rows][3] its row sums
     rpf::DevBuf<unsigned long long> d_spike_cnt; // [3] replaced samples, clamped pixels, skipped pixels
+    // the per-pass activity report (RPF_FLAG_PASS_REPORT; rpf_api_report.hip): nothing here is allocated without the flag
+    rpf_pass_report report[RPF_MAX_BOXES] = {}; // of the most recent call (begin_call clears them)
+    std::vector<rpf_report_row> report_rows[RPF_MAX_BOXES]; // ... and the row records each entry was folded from
+    rpf::DevBuf<double> d_rep_alpha, d_rep_beta, d_rep_wrc; // [H*W][3], [H*W][n_feat], [H*W]: where a reporting pass writes its weights
+    rpf::DevBuf<double> d_rep_pix;              // [rows][W][12] the per-pixel values between the two report kernels
+    rpf::DevBuf<rpf_report_row> d_rep_rows;     // [rows] the row records
     // sampled neighbourhoods (RPF_FLAG_SAMPLED_NBHD)
     rpf_sampling sampling{};                    // rpf_set_sampling
     bool sampling_set = false;
@@ -250,5 +256,14 @@ int32_t spike_clamp(rpf_ctx *ctx, const rpf_desc *d, double *d_colour, double th
                     hipStream_t s);
 int32_t spike_add(rpf_ctx *ctx, const rpf_desc *d, double *d_colour, const double delta[3], hipStream_t s);
 int32_t spike_pass(rpf_ctx *ctx, const rpf_desc *d, double *d_colour, hipStream_t s);
+
+// defined in rpf_api_report.hip, where each is described; every pass loop runs report_planes before setup_pass and report_pass
+// after route_pass, the multi-GPU driver folds the rows of every slab with rpf_pass_report_fold
+void report_clear(rpf_ctx *ctx);
+int32_t report_planes(rpf_ctx *ctx, const rpf_desc *d, rpf_debug &dev, hipStream_t s);
+int32_t report_rows(rpf_ctx *ctx, const rpf_desc *d, const double *col_in, const double *col_out, const int32_t *nbhd,
+                    const double *alpha, const double *beta, const double *wrc, rpf_report_row *rows_out, hipStream_t s);
+int32_t report_pass(rpf_ctx *ctx, const rpf_desc *d, int pass, int box, const double *col_in, const double *col_out,
+                    const rpf_debug &dev, hipStream_t s);
 
 } // namespace rpf

@@ -462,6 +462,7 @@ int32_t begin_call(rpf_ctx *ctx, hipStream_t s) {
     ctx->counters = rpf_counters{};
     ctx->counters.first_bad_pixel = -1;
     ctx->spike = rpf_spike_stats{}; // applied = 0 until this call's spike pass has run
+    report_clear(ctx);              // ... and every pass report's until that pass has reported (RPF_FLAG_PASS_REPORT)
     return RPF_OK;
 }
 
@@ -580,9 +581,12 @@ int32_t run_passes(rpf_ctx *ctx, const rpf_desc *d, const void *d_planes, double
     float ms_filter = 0.f, ms_stats = 0.f;
     if (timing) HIP_TRY(hipEventRecord(ctx->ev[0], s));
     double *cin = d_colour, *cout = ctx->d_colB; // ping-pong: the filtered colours replace the film's (rpf.cpp:732)
+    const bool report = (d->flags & RPF_FLAG_PASS_REPORT) != 0;
     for (int i = 0; i < d->n_box; ++i) {
         PassSetup ps_;
-        if ((st = setup_pass(ctx, d, d->box_sizes[i], i, d_planes, cin, cout, nullptr, ps_))) return st;
+        rpf_debug rep{}; // RPF_FLAG_PASS_REPORT: the pass writes alpha, beta and W_r_c into the context's scratch planes
+        if (report && (st = report_planes(ctx, d, rep, s))) return st;
+        if ((st = setup_pass(ctx, d, d->box_sizes[i], i, d_planes, cin, cout, report ? &rep : nullptr, ps_))) return st;
         if ((st = pass_through(ctx, d, cin, cout, 0, d->H, s))) return st;
         if (timing) HIP_TRY(hipEventRecord(ctx->ev[1], s));
         // stage 1a depends on the features only: formed once (the reference recomputes identical values per pass)
@@ -601,6 +605,8 @@ int32_t run_passes(rpf_ctx *ctx, const rpf_desc *d, const void *d_planes, double
             ms_stats += a;
             ms_filter += b;
         }
+        // the pass's report: behind route_pass (its redo launch included), outside the filter's timing bracket
+        if (report && (st = report_pass(ctx, d, i, d->box_sizes[i], cin, cout, rep, s))) return st;
         std::swap(cin, cout);
     }
     if (cin != d_colour) HIP_TRY(hipMemcpyAsync(d_colour, cin, 3 * ps * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -1043,8 +1049,9 @@ int32_t rpf_filter_ex(rpf_ctx *ctx, const rpf_desc *d, const void *planes, const
         if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
         return a.type == hipMemoryTypeHost;
     };
-    // (RPF_FLAG_SPIKE_CLAMP: no band may leave before delta is known)
-    if (!(d->flags & (RPF_FLAG_TIMING | RPF_FLAG_NO_OVERLAP | RPF_FLAG_SPIKE_CLAMP)) && !colour64_in && !colour64_out && pinned(planes) &&
+    // (RPF_FLAG_SPIKE_CLAMP: no band may leave before delta is known; RPF_FLAG_PASS_REPORT: a pass reports on whole rows of both buffers)
+    if (!(d->flags & (RPF_FLAG_TIMING | RPF_FLAG_NO_OVERLAP | RPF_FLAG_SPIKE_CLAMP | RPF_FLAG_PASS_REPORT)) && !colour64_in && !colour64_out &&
+        pinned(planes) &&
         pinned(ray_weight) && pinned(sample_rgb_out) && pinned(pixel_rgb_out))
         return run_host_pipeline(ctx, d, planes, ray_weight, sample_rgb_out, pixel_rgb_out);
     // serial variant (per-kernel event timing needs it): upload, passes, download
@@ -1140,6 +1147,9 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *d, int32_t box, cons
         *dev_slots[i] = ctx->d_dbg[i];
     }
     if ((st = begin_call(ctx, s))) return st;
+    // RPF_FLAG_PASS_REPORT: entry 0, from the caller's alpha / beta / W_r_c planes where they were asked for, scratch planes where not
+    const bool report = (d->flags & RPF_FLAG_PASS_REPORT) != 0;
+    if (report && (st = report_planes(ctx, d, dev, s))) return st;
     PassSetup ps_;
     if ((st = setup_pass(ctx, d, box, 0, ctx->d_planes, ctx->d_colA, ctx->d_colB, &dev, ps_))) return st;
     HIP_TRY(launch_copy_f64(ctx->d_colA, ctx->d_colB, 3 * ps, s));
@@ -1149,6 +1159,7 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *d, int32_t box, cons
     rpf_counters &c = ctx->counters;
     if ((st = route_pass(ctx, ps_.p, s, &c.filter_kernel_launches))) return st;
     if (timing) HIP_TRY(hipEventRecord(ctx->ev[1], s));
+    if (report && (st = report_pass(ctx, d, 0, box, ctx->d_colA, ctx->d_colB, dev, s))) return st;
     HIP_TRY(hipMemcpyAsync(colour_out, ctx->d_colB, 3 * ps * sizeof(double), hipMemcpyDeviceToHost, s));
     if (dbg && dbg->nbhd_size) // N is always produced in the context's own plane
         HIP_TRY(hipMemcpyAsync(ctx->d_dbg[0], ctx->d_nbhd, HW * 4, hipMemcpyDeviceToDevice, s));

@@ -30,6 +30,7 @@ struct rpf_multi {
     double spike_threshold = 1.0; // rpf_multi_set_spike
     int32_t spike_energy = 1;
     rpf_spike_stats spike{};      // the spike pass of the most recent call, merged over the slabs
+    rpf_pass_report report[RPF_MAX_BOXES] = {}; // RPF_FLAG_PASS_REPORT: the passes of the most recent call, merged over the slabs
     rpf_sampling sampling{};      // rpf_multi_set_sampling: the caller's configuration (every slab adds its first image row to row_origin)
     bool sampling_set = false;
 };
@@ -79,6 +80,7 @@ int32_t multi_run(rpf_multi *m, const rpf_desc *d, const void *planes_v, const f
                   float *pixel_rgb_out, const MFilm *mf) {
     if (!m || m->ctx.empty()) return RPF_E_BADARG;
     m->spike = rpf_spike_stats{};
+    for (rpf_pass_report &r : m->report) r = rpf_pass_report{};
     {
         const int32_t st = validate(m->ctx[0], d, true);
         if (st != RPF_OK) return mfail(m, st, m->ctx[0]->err);
@@ -220,6 +222,7 @@ int32_t multi_run(rpf_multi *m, const rpf_desc *d, const void *planes_v, const f
 
     float ms_filter = 0.f;
     int launches = 0;
+    const bool report = (d->flags & RPF_FLAG_PASS_REPORT) != 0;
     for (int i = 0; i < d->n_box; ++i) {
         const int box = d->box_sizes[i];
         if (i > 0 && G > 1 && (st = refresh()) != RPF_OK) return st; // pass 0: the upload already carried the halo
@@ -232,7 +235,9 @@ int32_t multi_run(rpf_multi *m, const rpf_desc *d, const void *planes_v, const f
             hipStream_t s = ctx->stream;
             PassSetup pp;
             int32_t e;
-            if ((e = setup_pass(ctx, &sd[g], box, i, ctx->d_planes, cin[g], cout[g], nullptr, pp))) return e;
+            rpf_debug rep{}; // RPF_FLAG_PASS_REPORT: the pass writes alpha, beta and W_r_c into the slab context's scratch planes
+            if (report && (e = report_planes(ctx, &sd[g], rep, s))) return e;
+            if ((e = setup_pass(ctx, &sd[g], box, i, ctx->d_planes, cin[g], cout[g], report ? &rep : nullptr, pp))) return e;
             // halo rows pass through (they are refreshed from the neighbour before the next pass)
             if ((e = pass_through(ctx, &sd[g], cin[g], cout[g], 0, sd[g].H, s))) return e;
             if (i == 0) HIP_TRY(launch_pixel_stats(pp.p, s)); // stage 1a depends on the features only
@@ -241,9 +246,22 @@ int32_t multi_run(rpf_multi *m, const rpf_desc *d, const void *planes_v, const f
             HIP_TRY(hipEventRecord(ctx->ev[1], s));
             HIP_TRY(hipEventSynchronize(ctx->ev[1]));
             HIP_TRY(hipEventElapsedTime(&ms[g], ctx->ev[0], ctx->ev[1]));
+            if (report && (e = report_pass(ctx, &sd[g], i, box, cin[g], cout[g], rep, s))) return e; // the rows the slab owns
             return RPF_OK;
         });
         if (st != RPF_OK) return st;
+        if (report) { // the row records of every slab in image-row order, folded by the one-context path's function: the same bits
+            std::vector<rpf_report_row> rows;
+            rows.reserve((size_t)H);
+            for (int g = 0; g < G; ++g) rows.insert(rows.end(), m->ctx[g]->report_rows[i].begin(), m->ctx[g]->report_rows[i].end());
+            rpf_pass_report r = m->ctx[0]->report[i]; // applied, box, draws and route: the first slab's
+            r.rows = (int32_t)rows.size();
+            r.pixels = (int64_t)rows.size() * W;
+            r.samples = r.pixels * S;
+            r.total = rpf_report_row{};
+            if (!rows.empty()) (void)rpf_pass_report_fold(rows.data(), (int64_t)rows.size(), &r.total);
+            m->report[i] = r;
+        }
         float mx = 0.f;
         for (int g = 0; g < G; ++g) { mx = std::max(mx, ms[g]); launches += nl[g]; std::swap(cin[g], cout[g]); }
         ms_filter += mx;
@@ -446,6 +464,13 @@ int32_t rpf_multi_set_schedule(rpf_multi *m, const rpf_schedule *cfg) {
 int32_t rpf_multi_query_spike(rpf_multi *m, rpf_spike_stats *out) {
     if (!m || !out) return RPF_E_BADARG;
     *out = m->spike;
+    return RPF_OK;
+}
+
+int32_t rpf_multi_query_pass_report(rpf_multi *m, int32_t pass, rpf_pass_report *out) {
+    if (!m) return RPF_E_BADARG;
+    if (!out || pass < 0 || pass >= RPF_MAX_BOXES) return mfail(m, RPF_E_BADARG, "rpf_multi_query_pass_report: out is NULL or pass outside [0, RPF_MAX_BOXES)");
+    *out = m->report[pass];
     return RPF_OK;
 }
 

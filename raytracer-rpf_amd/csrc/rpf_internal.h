@@ -346,6 +346,26 @@ hipError_t launch_spike_row_sums(const double *e, int rows, int W, double *row_s
 // c += delta[k] for every sample of rows [row_begin, row_end) of plane k
 hipError_t launch_spike_add(double *colour, int W, int H, int S, int row_begin, int row_end, const double delta[3], hipStream_t s);
 
+// ---- the per-pass activity report (rpf_report.hip, RPF_FLAG_PASS_REPORT) --------------------------------
+constexpr int kReportTileMaxS = 512;        // above it 48 * S bytes per pixel leave no useful tile: one thread per pixel on global memory
+constexpr int kReportLdsBudget = 64 * 1024; // LDS of one tile (one wavefront): 64 pixels up to S = 21, two at S = 512
+constexpr int kReportPixelValues = 12;      // doubles of scratch per filtered pixel: m_k | i_k | pm_k | pi_k
+// LDS image of the pixel kernel's tile, [6][tile][stride] doubles (a then b, three channels each); tile == 0: the direct form
+struct ReportCarve {
+    uint32_t stride, tile, bytes;
+};
+ReportCarve report_carve(int S);
+struct ReportPlanes {
+    const double *col_in, *col_out; // 3 fp64 planes [3][H][W][S] each
+    const int32_t *nbhd;            // [H*W]
+    const double *alpha, *beta, *wrc; // [H*W][3], [H*W][n_feat], [H*W]; any may be null
+    int32_t n_feat;
+};
+// rows [row_begin, row_end): pix [(row_end-row_begin)*W][kReportPixelValues] scratch (every entry written), rows_out
+// [row_end-row_begin] records (device; every field written).  class_cap: the eight class bounds (class_capacity(0 .. 7))
+hipError_t launch_pass_report(const ReportPlanes &in, int W, int H, int S, int row_begin, int row_end, const int32_t class_cap[8],
+                              double *pix, rpf_report_row *rows_out, hipStream_t s);
+
 int max_lds_per_block();
 hipError_t launch_udiv_selftest(uint64_t n, uint64_t seed, int mode, unsigned long long *d_mismatch, hipStream_t s);
 

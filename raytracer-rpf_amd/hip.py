@@ -67,6 +67,13 @@ SCHEDULE_FLAG = 8192
 # FLAG_* family for SAMPLED_NBHD_FLAG's reason (its table: tests/test_sampled_rest_cpu.py)
 SAMPLED_REST_FLAG = 16384
 SAMPLED_MAX = 8192  # RPF_SAMPLED_MAX
+# the per-pass activity report (Context.pass_report): every pass of the call leaves one PassReport, reduced on
+# the device from its input colours, its output colours (before the spike pass), N, alpha, beta and W_r_c over the filtered rows.
+# Changes no result, counter, route or launch count; every filter entry point and filter_pass_debug (entry 0) take it; in
+# Context.filter it implies the serial order of FLAG_NO_OVERLAP.  RPF_FLAG_PASS_REPORT of the header; the name stays outside the
+# FLAG_* family for SAMPLED_NBHD_FLAG's reason (tests/test_flag_table_cpu.py holds FLAG_* to eleven bits)
+PASS_REPORT_FLAG = 32768
+REPORT_NCLASS = 9  # RPF_REPORT_NCLASS: N <= 8, 16, 32, 64, 128, 256, 448, 832, and above
 FLAG_WIDE_NBHD = 64  # passes with 65535 < box*box*S <= 262144 on the wide layout-generic kernel (route 6); max_nbhd() tells the bound
 MAX_NDIM = 40     # the layout-generic kernels take 5 + n_random + n_feat up to this
 PLANES_F32, PLANES_F16 = 0, 1
@@ -81,7 +88,8 @@ EXPORTS = ["rpf_version", "rpf_status_string", "rpf_create", "rpf_destroy", "rpf
            "rpf_max_nbhd", "rpf_wide_table", "rpf_set_spike", "rpf_multi_set_spike", "rpf_query_spike", "rpf_multi_query_spike",
            "rpf_spike_clamp_device", "rpf_colour_add_device", "rpf_spike_delta", "rpf_set_sampling", "rpf_multi_set_sampling",
            "rpf_sampling_table", "rpf_sampling_draws", "rpf_set_membership", "rpf_multi_set_membership", "rpf_membership_preset",
-           "rpf_set_schedule", "rpf_multi_set_schedule", "rpf_schedule_preset", "rpf_max_draws"]
+           "rpf_set_schedule", "rpf_multi_set_schedule", "rpf_schedule_preset", "rpf_max_draws", "rpf_query_pass_report",
+           "rpf_query_pass_report_rows", "rpf_multi_query_pass_report", "rpf_pass_report_rows_device", "rpf_pass_report_fold"]
 
 # the film step: pbrt's PixelFilters (include/rpf_hip.h, rpf_film)
 PIXFILTER_BOX, PIXFILTER_TRIANGLE, PIXFILTER_GAUSSIAN, PIXFILTER_MITCHELL, PIXFILTER_SINC = range(5)
@@ -122,6 +130,41 @@ class SpikeStats(C.Structure):
     """rpf_spike_stats: the spike pass of the most recent call (applied = 0 and zeros when FLAG_SPIKE_CLAMP was off)"""
     _fields_ = [("spike_samples", C.c_int64), ("spike_pixels", C.c_int64), ("skipped_pixels", C.c_int64),
                 ("energy", C.c_double * 3), ("delta", C.c_double * 3), ("spike_ms", C.c_float), ("applied", C.c_int32)]
+
+
+class ReportRow(C.Structure):
+    """rpf_report_row, 920 bytes: the record of one row of one pass (or, as PassReport.total, the fold of the rows).  Offsets:
+    moved2 0 | in2 24 | pix_moved2 48 | pix_in2 72 | alpha_sum 96 | wrc_sum 120 | beta_sum 128 (MAX_NDIM doubles) | sum_nbhd 448 |
+    own_only_pixels 456 | class_pixels 464 (REPORT_NCLASS int64) | unchanged_samples 536 | nonfinite_samples 544 |
+    nonfinite_pixels 552 | weights_nonfinite 560 | alpha_zero 568 | beta_zero 592 (MAX_NDIM int64) | min_nbhd 912 | max_nbhd 916"""
+    _fields_ = [("moved2", C.c_double * 3), ("in2", C.c_double * 3), ("pix_moved2", C.c_double * 3), ("pix_in2", C.c_double * 3),
+                ("alpha_sum", C.c_double * 3), ("wrc_sum", C.c_double), ("beta_sum", C.c_double * MAX_NDIM),
+                ("sum_nbhd", C.c_int64), ("own_only_pixels", C.c_int64), ("class_pixels", C.c_int64 * REPORT_NCLASS),
+                ("unchanged_samples", C.c_int64), ("nonfinite_samples", C.c_int64), ("nonfinite_pixels", C.c_int64),
+                ("weights_nonfinite", C.c_int64), ("alpha_zero", C.c_int64 * 3), ("beta_zero", C.c_int64 * MAX_NDIM),
+                ("min_nbhd", C.c_int32), ("max_nbhd", C.c_int32)]
+
+
+class PassReport(C.Structure):
+    """rpf_pass_report, 960 bytes: applied 0 | box 4 | draws 8 | route 12 | rows 16 | pixels 24 | samples 32 | total 40.
+    applied = 0 and zeros when the most recent call did not fill the entry (PASS_REPORT_FLAG off, or fewer passes)"""
+    _fields_ = [("applied", C.c_int32), ("box", C.c_int32), ("draws", C.c_int32), ("route", C.c_int32), ("rows", C.c_int32),
+                ("pixels", C.c_int64), ("samples", C.c_int64), ("total", ReportRow)]
+
+
+def pass_report_fold(rows):
+    """rpf_pass_report_fold (no GPU needed): the ReportRow that folds `rows` (a ctypes array or a sequence of ReportRow) in their
+    order -- doubles as a serial chain, counts summed, min_nbhd / max_nbhd the minimum / maximum; the one fold Context and
+    MultiContext use.  None or no row: RPF_E_BADARG"""
+    n = 0 if rows is None else len(rows)
+    arr = None
+    if n:
+        arr = rows if isinstance(rows, C.Array) else (ReportRow * n)(*rows)
+    out = ReportRow()
+    st = load().rpf_pass_report_fold(arr, n, C.byref(out))
+    if st != OK:
+        raise RpfError(st, "rpf_pass_report_fold(n_rows=%r): a NULL pointer or a non-positive count" % (n,))
+    return out
 
 
 class Sampling(C.Structure):
@@ -435,6 +478,12 @@ def load():
             L.rpf_schedule_preset.argtypes = [C.c_int32, C.c_int32, C.POINTER(Schedule)]
         if hasattr(L, "rpf_max_draws"):  # (absent from a build of before the listed rest launch, loaded through RPF_HIP_LIB)
             L.rpf_max_draws.argtypes = [C.POINTER(Desc), C.POINTER(C.c_int32)]
+        if hasattr(L, "rpf_query_pass_report"):  # (absent from a build of before the pass report, loaded through RPF_HIP_LIB)
+            L.rpf_query_pass_report.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PassReport)]
+            L.rpf_query_pass_report_rows.argtypes = [C.c_void_p, C.c_int32, C.POINTER(ReportRow), C.c_int64]
+            L.rpf_multi_query_pass_report.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PassReport)]
+            L.rpf_pass_report_rows_device.argtypes = [C.c_void_p, C.POINTER(Desc)] + [C.c_void_p] * 6 + [C.POINTER(ReportRow), C.c_void_p]
+            L.rpf_pass_report_fold.argtypes = [C.POINTER(ReportRow), C.c_int64, C.POINTER(ReportRow)]
         L.rpf_host_alloc.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
         L.rpf_host_free.argtypes = [C.c_void_p, C.c_void_p]
         _lib = L
@@ -547,6 +596,30 @@ class Context:
     def set_schedule(self, cfg):
         """rpf_set_schedule: cfg a Schedule (make_schedule / schedule_preset), or None -> RPF_E_BADARG"""
         self._check(self._L.rpf_set_schedule(self._h, None if cfg is None else C.byref(cfg)))
+
+    # ---- the per-pass activity report (PASS_REPORT_FLAG) ------------------------------------------------------
+    def pass_report(self, pass_index):
+        """rpf_query_pass_report: the PassReport of pass `pass_index` of the most recent call (applied = 0: not filled)"""
+        r = PassReport()
+        self._check(self._L.rpf_query_pass_report(self._h, int(pass_index), C.byref(r)))
+        return r
+
+    def pass_report_rows(self, pass_index, n_rows=None):
+        """rpf_query_pass_report_rows: the row records of that pass as a list of ReportRow, in row order; n_rows None =
+        the report's own row count (what the ABI requires)"""
+        n = self.pass_report(pass_index).rows if n_rows is None else int(n_rows)
+        rows = (ReportRow * max(n, 1))()
+        self._check(self._L.rpf_query_pass_report_rows(self._h, int(pass_index), rows, n))
+        return list(rows[:max(n, 0)])
+
+    def pass_report_rows_device(self, desc, d_col_in, d_col_out, d_nbhd, d_alpha=None, d_beta=None, d_wrc=None, stream=None):
+        """rpf_pass_report_rows_device: the row records of rows [row_begin, row_end) of desc from device buffers (raw pointers;
+        the three weight planes may be None: their fields are then zero); returns a list of ReportRow"""
+        n = max(desc.row_end - desc.row_begin, 0)
+        rows = (ReportRow * max(n, 1))()
+        self._check(self._L.rpf_pass_report_rows_device(self._h, C.byref(desc), d_col_in, d_col_out, d_nbhd, d_alpha, d_beta, d_wrc,
+                                                        rows, stream))
+        return list(rows[:n])
 
     def spike_clamp_device(self, desc, d_colour, threshold=1.0, stream=None):
         """rpf_spike_clamp_device: the clamp half on rows [row_begin, row_end) of device colours (raw pointer, 3 fp64 planes);
@@ -735,6 +808,15 @@ class MultiContext:
         s = SpikeStats()
         self._L.rpf_multi_query_spike(self._h, C.byref(s))
         return s
+
+    def pass_report(self, pass_index):
+        """rpf_multi_query_pass_report: the PassReport of that pass of the most recent call, merged over the slabs (the rows of
+        every slab in image-row order, folded: the same numbers as one context; route and draws are the first slab's)"""
+        r = PassReport()
+        st = self._L.rpf_multi_query_pass_report(self._h, int(pass_index), C.byref(r))
+        if st != OK:
+            raise RpfError(st, self._L.rpf_multi_last_error(self._h).decode())
+        return r
 
     def filter(self, planes, desc, ray_weight=None, allow_nonfinite=False):
         nd, _, _, pdt = dims(desc)

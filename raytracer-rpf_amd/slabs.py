@@ -45,7 +45,8 @@ def check_desc(desc):
     would need the same ``set_membership`` and these helpers carry no such configuration; the test itself is a function of the
     pixel alone, so MultiContext (or a caller that configures each rank's context) gives the whole image's bits.  SCHEDULE_FLAG:
     every rank's context would need the same ``set_schedule`` and, since these helpers drive one pass per call, a ``pass0`` that
-    moves with each call; nothing here does either."""
+    moves with each call; nothing here does either.  PASS_REPORT_FLAG: a rank's one-pass calls each fill entry 0 of its own
+    context, and the merged report needs every rank's row records gathered in image-row order; nothing here gathers them."""
     from . import hip
     if desc.flags & hip.SAMPLED_NBHD_FLAG:
         raise NotImplementedError("slabs: SAMPLED_NBHD_FLAG (RPF_FLAG_SAMPLED_NBHD) is not supported across ranks yet: each rank must set "
@@ -59,6 +60,11 @@ def check_desc(desc):
         raise NotImplementedError("slabs: SCHEDULE_FLAG (RPF_FLAG_SCHEDULE) is not supported across ranks yet: each rank's context needs "
                                   "the same Context.set_schedule table and, for these one-pass calls, Schedule.pass0 set to the pass "
                                   "of each call (INTEGRATION.md section 2h), or use MultiContext, which does")
+    if desc.flags & hip.PASS_REPORT_FLAG:
+        raise NotImplementedError("slabs: PASS_REPORT_FLAG (RPF_FLAG_PASS_REPORT) is not supported across ranks yet: each rank would "
+                                  "report its own rows as entry 0 of every one-pass call, and nothing here gathers the row records "
+                                  "in image-row order for hip.pass_report_fold (INTEGRATION.md section 2i), or use MultiContext, "
+                                  "which does")
     return desc
 
 
