@@ -199,7 +199,7 @@ enum {
                                   of rejecting everything.  mult 3 and a negative floor on every feature is the reference's test
                                   on every input.  Own samples first, the visiting order and every stage behind the list are
                                   unchanged.  The flag covers every pass of a call.  A full-box pass takes route 9
-                                  (rpf_query_route): a count kernel lists the members of every pixel with N <= 832, the packed
+                                  (rpf_query_route; route 10 under RPF_FLAG_MEMBER_FUSED below): a count kernel lists the members of every pixel with N <= 832, the packed
                                   and one-wave layout-generic kernels filter them by size class, the wide kernel takes the
                                   pixels with N > 832 under the same test; redo_pixels is 0, filter_kernel_launches counts one
                                   launch per non-empty class plus one for a non-empty rest list, sum_nbhd / max_nbhd /
@@ -267,6 +267,27 @@ enum {
                                   clearing, the report kernels and one small read-back that drains the stream.  In rpf_filter it
                                   implies the serial order of RPF_FLAG_NO_OVERLAP.  RPF_E_NONFINITE is returned as before, and
                                   the report is still filled. */
+    RPF_FLAG_MEMBER_FUSED = 65536, /* opt-in, modifies RPF_FLAG_MEMBER_TEST: a full-box pass of the call runs on the compiled, fused
+                                  kernels behind a count kernel that applies the configured test (route 10; DESIGN.md section
+                                  14e) -- the structure of the size-binned route 2: the count kernel leaves N and the acceptance
+                                  masks, the pixels are dealt into the eleven size classes, the packed, one-wave and four-wave
+                                  compiled kernels rebuild their member lists from the masks, and the class N > 3136 goes to
+                                  the wide kernel under the same test.  A pass takes route 10 when it has no sampled draws, the
+                                  layout is one of the two compiled ones and the call is without RPF_FLAG_GENERIC,
+                                  box*box*S <= 65535 and option "wide" does not force it, and under RPF_FLAG_SCHEDULE its entry's
+                                  gains are both 1 (the entry's seed is honoured).  Every other pass of the call runs exactly as
+                                  without this flag (route 8 sampled, route 9 scheduled-gain, wide or layout-generic).
+                                  Membership, statistics and bin ids are route 9's bits; MI, alpha, beta, W_r_c and the colours
+                                  are those the compiled kernels give for that member list (route 2's kernels: the per-sample
+                                  stage-4 bars of the resident classes).  Options "packed", "waves_per_pixel", "split_weights",
+                                  "table_in_lds" and "strip_w" act as on route 2; "binning" has no effect.  redo_pixels is 0,
+                                  filter_kernel_launches counts one launch per non-empty class of the eleven, sum_nbhd /
+                                  max_nbhd / rpf_query_nbhd report the configured test's N.  A later pass of the same call with
+                                  the same box re-uses the masks and lists (never across rpf_set_membership, never from or
+                                  for a pass of another route).  No member pool is allocated.  rpf_layout_kernels answers as
+                                  for the word without the flag; rpf_max_nbhd and rpf_max_draws do not read it.  Refused before
+                                  any device work: the flag without RPF_FLAG_MEMBER_TEST (RPF_E_UNSUPPORTED; rpf_layout_kernels
+                                  answers the same way); every refusal of RPF_FLAG_MEMBER_TEST stands with it. */
     RPF_FLAG_STREAM_FAST = 512/* opt-in, modifies RPF_FLAG_GENERIC and / or RPF_FLAG_WIDE_NBHD: the two kernels that walk a
                                   neighbourhood of any size with 256 threads -- the generic filter kernel (route 3, the rest
                                   list N > 64 / N > 832 of routes 4 / 5) and the wide kernel (route 6, the rest list N > 832 of
@@ -463,7 +484,9 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *desc, int32_t box, c
  * sum_nbhd / max_nbhd are those of the sampled neighbourhoods.
  * A full-box pass under RPF_FLAG_MEMBER_TEST (route 9) counts one launch per non-empty packed or one-wave class and one for the
  * wide kernel when some pixel has N > 832; RPF_DEGEN_REF_ABORT is refused, so redo_pixels is 0; sum_nbhd / max_nbhd are those
- * of the neighbourhoods the configured test leaves. */
+ * of the neighbourhoods the configured test leaves.
+ * With RPF_FLAG_MEMBER_FUSED (route 10) such a pass counts as route 2 does: one launch per non-empty class of the eleven (the
+ * class N > 3136 is the wide kernel's); redo_pixels is 0. */
 int32_t rpf_query_counters(rpf_ctx *ctx, rpf_counters *out);
 
 /* neighbourhood size N of every pixel (rpf.cpp:586: the neighbourhood vector's size) as the last pass of the most recent
@@ -482,6 +505,8 @@ int32_t rpf_query_nbhd(rpf_ctx *ctx, int32_t *nbhd_out, int64_t count);
  * 8 = a sampled pass (RPF_FLAG_SAMPLED_NBHD with draws > 0: its member lists differ, by definition),
  * 9 = a full-box pass under RPF_FLAG_MEMBER_TEST (count kernel with the configured membership test, size classes, the wide
  * kernel for N > 832; its member lists are the reference's only under the reference's multiples and floors),
+ * 10 = such a pass under RPF_FLAG_MEMBER_FUSED on a compiled layout (count kernel with the configured test, then the compiled
+ * kernels of route 2 by size class; the same member lists as route 9),
  * -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1.  rpf_filter's row-band
  * pipeline runs that probe once per band, on the rows of the slab that are resident by then -- the last band of a pass on the
  * whole slab -- so the answer after such a call is the serial call's (bands above the last may have taken the other of 0 / 1:

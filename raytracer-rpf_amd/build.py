@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB = os.path.join(_HERE, "lib", "librpf_hip.so")
 # the fused per-pixel kernels compile as one translation unit per sample layout and size-class part (rpf_filter_impl.inc
-# with RPF_IMPL_PART = 1 / 2 / 3), in parallel: the single kernel TU of rounds 1-2 took 3.2 minutes
+# with RPF_IMPL_PART = 1 / 2 / 3; part 4, the *_member TUs below), in parallel: the single kernel TU of rounds 1-2 took 3.2 minutes
 KERNEL_TUS = ["rpf_impl_%s_%s.hip" % (lay, part) for lay in ("d19", "d27") for part in ("small", "mid", "large")] + ["rpf_kernels.hip"]
 KERNEL_TUS += ["rpf_film.hip"]  # the film step (pbrt's reconstruction filter): rpf_filter_film / rpf_film_splat_device
 KERNEL_TUS += ["rpf_generic.hip"]  # the layout-generic kernel pair (RPF_FLAG_GENERIC): n_random / n_feat at run time
@@ -20,6 +20,7 @@ KERNEL_TUS += ["rpf_generic_wide.hip"]  # the wide layout-generic kernel: 65535 
 KERNEL_TUS += ["rpf_spike.hip"]  # the spike pass after the last filter pass: clamp, row sums, energy add (RPF_FLAG_SPIKE_CLAMP)
 KERNEL_TUS += ["rpf_generic_wide_count.hip"]  # ... and the count pass that deals a wide pass by size class (RPF_FLAG_WIDE_CLASSES)
 KERNEL_TUS += ["rpf_generic_sampled_count.hip"]  # the count pass of a sampled pass: the draws of a pixel's key (RPF_FLAG_SAMPLED_NBHD)
+KERNEL_TUS += ["rpf_impl_d19_member.hip", "rpf_impl_d27_member.hip"]  # rpf_filter_impl.inc part 4: the count pass under the membership test (RPF_FLAG_MEMBER_FUSED)
 KERNEL_TUS += ["rpf_report.hip"]  # the per-pass activity report: per-pixel chains, per-row chains and counts (RPF_FLAG_PASS_REPORT)
 # the C ABI (host code only; rpf_api.h is what they share): context, validation and pass loops | pass router | film step | multi-GPU | spike pass | pass report
 # (the names start with rpf_api: the spill scan below skips them by that)

@@ -60,6 +60,7 @@ enum Route : int {
     kRouteWideClasses = 7,   // a wide pass counted first and dealt by size class
     kRouteSampled = 8,       // a sampled pass: the draws' count kernel, then the class kernels on its member lists
     kRouteMemberTest = 9,    // a full-box pass under RPF_FLAG_MEMBER_TEST: route 7's structure with the configured test
+    kRouteMemberFused = 10,  // ... with RPF_FLAG_MEMBER_FUSED, on a compiled layout: route 2's structure behind the configured test
 };
 
 static_assert(sizeof(rpf_sampling) == 48 && offsetof(rpf_sampling, draws) == 16, "rpf_sampling is ABI");
@@ -120,6 +121,7 @@ struct rpf_ctx {
     // previous pass's masks and lists (reset at every API entry: the planes may change between calls)
     bool flat_fresh = false;                    // d_flat / d_nan_flag describe the planes of the call in progress (stage 1a ran in it)
     bool bin_valid = false;
+    bool bin_member = false;                    // whose masks the cache holds: route 10's (the configured test) or route 2's (3 sigma)
     int bin_box = 0, bin_r0 = 0, bin_r1 = 0;
     uint32_t bin_counts[rpf::kNumClasses] = {};
     rpf::DevBuf<void> d_dbg[9];                 // debug planes

@@ -46,6 +46,7 @@ struct FlagRule {
 };
 constexpr uint32_t kPackedRoute = RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED;
 constexpr FlagRule kFlagRules[] = {
+    {RPF_FLAG_MEMBER_FUSED, RPF_FLAG_MEMBER_TEST, 0, 0, "RPF_FLAG_MEMBER_FUSED without RPF_FLAG_MEMBER_TEST: the flag modifies the membership-test route"},
     {RPF_FLAG_MEMBER_TEST, 0, 0, RPF_FLAG_FAST_WEIGHTS, "RPF_FLAG_MEMBER_TEST with RPF_FLAG_FAST_WEIGHTS: passes under the membership test are fp64 throughout"},
     {RPF_FLAG_MEMBER_TEST, 0, 0, RPF_FLAG_GENERIC_FAST, "RPF_FLAG_MEMBER_TEST with RPF_FLAG_GENERIC_FAST: passes under the membership test are fp64 throughout"},
     {RPF_FLAG_MEMBER_TEST, 0, 0, RPF_FLAG_STREAM_FAST, "RPF_FLAG_MEMBER_TEST with RPF_FLAG_STREAM_FAST: passes under the membership test are fp64 throughout"},
@@ -417,6 +418,12 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
             p.gain_c = ctx->schedule.gain_c[e]; p.gain_f = ctx->schedule.gain_f[e];
         }
     }
+    // RPF_FLAG_MEMBER_FUSED (route 10): a full-box pass of a call under the membership test that the compiled
+    // kernels can take -- a compiled layout without RPF_FLAG_GENERIC, not wide, no gain other than 1 (the bits above already say so:
+    // check_schedule and the branch above keep treating a gain-other-than-1 pass of such a call as layout-generic, route 9)
+    const bool member_fused = (d->flags & RPF_FLAG_MEMBER_FUSED) && member && p.lay.supported() &&
+                              !(p.generic & (kGenericOn | kGenericWide | kGenericSampled | kGenericSchedule)) && p.nmax <= kMaxNbhd;
+    if (member_fused) p.generic |= kGenericMemberFused;
     p.sigma_p = (double)(box / 4); // rpf.cpp:531: integer division
     p.plane_stride = (uint64_t)d->W * d->H * d->S;
     p.planes = d_planes; p.col_in = col_in; p.col_out = col_out;
@@ -437,7 +444,11 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
     if ((st = ctx->d_flat.ensure(ctx, HW))) return st;
     p.flat = ctx->d_flat; p.nan_flag = ctx->d_nan_flag;
     if (dbg_dev) p.dbg = *dbg_dev;
-    if (wide || (member && !(p.generic & kGenericSampled))) { // the wide kernel's carve-up: what 160 KiB leave of the joint table is one band of it
+    if (member_fused) { // the largest resident kernel of the pass, as on route 2, and -- its streaming class -- the wide kernel's carve-up
+        const int nres = std::min(p.nmax, kMaxResident), bres = bmax_of(nres);
+        out.lds = lds_layout(p.S, nres, bres, table_in_lds(p.S, nres, bres, ctx->tun, p.lay), ctx->tun, p.lay).total;
+        if (p.nmax > kMaxResident) out.lds = std::max(out.lds, generic_wide_carve(p.lay, p.nmax, false).total);
+    } else if (wide || (member && !(p.generic & kGenericSampled))) { // the wide kernel's carve-up: what 160 KiB leave of the joint table is one band of it
         out.lds = generic_wide_carve(p.lay, p.nmax, stream_fast(p)).total;
     } else if (p.generic) { // the generic kernel's own carve-up (one kernel for every neighbourhood size of the pass)
         out.lds = generic_carve(p.lay, p.nmax, stream_fast(p)).total;

@@ -221,10 +221,16 @@ int32_t route_unbinned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream
 }
 
 // The size-binned route: the neighbourhood sizes are counted first, then every kernel family filters the list of its class.
-int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream_t s, int *launches) {
+// member: null on route 2; the uploaded table on route 10 (route_member_fused below), the same structure
+// with three differences.  The count launch is the MEMBER form of nbhd_count_kernel, which gets stage 1a's flat plane only when
+// the flat proof is sound under the table (every floor below n_feat negative).  The streaming class N > 3136 repeats stage 1b,
+// so it runs on the kernel that does so under the same test: the wide kernel's MEMBER instantiation over the class's list, route
+// 9's rest launch (launch_wide: the 2^-44 table where that is exact, kWideSlots).  The membership cache is keyed by whose masks
+// it holds (bin_member): a route-10 pass is served by a route-10 pass only, a route-2 pass by a route-2 pass only.
+int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, const double *member, hipStream_t s, int *launches) {
     const size_t HW = (size_t)p.W * p.H;
     int32_t st;
-    ctx->last_route = kRouteBinned;
+    ctx->last_route = member ? kRouteMemberFused : kRouteBinned;
     if ((st = ctx->d_lists.ensure(ctx, (size_t)kNumClasses * HW * sizeof(uint32_t)))) return st;
     // the count pass keeps its acceptance masks (one u64 per 64 candidates) so the filter kernels only rebuild the list
     PassParams pc = p;
@@ -238,13 +244,24 @@ int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream_t
         pc.carry = ctx->d_carry;
     }
     uint32_t counts[kNumClasses];
-    if (ctx->bin_valid && ctx->bin_box == p.box && ctx->bin_r0 == p.row_begin && ctx->bin_r1 == p.row_end) {
+    if (ctx->bin_valid && ctx->bin_member == (member != nullptr) && ctx->bin_box == p.box && ctx->bin_r0 == p.row_begin && ctx->bin_r1 == p.row_end) {
         std::memcpy(counts, ctx->bin_counts, sizeof(counts));
     } else {
-        Range rg("rpf:count + classify (stage 1b test, size classes)");
+        Range rg(member ? "rpf:count + classify (configured membership test, size classes)" : "rpf:count + classify (stage 1b test, size classes)");
         ctx->bin_valid = false;
+        ctx->bin_member = member != nullptr;
         HIP_TRY(hipMemsetAsync(ctx->d_class_counts, 0, kNumClasses * sizeof(uint32_t), s));
-        HIP_TRY(launch_nbhd_count(pc, 1, nullptr, nullptr, nullptr, 0, s));
+        if (member) {
+            // p.flat says "some feature has sigma * 3 == 0 and a finite mean": N = S under the configured test exactly where that
+            // feature's floor is negative, and the plane does not say which feature it was
+            PassParams pm = pc;
+            bool sound = ctx->flat_fresh;
+            for (int k = 0; k < p.lay.nF; ++k) sound = sound && ctx->membership.floor[k] < 0.0;
+            if (!sound) pm.flat = nullptr;
+            HIP_TRY(launch_nbhd_count_member(pm, member, s));
+        } else {
+            HIP_TRY(launch_nbhd_count(pc, 1, nullptr, nullptr, nullptr, 0, s));
+        }
         HIP_TRY(launch_classify(pc, ctx->d_lists, ctx->d_class_counts, kNumClasses, -1, s));
         HIP_TRY(hipMemcpyAsync(counts, ctx->d_class_counts, sizeof(counts), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -264,6 +281,13 @@ int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream_t
             "rpf:filter class N<=832", "rpf:filter class N<=1600", "rpf:filter class N<=3136", "rpf:filter class streaming"};
         Range rg(kClassName[c]);
         const PassParams q = class_params(ctx, pc, c, counts[c]);
+        if (c == kNumClasses - 1 && member) { // ... under the configured test: the wide kernel runs its own stage 1b on the table
+            PassParams w = q;
+            w.masks = nullptr; w.mask_stride = 0; w.carry = nullptr;
+            w.redo_list = nullptr; w.redo_count = nullptr;
+            if ((st = launch_wide(ctx, w, counts[c], kWideSlots, nullptr, s, launches, false, member))) return st;
+            continue;
+        }
         if (c == kNumClasses - 1) { // neighbourhoods beyond the LDS-resident kernels: stream through global scratch (fp64 under every flag)
             if ((st = launch_streaming(ctx, q, counts[c], kBinnedSlots, nullptr, s, launches, false))) return st;
             continue;
@@ -415,6 +439,15 @@ int32_t route_member_test(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int 
     return route_wide_classes(ctx, p, ctx->d_member, s, launches);
 }
 
+// A full-box pass under RPF_FLAG_MEMBER_TEST | RPF_FLAG_MEMBER_FUSED on a compiled layout (route 10): route
+// 2's structure behind the count kernel's MEMBER form, whatever box*box*S <= 65535 is and whatever option "binning" says.
+// REF_ABORT is refused, so there is no redo list.
+int32_t route_member_fused(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream_t s, int *launches) {
+    if (!ctx->d_member || !ctx->member_fresh || !p.lay.supported() || p.nmax > kMaxNbhd || p.redo_list != nullptr)
+        return fail(ctx, RPF_E_BADARG, "pass under the membership test without its configuration (setup_pass prepares it)");
+    return route_binned(ctx, p, packed, ctx->d_member, s, launches);
+}
+
 // A sampled pass (RPF_FLAG_SAMPLED_NBHD with draws > 0): route 7 with another count kernel.
 // generic::launch_sampled_count lists, per pixel, the distinct draws of its key that pass the 3-sigma test; S + draws <= 832 puts
 // every pixel into one of the eight classes, so there is no rest launch, and REF_ABORT is refused, so there is no redo launch.
@@ -501,6 +534,7 @@ int32_t route_generic_classes(rpf_ctx *ctx, const PassParams &p_in, int n_classe
 // packed class, above 832 spp no one-wave class: such a pass runs as route 3 does.
 Route generic_route(const PassParams &p) {
     if (p.generic & kGenericSampled) return kRouteSampled; // (setup_pass marked it: draws > 0)
+    if (p.generic & kGenericMemberFused) return kRouteMemberFused; // (... a full-box pass the compiled kernels take under RPF_FLAG_MEMBER_FUSED)
     if (p.generic & kGenericMemberTest) return kRouteMemberTest; // (... a full-box pass of a call under RPF_FLAG_MEMBER_TEST)
     if (p.generic & kGenericWide) return (p.generic & kGenericWideClasses) ? kRouteWideClasses : kRouteWide; // (setup_pass marked it)
     if (!p.generic) return kRouteNone;
@@ -533,9 +567,13 @@ int32_t route_pass(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *lau
     // The membership cache of the size-binned route (bin_valid: the class counts on the host, d_lists and d_masks on the device)
     // outlives a pass only from one size-binned pass to the next: route_binned alone sets it, and every other route drops it
     // here, before it runs -- the unbinned route with its packed lists, routes 4 and 5 and the listed-member routes 7, 8 and 9
-    // write their own lists, masks and class counts into the same buffers
-    if (!bin) ctx->bin_valid = false;
+    // write their own lists, masks and class counts into the same buffers.  Route 10 is route_binned under another test: it keeps
+    // the cache, keyed by bin_member, so that neither of routes 2 and 10 is served the other's masks
+    if (!bin && route != kRouteMemberFused) ctx->bin_valid = false;
+    // small neighbourhoods (N <= 64) run on the packed kernels, several pixels per wave (rpf_packed_impl.inc); option "packed"
+    const bool packed = ctx->tun.packed != 0 && !p.fast_weights && ctx->tun.stage_mask == -1 && ctx->tun.lds_pad == 0;
     switch (route) {
+    case kRouteMemberFused: return route_member_fused(ctx, p, packed, s, launches);
     case kRouteSampled: return route_sampled(ctx, p, s, launches);
     case kRouteMemberTest: return route_member_test(ctx, p, s, launches);
     case kRouteWideClasses: return route_wide_classes(ctx, p, nullptr, s, launches);
@@ -545,9 +583,7 @@ int32_t route_pass(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *lau
     case kRouteGeneric: return route_generic(ctx, p, s, launches);
     default: break;
     }
-    // small neighbourhoods (N <= 64) run on the packed kernels, several pixels per wave (rpf_packed_impl.inc); option "packed"
-    const bool packed = ctx->tun.packed != 0 && !p.fast_weights && ctx->tun.stage_mask == -1 && ctx->tun.lds_pad == 0;
-    return bin ? route_binned(ctx, p, packed, s, launches) : route_unbinned(ctx, p, packed, s, launches);
+    return bin ? route_binned(ctx, p, packed, nullptr, s, launches) : route_unbinned(ctx, p, packed, s, launches);
 }
 
 } // namespace rpf

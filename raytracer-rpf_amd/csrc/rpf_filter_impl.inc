@@ -1,6 +1,7 @@
 // rpf_filter_impl.inc -- the dimension-dependent kernels: included by the rpf_impl_*.hip translation units once per supported
 // sample-vector layout and size-class part (RPF_IMPL_PART: 1 = K <= 8 kernels + stage 1a + count pass + streaming kernel,
-// 2 = K 13 / 25, 3 = K 49; the parts compile in parallel), inside the layout's namespace, with
+// 2 = K 13 / 25, 3 = K 49, 4 = the count pass under the membership test alone, so that the code objects of parts 1 to 3 are
+// what they were before it existed; the parts compile in parallel), inside the layout's namespace, with
 //     RPF_IMPL_NR   number of random-parameter columns  (reference: 2, sd.h:42 SD_N_RANDOM)
 //     RPF_IMPL_NF   number of scene-feature columns     (reference: 12, sd.h:40 SD_N_FEATURES)
 //     RPF_IMPL_PLANE_T  storage type of the feature planes (float, or __half for fp16 feature storage)
@@ -2240,7 +2241,7 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
     }
 }
 
-#if RPF_IMPL_PART == 1
+#if RPF_IMPL_PART == 1 || RPF_IMPL_PART == 4
 // ---- neighbourhood-size binning -----------------------------------------------------------------------------------
 // The cost and the LDS footprint of a pixel are set by its neighbourhood size N, and N is data dependent: box*box*S is
 // only its ceiling (path-traced buffers keep little more than the S own samples, SURVEY F10).  When the ceiling is above
@@ -2254,7 +2255,17 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
 // candidates outlive phase A, so most of those gathers are never issued (2.7 ms).  Every (candidate, feature) comparison is
 // the one of the one-pass test in filter_pixel_kernel on the same operands (ops.h:101-104), and a candidate passes iff all
 // of them do: same masks, same N.  Returns N.
-__device__ __forceinline__ int membership_pixel_two_phase(const PassParams &p, int x, int y, int lane, uint16_t *sQ, unsigned long long *sMW) {
+// MEMBER (RPF_FLAG_MEMBER_TEST | RPF_FLAG_MEMBER_FUSED, route 10; DESIGN.md section 14e): the configured test of section 14a on
+// mt = mult[RPF_MAX_NDIM] | floor[RPF_MAX_NDIM] (rpf_ctx::d_member).  lim_k = sd_k * mult_k (one rounding) and fl_k = sd_k > floor_k
+// ? -inf : floor_k are pixel-uniform: formed once per pixel from the scalar-loaded statistics and the table at wave-uniform
+// addresses, never per candidate; a candidate is rejected on k iff a >= lim_k && a > fl_k, and a comparison with a NaN is false.
+// The test is a conjunction of per-feature tests, so phase A, which applies the first kA of them, rejects only what the whole
+// conjunction rejects.  The flat proof is the 3-sigma one (sd_k == 0 gives lim_k == 0 for any finite positive multiple) and holds
+// exactly where floor_k < 0: p.flat is one bit over all features, so the host hands it over only when every floor below n_feat is
+// negative, and null otherwise.  The other instantiation is the code it was.
+template <bool MEMBER = false>
+__device__ __forceinline__ int membership_pixel_two_phase(const PassParams &p, int x, int y, int lane, uint16_t *sQ, unsigned long long *sMW,
+                                                          [[maybe_unused]] const double *mt = nullptr) {
     constexpr int kA = 2, kChunk = 1024, kPF = 7;
     const int W = p.W, H = p.H, S = p.S, b = p.b;
     const uint64_t HW = (uint64_t)H * W, pix = (uint64_t)y * W + x;
@@ -2271,10 +2282,17 @@ __device__ __forceinline__ int membership_pixel_two_phase(const PassParams &p, i
         return S;
     }
     double m12[kNFeat], lim12[kNFeat];
+    [[maybe_unused]] double fl12[kNFeat];
 #pragma unroll
     for (int k = 0; k < kNFeat; ++k) {
         m12[k] = p.pmean[(uint64_t)k * HW + pix];
-        lim12[k] = p.pstd[(uint64_t)k * HW + pix] * 3.0; // multiplyArray(std, 3), rpf.cpp:579
+        if constexpr (MEMBER) {
+            const double sd = p.pstd[(uint64_t)k * HW + pix], fl = mt[RPF_MAX_NDIM + k];
+            lim12[k] = sd * mt[k];
+            fl12[k] = sd > fl ? -__builtin_inf() : fl;
+        } else {
+            lim12[k] = p.pstd[(uint64_t)k * HW + pix] * 3.0; // multiplyArray(std, 3), rpf.cpp:579
+        }
     }
     auto cand_off = [&](int qq) -> uint32_t {
         int cell = (int)div_small((uint32_t)qq, magic_S); // (qq < 65536 * 64 / S ... the chunks keep n * d < 2^32: ncand * S < 2^32)
@@ -2310,7 +2328,11 @@ __device__ __forceinline__ int membership_pixel_two_phase(const PassParams &p, i
 #pragma unroll
                     for (int k = 0; k < kA; ++k) {
                         const double a = fabs((double)fa[u][k] - m12[k]);
-                        if (a >= lim12[k]) surv = false;       // allLessThan (ops.h:101-104)
+                        if constexpr (MEMBER) {
+                            if (a >= lim12[k] && a > fl12[k]) surv = false;
+                        } else {
+                            if (a >= lim12[k]) surv = false;       // allLessThan (ops.h:101-104)
+                        }
                     }
                     const unsigned long long m = __ballot(surv);
                     if (surv) sQ[qn + __popcll(m & ((1ull << lane) - 1ull))] = (uint16_t)(qb + lane - c0);
@@ -2333,7 +2355,11 @@ __device__ __forceinline__ int membership_pixel_two_phase(const PassParams &p, i
 #pragma unroll
             for (int k = kA; k < kNFeat; ++k) {
                 const double a = fabs((double)fbv[k - kA] - m12[k]);
-                if (pass && a >= lim12[k]) pass = false;
+                if constexpr (MEMBER) {
+                    if (pass && a >= lim12[k] && a > fl12[k]) pass = false;
+                } else {
+                    if (pass && a >= lim12[k]) pass = false;
+                }
             }
             if (pass) atomicOr(&sMW[ql >> 6], 1ull << (ql & 63));
             n += __popcll(__ballot(pass));
@@ -2347,6 +2373,9 @@ __device__ __forceinline__ int membership_pixel_two_phase(const PassParams &p, i
     return n;
 }
 
+#endif // RPF_IMPL_PART == 1 || RPF_IMPL_PART == 4
+
+#if RPF_IMPL_PART == 1
 // The pixels: every pixel of the slab (step 1, list null); the entries of `list` (its size read from *list_count: the
 // pixels stage 1a could not prove flat, rpf_kernels.hip prelist_kernel); or (step > 1: the route probe of the unbinned pass,
 // rpf_api.hip) the points of a lattice with that pitch, probe[0] += how many of them have N <= 64 without being proven flat,
@@ -2382,6 +2411,19 @@ __global__ __launch_bounds__(256) void nbhd_count_kernel(PassParams p, int step,
 }
 
 #endif // RPF_IMPL_PART == 1
+
+#if RPF_IMPL_PART == 4
+// The count kernel of route 10: every pixel of the slab (the same walk, the same LDS) under the configured test on mt
+__global__ __launch_bounds__(256) void nbhd_count_member_kernel(PassParams p, const double *mt) {
+    __shared__ uint16_t sQ[4][1024];
+    __shared__ unsigned long long sMW[4][16];
+    const int lane = threadIdx.x & (kWave - 1), wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int xi, yi;
+    if (!slab_pixel(p, (int)(blockIdx.x & 7u), (int64_t)(blockIdx.x >> 3) * 4 + wv, xi, yi)) return; // wave-uniform
+    (void)membership_pixel_two_phase<true>(p, xi, yi, lane, sQ[wv], sMW[wv], mt);
+}
+
+#endif // RPF_IMPL_PART == 4
 
 #if RPF_IMPL_PART == 1
 #include "rpf_packed_impl.inc"
@@ -2474,6 +2516,13 @@ hipError_t impl_filter_large(const PassParams &p, const LdsLayout &L, const LdsL
     if (samples_per_lane(p.nmax) != 49) return hipErrorInvalidValue;
     return launch_filter_k<49>(p, L, L2, L3, t_in_lds, grid, s);
 }
+#elif RPF_IMPL_PART == 4
+hipError_t impl_nbhd_count_member(const PassParams &p, const double *mt, hipStream_t s) {
+    if (p.row_end <= p.row_begin || mt == nullptr) return mt == nullptr ? hipErrorInvalidValue : hipSuccess;
+    const unsigned grid = (unsigned)(8 * (((int64_t)((p.row_end - p.row_begin + 7) / 8) * p.W + 3) / 4)); // 8 XCD bands
+    hipLaunchKernelGGL(nbhd_count_member_kernel, dim3(grid), dim3(256), 0, s, p, mt);
+    return hipGetLastError();
+}
 #else
-#error "RPF_IMPL_PART must be 1, 2 or 3"
+#error "RPF_IMPL_PART must be 1, 2, 3 or 4"
 #endif

@@ -52,6 +52,10 @@ enum GenericBits : int32_t {
     kGenericSchedule = 512,   // RPF_FLAG_SCHEDULE on a pass whose entry has a gain other than 1 (setup_pass; never on a fused pass, which
                               //   check_schedule refuses): stage 3c of the packed, one-wave, streaming and wide layout-generic kernels
                               //   forms alpha and beta from PassParams::gain_c / gain_f; selects no route
+    kGenericMemberFused = 1024, // RPF_FLAG_MEMBER_FUSED on a full-box pass of a call under RPF_FLAG_MEMBER_TEST that the compiled kernels can
+                              //   take (setup_pass: a compiled layout without RPF_FLAG_GENERIC, not wide, no kGenericSchedule): route 10
+                              //   (route_member_fused), the size-binned route behind the count kernel's MEMBER form.
+                              //   Host-side only: no kernel reads it, and the compiled kernels read no bit of `generic`
 };
 
 // everything one pass needs, passed by value to the kernels
@@ -165,6 +169,10 @@ hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, const 
 // probe[0] += how many of them have N <= 64 without being proven flat and probe[1] += how many are proven flat
 hipError_t launch_nbhd_count(const PassParams &p, int step, uint32_t *probe, const uint32_t *list, const uint32_t *list_count,
                              uint32_t list_max, hipStream_t s);
+// the same for route 10: every pixel of the slab under the configured test of RPF_FLAG_MEMBER_TEST (member: device,
+// mult[RPF_MAX_NDIM] | floor[RPF_MAX_NDIM]); N into p.nbhd and the masks into p.masks, which must be given.  p.flat: null unless
+// every floor below n_feat is negative (the flat proof is the 3-sigma test's)
+hipError_t launch_nbhd_count_member(const PassParams &p, const double *member, hipStream_t s);
 // max_class < kNumClasses: pixels of that class and above join the list of rest_class (-1: they are left out)
 hipError_t launch_classify(const PassParams &p, uint32_t *lists /*[kNumClasses][H*W]*/, uint32_t *counts /*[kNumClasses], zeroed*/,
                            int max_class, int rest_class, hipStream_t s);

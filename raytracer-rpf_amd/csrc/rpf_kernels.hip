@@ -240,6 +240,7 @@ __global__ __launch_bounds__(256) void nbhd_reduce_kernel(const int32_t *nbhd, u
     hipError_t impl_filter_large(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
     hipError_t impl_pixel_stats(const PassParams &p, uint64_t pix0, uint64_t pix1, hipStream_t s);                        \
     hipError_t impl_nbhd_count(const PassParams &p, int step, uint32_t *probe, const uint32_t *list, const uint32_t *list_count, uint32_t list_max, hipStream_t s); \
+    hipError_t impl_nbhd_count_member(const PassParams &p, const double *mt, hipStream_t s); \
     hipError_t impl_filter_packed(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s);    \
     }
 RPF_DECLARE_IMPL(d19) // the reference's 19 dims (2 random parameters, 12 features), fp32 planes
@@ -439,6 +440,11 @@ hipError_t launch_nbhd_count(const PassParams &p, int step, uint32_t *probe, con
     if (!p.lay.supported() || step < 1) return hipErrorInvalidValue;
     return p.lay.is_ref19() ? d19::impl_nbhd_count(p, step, probe, list, list_count, list_max, s)
                             : d27::impl_nbhd_count(p, step, probe, list, list_count, list_max, s);
+}
+
+hipError_t launch_nbhd_count_member(const PassParams &p, const double *member, hipStream_t s) {
+    if (!p.lay.supported() || member == nullptr || p.masks == nullptr) return hipErrorInvalidValue;
+    return p.lay.is_ref19() ? d19::impl_nbhd_count_member(p, member, s) : d27::impl_nbhd_count_member(p, member, s);
 }
 
 hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s) {

@@ -54,6 +54,12 @@ SAMPLED_NBHD_FLAG = 2048
 # with S > 832.  RPF_FLAG_MEMBER_TEST of the header; the name stays outside the FLAG_* family for SAMPLED_NBHD_FLAG's reason (its
 # table: tests/test_member_test_cpu.py)
 MEMBER_TEST_FLAG = 4096
+# modifies MEMBER_TEST_FLAG: a full-box pass of the call on a compiled layout (no FLAG_GENERIC, box*box*S <=
+# 65535, not forced wide, no schedule gain other than 1) runs on the compiled kernels behind a count kernel under the configured
+# test: route 10, route 2's structure, the same member lists as route 9.  Every other pass runs as without it.  Refused without
+# MEMBER_TEST_FLAG.  RPF_FLAG_MEMBER_FUSED of the header; the name stays outside the FLAG_* family for MEMBER_TEST_FLAG's reason
+# (its table: tests/test_member_fused_cpu.py)
+MEMBER_FUSED_FLAG = 65536
 # the per-pass schedule of the weight stage (Context.set_schedule): pass p of a call reads entry pass0 + p of
 # a table of (seed, gain_c, gain_f); the seed stands for the descriptor's sigma_seed, and alpha_k = clamp0(1 - gain_c W_r^{c,k}),
 # beta_k = clamp0(1 - gain_f W_r^{f,k}) W_c^{f,k}.  A pass with both gains 1 runs as without the flag on any route (the fused ones
@@ -565,7 +571,7 @@ class Context:
         (FLAG_GENERIC), 4 the same with small neighbourhoods packed (FLAG_GENERIC_PACKED), 5 the same with
         64 < N <= 832 on the one-wave generic kernels (FLAG_GENERIC_WAVE; 3 for a pass with S > 832), 6 the wide kernel
         (FLAG_WIDE_NBHD on a pass with box*box*S > 65535), 7 such a pass dealt by size class (FLAG_WIDE_CLASSES), 8 a sampled
-        pass (SAMPLED_NBHD_FLAG with draws > 0), 9 a full-box pass under MEMBER_TEST_FLAG; -1 before any pass.  FLAG_GENERIC_FAST and FLAG_STREAM_FAST change no route
+        pass (SAMPLED_NBHD_FLAG with draws > 0), 9 a full-box pass under MEMBER_TEST_FLAG, 10 such a pass on the compiled kernels (MEMBER_FUSED_FLAG); -1 before any pass.  FLAG_GENERIC_FAST and FLAG_STREAM_FAST change no route
         (rpf_query_route)"""
         r = C.c_int32(-1)
         self._check(self._L.rpf_query_route(self._h, C.byref(r)))
