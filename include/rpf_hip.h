@@ -288,6 +288,25 @@ enum {
                                   for the word without the flag; rpf_max_nbhd and rpf_max_draws do not read it.  Refused before
                                   any device work: the flag without RPF_FLAG_MEMBER_TEST (RPF_E_UNSUPPORTED; rpf_layout_kernels
                                   answers the same way); every refusal of RPF_FLAG_MEMBER_TEST stands with it. */
+    RPF_FLAG_SCHEDULE_FUSED = 131072, /* opt-in, modifies RPF_FLAG_SCHEDULE: a permission, not a route.  A pass
+                                  of the call whose entry has a gain other than 1 and which carries no layout-generic bit (a
+                                  compiled layout, no RPF_FLAG_GENERIC, not wide, not sampled, no membership test) is no longer
+                                  refused: it runs on the route it would take with gains of 1 -- route 0, 1 or 2, same probe, same
+                                  options, same launch counts -- on builds of the compiled kernels that form
+                                  alpha_k = clamp0(1 - gain_c * W_r^{c,k}) and beta_k = clamp0(1 - gain_f * W_r^{f,k}) * W_c^{f,k}
+                                  in stage 3c (the quotients are the unscheduled kernels' own; each product and difference is
+                                  rounded once; a NaN stays a NaN; W_r_c is untouched).  Under RPF_FLAG_MEMBER_TEST |
+                                  RPF_FLAG_MEMBER_FUSED such a pass takes route 10 instead of route 9.  The streaming class
+                                  N > 3136 of either runs the kernel it runs without the flag, under the same gains.
+                                  rpf_query_route, the counters, rpf_query_nbhd, rpf_layout_kernels, rpf_max_nbhd and
+                                  rpf_max_draws answer as for the same call with gains of 1.  Every pass that carries
+                                  layout-generic bits (RPF_FLAG_GENERIC, wide, sampled, route 9 without RPF_FLAG_MEMBER_FUSED)
+                                  runs exactly as without this flag, and a pass with both gains 1 runs the unscheduled kernels.
+                                  Taken by every filter entry point (rpf_filter_pass_debug reads entry pass0).  Refused before
+                                  any device work: the flag without RPF_FLAG_SCHEDULE (RPF_E_UNSUPPORTED; rpf_layout_kernels
+                                  answers the same way); a gain other than 1 on a pass of the compiled kernels together with
+                                  RPF_FLAG_FAST_WEIGHTS (RPF_E_UNSUPPORTED: the scheduled builds are fp64 only); every refusal
+                                  of RPF_FLAG_SCHEDULE stands (RPF_DEGEN_REF_ABORT with a gain other than 1 included). */
     RPF_FLAG_STREAM_FAST = 512/* opt-in, modifies RPF_FLAG_GENERIC and / or RPF_FLAG_WIDE_NBHD: the two kernels that walk a
                                   neighbourhood of any size with 256 threads -- the generic filter kernel (route 3, the rest
                                   list N > 64 / N > 832 of routes 4 / 5) and the wide kernel (route 6, the rest list N > 832 of

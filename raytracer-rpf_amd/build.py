@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB = os.path.join(_HERE, "lib", "librpf_hip.so")
 # the fused per-pixel kernels compile as one translation unit per sample layout and size-class part (rpf_filter_impl.inc
-# with RPF_IMPL_PART = 1 / 2 / 3; part 4, the *_member TUs below), in parallel: the single kernel TU of rounds 1-2 took 3.2 minutes
+# with RPF_IMPL_PART = 1 / 2 / 3; part 4, the *_member TUs below; the *_sched_* TUs, their scheduled builds), in parallel: the single kernel TU of rounds 1-2 took 3.2 minutes
 KERNEL_TUS = ["rpf_impl_%s_%s.hip" % (lay, part) for lay in ("d19", "d27") for part in ("small", "mid", "large")] + ["rpf_kernels.hip"]
 KERNEL_TUS += ["rpf_film.hip"]  # the film step (pbrt's reconstruction filter): rpf_filter_film / rpf_film_splat_device
 KERNEL_TUS += ["rpf_generic.hip"]  # the layout-generic kernel pair (RPF_FLAG_GENERIC): n_random / n_feat at run time
@@ -21,6 +21,8 @@ KERNEL_TUS += ["rpf_spike.hip"]  # the spike pass after the last filter pass: cl
 KERNEL_TUS += ["rpf_generic_wide_count.hip"]  # ... and the count pass that deals a wide pass by size class (RPF_FLAG_WIDE_CLASSES)
 KERNEL_TUS += ["rpf_generic_sampled_count.hip"]  # the count pass of a sampled pass: the draws of a pixel's key (RPF_FLAG_SAMPLED_NBHD)
 KERNEL_TUS += ["rpf_impl_d19_member.hip", "rpf_impl_d27_member.hip"]  # rpf_filter_impl.inc part 4: the count pass under the membership test (RPF_FLAG_MEMBER_FUSED)
+# ... and the scheduled builds of parts 1 to 3 (RPF_IMPL_SCHED: stage 3c from the entry's gains; RPF_FLAG_SCHEDULE_FUSED)
+KERNEL_TUS += ["rpf_impl_%s_sched_%s.hip" % (lay, part) for lay in ("d19", "d27") for part in ("small", "mid", "large")]
 KERNEL_TUS += ["rpf_report.hip"]  # the per-pass activity report: per-pixel chains, per-row chains and counts (RPF_FLAG_PASS_REPORT)
 # the C ABI (host code only; rpf_api.h is what they share): context, validation and pass loops | pass router | film step | multi-GPU | spike pass | pass report
 # (the names start with rpf_api: the spill scan below skips them by that)
@@ -73,19 +75,34 @@ def _build(LIB, OBJ_DIR, defs, shipped, force, verbose):
     os.makedirs(OBJ_DIR, exist_ok=True)
     flags = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17",
              "-I" + os.path.join(_ROOT, "include"), "-I" + os.path.join(_HERE, "csrc")] + list(defs)
-    objs, procs = [], []
+    objs, cmds = [], []
     for src in SOURCES:
         obj = os.path.join(OBJ_DIR, os.path.basename(src) + ".o")
         objs.append(obj)
         if force or _stale(obj, [src] + HEADERS):
             # -save-temps=obj keeps the device assembly next to the object: scripts/check_spills.py reads it below
-            cmd = [hipcc_path()] + flags + ["-save-temps=obj", "-c", src, "-o", obj]
+            cmds.append([hipcc_path()] + flags + ["-save-temps=obj", "-c", src, "-o", obj])
+    # at most MAX_JOBS compilers at a time, 16 at the most (30 translation units: one hipcc each all at once oversubscribes a
+    # machine that gives the build a share of its cores).  The largest units (the rpf_impl_* parts) start first
+    jobs = max(1, min(16, int(os.environ.get("MAX_JOBS", 16))))
+    cmds.sort(key=lambda c: not os.path.basename(c[-3]).startswith("rpf_impl_"))
+    running, failed = [], None
+    while (cmds and failed is None) or running:
+        while cmds and failed is None and len(running) < jobs:
+            cmd = cmds.pop(0)
             if verbose:
                 print(" ".join(cmd))
-            procs.append((cmd, subprocess.Popen(cmd)))
-    for cmd, pr in procs:
-        if pr.wait() != 0:
-            raise subprocess.CalledProcessError(pr.returncode, cmd)
+            running.append((cmd, subprocess.Popen(cmd)))
+        cmd, pr = running.pop(0)
+        try:
+            rc = pr.wait(timeout=0.2 if (cmds and failed is None) else None)
+        except subprocess.TimeoutExpired:
+            running.append((cmd, pr))
+            continue
+        if rc != 0 and failed is None:
+            failed = subprocess.CalledProcessError(rc, cmd)
+    if failed is not None:
+        raise failed
     import glob
     asm = sorted(f for f in glob.glob(os.path.join(OBJ_DIR, "*gfx950*.s")) if "rpf_api" not in os.path.basename(f))
     if asm:

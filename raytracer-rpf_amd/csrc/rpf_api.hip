@@ -46,6 +46,7 @@ struct FlagRule {
 };
 constexpr uint32_t kPackedRoute = RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED;
 constexpr FlagRule kFlagRules[] = {
+    {RPF_FLAG_SCHEDULE_FUSED, RPF_FLAG_SCHEDULE, 0, 0, "RPF_FLAG_SCHEDULE_FUSED without RPF_FLAG_SCHEDULE: the flag modifies the per-pass schedule"},
     {RPF_FLAG_MEMBER_FUSED, RPF_FLAG_MEMBER_TEST, 0, 0, "RPF_FLAG_MEMBER_FUSED without RPF_FLAG_MEMBER_TEST: the flag modifies the membership-test route"},
     {RPF_FLAG_MEMBER_TEST, 0, 0, RPF_FLAG_FAST_WEIGHTS, "RPF_FLAG_MEMBER_TEST with RPF_FLAG_FAST_WEIGHTS: passes under the membership test are fp64 throughout"},
     {RPF_FLAG_MEMBER_TEST, 0, 0, RPF_FLAG_GENERIC_FAST, "RPF_FLAG_MEMBER_TEST with RPF_FLAG_GENERIC_FAST: passes under the membership test are fp64 throughout"},
@@ -177,8 +178,9 @@ int32_t pass_generic_bits(const rpf_ctx *ctx, const rpf_desc *d, int box, int pa
 }
 
 // RPF_FLAG_SCHEDULE on the terms of check_sampled, after it and check_member_test: the table, the entries passes 0 .. n_pass - 1
-// read, and -- for a pass whose entry has a gain other than 1 -- the policy and that the pass runs layout-generic kernels.  A pass
-// with both gains 1 is any pass with another seed and is never refused here
+// read, and -- for a pass whose entry has a gain other than 1 -- the policy and that the pass runs layout-generic kernels or, under
+// RPF_FLAG_SCHEDULE_FUSED, the scheduled fp64 builds of the compiled ones.  A pass with both gains 1 is any pass with another seed
+// and is never refused here
 int32_t check_schedule(rpf_ctx *ctx, const rpf_desc *d, const int32_t *boxes, int n_pass) {
     if (!(d->flags & RPF_FLAG_SCHEDULE)) return RPF_OK;
     if (!ctx->schedule_set) return fail(ctx, RPF_E_BADARG, "RPF_FLAG_SCHEDULE without a prior rpf_set_schedule");
@@ -191,6 +193,13 @@ int32_t check_schedule(rpf_ctx *ctx, const rpf_desc *d, const int32_t *boxes, in
         if (d->degenerate_policy == RPF_DEGEN_REF_ABORT)
             return fail(ctx, RPF_E_UNSUPPORTED, "RPF_FLAG_SCHEDULE: a pass with a gain other than 1 under RPF_DEGEN_REF_ABORT: the reference has no "
                                                 "such rule to reproduce, and the redo launch would have to carry it (use RPF_DEGEN_EPS)");
+        if (pass_generic_bits(ctx, d, boxes[i], i) == 0 && (d->flags & RPF_FLAG_SCHEDULE_FUSED)) {
+            // RPF_FLAG_SCHEDULE_FUSED: the scheduled builds of the compiled kernels take the pass; they are fp64 only
+            if (d->flags & RPF_FLAG_FAST_WEIGHTS)
+                return fail(ctx, RPF_E_UNSUPPORTED, "RPF_FLAG_SCHEDULE_FUSED with RPF_FLAG_FAST_WEIGHTS: a pass with a gain other than 1 on the fused "
+                                                    "kernels runs their scheduled builds, which are fp64 throughout");
+            continue;
+        }
         if (pass_generic_bits(ctx, d, boxes[i], i) == 0)
             return fail(ctx, RPF_E_UNSUPPORTED, "RPF_FLAG_SCHEDULE: a pass with a gain other than 1 would run on the fused kernels, which do not know "
                                                 "the rule; a layout-generic route does: RPF_FLAG_GENERIC (| RPF_FLAG_GENERIC_PACKED | "
@@ -413,17 +422,24 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
         if (pass < 0 || e < 0 || e >= RPF_MAX_BOXES) return fail(ctx, RPF_E_BADARG, "RPF_FLAG_SCHEDULE: the pass reads beyond the table's last entry");
         p.seed = ctx->schedule.seed[e];
         if (ctx->schedule.gain_c[e] != 1.0 || ctx->schedule.gain_f[e] != 1.0) {
-            if (!p.generic) return fail(ctx, RPF_E_UNSUPPORTED, "RPF_FLAG_SCHEDULE: a pass with a gain other than 1 on the fused kernels");
-            p.generic |= kGenericSchedule;
+            // on the compiled kernels: only under RPF_FLAG_SCHEDULE_FUSED, on their scheduled, fp64 builds (the host-side bit; no
+            // kernel of that family reads `generic`)
+            if (!p.generic && (!(d->flags & RPF_FLAG_SCHEDULE_FUSED) || p.fast_weights))
+                return fail(ctx, RPF_E_UNSUPPORTED, "RPF_FLAG_SCHEDULE: a pass with a gain other than 1 on the fused kernels");
+            p.generic |= p.generic ? kGenericSchedule : kGenericScheduleFused;
             p.gain_c = ctx->schedule.gain_c[e]; p.gain_f = ctx->schedule.gain_f[e];
         }
     }
     // RPF_FLAG_MEMBER_FUSED (route 10): a full-box pass of a call under the membership test that the compiled
     // kernels can take -- a compiled layout without RPF_FLAG_GENERIC, not wide, no gain other than 1 (the bits above already say so:
     // check_schedule and the branch above keep treating a gain-other-than-1 pass of such a call as layout-generic, route 9)
+    // RPF_FLAG_SCHEDULE_FUSED lifts the last condition: the pass takes route 10 on the scheduled builds, kGenericSchedule gives way to
+    // the host-side kGenericScheduleFused
+    const int32_t no_fused = kGenericOn | kGenericWide | kGenericSampled | ((d->flags & RPF_FLAG_SCHEDULE_FUSED) ? 0 : kGenericSchedule);
     const bool member_fused = (d->flags & RPF_FLAG_MEMBER_FUSED) && member && p.lay.supported() &&
-                              !(p.generic & (kGenericOn | kGenericWide | kGenericSampled | kGenericSchedule)) && p.nmax <= kMaxNbhd;
+                              !(p.generic & no_fused) && p.nmax <= kMaxNbhd;
     if (member_fused) p.generic |= kGenericMemberFused;
+    if (member_fused && (p.generic & kGenericSchedule)) p.generic = (p.generic & ~kGenericSchedule) | kGenericScheduleFused;
     p.sigma_p = (double)(box / 4); // rpf.cpp:531: integer division
     p.plane_stride = (uint64_t)d->W * d->H * d->S;
     p.planes = d_planes; p.col_in = col_in; p.col_out = col_out;
@@ -450,7 +466,7 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
         if (p.nmax > kMaxResident) out.lds = std::max(out.lds, generic_wide_carve(p.lay, p.nmax, false).total);
     } else if (wide || (member && !(p.generic & kGenericSampled))) { // the wide kernel's carve-up: what 160 KiB leave of the joint table is one band of it
         out.lds = generic_wide_carve(p.lay, p.nmax, stream_fast(p)).total;
-    } else if (p.generic) { // the generic kernel's own carve-up (one kernel for every neighbourhood size of the pass)
+    } else if (route_bits(p.generic)) { // the generic kernel's own carve-up (one kernel for every neighbourhood size of the pass)
         out.lds = generic_carve(p.lay, p.nmax, stream_fast(p)).total;
     } else { // LDS of the largest resident kernel this pass can launch (larger neighbourhoods stream: generic::filter_pixel_kernel)
         const int nres = std::min(p.nmax, kMaxResident), bres = bmax_of(nres);

@@ -282,14 +282,15 @@ int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, const doubl
         Range rg(kClassName[c]);
         const PassParams q = class_params(ctx, pc, c, counts[c]);
         if (c == kNumClasses - 1 && member) { // ... under the configured test: the wide kernel runs its own stage 1b on the table
-            PassParams w = q;
+            PassParams w = scheduled_stream(q); // (a scheduled pass: the wide kernel forms its stage 3c on kGenericSchedule)
             w.masks = nullptr; w.mask_stride = 0; w.carry = nullptr;
             w.redo_list = nullptr; w.redo_count = nullptr;
             if ((st = launch_wide(ctx, w, counts[c], kWideSlots, nullptr, s, launches, false, member))) return st;
             continue;
         }
         if (c == kNumClasses - 1) { // neighbourhoods beyond the LDS-resident kernels: stream through global scratch (fp64 under every flag)
-            if ((st = launch_streaming(ctx, q, counts[c], kBinnedSlots, nullptr, s, launches, false))) return st;
+            // (a scheduled pass: generic::filter_pixel_kernel forms its stage 3c on kGenericSchedule, the one bit of `generic` it reads)
+            if ((st = launch_streaming(ctx, scheduled_stream(q), counts[c], kBinnedSlots, nullptr, s, launches, false))) return st;
             continue;
         }
         if (c < kNumPacked && packed) { HIP_TRY(launch_filter_packed(q, class_capacity(c), nullptr, s)); }
@@ -537,7 +538,7 @@ Route generic_route(const PassParams &p) {
     if (p.generic & kGenericMemberFused) return kRouteMemberFused; // (... a full-box pass the compiled kernels take under RPF_FLAG_MEMBER_FUSED)
     if (p.generic & kGenericMemberTest) return kRouteMemberTest; // (... a full-box pass of a call under RPF_FLAG_MEMBER_TEST)
     if (p.generic & kGenericWide) return (p.generic & kGenericWideClasses) ? kRouteWideClasses : kRouteWide; // (setup_pass marked it)
-    if (!p.generic) return kRouteNone;
+    if (!route_bits(p.generic)) return kRouteNone; // (kGenericScheduleFused picks the build of the compiled kernels, not a route)
     if ((p.generic & kGenericWave) && p.S <= class_capacity(kNumWave - 1)) return kRouteGenericWave;
     if ((p.generic & kGenericPacked) && p.S <= class_capacity(kNumPacked - 1)) return kRouteGenericPacked;
     return kRouteGeneric;

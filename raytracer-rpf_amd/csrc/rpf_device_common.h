@@ -275,5 +275,15 @@ __device__ __forceinline__ bool slab_pixel(const PassParams &p, int r, int64_t q
     return true;
 }
 
+// ---- stage 3c under RPF_FLAG_SCHEDULE (DESIGN.md sections 15 and 15e): clamp0(1 - g * w), w one of the ratios W_r^{c,k} /
+// W_r^{f,k}.  The product and the difference are rounded once each (the TUs build with -ffp-contract=off); v < 0 is false for a
+// NaN, which therefore stays a NaN, and -0.0 stays -0.0.  Shared by the layout-generic kernels (kGenericSchedule) and the scheduled
+// builds of the compiled ones (RPF_IMPL_SCHED, rpf_filter_impl.inc / rpf_packed_impl.inc)
+__device__ __forceinline__ double schedule_factor(double g, double w) {
+    const double t = g * w;
+    const double v = 1 - t;
+    return (v < 0) ? 0.0 : v;
+}
+
 } // namespace
 } // namespace rpf

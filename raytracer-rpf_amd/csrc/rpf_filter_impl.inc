@@ -8,6 +8,14 @@
 // Column layout of a sample vector (sd.h:62-94 generalised): [0,2) pFilm | [2,5) colour | [5,5+NR) random parameters |
 // [5+NR, 5+NR+NF) features.  Everything else (stages, parity rules) is described in rpf_kernels.hip / DESIGN.md.
 
+// RPF_IMPL_SCHED 1 (the rpf_impl_*_sched_* translation units, inside a nested namespace `sched`; RPF_FLAG_SCHEDULE_FUSED, DESIGN.md
+// section 15e): the same part with stage 3c formed from PassParams::gain_c / gain_f (schedule_factor), and nothing a scheduled pass
+// does not launch -- the non-FAST filter_pixel_kernel instantiations of PHASE 0 and PHASE 4 (and, in part 1, the packed kernels); no
+// stage 1a, count or PHASE 2 / 3 kernels: those have no stage 3c, and the unscheduled parts launch them (impl_filter_*_phase)
+#ifndef RPF_IMPL_SCHED
+#define RPF_IMPL_SCHED 0
+#endif
+constexpr bool kSched = RPF_IMPL_SCHED != 0;
 constexpr int kNR = RPF_IMPL_NR;               // random-parameter columns
 constexpr int kNFeat = RPF_IMPL_NF;            // scene-feature columns
 constexpr int kColP = 0, kColC = 2, kColR = 5, kColF = 5 + kNR;
@@ -130,7 +138,7 @@ __device__ __forceinline__ void gather_weighted(const Window &w, uint32_t rel, f
     }
 }
 
-#if RPF_IMPL_PART == 1
+#if RPF_IMPL_PART == 1 && !RPF_IMPL_SCHED
 // ------------------------------------------------------------------------------------------------
 // stage 1a: per-pixel mean / std of the 12 features over the pixel's own S samples, sequential sums
 // (rpf.cpp:338-347, ops.h:111-144).  Output planes [12][H*W] so the filter kernel reads them with
@@ -213,7 +221,7 @@ __global__ __launch_bounds__(256) void pixel_stats_tile_kernel(PassParams p, uin
     }
 }
 
-#endif // RPF_IMPL_PART == 1
+#endif // RPF_IMPL_PART == 1 && !RPF_IMPL_SCHED
 
 template <int KD, int KW, int PACK5>
 __device__ __forceinline__ void store_bins(uint32_t *sBinW, int c, int lane, const BinIds<KW, PACK5> &b) {
@@ -1689,14 +1697,22 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
 #pragma unroll
         for (int i = 0; i < 3; ++i) wsum += sD9[i] / (sD9[i] + sD9[3 + i] + e); // rpf.cpp:470, 485
         const double wrc = wsum / 3;                                           // rpf.cpp:487
+#if RPF_IMPL_SCHED
+        const double alpha_c = schedule_factor(p.gain_c, Drc / (Drc + Dpc + e)); // clamp0(1 - g_c W_r^{c,k}): DESIGN.md 15a, the quotient of rpf.cpp:470
+#else
         const double alpha_c = 1 - Drc / (Drc + Dpc + e);                      // rpf.cpp:470, 475
+#endif
         double num; // what rpf.cpp:464 reads as D_f_ck[k] (3-element array indexed to 11: SURVEY F3)
         if (p.beta_map == RPF_BETA_PAPER) num = Dcf;
         else if (p.beta_map == RPF_BETA_REF_GCC11_O2) num = k < 3 ? sD9[6 + c] : (k < 8 ? 0.0 : sDrf[max(k - 8, 0)]);
         else num = k < 3 ? sD9[6 + c] : (k < 4 ? 0.0 : sDrf[max(k - 4, 0)]);
         const double Wc = num / den;                       // rpf.cpp:464
         const double Wr = Drf / (Drf + Dpf + e);           // rpf.cpp:465
+#if RPF_IMPL_SCHED
+        const double beta_k = schedule_factor(p.gain_f, Wr) * Wc; // clamp0(1 - g_f W_r^{f,k}) W_c^{f,k}: DESIGN.md 15a
+#else
         const double beta_k = (1 - Wr) * Wc;               // rpf.cpp:479
+#endif
         if (lane < kNFeat) {
             sBeta[lane] = beta_k;
             if (p.dbg.beta) p.dbg.beta[pix * kNFeat + lane] = beta_k;
@@ -2241,7 +2257,7 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
     }
 }
 
-#if RPF_IMPL_PART == 1 || RPF_IMPL_PART == 4
+#if (RPF_IMPL_PART == 1 || RPF_IMPL_PART == 4) && !RPF_IMPL_SCHED
 // ---- neighbourhood-size binning -----------------------------------------------------------------------------------
 // The cost and the LDS footprint of a pixel are set by its neighbourhood size N, and N is data dependent: box*box*S is
 // only its ceiling (path-traced buffers keep little more than the S own samples, SURVEY F10).  When the ceiling is above
@@ -2373,9 +2389,9 @@ __device__ __forceinline__ int membership_pixel_two_phase(const PassParams &p, i
     return n;
 }
 
-#endif // RPF_IMPL_PART == 1 || RPF_IMPL_PART == 4
+#endif // (RPF_IMPL_PART == 1 || RPF_IMPL_PART == 4) && !RPF_IMPL_SCHED
 
-#if RPF_IMPL_PART == 1
+#if RPF_IMPL_PART == 1 && !RPF_IMPL_SCHED
 // The pixels: every pixel of the slab (step 1, list null); the entries of `list` (its size read from *list_count: the
 // pixels stage 1a could not prove flat, rpf_kernels.hip prelist_kernel); or (step > 1: the route probe of the unbinned pass,
 // rpf_api.hip) the points of a lattice with that pitch, probe[0] += how many of them have N <= 64 without being proven flat,
@@ -2410,7 +2426,7 @@ __global__ __launch_bounds__(256) void nbhd_count_kernel(PassParams p, int step,
     }
 }
 
-#endif // RPF_IMPL_PART == 1
+#endif // RPF_IMPL_PART == 1 && !RPF_IMPL_SCHED
 
 #if RPF_IMPL_PART == 4
 // The count kernel of route 10: every pixel of the slab (the same walk, the same LDS) under the configured test on mt
@@ -2440,13 +2456,24 @@ hipError_t launch_filter_inst(const PassParams &p, const LdsLayout &L, unsigned 
 // the fp32 pair-weight variant (RPF_FLAG_FAST_WEIGHTS) is built for the reference layout only
 template <int K, bool TL, int NW>
 hipError_t launch_filter_w(const PassParams &p, const LdsLayout &L, unsigned grid, hipStream_t s) {
-    if constexpr (kRef19) {
+    if constexpr (kSched) { // the scheduled builds are fp64 only: check_schedule refuses gains with RPF_FLAG_FAST_WEIGHTS
+        return p.fast_weights ? hipErrorNotSupported : launch_filter_inst<K, TL, false, NW>(p, L, grid, s);
+    } else if constexpr (kRef19) {
         if (p.fast_weights) return launch_filter_inst<K, TL, true, NW>(p, L, grid, s);
     } else {
         if (p.fast_weights) return hipErrorNotSupported;
     }
     return launch_filter_inst<K, TL, false, NW>(p, L, grid, s);
 }
+#if RPF_IMPL_SCHED
+// PHASE 3 (chains) or PHASE 2 (weights) of the split route on the unscheduled part that holds class K's kernels: the entry points
+// of parts 2 and 3 below, declared by the scheduled translation unit in the layout's namespace
+template <int K>
+hipError_t unscheduled_phase(const PassParams &p, const LdsLayout &L, int phase, unsigned grid, hipStream_t s) {
+    if constexpr (K == 25) return impl_filter_mid_phase(p, L, phase, grid, s);
+    else return impl_filter_large_phase(p, L, phase, grid, s);
+}
+#endif
 template <int K>
 hipError_t launch_filter_k(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds,
                            unsigned grid, hipStream_t s) {
@@ -2456,11 +2483,20 @@ hipError_t launch_filter_k(const PassParams &p, const LdsLayout &L, const LdsLay
         if (L.nw == 4 && L2.total != 0 && L3.total != 0 && p.carry != nullptr && p.masks != nullptr && !p.fast_weights) {
             // (eight waves per pixel -- six producers, in case the chain waves were waiting for gathers -- measured SLOWER: 3840x270x32
             // chains 37.9 -> 50.6 ms; the kernel is bound by its dependent fp64 additions, not by the gathers)
+#if RPF_IMPL_SCHED
+            // PHASE 3 and PHASE 2 hold no stage 3c: the unscheduled part's kernels run around the scheduled PHASE 4
+            hipError_t e = unscheduled_phase<K>(p, L3, 3, grid, s);
+            if (e != hipSuccess) return e;
+            e = t_in_lds ? launch_filter_inst<K, true, false, 4, 4>(p, L, grid, s) : launch_filter_inst<K, false, false, 4, 4>(p, L, grid, s);
+            if (e != hipSuccess) return e;
+            return unscheduled_phase<K>(p, L2, 2, grid, s);
+#else
             hipError_t e = launch_filter_inst<K, false, false, 4, 3>(p, L3, grid, s);
             if (e != hipSuccess) return e;
             e = t_in_lds ? launch_filter_inst<K, true, false, 4, 4>(p, L, grid, s) : launch_filter_inst<K, false, false, 4, 4>(p, L, grid, s);
             if (e != hipSuccess) return e;
             return L2.nw == 2 ? launch_filter_inst<K, false, false, 2, 2>(p, L2, grid, s) : launch_filter_inst<K, false, false, 4, 2>(p, L2, grid, s);
+#endif
         }
     }
     if constexpr (K >= 13) {
@@ -2470,7 +2506,13 @@ hipError_t launch_filter_k(const PassParams &p, const LdsLayout &L, const LdsLay
     return t_in_lds ? launch_filter_w<K, true, 1>(p, L, grid, s) : launch_filter_w<K, false, 1>(p, L, grid, s);
 }
 
-// entry points of this layout and part (called from the dispatchers at the end of rpf_kernels.hip)
+// entry points of this layout and part (called from the dispatchers at the end of rpf_kernels.hip); a scheduled build (namespace
+// sched) names its own impl_filter_*_sched, and of part 1 emits the filter entry alone
+#if RPF_IMPL_SCHED
+#define impl_filter_small impl_filter_small_sched
+#define impl_filter_mid impl_filter_mid_sched
+#define impl_filter_large impl_filter_large_sched
+#endif
 #if RPF_IMPL_PART == 1
 hipError_t impl_filter_small(const PassParams &p, const LdsLayout &L, bool t_in_lds, unsigned grid, hipStream_t s) {
     const LdsLayout none{};
@@ -2482,6 +2524,7 @@ hipError_t impl_filter_small(const PassParams &p, const LdsLayout &L, bool t_in_
     default: return hipErrorInvalidValue;
     }
 }
+#if !RPF_IMPL_SCHED
 hipError_t impl_pixel_stats(const PassParams &p, uint64_t pix0, uint64_t pix1, hipStream_t s) {
     if (p.S >= 16 && p.S <= 128 && pix1 > pix0) { // (below 16 spp neighbouring threads share their cache lines: the plain kernel reads at full rate)
         const int PB = p.S <= 32 ? 256 : (p.S <= 64 ? 128 : 64);
@@ -2503,6 +2546,7 @@ hipError_t impl_nbhd_count(const PassParams &p, int step, uint32_t *probe, const
     hipLaunchKernelGGL(nbhd_count_kernel, dim3(grid), dim3(256), 0, s, p, step, probe, list, list_count);
     return hipGetLastError();
 }
+#endif // !RPF_IMPL_SCHED
 #elif RPF_IMPL_PART == 2
 hipError_t impl_filter_mid(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s) {
     switch (samples_per_lane(p.nmax)) {
@@ -2511,11 +2555,28 @@ hipError_t impl_filter_mid(const PassParams &p, const LdsLayout &L, const LdsLay
     default: return hipErrorInvalidValue;
     }
 }
+#if !RPF_IMPL_SCHED
+// one kernel of the split route alone, for the scheduled build of this part (RPF_IMPL_SCHED, which compiles PHASE 4 only): PHASE 3,
+// the chains, on L = lds_layout_chains, or PHASE 2, the weights, on L = lds_layout_weights (two or four waves: L.nw)
+hipError_t impl_filter_mid_phase(const PassParams &p, const LdsLayout &L, int phase, unsigned grid, hipStream_t s) {
+    if (samples_per_lane(p.nmax) != 25 || (phase != 2 && phase != 3)) return hipErrorInvalidValue;
+    if (phase == 3) return launch_filter_inst<25, false, false, 4, 3>(p, L, grid, s);
+    return L.nw == 2 ? launch_filter_inst<25, false, false, 2, 2>(p, L, grid, s) : launch_filter_inst<25, false, false, 4, 2>(p, L, grid, s);
+}
+#endif
 #elif RPF_IMPL_PART == 3
 hipError_t impl_filter_large(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s) {
     if (samples_per_lane(p.nmax) != 49) return hipErrorInvalidValue;
     return launch_filter_k<49>(p, L, L2, L3, t_in_lds, grid, s);
 }
+#if !RPF_IMPL_SCHED
+// (as impl_filter_mid_phase, for the K = 49 class)
+hipError_t impl_filter_large_phase(const PassParams &p, const LdsLayout &L, int phase, unsigned grid, hipStream_t s) {
+    if (samples_per_lane(p.nmax) != 49 || (phase != 2 && phase != 3)) return hipErrorInvalidValue;
+    if (phase == 3) return launch_filter_inst<49, false, false, 4, 3>(p, L, grid, s);
+    return L.nw == 2 ? launch_filter_inst<49, false, false, 2, 2>(p, L, grid, s) : launch_filter_inst<49, false, false, 4, 2>(p, L, grid, s);
+}
+#endif
 #elif RPF_IMPL_PART == 4
 hipError_t impl_nbhd_count_member(const PassParams &p, const double *mt, hipStream_t s) {
     if (p.row_end <= p.row_begin || mt == nullptr) return mt == nullptr ? hipErrorInvalidValue : hipSuccess;
@@ -2525,4 +2586,12 @@ hipError_t impl_nbhd_count_member(const PassParams &p, const double *mt, hipStre
 }
 #else
 #error "RPF_IMPL_PART must be 1, 2, 3 or 4"
+#endif
+#if RPF_IMPL_SCHED
+#undef impl_filter_small
+#undef impl_filter_mid
+#undef impl_filter_large
+#if RPF_IMPL_PART == 4
+#error "part 4 has no scheduled build: the count pass has no stage 3c"
+#endif
 #endif

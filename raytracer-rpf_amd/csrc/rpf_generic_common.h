@@ -267,14 +267,8 @@ __device__ __forceinline__ double beta_numerator(int beta_map, int k, int c, dou
     return k < 3 ? sD9[6 + c] : (k < 4 ? 0.0 : sDrf[max(k - 4, 0)]);
 }
 
-// ---- stage 3c under RPF_FLAG_SCHEDULE (kGenericSchedule): clamp0(1 - g * w), w one of the ratios W_r^{c,k} /
-// W_r^{f,k}.  The product and the difference are rounded once each (the TUs build with -ffp-contract=off); v < 0 is false for a
-// NaN, which therefore stays a NaN, and -0.0 stays -0.0
-__device__ __forceinline__ double schedule_factor(double g, double w) {
-    const double t = g * w;
-    const double v = 1 - t;
-    return (v < 0) ? 0.0 : v;
-}
+// ---- stage 3c under RPF_FLAG_SCHEDULE (kGenericSchedule): schedule_factor, clamp0(1 - g * w), is in
+// rpf_device_common.h -- the scheduled builds of the compiled kernels form alpha and beta with the same statement
 
 // ---- debug outputs: FNV-1a of the member list in order (window coordinates of each member), and of a column's bin ids ------
 __device__ __forceinline__ uint32_t member_hash(const uint32_t *list, int n, int x, int y, int b, int box, int S, int W) {

@@ -50,13 +50,20 @@ enum GenericBits : int32_t {
                               //   setup_pass uploads).  A full-box pass: route 9 whatever the bits above say (route_member_test); a
                               //   sampled pass stays route 8 and its count kernel runs the test; stage 1a is not affected
     kGenericSchedule = 512,   // RPF_FLAG_SCHEDULE on a pass whose entry has a gain other than 1 (setup_pass; never on a fused pass, which
-                              //   check_schedule refuses): stage 3c of the packed, one-wave, streaming and wide layout-generic kernels
+                              //   check_schedule refuses or, under RPF_FLAG_SCHEDULE_FUSED, marks kGenericScheduleFused instead): stage 3c of the packed, one-wave, streaming and wide layout-generic kernels
                               //   forms alpha and beta from PassParams::gain_c / gain_f; selects no route
     kGenericMemberFused = 1024, // RPF_FLAG_MEMBER_FUSED on a full-box pass of a call under RPF_FLAG_MEMBER_TEST that the compiled kernels can
                               //   take (setup_pass: a compiled layout without RPF_FLAG_GENERIC, not wide, no kGenericSchedule): route 10
                               //   (route_member_fused), the size-binned route behind the count kernel's MEMBER form.
                               //   Host-side only: no kernel reads it, and the compiled kernels read no bit of `generic`
+    kGenericScheduleFused = 2048, // RPF_FLAG_SCHEDULE_FUSED on a pass of the compiled kernels whose entry has a gain other than 1 (setup_pass:
+                              //   no layout-generic bit, or route 10): the pass runs the scheduled builds of those kernels
+                              //   (rpf_impl_*_sched_*.hip: launch_filter_pass and launch_filter_packed dispatch on it), which form alpha
+                              //   and beta from PassParams::gain_c / gain_f; its streaming class gets a copy of the params with
+                              //   kGenericSchedule in its place (scheduled_stream).  Host-side only, selects no route
 };
+// what routes a pass: its bits without the one that only picks the build of the compiled kernels
+inline int32_t route_bits(int32_t generic) { return generic & ~kGenericScheduleFused; }
 
 // everything one pass needs, passed by value to the kernels
 struct PassParams {
@@ -117,6 +124,14 @@ static_assert(sizeof(PassParams) == 368 && offsetof(PassParams, generic) == 40 &
 // the two fp32 pair-weight selections: the class kernels of routes 4 / 5 | the streaming and wide kernels, and every kernel of a wide pass
 inline bool class_fast(const PassParams &p) { return (p.generic & kGenericClassFast) != 0; }
 inline bool stream_fast(const PassParams &p) { return (p.generic & kGenericStreamFast) != 0; }
+// the params of the streaming class of a pass on the compiled kernels (generic::filter_pixel_kernel on routes 0 to 2, the wide
+// kernel on route 10): a scheduled pass hands them kGenericSchedule, the one bit of `generic` those kernels read (stage 3c), for
+// its host-side kGenericScheduleFused; the gains are in p already
+inline PassParams scheduled_stream(const PassParams &p) {
+    PassParams q = p;
+    if (q.generic & kGenericScheduleFused) q.generic = (q.generic & ~kGenericScheduleFused) | kGenericSchedule;
+    return q;
+}
 
 // Per-context tuning / diagnostic overrides (rpf_set_option).  Defaults = the library's own choices; nothing here is
 // read from the environment.  stage_mask != -1 skips stages (timing ablation: results are wrong) and is reported in

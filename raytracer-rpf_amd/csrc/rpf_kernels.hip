@@ -242,6 +242,12 @@ __global__ __launch_bounds__(256) void nbhd_reduce_kernel(const int32_t *nbhd, u
     hipError_t impl_nbhd_count(const PassParams &p, int step, uint32_t *probe, const uint32_t *list, const uint32_t *list_count, uint32_t list_max, hipStream_t s); \
     hipError_t impl_nbhd_count_member(const PassParams &p, const double *mt, hipStream_t s); \
     hipError_t impl_filter_packed(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s);    \
+    namespace sched { /* the scheduled builds (rpf_impl_*_sched_*.hip): a pass that carries kGenericScheduleFused */        \
+    hipError_t impl_filter_small_sched(const PassParams &p, const LdsLayout &L, bool t_in_lds, unsigned grid, hipStream_t s); \
+    hipError_t impl_filter_mid_sched(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
+    hipError_t impl_filter_large_sched(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
+    hipError_t impl_filter_packed_sched(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s); \
+    }                                                                                                                     \
     }
 RPF_DECLARE_IMPL(d19) // the reference's 19 dims (2 random parameters, 12 features), fp32 planes
 RPF_DECLARE_IMPL(d27) // BASELINE configs[4]: 27 dims (4 random parameters, 18 features), fp16 feature storage
@@ -411,6 +417,20 @@ hipError_t launch_filter_pass(const PassParams &p, const Tuning &tun, hipStream_
     const int K = samples_per_lane(p.nmax);
     const bool r19 = p.lay.is_ref19();
     if (K == 0) return hipErrorInvalidValue;
+    // a scheduled pass (kGenericScheduleFused: RPF_FLAG_SCHEDULE_FUSED, a gain other than 1) runs the scheduled builds of the same parts
+    const bool sc = (p.generic & kGenericScheduleFused) != 0;
+    const auto small = [&](const PassParams &q, unsigned g) {
+        if (sc) return r19 ? d19::sched::impl_filter_small_sched(q, L, t_in_lds, g, s) : d27::sched::impl_filter_small_sched(q, L, t_in_lds, g, s);
+        return r19 ? d19::impl_filter_small(q, L, t_in_lds, g, s) : d27::impl_filter_small(q, L, t_in_lds, g, s);
+    };
+    const auto mid = [&](const PassParams &q, unsigned g) {
+        if (sc) return r19 ? d19::sched::impl_filter_mid_sched(q, L, L2, L3, t_in_lds, g, s) : d27::sched::impl_filter_mid_sched(q, L, L2, L3, t_in_lds, g, s);
+        return r19 ? d19::impl_filter_mid(q, L, L2, L3, t_in_lds, g, s) : d27::impl_filter_mid(q, L, L2, L3, t_in_lds, g, s);
+    };
+    const auto large = [&](const PassParams &q, unsigned g) {
+        if (sc) return r19 ? d19::sched::impl_filter_large_sched(q, L, L2, L3, t_in_lds, g, s) : d27::sched::impl_filter_large_sched(q, L, L2, L3, t_in_lds, g, s);
+        return r19 ? d19::impl_filter_large(q, L, L2, L3, t_in_lds, g, s) : d27::impl_filter_large(q, L, L2, L3, t_in_lds, g, s);
+    };
     if (L2.total != 0 && tun.split_chunk > 0 && p.pix_list != nullptr && p.list_count > (uint32_t)tun.split_chunk) {
         // experiment (option "split_chunk"): the three launches of the split route over one chunk of the pixel list after the
         // other, so that a chunk's samples, masks and hand-over records are still in the 256 MiB Infinity Cache when the next
@@ -420,15 +440,14 @@ hipError_t launch_filter_pass(const PassParams &p, const Tuning &tun, hipStream_
             q.pix_list = p.pix_list + off;
             q.list_count = (p.list_count - off < (uint32_t)tun.split_chunk) ? p.list_count - off : (uint32_t)tun.split_chunk;
             const unsigned g = (unsigned)(((q.list_count + 7u) / 8u) * 8u);
-            const hipError_t e = K <= 25 ? (r19 ? d19::impl_filter_mid(q, L, L2, L3, t_in_lds, g, s) : d27::impl_filter_mid(q, L, L2, L3, t_in_lds, g, s))
-                                         : (r19 ? d19::impl_filter_large(q, L, L2, L3, t_in_lds, g, s) : d27::impl_filter_large(q, L, L2, L3, t_in_lds, g, s));
+            const hipError_t e = K <= 25 ? mid(q, g) : large(q, g);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
     }
-    if (K <= 8) return r19 ? d19::impl_filter_small(p, L, t_in_lds, grid, s) : d27::impl_filter_small(p, L, t_in_lds, grid, s);
-    if (K <= 25) return r19 ? d19::impl_filter_mid(p, L, L2, L3, t_in_lds, grid, s) : d27::impl_filter_mid(p, L, L2, L3, t_in_lds, grid, s);
-    return r19 ? d19::impl_filter_large(p, L, L2, L3, t_in_lds, grid, s) : d27::impl_filter_large(p, L, L2, L3, t_in_lds, grid, s);
+    if (K <= 8) return small(p, grid);
+    if (K <= 25) return mid(p, grid);
+    return large(p, grid);
 }
 
 int class_capacity(int c) {
@@ -449,6 +468,9 @@ hipError_t launch_nbhd_count_member(const PassParams &p, const double *member, h
 
 hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s) {
     if (!p.lay.supported()) return hipErrorNotSupported;
+    if (p.generic & kGenericScheduleFused) // a scheduled pass: the scheduled build of the packed kernels (rpf_impl_*_sched_small.hip)
+        return p.lay.is_ref19() ? d19::sched::impl_filter_packed_sched(p, lanes_per_pixel, count_dev, s)
+                                : d27::sched::impl_filter_packed_sched(p, lanes_per_pixel, count_dev, s);
     return p.lay.is_ref19() ? d19::impl_filter_packed(p, lanes_per_pixel, count_dev, s) : d27::impl_filter_packed(p, lanes_per_pixel, count_dev, s);
 }
 

@@ -442,8 +442,13 @@ __global__ __launch_bounds__(64 * kPkWaves, kRef19 ? 2 : 1) void filter_packed_k
         const double wrc = wsum / 3;                                          // rpf.cpp:487
         // lane t: colour channel t (alpha), features t, t + G, ...
         const int c3 = min(t, 2);
+#if RPF_IMPL_SCHED
+        const double alpha_c = schedule_factor(p.gain_c, (c3 == 0 ? Drc[0] : (c3 == 1 ? Drc[1] : Drc[2])) / // clamp0(1 - g_c W_r^{c,k}): DESIGN.md 15a
+                                       ((c3 == 0 ? Drc[0] : (c3 == 1 ? Drc[1] : Drc[2])) + (c3 == 0 ? Dpc[0] : (c3 == 1 ? Dpc[1] : Dpc[2])) + eps));
+#else
         const double alpha_c = 1 - (c3 == 0 ? Drc[0] : (c3 == 1 ? Drc[1] : Drc[2])) /
                                        ((c3 == 0 ? Drc[0] : (c3 == 1 ? Drc[1] : Drc[2])) + (c3 == 0 ? Dpc[0] : (c3 == 1 ? Dpc[1] : Dpc[2])) + eps); // rpf.cpp:470, 475
+#endif
         wsync(); // every lane has read its MI values
         if (t < 3 && gvalid) {
             sWg[t] = alpha_c;
@@ -479,7 +484,11 @@ __global__ __launch_bounds__(64 * kPkWaves, kRef19 ? 2 : 1) void filter_packed_k
             }
             const double Wc = num / den;                       // rpf.cpp:464
             const double Wr = Drf / (Drf + Dpf + eps);         // rpf.cpp:465
+#if RPF_IMPL_SCHED
+            const double beta_k = schedule_factor(p.gain_f, Wr) * Wc; // clamp0(1 - g_f W_r^{f,k}) W_c^{f,k}: DESIGN.md 15a
+#else
             const double beta_k = (1 - Wr) * Wc;               // rpf.cpp:479
+#endif
             if (gvalid) {
                 sWg[4 + k] = beta_k;
                 if (p.dbg.beta) p.dbg.beta[pix * kNFeat + k] = beta_k;
@@ -641,8 +650,13 @@ hipError_t launch_packed_inst(const PassParams &p, const uint32_t *count_dev, ui
 
 // entry point: pixels of p.pix_list with N <= lanes_per_pixel (8, 16, 32, 64); needs the acceptance masks and the N plane
 // (count pass, or filter_pixel_kernel's re-route).  count_dev != null: the list size is read on the device and
-// p.list_count is only its upper bound (sizes the grid)
-hipError_t impl_filter_packed(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s) {
+// p.list_count is only its upper bound (sizes the grid).  (A scheduled build, RPF_IMPL_SCHED: impl_filter_packed_sched)
+#if RPF_IMPL_SCHED
+hipError_t impl_filter_packed_sched(
+#else
+hipError_t impl_filter_packed(
+#endif
+const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s) {
     if (p.masks == nullptr || p.pix_list == nullptr || p.S > lanes_per_pixel) return hipErrorInvalidValue;
     switch (lanes_per_pixel) {
     case 8: return launch_packed_inst<8>(p, count_dev, p.list_count, s);

@@ -67,6 +67,12 @@ MEMBER_FUSED_FLAG = 65536
 # pass, MEMBER_TEST_FLAG) and DEGEN_EPS.  Selects no route.  RPF_FLAG_SCHEDULE of the header; the name stays outside the FLAG_*
 # family for SAMPLED_NBHD_FLAG's reason (tests/test_flag_table_cpu.py holds FLAG_* to eleven bits)
 SCHEDULE_FLAG = 8192
+# modifies SCHEDULE_FLAG: a permission, not a route.  A pass with a gain other than 1 that carries no
+# layout-generic bit runs on the route it takes with gains of 1 (0, 1 or 2) on the scheduled builds of the compiled kernels, and
+# under MEMBER_TEST_FLAG | MEMBER_FUSED_FLAG it takes route 10 instead of 9; every other pass runs as without it.  Refused without
+# SCHEDULE_FLAG, and with FLAG_FAST_WEIGHTS on such a pass (the scheduled builds are fp64).  RPF_FLAG_SCHEDULE_FUSED of the header;
+# the name stays outside the FLAG_* family for SAMPLED_NBHD_FLAG's reason (its table: tests/test_schedule_fused_cpu.py)
+SCHEDULE_FUSED_FLAG = 131072
 # modifies SAMPLED_NBHD_FLAG: a sampled pass may have S + draws <= SAMPLED_MAX instead of 832; pixels that end
 # with N > 832 go to a rest launch that reads their listed members (route 8 still); a pass with S + draws <= 832 runs as without it;
 # max_draws() tells the bound.  Refused without SAMPLED_NBHD_FLAG.  RPF_FLAG_SAMPLED_REST of the header; the name stays outside the

@@ -194,10 +194,10 @@ def metadata(path):
 
 def demangle_short(name):
     m = re.search(r"(d19|d27)(\d+)(\w+?)(I.*)?E?v?NS_", name)
-    ns = re.search(r"3rpf\d+(d19|d27|generic)", name)
+    ns = re.search(r"3rpf\d+(d19|d27|generic)(5sched)?", name)  # (d19::sched / d27::sched: the scheduled builds, RPF_IMPL_SCHED)
     k = re.search(r"kernelILi(\d+)ELb(\d)ELb(\d)ELi(\d)ELi(\d)E", name)
     base = re.search(r"\d+([a-z_]+kernel)", name)
-    s = (ns.group(1) + "::" if ns else "") + (base.group(1) if base else name[:60])
+    s = (ns.group(1) + "::" + ("sched::" if ns.group(2) else "") if ns else "") + (base.group(1) if base else name[:60])
     if k:
         s += "<K=%s,TL=%s,FAST=%s,NW=%s,PHASE=%s>" % k.groups()
     # the layout-generic kernels: the plane type, and FAST where a kernel has the fp32 stage-4 instantiation (RPF_FLAG_GENERIC_FAST)
