@@ -307,6 +307,31 @@ enum {
                                   answers the same way); a gain other than 1 on a pass of the compiled kernels together with
                                   RPF_FLAG_FAST_WEIGHTS (RPF_E_UNSUPPORTED: the scheduled builds are fp64 only); every refusal
                                   of RPF_FLAG_SCHEDULE stands (RPF_DEGEN_REF_ABORT with a gain other than 1 included). */
+    RPF_FLAG_SAMPLED_FUSED = 262144, /* opt-in, modifies RPF_FLAG_SAMPLED_NBHD: a sampled pass of the call runs on the compiled, fused
+                                  kernels behind a count kernel that leaves the draws as acceptance masks (route 11; DESIGN.md
+                                  section 13f) -- the second half of the size-binned route 2: the count kernel forms the draws
+                                  of route 8 (same key, same table, same discards), applies stage 1b's test (the configured one
+                                  under RPF_FLAG_MEMBER_TEST) and leaves N and one bit per accepted candidate of the window; the
+                                  pixels are dealt into the ten resident size classes, and the packed, one-wave and four-wave
+                                  compiled kernels rebuild their member lists from the masks.  A pass takes route 11 when it has
+                                  draws[p] > 0, the layout is one of the two compiled ones and the call is without
+                                  RPF_FLAG_GENERIC, box*box*S <= 65535 and option "wide" does not force it, S + draws[p] <= 3136
+                                  (the largest resident class; with more draws the pass needs RPF_FLAG_SAMPLED_REST and stays on
+                                  route 8), its mask stride is within option "sampled_fused_stride", and under RPF_FLAG_SCHEDULE
+                                  its entry's gains are both 1 or the call carries RPF_FLAG_SCHEDULE_FUSED (the pass then runs
+                                  the scheduled builds).  Every other pass of the call runs exactly as without this flag.
+                                  Membership, statistics and bin ids are route 8's bits; MI, alpha, beta, W_r_c and the colours
+                                  are those the compiled kernels give for that member list (route 2's kernels: the per-sample
+                                  stage-4 bars of the resident classes).  The kernels are sized from min(box*box*S, S + draws).
+                                  Options "packed", "waves_per_pixel", "split_weights", "table_in_lds" and "strip_w" act as on
+                                  route 2; "binning" has no effect.  redo_pixels is 0, filter_kernel_launches counts one launch
+                                  per non-empty class (the count kernel is not counted), sum_nbhd / max_nbhd / rpf_query_nbhd
+                                  report the sampled N.  Masks and lists are never re-used by a later pass (the draws change
+                                  with the pass id), and no member pool is allocated: the masks take
+                                  ceil((box*box - 1) * S / 64) * 8 bytes per pixel.  rpf_layout_kernels answers as for the word
+                                  without the flag; rpf_max_nbhd and rpf_max_draws do not read it.  Refused before any device
+                                  work: the flag without RPF_FLAG_SAMPLED_NBHD (RPF_E_UNSUPPORTED; rpf_layout_kernels answers
+                                  the same way); every refusal of RPF_FLAG_SAMPLED_NBHD stands with it. */
     RPF_FLAG_STREAM_FAST = 512/* opt-in, modifies RPF_FLAG_GENERIC and / or RPF_FLAG_WIDE_NBHD: the two kernels that walk a
                                   neighbourhood of any size with 256 threads -- the generic filter kernel (route 3, the rest
                                   list N > 64 / N > 832 of routes 4 / 5) and the wide kernel (route 6, the rest list N > 832 of
@@ -445,10 +470,16 @@ int32_t rpf_filter_ex(rpf_ctx *ctx, const rpf_desc *desc, const void *planes, co
  *   "wide_pool"        wide passes of a call with RPF_FLAG_WIDE_CLASSES: entries of the member pool at the first count
  *                      launch: -1 auto (default: 8 per pixel of the slab), else that many (a test hook: a pool the data
  *                      exceeds is grown to the exact size and the count launch repeated; same results bit for bit)
- * These names (but "wide" and "wide_pool") steer the fused routes only: a call with RPF_FLAG_GENERIC, with or without RPF_FLAG_GENERIC_PACKED, runs
+ *   "sampled_fused_stride"  sampled passes of a call with RPF_FLAG_SAMPLED_FUSED: the largest mask stride, in 64-bit words per
+ *                      pixel (ceil((box*box - 1) * S / 64)), at which such a pass takes route 11: -1 no bound (default), else 0 ..
+ *                      1024; a pass above the bound stays on route 8 and runs exactly as without the flag.  No effect without
+ *                      the flag (DESIGN.md section 13f has the measurements behind the default)
+ * These names (but "wide", "wide_pool" and "sampled_fused_stride") steer the fused routes only: a call with RPF_FLAG_GENERIC, with or without RPF_FLAG_GENERIC_PACKED, runs
  * the same kernels whatever they say (they are accepted and have no effect there; options_active still reports them).
  * rpf_counters.options_active tells whether a result was produced under any override. */
 int32_t rpf_set_option(rpf_ctx *ctx, const char *name, int64_t value);
+/* RPF_OK when rpf_set_option would take (name, value), RPF_E_BADARG otherwise.  Needs no context and no device. */
+int32_t rpf_check_option(const char *name, int64_t value);
 
 /* Page-locked host memory for the buffers handed to rpf_filter(): a feature producer that writes its samples straight
  * into such planes (instead of the reference's heap SamplingFilm, sample_film.cpp:6-43) gets full-rate DMA and real
@@ -505,7 +536,10 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *desc, int32_t box, c
  * wide kernel when some pixel has N > 832; RPF_DEGEN_REF_ABORT is refused, so redo_pixels is 0; sum_nbhd / max_nbhd are those
  * of the neighbourhoods the configured test leaves.
  * With RPF_FLAG_MEMBER_FUSED (route 10) such a pass counts as route 2 does: one launch per non-empty class of the eleven (the
- * class N > 3136 is the wide kernel's); redo_pixels is 0. */
+ * class N > 3136 is the wide kernel's); redo_pixels is 0.
+ * With RPF_FLAG_SAMPLED_FUSED (route 11) a sampled pass counts one launch per non-empty class of the ten resident ones (its count
+ * kernel is not counted, and no pixel reaches the streaming class); redo_pixels is 0; sum_nbhd / max_nbhd are those of the
+ * sampled neighbourhoods. */
 int32_t rpf_query_counters(rpf_ctx *ctx, rpf_counters *out);
 
 /* neighbourhood size N of every pixel (rpf.cpp:586: the neighbourhood vector's size) as the last pass of the most recent
@@ -526,6 +560,8 @@ int32_t rpf_query_nbhd(rpf_ctx *ctx, int32_t *nbhd_out, int64_t count);
  * kernel for N > 832; its member lists are the reference's only under the reference's multiples and floors),
  * 10 = such a pass under RPF_FLAG_MEMBER_FUSED on a compiled layout (count kernel with the configured test, then the compiled
  * kernels of route 2 by size class; the same member lists as route 9),
+ * 11 = a sampled pass under RPF_FLAG_SAMPLED_FUSED on a compiled layout (the draws' count kernel leaves acceptance masks, then
+ * the compiled kernels of route 2 by size class; the same member lists as route 8),
  * -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1.  rpf_filter's row-band
  * pipeline runs that probe once per band, on the rows of the slab that are resident by then -- the last band of a pass on the
  * whole slab -- so the answer after such a call is the serial call's (bands above the last may have taken the other of 0 / 1:

@@ -20,6 +20,7 @@ KERNEL_TUS += ["rpf_generic_wide.hip"]  # the wide layout-generic kernel: 65535 
 KERNEL_TUS += ["rpf_spike.hip"]  # the spike pass after the last filter pass: clamp, row sums, energy add (RPF_FLAG_SPIKE_CLAMP)
 KERNEL_TUS += ["rpf_generic_wide_count.hip"]  # ... and the count pass that deals a wide pass by size class (RPF_FLAG_WIDE_CLASSES)
 KERNEL_TUS += ["rpf_generic_sampled_count.hip"]  # the count pass of a sampled pass: the draws of a pixel's key (RPF_FLAG_SAMPLED_NBHD)
+KERNEL_TUS += ["rpf_generic_sampled_mask.hip"]  # ... and the count pass that leaves the draws as acceptance masks for the compiled kernels (RPF_FLAG_SAMPLED_FUSED)
 KERNEL_TUS += ["rpf_impl_d19_member.hip", "rpf_impl_d27_member.hip"]  # rpf_filter_impl.inc part 4: the count pass under the membership test (RPF_FLAG_MEMBER_FUSED)
 # ... and the scheduled builds of parts 1 to 3 (RPF_IMPL_SCHED: stage 3c from the entry's gains; RPF_FLAG_SCHEDULE_FUSED)
 KERNEL_TUS += ["rpf_impl_%s_sched_%s.hip" % (lay, part) for lay in ("d19", "d27") for part in ("small", "mid", "large")]
@@ -32,6 +33,7 @@ HEADERS = [os.path.join(_HERE, "csrc", "rpf_internal.h"), os.path.join(_HERE, "c
            os.path.join(_HERE, "csrc", "rpf_filter_impl.inc"), os.path.join(_HERE, "csrc", "rpf_packed_impl.inc"),
            os.path.join(_HERE, "csrc", "rpf_device_common.h"), os.path.join(_HERE, "csrc", "rpf_reflog.h"),
            os.path.join(_HERE, "csrc", "rpf_generic_common.h"),  # what the rpf_generic*.hip share
+           os.path.join(_HERE, "csrc", "rpf_generic_sampled_draws.h"),  # ... the draws of a sampled pass, which its two count TUs share
            os.path.join(_HERE, "csrc", "rpf_generic_stream_stages.inc"),  # ... and the stage bodies of rpf_generic.hip and rpf_generic_wide.hip
            os.path.join(_ROOT, "include", "rpf_hip.h")]
 
@@ -82,7 +84,7 @@ def _build(LIB, OBJ_DIR, defs, shipped, force, verbose):
         if force or _stale(obj, [src] + HEADERS):
             # -save-temps=obj keeps the device assembly next to the object: scripts/check_spills.py reads it below
             cmds.append([hipcc_path()] + flags + ["-save-temps=obj", "-c", src, "-o", obj])
-    # at most MAX_JOBS compilers at a time, 16 at the most (30 translation units: one hipcc each all at once oversubscribes a
+    # at most MAX_JOBS compilers at a time, 16 at the most (31 translation units: one hipcc each all at once oversubscribes a
     # machine that gives the build a share of its cores).  The largest units (the rpf_impl_* parts) start first
     jobs = max(1, min(16, int(os.environ.get("MAX_JOBS", 16))))
     cmds.sort(key=lambda c: not os.path.basename(c[-3]).startswith("rpf_impl_"))

@@ -46,6 +46,7 @@ struct FlagRule {
 };
 constexpr uint32_t kPackedRoute = RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED;
 constexpr FlagRule kFlagRules[] = {
+    {RPF_FLAG_SAMPLED_FUSED, RPF_FLAG_SAMPLED_NBHD, 0, 0, "RPF_FLAG_SAMPLED_FUSED without RPF_FLAG_SAMPLED_NBHD: the flag modifies the sampled route"},
     {RPF_FLAG_SCHEDULE_FUSED, RPF_FLAG_SCHEDULE, 0, 0, "RPF_FLAG_SCHEDULE_FUSED without RPF_FLAG_SCHEDULE: the flag modifies the per-pass schedule"},
     {RPF_FLAG_MEMBER_FUSED, RPF_FLAG_MEMBER_TEST, 0, 0, "RPF_FLAG_MEMBER_FUSED without RPF_FLAG_MEMBER_TEST: the flag modifies the membership-test route"},
     {RPF_FLAG_MEMBER_TEST, 0, 0, RPF_FLAG_FAST_WEIGHTS, "RPF_FLAG_MEMBER_TEST with RPF_FLAG_FAST_WEIGHTS: passes under the membership test are fp64 throughout"},
@@ -440,6 +441,19 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
                               !(p.generic & no_fused) && p.nmax <= kMaxNbhd;
     if (member_fused) p.generic |= kGenericMemberFused;
     if (member_fused && (p.generic & kGenericSchedule)) p.generic = (p.generic & ~kGenericSchedule) | kGenericScheduleFused;
+    // RPF_FLAG_SAMPLED_FUSED (route 11): a sampled pass that the compiled kernels can take behind the draws'
+    // mask kernel -- a compiled layout without RPF_FLAG_GENERIC, not wide, S + draws within the largest resident class (the
+    // streaming class repeats a full-box stage 1b and cannot read a sampled list: it is empty by construction), no gain other than
+    // 1 unless RPF_FLAG_SCHEDULE_FUSED hands the pass to the scheduled builds, and a mask stride within option
+    // "sampled_fused_stride".  Every other sampled pass stays on route 8 with the bits it had
+    const int64_t window_words = std::max<int64_t>(1, ((int64_t)(box * box - 1) * d->S + 63) / 64);
+    const int32_t no_sampled_fused = kGenericOn | kGenericWide | ((d->flags & RPF_FLAG_SCHEDULE_FUSED) ? 0 : kGenericSchedule);
+    const bool sampled_fused = (d->flags & RPF_FLAG_SAMPLED_FUSED) && (p.generic & kGenericSampled) && p.lay.supported() &&
+                               !(p.generic & no_sampled_fused) && p.nmax <= kMaxNbhd &&
+                               (int64_t)d->S + ctx->samp_now.draws <= kMaxResident &&
+                               (ctx->tun.sampled_fused_stride < 0 || window_words <= ctx->tun.sampled_fused_stride);
+    if (sampled_fused) p.generic |= kGenericSampledFused;
+    if (sampled_fused && (p.generic & kGenericSchedule)) p.generic = (p.generic & ~kGenericSchedule) | kGenericScheduleFused;
     p.sigma_p = (double)(box / 4); // rpf.cpp:531: integer division
     p.plane_stride = (uint64_t)d->W * d->H * d->S;
     p.planes = d_planes; p.col_in = col_in; p.col_out = col_out;
@@ -460,7 +474,10 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
     if ((st = ctx->d_flat.ensure(ctx, HW))) return st;
     p.flat = ctx->d_flat; p.nan_flag = ctx->d_nan_flag;
     if (dbg_dev) p.dbg = *dbg_dev;
-    if (member_fused) { // the largest resident kernel of the pass, as on route 2, and -- its streaming class -- the wide kernel's carve-up
+    if (sampled_fused) { // the largest resident kernel of the pass: no list is longer than S + draws, whatever the window holds
+        const int nres = (int)std::min<int64_t>(p.nmax, (int64_t)d->S + ctx->samp_now.draws), bres = bmax_of(nres);
+        out.lds = lds_layout(p.S, nres, bres, table_in_lds(p.S, nres, bres, ctx->tun, p.lay), ctx->tun, p.lay).total;
+    } else if (member_fused) { // the largest resident kernel of the pass, as on route 2, and -- its streaming class -- the wide kernel's carve-up
         const int nres = std::min(p.nmax, kMaxResident), bres = bmax_of(nres);
         out.lds = lds_layout(p.S, nres, bres, table_in_lds(p.S, nres, bres, ctx->tun, p.lay), ctx->tun, p.lay).total;
         if (p.nmax > kMaxResident) out.lds = std::max(out.lds, generic_wide_carve(p.lay, p.nmax, false).total);
@@ -1030,11 +1047,9 @@ int32_t rpf_host_free(rpf_ctx *ctx, void *ptr) { // ctx may be NULL (a buffer ca
     return RPF_OK;
 }
 
-int32_t rpf_set_option(rpf_ctx *ctx, const char *name, int64_t value) {
-    if (!ctx) return RPF_E_BADARG;
-    if (!name) return fail(ctx, RPF_E_BADARG, "option name is NULL");
-    const std::string n(name);
-    Tuning &t = ctx->tun;
+namespace {
+// one (name, value) of rpf_set_option applied to t: false for an unknown name or a value outside its range (t is then unchanged)
+bool apply_option(Tuning &t, const std::string &n, int64_t value) {
     if (n == "stage_mask") t.stage_mask = (int32_t)value;
     else if (n == "binning" && value >= -1 && value <= 1) t.binning = (int32_t)value;
     else if (n == "waves_per_pixel" && (value == 0 || value == 1 || value == 4)) t.waves_per_pixel = (int32_t)value;
@@ -1045,12 +1060,29 @@ int32_t rpf_set_option(rpf_ctx *ctx, const char *name, int64_t value) {
     else if (n == "packed" && value >= -1 && value <= 1) t.packed = (int32_t)value;
     else if (n == "wide" && (value == -1 || value == 1)) t.wide = (int32_t)value;
     else if (n == "wide_pool" && value >= -1 && value <= ((int64_t)1 << 40)) t.wide_pool = value;
+    else if (n == "sampled_fused_stride" && value >= -1 && value <= 1024) t.sampled_fused_stride = (int32_t)value;
     else if (n == "split_chunk" && value >= 0 && value <= (1 << 30)) t.split_chunk = (int32_t)value;
     else if (n == "count_first" && value >= -1 && value <= 1) t.count_first = (int32_t)value;
     else if (n == "lds_pad" && value >= 0 && value <= 160 * 1024) t.lds_pad = (int32_t)value;
-    else return fail(ctx, RPF_E_BADARG, "unknown option or value out of range: " + n);
+    else return false;
+    return true;
+}
+} // namespace
+
+int32_t rpf_set_option(rpf_ctx *ctx, const char *name, int64_t value) {
+    if (!ctx) return RPF_E_BADARG;
+    if (!name) return fail(ctx, RPF_E_BADARG, "option name is NULL");
+    const std::string n(name);
+    if (!apply_option(ctx->tun, n, value)) return fail(ctx, RPF_E_BADARG, "unknown option or value out of range: " + n);
     ctx->bin_valid = false;
     return RPF_OK;
+}
+
+// whether rpf_set_option would take the pair; needs no context and no device (like rpf_layout_kernels)
+int32_t rpf_check_option(const char *name, int64_t value) {
+    if (!name) return RPF_E_BADARG;
+    Tuning t;
+    return apply_option(t, name, value) ? RPF_OK : RPF_E_BADARG;
 }
 
 int32_t rpf_filter(rpf_ctx *ctx, const rpf_desc *d, const void *planes, const float *ray_weight,

@@ -1,6 +1,7 @@
 // rpf_api_routes.hip -- the pass router of the C ABI: route_pass, which runs one filter pass on the route its flags, its sizes
 // and the options pick, and what only the routes use -- the slot rules of the streaming and wide kernels, the redo list, the
-// class launches, and count_and_deal, the one count-and-deal step of the listed-member routes 7, 8 and 9.  Host code only;
+// class launches, count_and_deal, the one count-and-deal step of the listed-member routes 7, 8 and 9, and binned_params /
+// deal_classes / filter_classes, the steps the routes behind a mask-leaving count pass share (2, 10 and 11).  Host code only;
 // rpf_api.hip prepares a pass (setup_pass) and calls route_pass from its pass loops.
 #include <hip/hip_runtime.h>
 
@@ -220,20 +221,15 @@ int32_t route_unbinned(rpf_ctx *ctx, const PassParams &p, bool packed, hipStream
     return launch_redo(ctx, p, s, launches);
 }
 
-// The size-binned route: the neighbourhood sizes are counted first, then every kernel family filters the list of its class.
-// member: null on route 2; the uploaded table on route 10 (route_member_fused below; DESIGN.md section 14e), the same structure
-// with three differences.  The count launch is the MEMBER form of nbhd_count_kernel, which gets stage 1a's flat plane only when
-// the flat proof is sound under the table (every floor below n_feat negative).  The streaming class N > 3136 repeats stage 1b,
-// so it runs on the kernel that does so under the same test: the wide kernel's MEMBER instantiation over the class's list, route
-// 9's rest launch (launch_wide: the 2^-44 table where that is exact, kWideSlots).  The membership cache is keyed by whose masks
-// it holds (bin_member): a route-10 pass is served by a route-10 pass only, a route-2 pass by a route-2 pass only.
-int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, const double *member, hipStream_t s, int *launches) {
+// What the passes that run the compiled class kernels behind a count pass share (routes 2, 10 and 11): the buffers, the deal and
+// the class loop.  binned_params: p's copy with the class lists, the acceptance masks (one u64 per 64 candidates of the window,
+// which the count pass keeps so that the filter kernels only rebuild the list) and, where the 32- / 64-spp classes run as three
+// kernels, the hand-over buffer.
+int32_t binned_params(rpf_ctx *ctx, const PassParams &p, PassParams &pc) {
     const size_t HW = (size_t)p.W * p.H;
     int32_t st;
-    ctx->last_route = member ? kRouteMemberFused : kRouteBinned;
     if ((st = ctx->d_lists.ensure(ctx, (size_t)kNumClasses * HW * sizeof(uint32_t)))) return st;
-    // the count pass keeps its acceptance masks (one u64 per 64 candidates) so the filter kernels only rebuild the list
-    PassParams pc = p;
+    pc = p;
     pc.mask_stride = mask_stride(p);
     if ((st = ctx->d_masks.ensure(ctx, HW * pc.mask_stride * sizeof(uint64_t)))) return st;
     pc.masks = ctx->d_masks;
@@ -243,36 +239,27 @@ int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, const doubl
         if ((st = ctx->d_carry.ensure(ctx, HW * (size_t)kCarryStride * sizeof(double)))) return st;
         pc.carry = ctx->d_carry;
     }
-    uint32_t counts[kNumClasses];
-    if (ctx->bin_valid && ctx->bin_member == (member != nullptr) && ctx->bin_box == p.box && ctx->bin_r0 == p.row_begin && ctx->bin_r1 == p.row_end) {
-        std::memcpy(counts, ctx->bin_counts, sizeof(counts));
-    } else {
-        Range rg(member ? "rpf:count + classify (configured membership test, size classes)" : "rpf:count + classify (stage 1b test, size classes)");
-        ctx->bin_valid = false;
-        ctx->bin_member = member != nullptr;
-        HIP_TRY(hipMemsetAsync(ctx->d_class_counts, 0, kNumClasses * sizeof(uint32_t), s));
-        if (member) {
-            // p.flat says "some feature has sigma * 3 == 0 and a finite mean": N = S under the configured test exactly where that
-            // feature's floor is negative, and the plane does not say which feature it was
-            PassParams pm = pc;
-            bool sound = ctx->flat_fresh;
-            for (int k = 0; k < p.lay.nF; ++k) sound = sound && ctx->membership.floor[k] < 0.0;
-            if (!sound) pm.flat = nullptr;
-            HIP_TRY(launch_nbhd_count_member(pm, member, s));
-        } else {
-            HIP_TRY(launch_nbhd_count(pc, 1, nullptr, nullptr, nullptr, 0, s));
-        }
-        HIP_TRY(launch_classify(pc, ctx->d_lists, ctx->d_class_counts, kNumClasses, -1, s));
-        HIP_TRY(hipMemcpyAsync(counts, ctx->d_class_counts, sizeof(counts), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        std::memcpy(ctx->bin_counts, counts, sizeof(counts));
-        ctx->bin_box = p.box; ctx->bin_r0 = p.row_begin; ctx->bin_r1 = p.row_end;
-        ctx->bin_valid = true;
-    }
+    return RPF_OK;
+}
+
+// ... the deal behind the count launch (d_class_counts zeroed ahead of it): the pixels into the eleven class lists by the N the
+// count pass left, and the list sizes read back (one synchronisation of s)
+int32_t deal_classes(rpf_ctx *ctx, const PassParams &pc, uint32_t counts[kNumClasses], hipStream_t s) {
+    HIP_TRY(launch_classify(pc, ctx->d_lists, ctx->d_class_counts, kNumClasses, -1, s));
+    HIP_TRY(hipMemcpyAsync(counts, ctx->d_class_counts, kNumClasses * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return RPF_OK;
+}
+
+// ... and one launch per non-empty class, then the redo launch.  member: route 10's table (its streaming class is the wide
+// kernel's), else null
+int32_t filter_classes(rpf_ctx *ctx, const PassParams &pc, bool packed, const double *member, const uint32_t counts[kNumClasses],
+                       hipStream_t s, int *launches) {
+    int32_t st;
     // the four-wave kernels keep one acceptance mask per 64 candidates of the WINDOW in a 64-entry LDS array: windows
     // beyond 4096 candidates (boxes 17 and up) run their resident classes on the one-wave instantiations
     Tuning tun = ctx->tun;
-    if ((int64_t)(p.box * p.box - 1) * p.S > 4096) tun.waves_per_pixel = 1;
+    if ((int64_t)(pc.box * pc.box - 1) * pc.S > 4096) tun.waves_per_pixel = 1;
     for (int c = 0; c < kNumClasses; ++c) {
         if (counts[c] == 0) continue;
         static const char *const kClassName[kNumClasses] = {
@@ -298,6 +285,45 @@ int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, const doubl
         if (launches) ++*launches;
     }
     return launch_redo(ctx, pc, s, launches);
+}
+
+// The size-binned route: the neighbourhood sizes are counted first, then every kernel family filters the list of its class.
+// member: null on route 2; the uploaded table on route 10 (route_member_fused below; DESIGN.md section 14e), the same structure
+// with three differences.  The count launch is the MEMBER form of nbhd_count_kernel, which gets stage 1a's flat plane only when
+// the flat proof is sound under the table (every floor below n_feat negative).  The streaming class N > 3136 repeats stage 1b,
+// so it runs on the kernel that does so under the same test: the wide kernel's MEMBER instantiation over the class's list, route
+// 9's rest launch (launch_wide: the 2^-44 table where that is exact, kWideSlots).  The membership cache is keyed by whose masks
+// it holds (bin_member): a route-10 pass is served by a route-10 pass only, a route-2 pass by a route-2 pass only.
+int32_t route_binned(rpf_ctx *ctx, const PassParams &p, bool packed, const double *member, hipStream_t s, int *launches) {
+    int32_t st;
+    ctx->last_route = member ? kRouteMemberFused : kRouteBinned;
+    PassParams pc;
+    if ((st = binned_params(ctx, p, pc))) return st;
+    uint32_t counts[kNumClasses];
+    if (ctx->bin_valid && ctx->bin_member == (member != nullptr) && ctx->bin_box == p.box && ctx->bin_r0 == p.row_begin && ctx->bin_r1 == p.row_end) {
+        std::memcpy(counts, ctx->bin_counts, sizeof(counts));
+    } else {
+        Range rg(member ? "rpf:count + classify (configured membership test, size classes)" : "rpf:count + classify (stage 1b test, size classes)");
+        ctx->bin_valid = false;
+        ctx->bin_member = member != nullptr;
+        HIP_TRY(hipMemsetAsync(ctx->d_class_counts, 0, kNumClasses * sizeof(uint32_t), s));
+        if (member) {
+            // p.flat says "some feature has sigma * 3 == 0 and a finite mean": N = S under the configured test exactly where that
+            // feature's floor is negative, and the plane does not say which feature it was
+            PassParams pm = pc;
+            bool sound = ctx->flat_fresh;
+            for (int k = 0; k < p.lay.nF; ++k) sound = sound && ctx->membership.floor[k] < 0.0;
+            if (!sound) pm.flat = nullptr;
+            HIP_TRY(launch_nbhd_count_member(pm, member, s));
+        } else {
+            HIP_TRY(launch_nbhd_count(pc, 1, nullptr, nullptr, nullptr, 0, s));
+        }
+        if ((st = deal_classes(ctx, pc, counts, s))) return st;
+        std::memcpy(ctx->bin_counts, counts, sizeof(counts));
+        ctx->bin_box = p.box; ctx->bin_r0 = p.row_begin; ctx->bin_r1 = p.row_end;
+        ctx->bin_valid = true;
+    }
+    return filter_classes(ctx, pc, packed, member, counts, s, launches);
 }
 
 // The layout-generic route (RPF_FLAG_GENERIC): one launch per pass, every neighbourhood size on the same kernel; member
@@ -491,6 +517,44 @@ int32_t route_sampled(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *
     return RPF_OK;
 }
 
+// A sampled pass under RPF_FLAG_SAMPLED_FUSED on a compiled layout (route 11): the size-binned route's deal
+// and class loop behind generic::sampled_count_mask_kernel, which leaves N and the acceptance masks of the draws route 8 lists.  A
+// sampled neighbourhood is an acceptance mask over the window with few bits set, so the compiled packed, one-wave and four-wave
+// kernels rebuild route 8's member lists from the masks as they do on route 2.  No list is longer than S + draws: the kernels are
+// sized from min(box*box*S, S + draws), setup_pass admits S + draws <= 3136 only, and a non-empty streaming class -- it would
+// repeat a full-box stage 1b -- is an internal error.  Under RPF_FLAG_MEMBER_TEST the draws meet the configured test, as on route
+// 8.  REF_ABORT is refused on a sampled pass, so there is no redo list.  The masks and lists of this pass are no other pass's
+// (its draws change with the pass id): route_pass dropped the membership cache before it ran, and it sets none.
+int32_t route_sampled_fused(rpf_ctx *ctx, const PassParams &p_in, bool packed, hipStream_t s, int *launches) {
+    int32_t st;
+    ctx->last_route = kRouteSampledFused;
+    PassParams p = p_in;
+    p.redo_list = nullptr; p.redo_count = nullptr;
+    if (p.row_end <= p.row_begin) return RPF_OK;
+    const SampledPass sp = ctx->samp_now;
+    if (sp.draws < 1 || sp.draws > sp.max_draws || !ctx->d_samp_table || ctx->samp_table_box != p.box || !p.lay.supported() ||
+        p.nmax > kMaxNbhd || (int64_t)p.S + sp.draws > kMaxResident)
+        return fail(ctx, RPF_E_BADARG, "sampled pass without its configuration (setup_pass prepares it)");
+    generic::SampledCountArgs a = {ctx->d_samp_table, ctx->sampling.seed, sp.pass_id, ctx->sampling.row_origin, sp.draws};
+    if (p.generic & kGenericMemberTest) { // with RPF_FLAG_MEMBER_TEST the draws meet the configured test
+        if (!ctx->d_member || !ctx->member_fresh) return fail(ctx, RPF_E_BADARG, "pass under the membership test without its configuration (setup_pass prepares it)");
+        a.member = ctx->d_member;
+    }
+    p.nmax = (int32_t)std::min<int64_t>(p.nmax, (int64_t)p.S + sp.draws); // the longest list of the pass sizes its kernels
+    p.bmax = bmax_of(p.nmax);
+    PassParams pc;
+    if ((st = binned_params(ctx, p, pc))) return st;
+    uint32_t counts[kNumClasses];
+    {
+        Range rg("rpf:sampled count + classify (draws, stage 1b test, acceptance masks, size classes)");
+        HIP_TRY(hipMemsetAsync(ctx->d_class_counts, 0, kNumClasses * sizeof(uint32_t), s));
+        HIP_TRY(generic::launch_sampled_count_mask(pc, a, s));
+        if ((st = deal_classes(ctx, pc, counts, s))) return st;
+    }
+    if (counts[kNumClasses - 1] != 0) return fail(ctx, RPF_E_HIP, "sampled count pass: a pixel with N > 3136");
+    return filter_classes(ctx, pc, packed, nullptr, counts, s, launches);
+}
+
 // Routes 4 and 5, the layout-generic route with its small neighbourhoods on class kernels (RPF_FLAG_GENERIC |
 // RPF_FLAG_GENERIC_PACKED on a pass with S <= 64; ... | RPF_FLAG_GENERIC_WAVE on one with S <= 832): stage 1b as its own launch
 // (generic::nbhd_count_kernel: N and the acceptance masks), the pixels dealt by N into n_classes classes -- four lane classes
@@ -534,6 +598,7 @@ int32_t route_generic_classes(rpf_ctx *ctx, const PassParams &p_in, int n_classe
 // Which layout-generic route a pass takes (kRouteNone: none, a pass on the compiled kernels).  Above 64 spp N >= S fits no
 // packed class, above 832 spp no one-wave class: such a pass runs as route 3 does.
 Route generic_route(const PassParams &p) {
+    if (p.generic & kGenericSampledFused) return kRouteSampledFused; // (... a sampled pass the compiled kernels take under RPF_FLAG_SAMPLED_FUSED)
     if (p.generic & kGenericSampled) return kRouteSampled; // (setup_pass marked it: draws > 0)
     if (p.generic & kGenericMemberFused) return kRouteMemberFused; // (... a full-box pass the compiled kernels take under RPF_FLAG_MEMBER_FUSED)
     if (p.generic & kGenericMemberTest) return kRouteMemberTest; // (... a full-box pass of a call under RPF_FLAG_MEMBER_TEST)
@@ -567,14 +632,15 @@ int32_t route_pass(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *lau
     if (route == kRouteNone && p.nmax > kMaxResident) bin = true; // the streaming kernel takes the pixels no resident kernel can hold
     // The membership cache of the size-binned route (bin_valid: the class counts on the host, d_lists and d_masks on the device)
     // outlives a pass only from one size-binned pass to the next: route_binned alone sets it, and every other route drops it
-    // here, before it runs -- the unbinned route with its packed lists, routes 4 and 5 and the listed-member routes 7, 8 and 9
-    // write their own lists, masks and class counts into the same buffers.  Route 10 is route_binned under another test: it keeps
+    // here, before it runs -- the unbinned route with its packed lists, routes 4 and 5, the listed-member routes 7, 8 and 9 and
+    // route 11 write their own lists, masks and class counts into the same buffers.  Route 10 is route_binned under another test: it keeps
     // the cache, keyed by bin_member, so that neither of routes 2 and 10 is served the other's masks
     if (!bin && route != kRouteMemberFused) ctx->bin_valid = false;
     // small neighbourhoods (N <= 64) run on the packed kernels, several pixels per wave (rpf_packed_impl.inc); option "packed"
     const bool packed = ctx->tun.packed != 0 && !p.fast_weights && ctx->tun.stage_mask == -1 && ctx->tun.lds_pad == 0;
     switch (route) {
     case kRouteMemberFused: return route_member_fused(ctx, p, packed, s, launches);
+    case kRouteSampledFused: return route_sampled_fused(ctx, p, packed, s, launches);
     case kRouteSampled: return route_sampled(ctx, p, s, launches);
     case kRouteMemberTest: return route_member_test(ctx, p, s, launches);
     case kRouteWideClasses: return route_wide_classes(ctx, p, nullptr, s, launches);

@@ -1,5 +1,6 @@
 // rpf_generic_common.h -- what the layout-generic translation units share (rpf_generic.hip, rpf_generic_packed.hip,
-// rpf_generic_wave.hip, rpf_generic_wide.hip, rpf_generic_wide_count.hip, rpf_generic_sampled_count.hip; routes 3 to 9).  Only they include it.  Device
+// rpf_generic_wave.hip, rpf_generic_wide.hip, rpf_generic_wide_count.hip, rpf_generic_sampled_count.hip, rpf_generic_sampled_mask.hip;
+// routes 3 to 9 and the count pass of route 11).  Only they include it.  Device
 // code has internal linkage, like rpf_device_common.h: each TU carries its own copy.
 //
 // For every TU: the column counts of a layout (GenericDims), up16 and the size of the fp64 block of the LDS carve-ups (host side), the

@@ -27,7 +27,7 @@
 // an entry is written at or below the index it was read from, behind a barrier that follows every read of the step, and the last
 // key of a step is handed to the next in a register, since the slot it stood in may have been written.  One cursor reservation per
 // pixel (publish_members_block).  LDS: P words + the threshold table + six words, 34840 bytes at P = 8192 (dynamic, sized at launch).
-#include "rpf_generic_common.h"
+#include "rpf_generic_sampled_draws.h"
 
 #include <algorithm>
 
@@ -36,25 +36,7 @@ namespace generic {
 namespace {
 
 constexpr int kScCap = 832;            // the largest class of the one-wave kernels: S + D <= kScCap
-constexpr int kScTable = 512;          // room for the box - 1 thresholds (box <= 511: box*box*S <= 262144)
-constexpr uint32_t kScNone = ~0u;      // a discarded draw
-constexpr uint64_t kScG = 0x9E3779B97F4A7C15ull;
-
-__device__ __forceinline__ uint64_t sc_mix(uint64_t z) { // the SplitMix64 finaliser
-    z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-    z ^= z >> 27; z *= 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    return z;
-}
-// #{k < n : t[k] <= u} of a non-decreasing table
-__device__ __forceinline__ int sc_count_le(const uint32_t *t, int n, uint32_t u) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (t[mid] <= u) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
+// (kScTable, kScNone, sc_mix, sc_count_le, sc_pixel_key and sc_draw: rpf_generic_sampled_draws.h, shared with route 11's count kernel)
 
 struct SampledCountOut {
     MemberPool m;                // base: of a pixel with N > S
@@ -63,28 +45,6 @@ struct SampledCountOut {
     int32_t pass_id, row_origin, draws;
     const double *member;        // MEMBER: mult[RPF_MAX_NDIM] | floor[RPF_MAX_NDIM]; the other instantiation does not read it
 };
-
-// ---- the statements the two count kernels share: the key of pixel (x, y) and draw q of it -----------------
-__device__ __forceinline__ uint64_t sc_pixel_key(const SampledCountOut &o, int x, int y) {
-    uint64_t h = sc_mix(o.seed + kScG);
-    h = sc_mix(h ^ (uint64_t)(uint32_t)o.pass_id);
-    h = sc_mix(h ^ (uint64_t)((uint32_t)o.row_origin + (uint32_t)y)); // (mod 2^32)
-    return sc_mix(h ^ (uint64_t)(uint32_t)x);
-}
-// the visiting-order index qq of draw q in the window of (x, y), kScNone for a draw that is discarded (off the image, the centre)
-__device__ __forceinline__ uint32_t sc_draw(uint64_t h, int q, const uint32_t *sT, int nT, const Window &win, int x, int y, int b, int W, int H,
-                                            int S) {
-    const uint64_t r = sc_mix(h + (uint64_t)(q + 1) * kScG), r2 = sc_mix(r ^ kScG);
-    const int xn = x + sc_count_le(sT, nT, (uint32_t)r) - b, yn = y + sc_count_le(sT, nT, (uint32_t)(r >> 32)) - b;
-    const int s = (int)(((uint64_t)(uint32_t)r2 * (uint32_t)S) >> 32);
-    uint32_t qq = kScNone;
-    if (xn >= 0 && xn < W && yn >= 0 && yn < H && !(xn == x && yn == y)) {
-        int cell = (xn - win.x0) * win.nyv + (yn - win.y0);
-        if (cell > win.centre_rank) --cell; // candidate_offset's numbering skips the centre
-        qq = (uint32_t)(cell * S + s);
-    }
-    return qq;
-}
 
 // One wave per pixel of rows [row_begin, row_end).  MEMBER (with RPF_FLAG_MEMBER_TEST): the draws meet
 // passes_member_wave instead of the 3-sigma test, and nothing else differs; the first instantiation is the code it was.

@@ -61,6 +61,11 @@ enum GenericBits : int32_t {
                               //   (rpf_impl_*_sched_*.hip: launch_filter_pass and launch_filter_packed dispatch on it), which form alpha
                               //   and beta from PassParams::gain_c / gain_f; its streaming class gets a copy of the params with
                               //   kGenericSchedule in its place (scheduled_stream).  Host-side only, selects no route
+    kGenericSampledFused = 4096, // RPF_FLAG_SAMPLED_FUSED on a pass that carries kGenericSampled and that the compiled kernels can take
+                              //   (setup_pass: a compiled layout without RPF_FLAG_GENERIC, not wide, S + draws <= kMaxResident, no
+                              //   kGenericSchedule, option "sampled_fused_stride"): route 11 (route_sampled_fused),
+                              //   the size-binned route's class kernels behind generic::sampled_count_mask_kernel.  generic_route looks at
+                              //   it before kGenericSampled.  Host-side only: no kernel reads it
 };
 // what routes a pass: its bits without the one that only picks the build of the compiled kernels
 inline int32_t route_bits(int32_t generic) { return generic & ~kGenericScheduleFused; }
@@ -149,8 +154,9 @@ struct Tuning {
     int32_t count_first = -1;    // box*box*S <= 512: stage 1b as its own launch ahead of the filter kernels (the small-N route): -1 auto (probe), 0 off, 1 on; same results
     int32_t wide = -1;           // RPF_FLAG_WIDE_NBHD: -1 auto (passes with box*box*S > 65535 on the wide kernel), 1 every pass of such a call (test hook)
     int32_t packed = -1;         // small neighbourhoods (N <= 64) on the packed kernels, several pixels per wave: -1 auto (on), 0 off, 1 on
+    int32_t sampled_fused_stride = -1; // RPF_FLAG_SAMPLED_FUSED: the largest mask stride (u64 words per pixel, ceil((box*box - 1) * S / 64)) at which a sampled pass takes route 11: -1 no bound, else that many; a pass above it stays on route 8 (test hook)
     int64_t wide_pool = -1;      // RPF_FLAG_WIDE_CLASSES: entries of the member pool at the first count launch: -1 auto (8 per pixel of the slab), else that many (test hook: a pool too small is grown to the exact size and the count launch repeated; same results)
-    bool is_default() const { return waves_per_pixel == 0 && table_in_lds == -1 && lds_pad == 0 && binning == -1 && stage_mask == -1 && screen == 1 && strip_w == 0 && split_chunk == 0 && count_first == -1 && split_weights == -1 && packed == -1 && wide == -1 && wide_pool == -1; }
+    bool is_default() const { return waves_per_pixel == 0 && table_in_lds == -1 && lds_pad == 0 && binning == -1 && stage_mask == -1 && screen == 1 && strip_w == 0 && split_chunk == 0 && count_first == -1 && split_weights == -1 && packed == -1 && wide == -1 && wide_pool == -1 && sampled_fused_stride == -1; }
 };
 
 struct LdsLayout {
@@ -350,6 +356,11 @@ struct SampledCountArgs {
     const double *member = nullptr;
 };
 hipError_t launch_sampled_count(const PassParams &p, const SampledCountArgs &a, const MemberPool &m, hipStream_t s);
+// the count pass of route 11 (rpf_generic_sampled_mask.hip), S + draws <= kMaxResident and box*box*S <=
+// kMaxNbhd: the same draws under the same test, left as route 2's count pass leaves its result -- N = S + the accepted draws into
+// p.nbhd and, for every pixel of rows [p.row_begin, p.row_end), the ceil(ncand / 64) acceptance words of its window into p.masks
+// ([H*W][p.mask_stride] u64, which must be given: bit qq = candidate qq of the visiting order).  No pool, no cursor
+hipError_t launch_sampled_count_mask(const PassParams &p, const SampledCountArgs &a, hipStream_t s);
 } // namespace generic
 
 // ---- the spike pass (rpf_spike.hip, RPF_FLAG_SPIKE_CLAMP) -----------------------------------------------

