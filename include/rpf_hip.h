@@ -332,6 +332,34 @@ enum {
                                   without the flag; rpf_max_nbhd and rpf_max_draws do not read it.  Refused before any device
                                   work: the flag without RPF_FLAG_SAMPLED_NBHD (RPF_E_UNSUPPORTED; rpf_layout_kernels answers
                                   the same way); every refusal of RPF_FLAG_SAMPLED_NBHD stands with it. */
+    RPF_FLAG_SAMPLED_LISTED = 524288, /* opt-in, modifies RPF_FLAG_SAMPLED_NBHD: a sampled pass of the call runs on the listed builds of
+                                  the compiled, fused kernels, which take their member lists from route 8's member pool instead of
+                                  rebuilding them from acceptance masks (route 12).  The count kernel lists
+                                  the accepted draws of route 8 (same key, same table, same discards, stage 1b's test or under
+                                  RPF_FLAG_MEMBER_TEST the configured one) as plane offsets behind one cursor reservation per pixel
+                                  -- for box*box*S <= 65535 the bitmap kernel of route 11 with a listing tail, above that route
+                                  8's own count launch -- the pixels are dealt into the ten resident size classes, and the packed,
+                                  one-wave and four-wave compiled kernels copy their lists.  A pass takes route 12 when it has
+                                  draws[p] > 0, the layout is one of the two compiled ones and the call is without
+                                  RPF_FLAG_GENERIC, S + draws[p] <= 3136, the pass is accepted at all (the window span check;
+                                  box*box*S <= 262144 with RPF_FLAG_WIDE_NBHD above 65535), option "wide" does not force it, and
+                                  under RPF_FLAG_SCHEDULE its entry's gains are both 1 or the call carries RPF_FLAG_SCHEDULE_FUSED
+                                  (the pass then runs the scheduled listed builds).  Every other pass of the call runs exactly as
+                                  without this flag.  It does not need RPF_FLAG_SAMPLED_FUSED; with both, a pass that both routes
+                                  can take runs on route 12 when its mask stride is at least option "sampled_listed_stride", and
+                                  a pass route 11 cannot take (wide, or above "sampled_fused_stride") runs on route 12.  Results
+                                  are route 11's bit for bit where both apply: membership, statistics and bin ids are route 8's
+                                  bits; MI, alpha, beta, W_r_c and the colours are those the compiled kernels give for that list.
+                                  The kernels are sized from min(box*box*S, S + draws), on a wide pass too.  No mask buffer is
+                                  allocated: the pool takes 4 * (N - S) bytes per pixel, at most 4 * draws, under route 8's rules
+                                  (option "wide_pool": grown once to the cursor's figure, the count repeated).  Options "packed",
+                                  "waves_per_pixel", "split_weights", "table_in_lds" and "strip_w" act as on route 2 (the four-wave
+                                  kernels are not shut out at windows above 4096 candidates: a list needs no mask array).
+                                  rpf_layout_kernels answers as for the word without the flag; rpf_max_nbhd and rpf_max_draws do
+                                  not read it: S + draws > 832 still needs RPF_FLAG_SAMPLED_REST, a pass above 65535
+                                  RPF_FLAG_WIDE_NBHD.  Refused before any device work: the flag without RPF_FLAG_SAMPLED_NBHD
+                                  (RPF_E_UNSUPPORTED; rpf_layout_kernels answers the same way); every refusal of
+                                  RPF_FLAG_SAMPLED_NBHD stands with it. */
     RPF_FLAG_STREAM_FAST = 512/* opt-in, modifies RPF_FLAG_GENERIC and / or RPF_FLAG_WIDE_NBHD: the two kernels that walk a
                                   neighbourhood of any size with 256 threads -- the generic filter kernel (route 3, the rest
                                   list N > 64 / N > 832 of routes 4 / 5) and the wide kernel (route 6, the rest list N > 832 of
@@ -474,7 +502,12 @@ int32_t rpf_filter_ex(rpf_ctx *ctx, const rpf_desc *desc, const void *planes, co
  *                      pixel (ceil((box*box - 1) * S / 64)), at which such a pass takes route 11: -1 no bound (default), else 0 ..
  *                      1024; a pass above the bound stays on route 8 and runs exactly as without the flag.  No effect without
  *                      the flag (DESIGN.md section 13f has the measurements behind the default)
- * These names (but "wide", "wide_pool" and "sampled_fused_stride") steer the fused routes only: a call with RPF_FLAG_GENERIC, with or without RPF_FLAG_GENERIC_PACKED, runs
+ *   "sampled_listed_stride"  sampled passes of a call with RPF_FLAG_SAMPLED_LISTED and RPF_FLAG_SAMPLED_FUSED both: the smallest
+ *                      mask stride (the same figure) from which a pass that both routes can take runs on route 12: -1 auto (default:
+ *                      the measured value of DESIGN.md section 13g, 144: box 17 x 32 spp and every wider window), else 0 .. 1025 (1025: never where route 11 applies).  A pass
+ *                      that route 11 cannot take (wide, or above "sampled_fused_stride") runs on route 12 whatever it says.  No
+ *                      effect without both flags
+ * These names (but "wide", "wide_pool", "sampled_fused_stride" and "sampled_listed_stride") steer the fused routes only: a call with RPF_FLAG_GENERIC, with or without RPF_FLAG_GENERIC_PACKED, runs
  * the same kernels whatever they say (they are accepted and have no effect there; options_active still reports them).
  * rpf_counters.options_active tells whether a result was produced under any override. */
 int32_t rpf_set_option(rpf_ctx *ctx, const char *name, int64_t value);
@@ -539,7 +572,10 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *desc, int32_t box, c
  * class N > 3136 is the wide kernel's); redo_pixels is 0.
  * With RPF_FLAG_SAMPLED_FUSED (route 11) a sampled pass counts one launch per non-empty class of the ten resident ones (its count
  * kernel is not counted, and no pixel reaches the streaming class); redo_pixels is 0; sum_nbhd / max_nbhd are those of the
- * sampled neighbourhoods. */
+ * sampled neighbourhoods.
+ * With RPF_FLAG_SAMPLED_LISTED (route 12) a sampled pass counts as on route 11: one launch per non-empty class of the ten resident
+ * ones (the count kernel -- repeated once when the member pool had to grow -- is not counted, and no pixel reaches the streaming
+ * class); redo_pixels is 0; sum_nbhd / max_nbhd are those of the sampled neighbourhoods. */
 int32_t rpf_query_counters(rpf_ctx *ctx, rpf_counters *out);
 
 /* neighbourhood size N of every pixel (rpf.cpp:586: the neighbourhood vector's size) as the last pass of the most recent
@@ -562,6 +598,8 @@ int32_t rpf_query_nbhd(rpf_ctx *ctx, int32_t *nbhd_out, int64_t count);
  * kernels of route 2 by size class; the same member lists as route 9),
  * 11 = a sampled pass under RPF_FLAG_SAMPLED_FUSED on a compiled layout (the draws' count kernel leaves acceptance masks, then
  * the compiled kernels of route 2 by size class; the same member lists as route 8),
+ * 12 = a sampled pass under RPF_FLAG_SAMPLED_LISTED on a compiled layout (a count kernel lists the draws into the member pool, then
+ * the listed builds of the compiled kernels by size class; the same member lists as route 8, wide windows included),
  * -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1.  rpf_filter's row-band
  * pipeline runs that probe once per band, on the rows of the slab that are resident by then -- the last band of a pass on the
  * whole slab -- so the answer after such a call is the serial call's (bands above the last may have taken the other of 0 / 1:

@@ -24,6 +24,8 @@ KERNEL_TUS += ["rpf_generic_sampled_mask.hip"]  # ... and the count pass that le
 KERNEL_TUS += ["rpf_impl_d19_member.hip", "rpf_impl_d27_member.hip"]  # rpf_filter_impl.inc part 4: the count pass under the membership test (RPF_FLAG_MEMBER_FUSED)
 # ... and the scheduled builds of parts 1 to 3 (RPF_IMPL_SCHED: stage 3c from the entry's gains; RPF_FLAG_SCHEDULE_FUSED)
 KERNEL_TUS += ["rpf_impl_%s_sched_%s.hip" % (lay, part) for lay in ("d19", "d27") for part in ("small", "mid", "large")]
+# ... their listed builds (RPF_IMPL_LISTED: stage 1b from the member pool; RPF_FLAG_SAMPLED_LISTED), and the listed scheduled ones
+KERNEL_TUS += ["rpf_impl_%s_listed_%s%s.hip" % (lay, sc, part) for lay in ("d19", "d27") for sc in ("", "sched_") for part in ("small", "mid", "large")]
 KERNEL_TUS += ["rpf_report.hip"]  # the per-pass activity report: per-pixel chains, per-row chains and counts (RPF_FLAG_PASS_REPORT)
 # the C ABI (host code only; rpf_api.h is what they share): context, validation and pass loops | pass router | film step | multi-GPU | spike pass | pass report
 # (the names start with rpf_api: the spill scan below skips them by that)
@@ -34,6 +36,7 @@ HEADERS = [os.path.join(_HERE, "csrc", "rpf_internal.h"), os.path.join(_HERE, "c
            os.path.join(_HERE, "csrc", "rpf_device_common.h"), os.path.join(_HERE, "csrc", "rpf_reflog.h"),
            os.path.join(_HERE, "csrc", "rpf_generic_common.h"),  # what the rpf_generic*.hip share
            os.path.join(_HERE, "csrc", "rpf_generic_sampled_draws.h"),  # ... the draws of a sampled pass, which its two count TUs share
+           os.path.join(_HERE, "csrc", "rpf_generic_sampled_bitmap.inc"),  # ... the steps the bitmap count kernels of routes 11 and 12 share
            os.path.join(_HERE, "csrc", "rpf_generic_stream_stages.inc"),  # ... and the stage bodies of rpf_generic.hip and rpf_generic_wide.hip
            os.path.join(_ROOT, "include", "rpf_hip.h")]
 
@@ -84,7 +87,7 @@ def _build(LIB, OBJ_DIR, defs, shipped, force, verbose):
         if force or _stale(obj, [src] + HEADERS):
             # -save-temps=obj keeps the device assembly next to the object: scripts/check_spills.py reads it below
             cmds.append([hipcc_path()] + flags + ["-save-temps=obj", "-c", src, "-o", obj])
-    # at most MAX_JOBS compilers at a time, 16 at the most (31 translation units: one hipcc each all at once oversubscribes a
+    # at most MAX_JOBS compilers at a time, 16 at the most (43 translation units: one hipcc each all at once oversubscribes a
     # machine that gives the build a share of its cores).  The largest units (the rpf_impl_* parts) start first
     jobs = max(1, min(16, int(os.environ.get("MAX_JOBS", 16))))
     cmds.sort(key=lambda c: not os.path.basename(c[-3]).startswith("rpf_impl_"))

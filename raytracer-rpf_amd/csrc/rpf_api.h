@@ -62,6 +62,7 @@ enum Route : int {
     kRouteMemberTest = 9,    // a full-box pass under RPF_FLAG_MEMBER_TEST: route 7's structure with the configured test
     kRouteMemberFused = 10,  // ... with RPF_FLAG_MEMBER_FUSED, on a compiled layout: route 2's structure behind the configured test
     kRouteSampledFused = 11, // a sampled pass under RPF_FLAG_SAMPLED_FUSED on a compiled layout: route 2's class kernels behind the draws' mask kernel
+    kRouteSampledListed = 12, // ... under RPF_FLAG_SAMPLED_LISTED: the listed builds of route 2's class kernels behind a count kernel that lists into the member pool
 };
 
 static_assert(sizeof(rpf_sampling) == 48 && offsetof(rpf_sampling, draws) == 16, "rpf_sampling is ABI");

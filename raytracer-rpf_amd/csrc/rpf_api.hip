@@ -46,6 +46,7 @@ struct FlagRule {
 };
 constexpr uint32_t kPackedRoute = RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED;
 constexpr FlagRule kFlagRules[] = {
+    {RPF_FLAG_SAMPLED_LISTED, RPF_FLAG_SAMPLED_NBHD, 0, 0, "RPF_FLAG_SAMPLED_LISTED without RPF_FLAG_SAMPLED_NBHD: the flag modifies the sampled route"},
     {RPF_FLAG_SAMPLED_FUSED, RPF_FLAG_SAMPLED_NBHD, 0, 0, "RPF_FLAG_SAMPLED_FUSED without RPF_FLAG_SAMPLED_NBHD: the flag modifies the sampled route"},
     {RPF_FLAG_SCHEDULE_FUSED, RPF_FLAG_SCHEDULE, 0, 0, "RPF_FLAG_SCHEDULE_FUSED without RPF_FLAG_SCHEDULE: the flag modifies the per-pass schedule"},
     {RPF_FLAG_MEMBER_FUSED, RPF_FLAG_MEMBER_TEST, 0, 0, "RPF_FLAG_MEMBER_FUSED without RPF_FLAG_MEMBER_TEST: the flag modifies the membership-test route"},
@@ -388,7 +389,7 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
             ? "box*box*S > 65535: neighbourhood too large (16-bit histogram cells, one-byte bin ids) without RPF_FLAG_WIDE_NBHD"
             : "box*box*S > 262144: neighbourhood too large for the wide kernel of RPF_FLAG_WIDE_NBHD (16-bit bin ids, B <= 512)");
     p.nmax = (int)nmax64;
-    const bool wide = (p.generic & kGenericWide) != 0;
+    bool wide = (p.generic & kGenericWide) != 0; // (a route-12 pass drops the bit below)
     // a sampled pass (validate checked the configuration): draws[pass] > 0; with 0 draws the pass carries no bit and runs as without the flag
     ctx->samp_now = SampledPass{};
     ctx->probe_r0 = ctx->probe_r1 = 0; // ... and its route probe reads the rows of its route_pass calls unless the caller names others
@@ -452,8 +453,25 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
                                !(p.generic & no_sampled_fused) && p.nmax <= kMaxNbhd &&
                                (int64_t)d->S + ctx->samp_now.draws <= kMaxResident &&
                                (ctx->tun.sampled_fused_stride < 0 || window_words <= ctx->tun.sampled_fused_stride);
-    if (sampled_fused) p.generic |= kGenericSampledFused;
-    if (sampled_fused && (p.generic & kGenericSchedule)) p.generic = (p.generic & ~kGenericSchedule) | kGenericScheduleFused;
+    // RPF_FLAG_SAMPLED_LISTED (route 12): a sampled pass that the listed builds of the compiled kernels can
+    // take behind a count kernel that lists into the member pool -- route 11's conditions without the two its masks impose: the
+    // window may be wide by its size (the pass is accepted at all: nbhd_cap above; a pass that option "wide" forces is not taken),
+    // and no mask stride bounds it.  Where route 11 applies as well, option "sampled_listed_stride" decides: route 12 from that
+    // stride on.  A wide pass loses its wide bits: it is sized and set up from min(box*box*S, S + draws), not as a wide-kernel pass
+    const int32_t no_sampled_listed = kGenericOn | ((d->flags & RPF_FLAG_SCHEDULE_FUSED) ? 0 : kGenericSchedule);
+    const int32_t listed_from = ctx->tun.sampled_listed_stride < 0 ? kSampledListedStride : ctx->tun.sampled_listed_stride;
+    const bool sampled_listed = (d->flags & RPF_FLAG_SAMPLED_LISTED) && (p.generic & kGenericSampled) && p.lay.supported() &&
+                                !(p.generic & no_sampled_listed) && ctx->tun.wide != 1 &&
+                                (int64_t)d->S + ctx->samp_now.draws <= kMaxResident &&
+                                (!sampled_fused || window_words >= listed_from);
+    if (sampled_listed) {
+        p.generic = (p.generic & ~(kGenericWide | kGenericWideClasses | kGenericStreamFast)) | kGenericSampledListed;
+        if (p.generic & kGenericSchedule) p.generic = (p.generic & ~kGenericSchedule) | kGenericScheduleFused;
+        wide = false;
+    } else if (sampled_fused) {
+        p.generic |= kGenericSampledFused;
+        if (p.generic & kGenericSchedule) p.generic = (p.generic & ~kGenericSchedule) | kGenericScheduleFused;
+    }
     p.sigma_p = (double)(box / 4); // rpf.cpp:531: integer division
     p.plane_stride = (uint64_t)d->W * d->H * d->S;
     p.planes = d_planes; p.col_in = col_in; p.col_out = col_out;
@@ -466,7 +484,7 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
     if ((st = ensure_tables(ctx, std::min(p.nmax, kMaxNbhd)))) return st;
     if (wide && (st = ensure_wide_table(ctx, p.nmax))) return st;
     // (route 9's rest launch reads the 2^-44 table where that is exact, as a forced wide pass does, and route 6's table above)
-    if (member && !wide && p.nmax > kTFixExact && (st = ensure_wide_table(ctx, p.nmax))) return st;
+    if (member && !wide && !sampled_listed && p.nmax > kTFixExact && (st = ensure_wide_table(ctx, p.nmax))) return st;
     if (member && (st = ensure_member_table(ctx))) return st;
     if ((p.generic & kGenericSampled) && (st = ensure_sampling_table(ctx, box))) return st;
     p.pmean = ctx->d_pmean; p.pstd = ctx->d_pstd; p.tfix = ctx->d_tfix; p.dfix = ctx->d_dfix;
@@ -474,7 +492,7 @@ int32_t setup_pass(rpf_ctx *ctx, const rpf_desc *d, int box, int pass, const voi
     if ((st = ctx->d_flat.ensure(ctx, HW))) return st;
     p.flat = ctx->d_flat; p.nan_flag = ctx->d_nan_flag;
     if (dbg_dev) p.dbg = *dbg_dev;
-    if (sampled_fused) { // the largest resident kernel of the pass: no list is longer than S + draws, whatever the window holds
+    if (sampled_fused || sampled_listed) { // the largest resident kernel of the pass: no list is longer than S + draws, whatever the window holds
         const int nres = (int)std::min<int64_t>(p.nmax, (int64_t)d->S + ctx->samp_now.draws), bres = bmax_of(nres);
         out.lds = lds_layout(p.S, nres, bres, table_in_lds(p.S, nres, bres, ctx->tun, p.lay), ctx->tun, p.lay).total;
     } else if (member_fused) { // the largest resident kernel of the pass, as on route 2, and -- its streaming class -- the wide kernel's carve-up
@@ -1061,6 +1079,7 @@ bool apply_option(Tuning &t, const std::string &n, int64_t value) {
     else if (n == "wide" && (value == -1 || value == 1)) t.wide = (int32_t)value;
     else if (n == "wide_pool" && value >= -1 && value <= ((int64_t)1 << 40)) t.wide_pool = value;
     else if (n == "sampled_fused_stride" && value >= -1 && value <= 1024) t.sampled_fused_stride = (int32_t)value;
+    else if (n == "sampled_listed_stride" && value >= -1 && value <= 1025) t.sampled_listed_stride = (int32_t)value;
     else if (n == "split_chunk" && value >= 0 && value <= (1 << 30)) t.split_chunk = (int32_t)value;
     else if (n == "count_first" && value >= -1 && value <= 1) t.count_first = (int32_t)value;
     else if (n == "lds_pad" && value >= 0 && value <= 160 * 1024) t.lds_pad = (int32_t)value;

@@ -1,6 +1,6 @@
 // rpf_api_routes.hip -- the pass router of the C ABI: route_pass, which runs one filter pass on the route its flags, its sizes
 // and the options pick, and what only the routes use -- the slot rules of the streaming and wide kernels, the redo list, the
-// class launches, count_and_deal, the one count-and-deal step of the listed-member routes 7, 8 and 9, and binned_params /
+// class launches, count_and_deal, the one count-and-deal step of the listed-member routes 7, 8, 9 and 12, and binned_params /
 // deal_classes / filter_classes, the steps the routes behind a mask-leaving count pass share (2, 10 and 11).  Host code only;
 // rpf_api.hip prepares a pass (setup_pass) and calls route_pass from its pass loops.
 #include <hip/hip_runtime.h>
@@ -258,8 +258,9 @@ int32_t filter_classes(rpf_ctx *ctx, const PassParams &pc, bool packed, const do
     int32_t st;
     // the four-wave kernels keep one acceptance mask per 64 candidates of the WINDOW in a 64-entry LDS array: windows
     // beyond 4096 candidates (boxes 17 and up) run their resident classes on the one-wave instantiations
+    // (a listed pass, route 12, has no such array: its "auto" is the classes' own choice at every window)
     Tuning tun = ctx->tun;
-    if ((int64_t)(pc.box * pc.box - 1) * pc.S > 4096) tun.waves_per_pixel = 1;
+    if (!(pc.generic & kGenericSampledListed) && (int64_t)(pc.box * pc.box - 1) * pc.S > 4096) tun.waves_per_pixel = 1;
     for (int c = 0; c < kNumClasses; ++c) {
         if (counts[c] == 0) continue;
         static const char *const kClassName[kNumClasses] = {
@@ -374,11 +375,15 @@ struct ListedPass {
     bool held_pool;
     const char *count_label;   // the roctx range of the step
     const char *overflow_msg;  // the refusal when the pool overflows at its exact size
+    // the deal (launch_classify's max_class and rest_class): the eight classes of route 5 and a rest class on routes 7, 8 and 9, the
+    // eleven classes of route 2 on route 12
+    int max_class = kNumWave, rest_class = kRestClass;
 };
 
 // The count-and-deal step of a listed-member pass over p's rows (not empty): `count` -- hipError_t(const PassParams &, const
 // generic::MemberPool &, hipStream_t), the route's count kernel -- lists each pixel's members behind its own samples into the
-// member pool behind one cursor and writes N; the pixels are dealt into the eight classes of route 5 and a rest class; one
+// member pool behind one cursor and writes N; the pixels are dealt into the eight classes of route 5 and a rest class (route 12:
+// lp's deal, the eleven classes of route 2); one
 // read-back brings the list sizes (counts) and the cursor.  The pool holds `wide_pool` entries (option), else 8 per pixel of the
 // slab or, where lp says so, what it already holds if that is more; when the cursor says the data needed more, the pool is grown
 // to exactly that and the count and the deal are repeated, once: the cursor ends at the sum of N - S over the listed pixels
@@ -400,7 +405,7 @@ int32_t count_and_deal(rpf_ctx *ctx, PassParams &p, const ListedPass &lp, Count 
         unsigned long long used = 0;
         HIP_TRY(hipMemsetAsync(ctx->d_class_counts, 0, kNumClasses * sizeof(uint32_t), s));
         HIP_TRY(count(p, generic::MemberPool{ctx->d_wc_pool, capacity, ctx->d_wc_base, ctx->d_wc_cursor}, s));
-        HIP_TRY(launch_classify(p, ctx->d_lists, ctx->d_class_counts, kNumWave, kRestClass, s));
+        HIP_TRY(launch_classify(p, ctx->d_lists, ctx->d_class_counts, lp.max_class, lp.rest_class, s));
         HIP_TRY(hipMemcpyAsync(counts, ctx->d_class_counts, kNumClasses * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(&used, ctx->d_wc_cursor, sizeof(used), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
@@ -555,6 +560,53 @@ int32_t route_sampled_fused(rpf_ctx *ctx, const PassParams &p_in, bool packed, h
     return filter_classes(ctx, pc, packed, nullptr, counts, s, launches);
 }
 
+// A sampled pass under RPF_FLAG_SAMPLED_LISTED on a compiled layout (route 12): route 8's count-and-deal step
+// with the deal of route 2 -- the eleven classes -- and then the size-binned route's class loop on the listed builds of the compiled
+// kernels (kGenericSampledListed in p.generic: launch_filter_pass and launch_filter_packed dispatch on it), which copy their member
+// lists from the pool.  The count kernel: for a window of at most 65535 candidates generic::sampled_count_list_kernel, route 11's
+// bitmap kernel with a listing tail; above that route 8's own launch (the enumeration sort, or the block kernel above S + draws =
+// 832), whose candidate indices are 32 bits wide.  Either way the pool content is route 8's.  No list is longer than S + draws: the
+// kernels are sized from min(box*box*S, S + draws) on a wide window too, setup_pass admits S + draws <= 3136 only, and a non-empty
+// streaming class is an internal error.  No mask buffer; pool capacity and growth are route 7's (option "wide_pool").  REF_ABORT is
+// refused on a sampled pass, so there is no redo list.  The lists of this pass are no other pass's: route_pass dropped the
+// membership cache before it ran, and it sets none.
+int32_t route_sampled_listed(rpf_ctx *ctx, const PassParams &p_in, bool packed, hipStream_t s, int *launches) {
+    int32_t st;
+    ctx->last_route = kRouteSampledListed;
+    PassParams p = p_in;
+    p.redo_list = nullptr; p.redo_count = nullptr;
+    if (p.row_end <= p.row_begin) return RPF_OK;
+    const SampledPass sp = ctx->samp_now;
+    if (sp.draws < 1 || sp.draws > sp.max_draws || !ctx->d_samp_table || ctx->samp_table_box != p.box || !p.lay.supported() ||
+        (int64_t)p.S + sp.draws > kMaxResident || (p.generic & (kGenericWide | kGenericSampledFused)))
+        return fail(ctx, RPF_E_BADARG, "sampled pass without its configuration (setup_pass prepares it)");
+    generic::SampledCountArgs a = {ctx->d_samp_table, ctx->sampling.seed, sp.pass_id, ctx->sampling.row_origin, sp.draws};
+    if (p.generic & kGenericMemberTest) { // with RPF_FLAG_MEMBER_TEST the draws meet the configured test
+        if (!ctx->d_member || !ctx->member_fresh) return fail(ctx, RPF_E_BADARG, "pass under the membership test without its configuration (setup_pass prepares it)");
+        a.member = ctx->d_member;
+    }
+    const bool bitmap = p.nmax <= kMaxNbhd; // the window's candidate indices fit the bitmap kernel's 16-bit queue
+    p.nmax = (int32_t)std::min<int64_t>(p.nmax, (int64_t)p.S + sp.draws); // the longest list of the pass sizes its kernels
+    p.bmax = bmax_of(p.nmax);
+    p.reroute_masks = nullptr;
+    p.carry = nullptr;
+    if (p.nmax > class_capacity(kNumClasses - 4) && ctx->tun.split_weights != 0) {
+        // the 32- and 64-spp classes run as three kernels (chains; bins + MI; weights): per-pixel hand-over buffer (binned_params)
+        if ((st = ctx->d_carry.ensure(ctx, (size_t)p.W * p.H * (size_t)kCarryStride * sizeof(double)))) return st;
+        p.carry = ctx->d_carry;
+    }
+    uint32_t counts[kNumClasses];
+    const ListedPass lp = {true, "rpf:sampled count + classify (draws, stage 1b test, listed members, size classes)",
+                           "sampled count pass: the member pool overflowed at its exact size", kNumClasses, -1};
+    // (both launches zero the cursor themselves)
+    const auto count = [&](const PassParams &q, const generic::MemberPool &m, hipStream_t cs) {
+        return bitmap ? generic::launch_sampled_count_list(q, a, m, cs) : generic::launch_sampled_count(q, a, m, cs);
+    };
+    if ((st = count_and_deal(ctx, p, lp, count, counts, s))) return st;
+    if (counts[kNumClasses - 1] != 0) return fail(ctx, RPF_E_HIP, "sampled count pass: a pixel with N > 3136");
+    return filter_classes(ctx, p, packed, nullptr, counts, s, launches);
+}
+
 // Routes 4 and 5, the layout-generic route with its small neighbourhoods on class kernels (RPF_FLAG_GENERIC |
 // RPF_FLAG_GENERIC_PACKED on a pass with S <= 64; ... | RPF_FLAG_GENERIC_WAVE on one with S <= 832): stage 1b as its own launch
 // (generic::nbhd_count_kernel: N and the acceptance masks), the pixels dealt by N into n_classes classes -- four lane classes
@@ -598,6 +650,7 @@ int32_t route_generic_classes(rpf_ctx *ctx, const PassParams &p_in, int n_classe
 // Which layout-generic route a pass takes (kRouteNone: none, a pass on the compiled kernels).  Above 64 spp N >= S fits no
 // packed class, above 832 spp no one-wave class: such a pass runs as route 3 does.
 Route generic_route(const PassParams &p) {
+    if (p.generic & kGenericSampledListed) return kRouteSampledListed; // (... a sampled pass the listed builds take under RPF_FLAG_SAMPLED_LISTED)
     if (p.generic & kGenericSampledFused) return kRouteSampledFused; // (... a sampled pass the compiled kernels take under RPF_FLAG_SAMPLED_FUSED)
     if (p.generic & kGenericSampled) return kRouteSampled; // (setup_pass marked it: draws > 0)
     if (p.generic & kGenericMemberFused) return kRouteMemberFused; // (... a full-box pass the compiled kernels take under RPF_FLAG_MEMBER_FUSED)
@@ -633,7 +686,7 @@ int32_t route_pass(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *lau
     // The membership cache of the size-binned route (bin_valid: the class counts on the host, d_lists and d_masks on the device)
     // outlives a pass only from one size-binned pass to the next: route_binned alone sets it, and every other route drops it
     // here, before it runs -- the unbinned route with its packed lists, routes 4 and 5, the listed-member routes 7, 8 and 9 and
-    // route 11 write their own lists, masks and class counts into the same buffers.  Route 10 is route_binned under another test: it keeps
+    // routes 11 and 12 write their own lists, masks and class counts into the same buffers.  Route 10 is route_binned under another test: it keeps
     // the cache, keyed by bin_member, so that neither of routes 2 and 10 is served the other's masks
     if (!bin && route != kRouteMemberFused) ctx->bin_valid = false;
     // small neighbourhoods (N <= 64) run on the packed kernels, several pixels per wave (rpf_packed_impl.inc); option "packed"
@@ -641,6 +694,7 @@ int32_t route_pass(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *lau
     switch (route) {
     case kRouteMemberFused: return route_member_fused(ctx, p, packed, s, launches);
     case kRouteSampledFused: return route_sampled_fused(ctx, p, packed, s, launches);
+    case kRouteSampledListed: return route_sampled_listed(ctx, p, packed, s, launches);
     case kRouteSampled: return route_sampled(ctx, p, s, launches);
     case kRouteMemberTest: return route_member_test(ctx, p, s, launches);
     case kRouteWideClasses: return route_wide_classes(ctx, p, nullptr, s, launches);

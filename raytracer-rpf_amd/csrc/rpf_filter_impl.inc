@@ -16,6 +16,17 @@
 #define RPF_IMPL_SCHED 0
 #endif
 constexpr bool kSched = RPF_IMPL_SCHED != 0;
+// RPF_IMPL_LISTED 1 (the rpf_impl_*_listed_* translation units, inside a nested namespace `listed`, and `listed::sched` together
+// with RPF_IMPL_SCHED; RPF_FLAG_SAMPLED_LISTED, DESIGN.md section 13g): the same part with stage 1b reading the member list a
+// count kernel left -- N from p.nbhd, the N - S plane offsets behind the own samples from p.members / p.member_base -- instead
+// of testing the window or walking its acceptance masks; everything behind stage 1b is the text it was.  Such a build reads
+// neither p.masks nor p.reroute_masks nor stage 1a's flat plane and does not write p.nbhd.  It holds the non-FAST
+// filter_pixel_kernel instantiations (PHASES 0, 2, 3 and 4; with RPF_IMPL_SCHED PHASES 0 and 4, the listed part launches 2 and
+// 3) and, in part 1, the packed kernels; no stage 1a and no count kernels
+#ifndef RPF_IMPL_LISTED
+#define RPF_IMPL_LISTED 0
+#endif
+constexpr bool kListed = RPF_IMPL_LISTED != 0;
 constexpr int kNR = RPF_IMPL_NR;               // random-parameter columns
 constexpr int kNFeat = RPF_IMPL_NF;            // scene-feature columns
 constexpr int kColP = 0, kColC = 2, kColR = 5, kColF = 5 + kNR;
@@ -138,7 +149,7 @@ __device__ __forceinline__ void gather_weighted(const Window &w, uint32_t rel, f
     }
 }
 
-#if RPF_IMPL_PART == 1 && !RPF_IMPL_SCHED
+#if RPF_IMPL_PART == 1 && !RPF_IMPL_SCHED && !RPF_IMPL_LISTED
 // ------------------------------------------------------------------------------------------------
 // stage 1a: per-pixel mean / std of the 12 features over the pixel's own S samples, sequential sums
 // (rpf.cpp:338-347, ops.h:111-144).  Output planes [12][H*W] so the filter kernel reads them with
@@ -221,7 +232,7 @@ __global__ __launch_bounds__(256) void pixel_stats_tile_kernel(PassParams p, uin
     }
 }
 
-#endif // RPF_IMPL_PART == 1 && !RPF_IMPL_SCHED
+#endif // RPF_IMPL_PART == 1 && !RPF_IMPL_SCHED && !RPF_IMPL_LISTED
 
 template <int KD, int KW, int PACK5>
 __device__ __forceinline__ void store_bins(uint32_t *sBinW, int c, int lane, const BinIds<KW, PACK5> &b) {
@@ -1094,7 +1105,19 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
     for (int s = tid; s < S; s += kThreads) sOff[s] = own_rel + (uint32_t)s; // own samples first
 
     int n = S;
-    if constexpr (NW > 1) {
+    if constexpr (kListed) {
+        // a listed build (RPF_IMPL_LISTED): the count kernel listed the members behind the own samples as plane offsets, in the
+        // reference's visiting order; every thread of the workgroup copies, whatever NW and PHASE are.  The window's first sample
+        // comes off, so that the entries are the window-relative offsets everything behind expects.  (n <= nmax by the class
+        // deal: the bound only guards LDS.  member_base is read only where a pixel lists members: the count kernel reserves none
+        // for N = S)
+        n = min(p.nbhd[pix], p.nmax);
+        if (n > S) {
+            const uint32_t *pl = p.members + p.member_base[pix];
+            const uint32_t origin = (uint32_t)(y0 * W + x0) * (uint32_t)S;
+            for (int i = tid; i < n - S; i += kThreads) sOff[S + i] = pl[i] - origin;
+        }
+    } else if constexpr (NW > 1) {
         // Several waves: the 64-candidate blocks are dealt round-robin to the waves.  Pass A tests a wave's blocks and
         // leaves one acceptance mask per block in LDS; pass B turns the masks into list positions (an exclusive scan
         // over <= 64 block counts, done by every wave for itself) and appends, so the list order is the reference's.
@@ -1236,8 +1259,10 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
         }
     }
     bsync();
-    if (tid == 0) p.nbhd[pix] = n;
-    if constexpr (NW == 1 && PHASE == 0) { // (every one-wave kernel: the unbinned route reaches K = 13 at 448 < box*box*S <= 512)
+    if constexpr (!kListed) { // (a listed build took N from there)
+        if (tid == 0) p.nbhd[pix] = n;
+    }
+    if constexpr (NW == 1 && PHASE == 0 && !kListed) { // (every one-wave kernel: the unbinned route reaches K = 13 at 448 < box*box*S <= 512)
         // a small neighbourhood (the regime of path-traced buffers, SURVEY F10) is not this kernel's business: the packed
         // kernels filter 8 / 4 / 2 / 1 such pixels per wave from the masks left above (rpf_packed_impl.inc)
         if (p.reroute_masks != nullptr && n <= 64) return; // wave-uniform; classify_kernel lists the pixel by its N
@@ -2257,7 +2282,7 @@ __global__ __launch_bounds__(64 * NW, PHASE == 2 ? 2 : PHASE == 3 ? (kRef19 ? 3 
     }
 }
 
-#if (RPF_IMPL_PART == 1 || RPF_IMPL_PART == 4) && !RPF_IMPL_SCHED
+#if (RPF_IMPL_PART == 1 || RPF_IMPL_PART == 4) && !RPF_IMPL_SCHED && !RPF_IMPL_LISTED
 // ---- neighbourhood-size binning -----------------------------------------------------------------------------------
 // The cost and the LDS footprint of a pixel are set by its neighbourhood size N, and N is data dependent: box*box*S is
 // only its ceiling (path-traced buffers keep little more than the S own samples, SURVEY F10).  When the ceiling is above
@@ -2389,9 +2414,9 @@ __device__ __forceinline__ int membership_pixel_two_phase(const PassParams &p, i
     return n;
 }
 
-#endif // (RPF_IMPL_PART == 1 || RPF_IMPL_PART == 4) && !RPF_IMPL_SCHED
+#endif // (RPF_IMPL_PART == 1 || RPF_IMPL_PART == 4) && !RPF_IMPL_SCHED && !RPF_IMPL_LISTED
 
-#if RPF_IMPL_PART == 1 && !RPF_IMPL_SCHED
+#if RPF_IMPL_PART == 1 && !RPF_IMPL_SCHED && !RPF_IMPL_LISTED
 // The pixels: every pixel of the slab (step 1, list null); the entries of `list` (its size read from *list_count: the
 // pixels stage 1a could not prove flat, rpf_kernels.hip prelist_kernel); or (step > 1: the route probe of the unbinned pass,
 // rpf_api.hip) the points of a lattice with that pitch, probe[0] += how many of them have N <= 64 without being proven flat,
@@ -2426,7 +2451,7 @@ __global__ __launch_bounds__(256) void nbhd_count_kernel(PassParams p, int step,
     }
 }
 
-#endif // RPF_IMPL_PART == 1 && !RPF_IMPL_SCHED
+#endif // RPF_IMPL_PART == 1 && !RPF_IMPL_SCHED && !RPF_IMPL_LISTED
 
 #if RPF_IMPL_PART == 4
 // The count kernel of route 10: every pixel of the slab (the same walk, the same LDS) under the configured test on mt
@@ -2456,7 +2481,8 @@ hipError_t launch_filter_inst(const PassParams &p, const LdsLayout &L, unsigned 
 // the fp32 pair-weight variant (RPF_FLAG_FAST_WEIGHTS) is built for the reference layout only
 template <int K, bool TL, int NW>
 hipError_t launch_filter_w(const PassParams &p, const LdsLayout &L, unsigned grid, hipStream_t s) {
-    if constexpr (kSched) { // the scheduled builds are fp64 only: check_schedule refuses gains with RPF_FLAG_FAST_WEIGHTS
+    if constexpr (kSched || kListed) { // the scheduled builds are fp64 only: check_schedule refuses gains with RPF_FLAG_FAST_WEIGHTS
+        // (... and the listed ones: RPF_FLAG_FAST_WEIGHTS is refused on a sampled pass)
         return p.fast_weights ? hipErrorNotSupported : launch_filter_inst<K, TL, false, NW>(p, L, grid, s);
     } else if constexpr (kRef19) {
         if (p.fast_weights) return launch_filter_inst<K, TL, true, NW>(p, L, grid, s);
@@ -2468,10 +2494,17 @@ hipError_t launch_filter_w(const PassParams &p, const LdsLayout &L, unsigned gri
 #if RPF_IMPL_SCHED
 // PHASE 3 (chains) or PHASE 2 (weights) of the split route on the unscheduled part that holds class K's kernels: the entry points
 // of parts 2 and 3 below, declared by the scheduled translation unit in the layout's namespace
+// (a listed scheduled build, namespace listed::sched: the entry points of the listed parts, which its translation unit declares in
+// namespace listed)
 template <int K>
 hipError_t unscheduled_phase(const PassParams &p, const LdsLayout &L, int phase, unsigned grid, hipStream_t s) {
+#if RPF_IMPL_LISTED
+    if constexpr (K == 25) return impl_filter_mid_phase_listed(p, L, phase, grid, s);
+    else return impl_filter_large_phase_listed(p, L, phase, grid, s);
+#else
     if constexpr (K == 25) return impl_filter_mid_phase(p, L, phase, grid, s);
     else return impl_filter_large_phase(p, L, phase, grid, s);
+#endif
 }
 #endif
 template <int K>
@@ -2480,7 +2513,7 @@ hipError_t launch_filter_k(const PassParams &p, const LdsLayout &L, const LdsLay
     if constexpr (K == 49 || K == 25) {
         // the split route of the 32- and 64-spp classes (see PHASE above): chains, then bins + MI + weights' coefficients,
         // then the weights (on two waves per pixel where two sweeps cover the own samples)
-        if (L.nw == 4 && L2.total != 0 && L3.total != 0 && p.carry != nullptr && p.masks != nullptr && !p.fast_weights) {
+        if (L.nw == 4 && L2.total != 0 && L3.total != 0 && p.carry != nullptr && (kListed || p.masks != nullptr) && !p.fast_weights) {
             // (eight waves per pixel -- six producers, in case the chain waves were waiting for gathers -- measured SLOWER: 3840x270x32
             // chains 37.9 -> 50.6 ms; the kernel is bound by its dependent fp64 additions, not by the gathers)
 #if RPF_IMPL_SCHED
@@ -2508,10 +2541,22 @@ hipError_t launch_filter_k(const PassParams &p, const LdsLayout &L, const LdsLay
 
 // entry points of this layout and part (called from the dispatchers at the end of rpf_kernels.hip); a scheduled build (namespace
 // sched) names its own impl_filter_*_sched, and of part 1 emits the filter entry alone
-#if RPF_IMPL_SCHED
+// (a listed build, namespace listed: impl_filter_*_listed and impl_filter_*_phase_listed; namespace listed::sched:
+// impl_filter_*_listed_sched)
+#if RPF_IMPL_SCHED && RPF_IMPL_LISTED
+#define impl_filter_small impl_filter_small_listed_sched
+#define impl_filter_mid impl_filter_mid_listed_sched
+#define impl_filter_large impl_filter_large_listed_sched
+#elif RPF_IMPL_SCHED
 #define impl_filter_small impl_filter_small_sched
 #define impl_filter_mid impl_filter_mid_sched
 #define impl_filter_large impl_filter_large_sched
+#elif RPF_IMPL_LISTED
+#define impl_filter_small impl_filter_small_listed
+#define impl_filter_mid impl_filter_mid_listed
+#define impl_filter_large impl_filter_large_listed
+#define impl_filter_mid_phase impl_filter_mid_phase_listed
+#define impl_filter_large_phase impl_filter_large_phase_listed
 #endif
 #if RPF_IMPL_PART == 1
 hipError_t impl_filter_small(const PassParams &p, const LdsLayout &L, bool t_in_lds, unsigned grid, hipStream_t s) {
@@ -2524,7 +2569,7 @@ hipError_t impl_filter_small(const PassParams &p, const LdsLayout &L, bool t_in_
     default: return hipErrorInvalidValue;
     }
 }
-#if !RPF_IMPL_SCHED
+#if !RPF_IMPL_SCHED && !RPF_IMPL_LISTED
 hipError_t impl_pixel_stats(const PassParams &p, uint64_t pix0, uint64_t pix1, hipStream_t s) {
     if (p.S >= 16 && p.S <= 128 && pix1 > pix0) { // (below 16 spp neighbouring threads share their cache lines: the plain kernel reads at full rate)
         const int PB = p.S <= 32 ? 256 : (p.S <= 64 ? 128 : 64);
@@ -2546,7 +2591,7 @@ hipError_t impl_nbhd_count(const PassParams &p, int step, uint32_t *probe, const
     hipLaunchKernelGGL(nbhd_count_kernel, dim3(grid), dim3(256), 0, s, p, step, probe, list, list_count);
     return hipGetLastError();
 }
-#endif // !RPF_IMPL_SCHED
+#endif // !RPF_IMPL_SCHED && !RPF_IMPL_LISTED
 #elif RPF_IMPL_PART == 2
 hipError_t impl_filter_mid(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s) {
     switch (samples_per_lane(p.nmax)) {
@@ -2587,11 +2632,15 @@ hipError_t impl_nbhd_count_member(const PassParams &p, const double *mt, hipStre
 #else
 #error "RPF_IMPL_PART must be 1, 2, 3 or 4"
 #endif
-#if RPF_IMPL_SCHED
+#if RPF_IMPL_SCHED || RPF_IMPL_LISTED
 #undef impl_filter_small
 #undef impl_filter_mid
 #undef impl_filter_large
+#if RPF_IMPL_LISTED && !RPF_IMPL_SCHED
+#undef impl_filter_mid_phase
+#undef impl_filter_large_phase
+#endif
 #if RPF_IMPL_PART == 4
-#error "part 4 has no scheduled build: the count pass has no stage 3c"
+#error "part 4 has no scheduled and no listed build: the count pass has no stage 3c and lists nothing"
 #endif
 #endif

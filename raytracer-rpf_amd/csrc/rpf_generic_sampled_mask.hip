@@ -22,7 +22,12 @@
 // No member pool, no cursor, no flat-pixel proof (S + D bounds N by construction).
 // LDS (dynamic, sized at the launch): the threshold table (512 words), then per wave mask_stride u64 and draws u16 rounded up to
 // 8 bytes: 2048 + 4 * (8 * 1024 + 2 * 3136) = 59904 bytes at the widest window and the most draws.
+//
+// sampled_count_list_kernel (RPF_FLAG_SAMPLED_LISTED, route 12) is steps 1 to 4 with another last step: the
+// accepted plane offsets go to route 8's member pool, for the listed builds of the compiled kernels.  Same LDS; no mask buffer.
 #include "rpf_generic_sampled_draws.h"
+
+#include <algorithm>
 
 namespace rpf {
 namespace generic {
@@ -36,43 +41,50 @@ struct SampledMaskOut {
     const double *member;        // MEMBER: mult[RPF_MAX_NDIM] | floor[RPF_MAX_NDIM]; the other instantiation does not read it
 };
 
+// the second argument of sampled_count_list_kernel (route 12): the member pool in front, as in the count
+// kernels of routes 7 to 9, then what SampledMaskOut holds
+struct SampledListOut {
+    MemberPool m;                // base: of a pixel with N > S
+    const uint32_t *table;
+    uint64_t seed;
+    int32_t pass_id, row_origin, draws;
+    uint32_t queue_bytes;
+    const double *member;
+};
+
 // One wave per pixel of rows [row_begin, row_end).  p.masks / p.mask_stride: the window's words; ncand <= 64 * p.mask_stride.
 template <class T, bool MEMBER = false>
 __global__ __launch_bounds__(256) void sampled_count_mask_kernel(PassParams p, SampledMaskOut o) {
     extern __shared__ __align__(16) unsigned char sm_lds[];
-    uint32_t *sT = reinterpret_cast<uint32_t *>(sm_lds); // [kScTable]
-    const int nT = p.box - 1;
-    for (int k = threadIdx.x; k < nT; k += 256) sT[k] = o.table[k];
-    __syncthreads(); // the only barrier: before any wave leaves
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t npix = (uint32_t)(p.row_end - p.row_begin) * (uint32_t)p.W;
-    const uint32_t e = blockIdx.x * 4u + (uint32_t)wv;
-    if (e >= npix) return; // wave-uniform
-    const uint32_t wave_bytes = p.mask_stride * 8u + o.queue_bytes;
-    unsigned long long *bits = reinterpret_cast<unsigned long long *>(sm_lds + kScTable * 4u + (uint32_t)wv * wave_bytes); // [mask_stride]
-    uint16_t *queue = reinterpret_cast<uint16_t *>(bits + p.mask_stride);                                            // [draws]
-    const int W = p.W, H = p.H, S = p.S, b = p.b;
-    const uint64_t HW = (uint64_t)H * W;
-    const uint64_t pix = (uint64_t)p.row_begin * W + e;
-    const int y = (int)(pix / (uint32_t)W), x = (int)(pix - (uint64_t)y * W);
-    const int nF = p.lay.nF, colF = 5 + p.lay.nR;
-    const int D = o.draws; // 1 .. kMaxResident - S (the route's condition)
+#include "rpf_generic_sampled_bitmap.inc"
+    // ---- 5: the words and N ----------------------------------------------------------------------------------------------------
+    uint64_t *pm = p.masks + pix * p.mask_stride;
+    for (int w = lane; w < nw; w += 64) pm[w] = bits[w];
+    if (lane == 0) p.nbhd[pix] = S + acc;
+}
 
-    const uint64_t h = sc_pixel_key(o, x, y);
-    const Window win = make_window(x, y, b, W, H, S);
-    const int nw = (win.ncand + 63) >> 6; // <= p.mask_stride (the launch checks the stride against the box)
-
-    // ---- 1, 2: the bitmap of the pixel's D draws ------------------------------------------------------
-    for (int w = lane; w < nw; w += 64) bits[w] = 0ull;
-    wsync();
-    for (int q = lane; q < D; q += 64) {
-        const uint32_t qq = sc_draw(h, q, sT, nT, win, x, y, b, W, H, S); // < ncand, or kScNone
-        if (qq != kScNone) atomicOr(&bits[qq >> 6], 1ull << (qq & 63u));
+// The listing form (route 12): steps 1 to 4 as above -- p.mask_stride says how many words a wave's bitmap
+// has, p.masks is not read -- then
+//   5. N = S + the accepted entries, and for acc > 0 one cursor reservation for the pixel (publish_members' statements: a pool too
+//      small loses the writes, never the reservation); the bits that are left are walked once more, in ascending qq as in step 3,
+//      and the plane offset of each (candidate_offset) goes to its rank behind the reservation.
+// The pool content is sampled_count_kernel's: the same draws, the same test, the same order.  Nothing is staged: the bitmap is the list.
+template <class T, bool MEMBER = false>
+__global__ __launch_bounds__(256) void sampled_count_list_kernel(PassParams p, SampledListOut o) {
+    extern __shared__ __align__(16) unsigned char sm_lds[];
+#include "rpf_generic_sampled_bitmap.inc"
+    if (lane == 0) p.nbhd[pix] = S + acc;
+    if (acc == 0) return; // wave-uniform
+    uint32_t lo = 0u, hi = 0u;
+    if (lane == 0) {
+        const unsigned long long at = atomicAdd(o.m.cursor, (unsigned long long)acc);
+        o.m.base[pix] = at;
+        lo = (uint32_t)at; hi = (uint32_t)(at >> 32);
     }
-    wsync();
-    // ---- 3: the set bits in ascending qq, at most min(D, ncand) of them ------------------------------------------------------
-    int qn = 0;
+    const uint64_t at0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)hi) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)lo);
+    if (at0 + (uint64_t)acc > o.m.capacity) return; // wave-uniform: the host grows the pool and repeats the launch
+    uint32_t *out = o.m.pool + at0;
+    int done = 0; // ranks handed out so far: ends at acc
     for (int w0 = 0; w0 < nw; w0 += 64) {
         const int w = w0 + lane;
         unsigned long long m = w < nw ? bits[w] : 0ull;
@@ -83,30 +95,13 @@ __global__ __launch_bounds__(256) void sampled_count_mask_kernel(PassParams p, S
             const int t = __shfl_up(incl, d, 64);
             if (lane >= d) incl += t;
         }
-        int at = qn + incl - cnt;
+        int at = done + incl - cnt;
         while (m != 0ull) {
-            queue[at++] = (uint16_t)(w * 64 + (__ffsll((long long)m) - 1));
+            out[at++] = candidate_offset(win, W, S, w * 64 + (__ffsll((long long)m) - 1));
             m &= m - 1ull;
         }
-        qn += __shfl(incl, 63, 64);
+        done += __shfl(incl, 63, 64);
     }
-    wsync();
-    // ---- 4: stage 1b's test on the distinct draws, 64 at a time (rpf.cpp:576-586) ----------------------------------------------
-    int acc = 0;
-    for (int kb = 0; kb < qn; kb += 64) {
-        const int k = kb + lane;
-        const bool live = k < qn;
-        const uint32_t qq = live ? (uint32_t)queue[k] : 0u;
-        const uint32_t off = live ? candidate_offset(win, W, S, (int)qq) : 0u;
-        const bool pass = passes_stage1b_wave<T, MEMBER>(p, o.member, colF, nF, off, HW, pix, live);
-        if (live && !pass) atomicAnd(&bits[qq >> 6], ~(1ull << (qq & 63u)));
-        acc += __popcll(__ballot(pass));
-    }
-    wsync();
-    // ---- 5: the words and N ----------------------------------------------------------------------------------------------------
-    uint64_t *pm = p.masks + pix * p.mask_stride;
-    for (int w = lane; w < nw; w += 64) pm[w] = bits[w];
-    if (lane == 0) p.nbhd[pix] = S + acc;
 }
 
 } // namespace
@@ -127,6 +122,31 @@ hipError_t launch_sampled_count_mask(const PassParams &p, const SampledCountArgs
     const dim3 grid((unsigned)((npix + 3) / 4));
     dispatch_count_kernel(p, a.member, [&](auto plane, auto with_member) {
         hipLaunchKernelGGL((sampled_count_mask_kernel<typename decltype(plane)::type, decltype(with_member)::value>), grid, dim3(256), lds, s, p, o);
+    });
+    return hipGetLastError();
+}
+
+hipError_t launch_sampled_count_list(const PassParams &p, const SampledCountArgs &a, const MemberPool &m, hipStream_t s) {
+    if (m.pool == nullptr || m.base == nullptr || m.cursor == nullptr || a.table == nullptr || p.nbhd == nullptr) return hipErrorInvalidValue;
+    if (p.S < 1 || a.draws < 1 || (int64_t)p.S + a.draws > kMaxResident || p.box < 1 || p.box - 1 > kScTable || !p.lay.generic_ok())
+        return hipErrorInvalidValue;
+    // the bitmap holds the window: every qq in 16 bits
+    const int64_t window = (int64_t)(p.box * p.box - 1) * p.S;
+    if (window > kMaxNbhd) return hipErrorInvalidValue;
+    if (p.row_end <= p.row_begin) return hipSuccess;
+    hipError_t e;
+    if ((e = hipMemsetAsync(m.cursor, 0, sizeof(unsigned long long), s)) != hipSuccess) return e;
+    const uint64_t npix = (uint64_t)(p.row_end - p.row_begin) * p.W;
+    const uint32_t words = (uint32_t)std::max<int64_t>(1, (window + 63) / 64); // <= 1024
+    const uint32_t queue_bytes = ((uint32_t)a.draws * 2u + 7u) & ~7u;
+    const SampledListOut o{m, a.table, a.seed, a.pass_id, a.row_origin, a.draws, queue_bytes, a.member};
+    PassParams q = p; // the bitmap's words travel where the mask kernel has them; no mask buffer
+    q.masks = nullptr; q.mask_stride = words;
+    const size_t lds = (size_t)kScTable * 4 + 4 * ((size_t)words * 8 + queue_bytes);
+    if (lds > 65536) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((npix + 3) / 4));
+    dispatch_count_kernel(p, a.member, [&](auto plane, auto with_member) {
+        hipLaunchKernelGGL((sampled_count_list_kernel<typename decltype(plane)::type, decltype(with_member)::value>), grid, dim3(256), lds, s, q, o);
     });
     return hipGetLastError();
 }

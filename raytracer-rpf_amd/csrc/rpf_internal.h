@@ -66,6 +66,13 @@ enum GenericBits : int32_t {
                               //   kGenericSchedule, option "sampled_fused_stride"): route 11 (route_sampled_fused),
                               //   the size-binned route's class kernels behind generic::sampled_count_mask_kernel.  generic_route looks at
                               //   it before kGenericSampled.  Host-side only: no kernel reads it
+    kGenericSampledListed = 8192, // RPF_FLAG_SAMPLED_LISTED on a pass that carries kGenericSampled and that the listed builds of the compiled
+                              //   kernels can take (setup_pass: a compiled layout without RPF_FLAG_GENERIC, S + draws <= kMaxResident, not
+                              //   forced wide, no kGenericSchedule; with kGenericSampledFused possible too, option "sampled_listed_stride"
+                              //   picks one): route 12 (route_sampled_listed), the size-binned route's class kernels
+                              //   in their listed builds (rpf_impl_*_listed_*.hip: launch_filter_pass and launch_filter_packed dispatch on
+                              //   it) behind a count kernel that lists into the member pool.  Never together with kGenericSampledFused or
+                              //   kGenericWide; generic_route looks at it before kGenericSampled.  Host-side only: no kernel reads it
 };
 // what routes a pass: its bits without the one that only picks the build of the compiled kernels
 inline int32_t route_bits(int32_t generic) { return generic & ~kGenericScheduleFused; }
@@ -155,9 +162,13 @@ struct Tuning {
     int32_t wide = -1;           // RPF_FLAG_WIDE_NBHD: -1 auto (passes with box*box*S > 65535 on the wide kernel), 1 every pass of such a call (test hook)
     int32_t packed = -1;         // small neighbourhoods (N <= 64) on the packed kernels, several pixels per wave: -1 auto (on), 0 off, 1 on
     int32_t sampled_fused_stride = -1; // RPF_FLAG_SAMPLED_FUSED: the largest mask stride (u64 words per pixel, ceil((box*box - 1) * S / 64)) at which a sampled pass takes route 11: -1 no bound, else that many; a pass above it stays on route 8 (test hook)
+    int32_t sampled_listed_stride = -1; // RPF_FLAG_SAMPLED_LISTED together with RPF_FLAG_SAMPLED_FUSED: the smallest mask stride from which a sampled pass that both routes can take runs on route 12: -1 auto (kSampledListedStride), else 0 .. 1025 (0: always route 12, 1025: never where route 11 applies); a pass route 11 cannot take is route 12's whatever it says
     int64_t wide_pool = -1;      // RPF_FLAG_WIDE_CLASSES: entries of the member pool at the first count launch: -1 auto (8 per pixel of the slab), else that many (test hook: a pool too small is grown to the exact size and the count launch repeated; same results)
-    bool is_default() const { return waves_per_pixel == 0 && table_in_lds == -1 && lds_pad == 0 && binning == -1 && stage_mask == -1 && screen == 1 && strip_w == 0 && split_chunk == 0 && count_first == -1 && split_weights == -1 && packed == -1 && wide == -1 && wide_pool == -1 && sampled_fused_stride == -1; }
+    bool is_default() const { return waves_per_pixel == 0 && table_in_lds == -1 && lds_pad == 0 && binning == -1 && stage_mask == -1 && screen == 1 && strip_w == 0 && split_chunk == 0 && count_first == -1 && split_weights == -1 && packed == -1 && wide == -1 && wide_pool == -1 && sampled_fused_stride == -1 && sampled_listed_stride == -1; }
 };
+// what option "sampled_listed_stride" = -1 stands for: the smallest mask stride of the measured schedules from which route 12 beat
+// route 11 on both frames by more than either side's spread (DESIGN.md section 13g has the table): box 17 x 32 spp; 1025 would say: at no stride
+constexpr int32_t kSampledListedStride = 144;
 
 struct LdsLayout {
     uint32_t off_T, off_stat, off_hx, off_pair, off_mi, off_own, off_off, off_union, off_hist, total;
@@ -361,6 +372,11 @@ hipError_t launch_sampled_count(const PassParams &p, const SampledCountArgs &a, 
 // p.nbhd and, for every pixel of rows [p.row_begin, p.row_end), the ceil(ncand / 64) acceptance words of its window into p.masks
 // ([H*W][p.mask_stride] u64, which must be given: bit qq = candidate qq of the visiting order).  No pool, no cursor
 hipError_t launch_sampled_count_mask(const PassParams &p, const SampledCountArgs &a, hipStream_t s);
+// the count pass of route 12 for windows of box*box*S <= kMaxNbhd (rpf_generic_sampled_mask.hip), S + draws <=
+// kMaxResident: the mask kernel's bitmap, draws, compaction and test, and launch_sampled_count's result -- the accepted plane offsets
+// in ascending visiting order into m.pool[m.base[pix] ..] behind one cursor reservation per pixel with N > S, N into p.nbhd,
+// *m.cursor (zeroed here) as launch_wide_count leaves it.  Reads neither p.masks nor p.mask_stride
+hipError_t launch_sampled_count_list(const PassParams &p, const SampledCountArgs &a, const MemberPool &m, hipStream_t s);
 } // namespace generic
 
 // ---- the spike pass (rpf_spike.hip, RPF_FLAG_SPIKE_CLAMP) -----------------------------------------------

@@ -248,6 +248,18 @@ __global__ __launch_bounds__(256) void nbhd_reduce_kernel(const int32_t *nbhd, u
     hipError_t impl_filter_large_sched(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
     hipError_t impl_filter_packed_sched(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s); \
     }                                                                                                                     \
+    namespace listed { /* the listed builds (rpf_impl_*_listed_*.hip): a pass that carries kGenericSampledListed */         \
+    hipError_t impl_filter_small_listed(const PassParams &p, const LdsLayout &L, bool t_in_lds, unsigned grid, hipStream_t s); \
+    hipError_t impl_filter_mid_listed(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
+    hipError_t impl_filter_large_listed(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
+    hipError_t impl_filter_packed_listed(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s); \
+    namespace sched { /* ... and kGenericScheduleFused with it (rpf_impl_*_listed_sched_*.hip) */                           \
+    hipError_t impl_filter_small_listed_sched(const PassParams &p, const LdsLayout &L, bool t_in_lds, unsigned grid, hipStream_t s); \
+    hipError_t impl_filter_mid_listed_sched(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
+    hipError_t impl_filter_large_listed_sched(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
+    hipError_t impl_filter_packed_listed_sched(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s); \
+    }                                                                                                                     \
+    }                                                                                                                     \
     }
 RPF_DECLARE_IMPL(d19) // the reference's 19 dims (2 random parameters, 12 features), fp32 planes
 RPF_DECLARE_IMPL(d27) // BASELINE configs[4]: 27 dims (4 random parameters, 18 features), fp16 feature storage
@@ -419,15 +431,24 @@ hipError_t launch_filter_pass(const PassParams &p, const Tuning &tun, hipStream_
     if (K == 0) return hipErrorInvalidValue;
     // a scheduled pass (kGenericScheduleFused: RPF_FLAG_SCHEDULE_FUSED, a gain other than 1) runs the scheduled builds of the same parts
     const bool sc = (p.generic & kGenericScheduleFused) != 0;
+    // a listed pass (kGenericSampledListed: RPF_FLAG_SAMPLED_LISTED, route 12) runs the listed builds, which copy their member lists from the pool
+    const bool li = (p.generic & kGenericSampledListed) != 0;
+    if (li && (p.members == nullptr || p.member_base == nullptr || p.pix_list == nullptr || p.fast_weights)) return hipErrorInvalidValue;
     const auto small = [&](const PassParams &q, unsigned g) {
+        if (li && sc) return r19 ? d19::listed::sched::impl_filter_small_listed_sched(q, L, t_in_lds, g, s) : d27::listed::sched::impl_filter_small_listed_sched(q, L, t_in_lds, g, s);
+        if (li) return r19 ? d19::listed::impl_filter_small_listed(q, L, t_in_lds, g, s) : d27::listed::impl_filter_small_listed(q, L, t_in_lds, g, s);
         if (sc) return r19 ? d19::sched::impl_filter_small_sched(q, L, t_in_lds, g, s) : d27::sched::impl_filter_small_sched(q, L, t_in_lds, g, s);
         return r19 ? d19::impl_filter_small(q, L, t_in_lds, g, s) : d27::impl_filter_small(q, L, t_in_lds, g, s);
     };
     const auto mid = [&](const PassParams &q, unsigned g) {
+        if (li && sc) return r19 ? d19::listed::sched::impl_filter_mid_listed_sched(q, L, L2, L3, t_in_lds, g, s) : d27::listed::sched::impl_filter_mid_listed_sched(q, L, L2, L3, t_in_lds, g, s);
+        if (li) return r19 ? d19::listed::impl_filter_mid_listed(q, L, L2, L3, t_in_lds, g, s) : d27::listed::impl_filter_mid_listed(q, L, L2, L3, t_in_lds, g, s);
         if (sc) return r19 ? d19::sched::impl_filter_mid_sched(q, L, L2, L3, t_in_lds, g, s) : d27::sched::impl_filter_mid_sched(q, L, L2, L3, t_in_lds, g, s);
         return r19 ? d19::impl_filter_mid(q, L, L2, L3, t_in_lds, g, s) : d27::impl_filter_mid(q, L, L2, L3, t_in_lds, g, s);
     };
     const auto large = [&](const PassParams &q, unsigned g) {
+        if (li && sc) return r19 ? d19::listed::sched::impl_filter_large_listed_sched(q, L, L2, L3, t_in_lds, g, s) : d27::listed::sched::impl_filter_large_listed_sched(q, L, L2, L3, t_in_lds, g, s);
+        if (li) return r19 ? d19::listed::impl_filter_large_listed(q, L, L2, L3, t_in_lds, g, s) : d27::listed::impl_filter_large_listed(q, L, L2, L3, t_in_lds, g, s);
         if (sc) return r19 ? d19::sched::impl_filter_large_sched(q, L, L2, L3, t_in_lds, g, s) : d27::sched::impl_filter_large_sched(q, L, L2, L3, t_in_lds, g, s);
         return r19 ? d19::impl_filter_large(q, L, L2, L3, t_in_lds, g, s) : d27::impl_filter_large(q, L, L2, L3, t_in_lds, g, s);
     };
@@ -468,6 +489,13 @@ hipError_t launch_nbhd_count_member(const PassParams &p, const double *member, h
 
 hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s) {
     if (!p.lay.supported()) return hipErrorNotSupported;
+    if (p.generic & kGenericSampledListed) { // a listed pass: the listed build of the packed kernels (rpf_impl_*_listed_small.hip), scheduled or not
+        if (p.generic & kGenericScheduleFused)
+            return p.lay.is_ref19() ? d19::listed::sched::impl_filter_packed_listed_sched(p, lanes_per_pixel, count_dev, s)
+                                    : d27::listed::sched::impl_filter_packed_listed_sched(p, lanes_per_pixel, count_dev, s);
+        return p.lay.is_ref19() ? d19::listed::impl_filter_packed_listed(p, lanes_per_pixel, count_dev, s)
+                                : d27::listed::impl_filter_packed_listed(p, lanes_per_pixel, count_dev, s);
+    }
     if (p.generic & kGenericScheduleFused) // a scheduled pass: the scheduled build of the packed kernels (rpf_impl_*_sched_small.hip)
         return p.lay.is_ref19() ? d19::sched::impl_filter_packed_sched(p, lanes_per_pixel, count_dev, s)
                                 : d27::sched::impl_filter_packed_sched(p, lanes_per_pixel, count_dev, s);

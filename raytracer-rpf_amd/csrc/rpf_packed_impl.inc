@@ -221,7 +221,10 @@ __global__ __launch_bounds__(64 * kPkWaves, kRef19 ? 2 : 1) void filter_packed_k
     const int centre_rank = (x - x0) * nyv + (y - y0);
     const int ncand = ((x1 - x0 + 1) * nyv - 1) * S;
     uint32_t off = (uint32_t)(pix * S) + (uint32_t)min(t, S - 1); // own samples first
-    {
+    if constexpr (kListed) {
+        // a listed build (RPF_IMPL_LISTED): the count kernel listed the members behind the own samples as plane offsets, in order
+        if (live && t >= S) off = p.members[p.member_base[pix] + (uint64_t)(t - S)];
+    } else {
         int rank = (live && t >= S) ? t - S : -1;            // the rank-th accepted candidate of the window
         const int nwords = (ncand + 63) >> 6;
         const uint64_t *pm = p.masks + pix * p.mask_stride;
@@ -651,13 +654,19 @@ hipError_t launch_packed_inst(const PassParams &p, const uint32_t *count_dev, ui
 // entry point: pixels of p.pix_list with N <= lanes_per_pixel (8, 16, 32, 64); needs the acceptance masks and the N plane
 // (count pass, or filter_pixel_kernel's re-route).  count_dev != null: the list size is read on the device and
 // p.list_count is only its upper bound (sizes the grid).  (A scheduled build, RPF_IMPL_SCHED: impl_filter_packed_sched)
-#if RPF_IMPL_SCHED
+// (A listed build, RPF_IMPL_LISTED: impl_filter_packed_listed / impl_filter_packed_listed_sched; it needs the member pool for the masks)
+#if RPF_IMPL_SCHED && RPF_IMPL_LISTED
+hipError_t impl_filter_packed_listed_sched(
+#elif RPF_IMPL_LISTED
+hipError_t impl_filter_packed_listed(
+#elif RPF_IMPL_SCHED
 hipError_t impl_filter_packed_sched(
 #else
 hipError_t impl_filter_packed(
 #endif
 const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s) {
-    if (p.masks == nullptr || p.pix_list == nullptr || p.S > lanes_per_pixel) return hipErrorInvalidValue;
+    if (kListed ? (p.members == nullptr || p.member_base == nullptr) : p.masks == nullptr) return hipErrorInvalidValue;
+    if (p.pix_list == nullptr || p.S > lanes_per_pixel) return hipErrorInvalidValue;
     switch (lanes_per_pixel) {
     case 8: return launch_packed_inst<8>(p, count_dev, p.list_count, s);
     case 16: return launch_packed_inst<16>(p, count_dev, p.list_count, s);

@@ -90,7 +90,14 @@ SAMPLED_MAX = 8192  # RPF_SAMPLED_MAX
 # cannot be one more integer of the module's dict without failing that test.  Such bits are kept in this table and served by the
 # module's __getattr__ / __dir__ (PEP 562): hip.SAMPLED_FUSED_FLAG, getattr and dir(hip) work as for the others, vars(hip) does not
 # list it.  Once that test's census is bounded by its own bit, the entry becomes a plain constant like its neighbours
-_LATER_BITS = {"SAMPLED_FUSED_FLAG": 262144}
+#
+# SAMPLED_LISTED_FLAG (RPF_FLAG_SAMPLED_LISTED of the header) modifies SAMPLED_NBHD_FLAG too: a sampled pass of
+# the call on a compiled layout (no FLAG_GENERIC, S + draws <= 3136, not forced wide, no schedule gain other than 1 unless
+# SCHEDULE_FUSED_FLAG) runs on the listed builds of the compiled kernels, which copy route 8's member lists from the member pool:
+# route 12.  Wide windows (box*box*S > 65535 with FLAG_WIDE_NBHD) included; no mask buffer.  With SAMPLED_FUSED_FLAG as well, option
+# "sampled_listed_stride" picks between routes 11 and 12 where both apply.  Every other pass runs as without it.  Refused without
+# SAMPLED_NBHD_FLAG.  Its table: tests/test_sampled_listed_cpu.py
+_LATER_BITS = {"SAMPLED_FUSED_FLAG": 262144, "SAMPLED_LISTED_FLAG": 524288}
 
 
 def __getattr__(name):
@@ -609,7 +616,7 @@ class Context:
         (FLAG_GENERIC), 4 the same with small neighbourhoods packed (FLAG_GENERIC_PACKED), 5 the same with
         64 < N <= 832 on the one-wave generic kernels (FLAG_GENERIC_WAVE; 3 for a pass with S > 832), 6 the wide kernel
         (FLAG_WIDE_NBHD on a pass with box*box*S > 65535), 7 such a pass dealt by size class (FLAG_WIDE_CLASSES), 8 a sampled
-        pass (SAMPLED_NBHD_FLAG with draws > 0), 9 a full-box pass under MEMBER_TEST_FLAG, 10 such a pass on the compiled kernels (MEMBER_FUSED_FLAG), 11 a sampled pass on the compiled kernels (SAMPLED_FUSED_FLAG); -1 before any pass.  FLAG_GENERIC_FAST and FLAG_STREAM_FAST change no route
+        pass (SAMPLED_NBHD_FLAG with draws > 0), 9 a full-box pass under MEMBER_TEST_FLAG, 10 such a pass on the compiled kernels (MEMBER_FUSED_FLAG), 11 a sampled pass on the compiled kernels (SAMPLED_FUSED_FLAG), 12 a sampled pass on their listed builds (SAMPLED_LISTED_FLAG); -1 before any pass.  FLAG_GENERIC_FAST and FLAG_STREAM_FAST change no route
         (rpf_query_route)"""
         r = C.c_int32(-1)
         self._check(self._L.rpf_query_route(self._h, C.byref(r)))

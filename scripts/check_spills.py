@@ -194,10 +194,11 @@ def metadata(path):
 
 def demangle_short(name):
     m = re.search(r"(d19|d27)(\d+)(\w+?)(I.*)?E?v?NS_", name)
-    ns = re.search(r"3rpf\d+(d19|d27|generic)(5sched)?", name)  # (d19::sched / d27::sched: the scheduled builds, RPF_IMPL_SCHED)
+    # (d19::sched / d27::sched: the scheduled builds, RPF_IMPL_SCHED; ::listed and ::listed::sched: the listed ones, RPF_IMPL_LISTED)
+    ns = re.search(r"3rpf\d+(d19|d27|generic)(6listed)?(5sched)?", name)
     k = re.search(r"kernelILi(\d+)ELb(\d)ELb(\d)ELi(\d)ELi(\d)E", name)
     base = re.search(r"\d+([a-z_]+kernel)", name)
-    s = (ns.group(1) + "::" + ("sched::" if ns.group(2) else "") if ns else "") + (base.group(1) if base else name[:60])
+    s = (ns.group(1) + "::" + ("listed::" if ns.group(2) else "") + ("sched::" if ns.group(3) else "") if ns else "") + (base.group(1) if base else name[:60])
     if k:
         s += "<K=%s,TL=%s,FAST=%s,NW=%s,PHASE=%s>" % k.groups()
     # the layout-generic kernels: the plane type, and FAST where a kernel has the fp32 stage-4 instantiation (RPF_FLAG_GENERIC_FAST)
@@ -205,7 +206,7 @@ def demangle_short(name):
     # only flag of the count kernels; LISTED where generic::filter_pixel_kernel reads listed members (its third parameter)
     t = re.search(r"3rpf7generic.*kernelI(f|6__half)(?:Lb([01])E)?(?:Lb([01])E)?E", name)
     if t:
-        count = re.search(r"(wide|sampled)_count(_block|_mask)?_kernel", name) is not None
+        count = re.search(r"(wide|sampled)_count(_block|_mask|_list)?_kernel", name) is not None
         pixel = re.search(r"\d+filter_pixel_kernel", name) is not None
         fast = t.group(2) == "1" and not count
         member = (t.group(3) == "1" and not pixel) or (count and t.group(2) == "1")
