@@ -82,13 +82,13 @@ def stats_of(oracle, planes, policy=EPS, n_random=2, n_feat=12):
     return oracle.pixel_stats(p32, oracle.make_desc(W, H, S, policy=policy, **lay))
 
 
-def counts(oracle, planes, mt, box, n_random=2, n_feat=12, cfg=None, pass_id=0):
+def counts(oracle, planes, mt, box, n_random=2, n_feat=12, cfg=None, pass_id=0, rows=None):
     """(N [H, W], member codes per pixel) without the later stages"""
     p32 = np.ascontiguousarray(planes, np.float32)
     _, H, W, S = p32.shape
     pmean, pstd = stats_of(oracle, p32, EPS, n_random, n_feat)
     n, codes = np.zeros((H, W), np.int32), {}
-    for y in range(H):
+    for y in (range(H) if rows is None else rows):
         for x in range(W):
             _, c = members(p32, pmean, pstd, mt, y, x, box, n_random, n_feat, None, cfg, pass_id)
             n[y, x], codes[(y, x)] = len(c), c
@@ -96,10 +96,10 @@ def counts(oracle, planes, mt, box, n_random=2, n_feat=12, cfg=None, pass_id=0):
 
 
 def member_pass(oracle, planes, mt, box, seed_sigma=0.002, policy=EPS, beta_map=0, eps=1e-10, n_random=2, n_feat=12,
-                colour64=None, weights=True, cfg=None, pass_id=0):
+                colour64=None, weights=True, cfg=None, pass_id=0, rows=None):
     """one pass over every pixel of fp32 (or fp16-valued) `planes` [ndim, H, W, S] under the test mt = (mult, floor): nbhd_size,
     member_hash, mean, stddev and -- weights, the 19-dim layout only -- mi, alpha, beta, wrc, colour; `codes`: the member codes
-    of every pixel"""
+    of every pixel.  rows (here, in counts and in stage4_on): restate these rows alone, the others stay zero"""
     p32 = np.ascontiguousarray(planes, np.float32)
     nd, H, W, S = p32.shape
     pmean, pstd = stats_of(oracle, p32, policy, n_random, n_feat)
@@ -109,7 +109,7 @@ def member_pass(oracle, planes, mt, box, seed_sigma=0.002, policy=EPS, beta_map=
         assert (n_random, n_feat) == (2, 12)
         out.update(mi=np.zeros((H, W, 96)), alpha=np.zeros((H, W, 3)), beta=np.zeros((H, W, 12)), wrc=np.zeros((H, W)),
                    colour=np.zeros((3, H, W, S)))
-    for y in range(H):
+    for y in (range(H) if rows is None else rows):
         for x in range(W):
             nb, codes = members(p32, pmean, pstd, mt, y, x, box, n_random, n_feat, colour64, cfg, pass_id)
             M, SD = oracle.mean_std(nb)
@@ -127,14 +127,14 @@ def member_pass(oracle, planes, mt, box, seed_sigma=0.002, policy=EPS, beta_map=
     return out
 
 
-def stage4_on(oracle, planes, got, mt, box, seed_sigma, policy=EPS, colour64=None, cfg=None, pass_id=0):
+def stage4_on(oracle, planes, got, mt, box, seed_sigma, policy=EPS, colour64=None, cfg=None, pass_id=0, rows=None):
     """fast_weights_ref's stage 4 for a pass under the test: the colours of every pixel from the restatement's member rows and
     the stage outputs `got` (the device's own: the design of tests/test_stage4_per_sample_gpu.py); [3, H, W, S]"""
     p32 = np.ascontiguousarray(planes, np.float32)
     _, H, W, S = p32.shape
     pmean, pstd = stats_of(oracle, p32, policy)
-    out = np.empty((3, H, W, S))
-    for y in range(H):
+    out = np.empty((3, H, W, S)) if rows is None else np.zeros((3, H, W, S))
+    for y in (range(H) if rows is None else rows):
         for x in range(W):
             nb, _ = members(p32, pmean, pstd, mt, y, x, box, colour64=colour64, cfg=cfg, pass_id=pass_id)
             assert nb.shape[0] == got["nbhd_size"][y, x], ((y, x), nb.shape[0], int(got["nbhd_size"][y, x]))

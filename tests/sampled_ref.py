@@ -147,10 +147,10 @@ def is_subsequence(a, b):
 
 
 def sampled_pass(oracle, planes, cfg, pass_id, box, seed_sigma=0.002, policy=EPS, beta_map=0, eps=1e-10, n_random=2, n_feat=12,
-                 colour64=None, weights=True):
+                 colour64=None, weights=True, rows=None):
     """one sampled pass over every pixel of fp32 (or fp16-valued) `planes` [ndim, H, W, S]: nbhd_size, member_hash, mean, stddev
     and -- weights, the 19-dim layout only: rpf_oracle_cf_weights is 19-dim -- mi, alpha, beta, wrc, colour; `codes`: the member
-    codes of every pixel.  cfg = (seed, row_origin, D)"""
+    codes of every pixel.  cfg = (seed, row_origin, D); rows: restate these rows alone (the others stay zero)"""
     p32 = np.ascontiguousarray(planes, np.float32)
     nd, H, W, S = p32.shape
     lay = dict(n_random=n_random, n_feat=n_feat) if (n_random, n_feat) != (2, 12) else {}
@@ -161,7 +161,7 @@ def sampled_pass(oracle, planes, cfg, pass_id, box, seed_sigma=0.002, policy=EPS
         assert (n_random, n_feat) == (2, 12)
         out.update(mi=np.zeros((H, W, 96)), alpha=np.zeros((H, W, 3)), beta=np.zeros((H, W, 12)), wrc=np.zeros((H, W)),
                    colour=np.zeros((3, H, W, S)))
-    for y in range(H):
+    for y in (range(H) if rows is None else rows):
         for x in range(W):
             nb, codes, _ = members(p32, pmean, pstd, cfg, pass_id, y, x, box, n_random, n_feat, colour64)
             M, SD = oracle.mean_std(nb)
@@ -179,17 +179,18 @@ def sampled_pass(oracle, planes, cfg, pass_id, box, seed_sigma=0.002, policy=EPS
     return out
 
 
-def stage4_on(oracle, planes, got, cfg, pass_id, box, seed_sigma, policy=EPS, colour64=None):
+def stage4_on(oracle, planes, got, cfg, pass_id, box, seed_sigma, policy=EPS, colour64=None, rows=None, n_random=2, n_feat=12):
     """fast_weights_ref.stage4 for a sampled pass: the colours of every pixel from the restatement's member rows and the stage
     outputs `got` (the device's own: the design of tests/test_stage4_per_sample_gpu.py); [3, H, W, S]"""
     p32 = np.ascontiguousarray(planes, np.float32)
     _, H, W, S = p32.shape
-    pmean, pstd = oracle.pixel_stats(p32, oracle.make_desc(W, H, S, policy=policy))
-    out = np.empty((3, H, W, S))
-    for y in range(H):
+    lay = dict(n_random=n_random, n_feat=n_feat) if (n_random, n_feat) != (2, 12) else {}
+    pmean, pstd = oracle.pixel_stats(p32, oracle.make_desc(W, H, S, policy=policy, **lay))
+    out = np.empty((3, H, W, S)) if rows is None else np.zeros((3, H, W, S))
+    for y in (range(H) if rows is None else rows):
         for x in range(W):
-            nb, _, _ = members(p32, pmean, pstd, cfg, pass_id, y, x, box, colour64=colour64)
+            nb, _, _ = members(p32, pmean, pstd, cfg, pass_id, y, x, box, n_random, n_feat, colour64)
             assert nb.shape[0] == got["nbhd_size"][y, x], ((y, x), nb.shape[0], int(got["nbhd_size"][y, x]))
             out[:, y, x, :] = R.pixel_colours(nb, S, got["mean"][y, x], got["stddev"][y, x], got["alpha"][y, x], got["beta"][y, x],
-                                              got["wrc"][y, x], box, seed_sigma, policy, np.float64, form="direct")
+                                              got["wrc"][y, x], box, seed_sigma, policy, np.float64, n_random, n_feat, form="direct")
     return out

@@ -106,14 +106,14 @@ def shares(mi, gain, which, eps_or_0, n_random=2, n_feat=12):
         return float((v < 0).mean()), float(((v > 0) & (v < 1)).mean())
 
 
-def pixel_colours(nb, S, M, SD, alpha, beta, wrc, box, seed, policy):
+def pixel_colours(nb, S, M, SD, alpha, beta, wrc, box, seed, policy, n_random=2, n_feat=12):
     """fast_weights_ref.pixel_colours(..., np.float64, form="direct").  A box below 4 has sigma_p = box // 4 = 0 (rpf.cpp:531:
     integer division), and that function forms 1 / (2 sigma_p^2) in Python floats, which raise where IEEE arithmetic gives inf:
     for such a box the same statements follow here with the quotient in numpy doubles.  (inf * 0 = NaN: an own sample meets
     itself at distance 0, its weight and so its colour are NaN, and under EPS the colour falls back to the input.)"""
     if box // 4 > 0:
-        return R.pixel_colours(nb, S, M, SD, alpha, beta, wrc, box, seed, policy, np.float64, form="direct")
-    cols = R.weighted_columns()
+        return R.pixel_colours(nb, S, M, SD, alpha, beta, wrc, box, seed, policy, np.float64, n_random, n_feat, form="direct")
+    cols = R.weighted_columns(n_random, n_feat)
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         z = np.where(SD == 0, 0.0, (nb - M) / SD)[:, cols]
         sigma_p = np.float64(box // 4)
@@ -162,21 +162,21 @@ def scheduled_pass(oracle, planes, entry, box, policy=EPS, beta_map=0, eps=1e-10
     return out
 
 
-def stage4_on(oracle, planes, got, seed, box, policy=EPS, colour64=None, mt=None, cfg=None, pass_id=0):
+def stage4_on(oracle, planes, got, seed, box, policy=EPS, colour64=None, mt=None, cfg=None, pass_id=0, rows=None, n_random=2, n_feat=12):
     """fast_weights_ref's stage 4 on the stage outputs `got` (the device's own: mean, stddev, alpha, beta, wrc) and the
-    restatement's member rows; [3, H, W, S]"""
+    restatement's member rows; [3, H, W, S].  rows: restate these rows alone, the others stay zero"""
     p32 = np.ascontiguousarray(planes, np.float32)
     _, H, W, S = p32.shape
-    pmean, pstd = MR.stats_of(oracle, p32, policy)
-    out = np.empty((3, H, W, S))
-    for y in range(H):
+    pmean, pstd = MR.stats_of(oracle, p32, policy, n_random, n_feat)
+    out = np.empty((3, H, W, S)) if rows is None else np.zeros((3, H, W, S))
+    for y in (range(H) if rows is None else rows):
         for x in range(W):
             if mt is None and cfg is None:
-                nb = R.neighbourhood(p32, pmean, pstd, y, x, box, colour64=colour64)
+                nb = R.neighbourhood(p32, pmean, pstd, y, x, box, n_random, n_feat, colour64=colour64)
             else:
-                nb, _ = MR.members(p32, pmean, pstd, mt if mt is not None else MR.reference(), y, x, box, colour64=colour64, cfg=cfg,
-                                   pass_id=pass_id)
+                nb, _ = MR.members(p32, pmean, pstd, mt if mt is not None else MR.reference(n_feat), y, x, box, n_random, n_feat,
+                                   colour64=colour64, cfg=cfg, pass_id=pass_id)
             assert nb.shape[0] == got["nbhd_size"][y, x], ((y, x), nb.shape[0], int(got["nbhd_size"][y, x]))
             out[:, y, x, :] = pixel_colours(nb, S, got["mean"][y, x], got["stddev"][y, x], got["alpha"][y, x], got["beta"][y, x],
-                                            got["wrc"][y, x], box, seed, policy)
+                                            got["wrc"][y, x], box, seed, policy, n_random, n_feat)
     return out
