@@ -360,6 +360,21 @@ enum {
                                   RPF_FLAG_WIDE_NBHD.  Refused before any device work: the flag without RPF_FLAG_SAMPLED_NBHD
                                   (RPF_E_UNSUPPORTED; rpf_layout_kernels answers the same way); every refusal of
                                   RPF_FLAG_SAMPLED_NBHD stands with it. */
+    RPF_FLAG_GENERIC_QUAD = 1048576, /* opt-in, modifies RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED | RPF_FLAG_GENERIC_WAVE: the
+                                  pixels whose neighbourhood holds 832 < N <= 3136 samples run on the four-wave layout-generic
+                                  kernels -- a 256-thread workgroup per pixel with the member list, the bin ids and T[0 .. capacity]
+                                  resident in LDS, size classes N <= 1600 and 3136, the member list rebuilt from the count pass's
+                                  acceptance masks without a second 3-sigma test -- behind the count pass of the packed flag; only
+                                  N > 3136 stays on the generic filter kernel.  A layout whose LDS carve-up
+                                  does not fit a class (rpf_generic_quad_carve below tells) is not offered it: those pixels stay
+                                  on the generic filter kernel.  Same layouts as the generic flag.  Same membership, bins,
+                                  statistics, MI, alpha, beta and W_r_c as under the generic flag alone; the colours agree to
+                                  rounding.  rpf_query_route says 13 for a pass with S <= 3136 (a pass with 832 < S <= 3136 has
+                                  empty packed and one-wave classes; a pass with S > 3136 is route 3).  A wide, sampled or
+                                  member-test pass of the call runs as without the flag.  fp64 only: without all three of
+                                  RPF_FLAG_GENERIC, RPF_FLAG_GENERIC_PACKED and RPF_FLAG_GENERIC_WAVE, or together with
+                                  RPF_FLAG_FAST_WEIGHTS, RPF_FLAG_GENERIC_FAST or RPF_FLAG_STREAM_FAST, it is RPF_E_UNSUPPORTED,
+                                  from every filter entry point and from rpf_layout_kernels, before any device work. */
     RPF_FLAG_STREAM_FAST = 512/* opt-in, modifies RPF_FLAG_GENERIC and / or RPF_FLAG_WIDE_NBHD: the two kernels that walk a
                                   neighbourhood of any size with 256 threads -- the generic filter kernel (route 3, the rest
                                   list N > 64 / N > 832 of routes 4 / 5) and the wide kernel (route 6, the rest list N > 832 of
@@ -575,7 +590,10 @@ int32_t rpf_filter_pass_debug(rpf_ctx *ctx, const rpf_desc *desc, int32_t box, c
  * sampled neighbourhoods.
  * With RPF_FLAG_SAMPLED_LISTED (route 12) a sampled pass counts as on route 11: one launch per non-empty class of the ten resident
  * ones (the count kernel -- repeated once when the member pool had to grow -- is not counted, and no pixel reaches the streaming
- * class); redo_pixels is 0; sum_nbhd / max_nbhd are those of the sampled neighbourhoods. */
+ * class); redo_pixels is 0; sum_nbhd / max_nbhd are those of the sampled neighbourhoods.
+ * With RPF_FLAG_GENERIC_QUAD (route 13) a pass counts as route 5 does, with one launch more per non-empty four-wave class
+ * (N <= 1600, 3136): the generic filter kernel's launch is for N > 3136, or N above the last class the layout is offered;
+ * redo_pixels includes the pixels the four-wave kernels put on the redo list. */
 int32_t rpf_query_counters(rpf_ctx *ctx, rpf_counters *out);
 
 /* neighbourhood size N of every pixel (rpf.cpp:586: the neighbourhood vector's size) as the last pass of the most recent
@@ -600,6 +618,8 @@ int32_t rpf_query_nbhd(rpf_ctx *ctx, int32_t *nbhd_out, int64_t count);
  * the compiled kernels of route 2 by size class; the same member lists as route 8),
  * 12 = a sampled pass under RPF_FLAG_SAMPLED_LISTED on a compiled layout (a count kernel lists the draws into the member pool, then
  * the listed builds of the compiled kernels by size class; the same member lists as route 8, wide windows included),
+ * 13 = route 5 with 832 < N <= 3136 on the four-wave layout-generic kernels (... | RPF_FLAG_GENERIC_QUAD on a pass with
+ * S <= 3136),
  * -1 = no pass yet.  Option "count_first" (0 / 1) overrides the probe that chooses between 0 and 1.  rpf_filter's row-band
  * pipeline runs that probe once per band, on the rows of the slab that are resident by then -- the last band of a pass on the
  * whole slab -- so the answer after such a call is the serial call's (bands above the last may have taken the other of 0 / 1:
@@ -675,6 +695,13 @@ int32_t rpf_max_nbhd(const rpf_desc *desc, int32_t *nmax_out);
  * check calls this function, so the two cannot drift).  Only S and flags are read.  Needs no context and no device.
  * RPF_E_BADARG for a NULL pointer or S <= 0. */
 int32_t rpf_max_draws(const rpf_desc *desc, int32_t *dmax_out);
+
+/* What the layout of desc gets from RPF_FLAG_GENERIC_QUAD at the size class `capacity` (1600 or 3136): RPF_OK when the LDS
+ * carve-up of the four-wave kernel fits 160 KiB, with *workgroups_per_cu_out = the workgroups a compute unit holds and
+ * *lds_bytes_out = the bytes of one workgroup; RPF_E_UNSUPPORTED when it does not fit (route 13 then leaves the pixels of that
+ * class to the generic filter kernel) or the layout is none the layout-generic kernels take; RPF_E_BADARG for any other capacity
+ * or a NULL desc.  Only n_random, n_feat and plane_dtype are read.  Needs no context and no device.  Either output may be NULL. */
+int32_t rpf_generic_quad_carve(const rpf_desc *desc, int32_t capacity, int32_t *workgroups_per_cu_out, int64_t *lds_bytes_out);
 
 /* The table the wide kernel forms MI from: table_out[k] = round(k ln k * 2^41), k = 0 .. nmax (nmax + 1 entries), computed on
  * the host in long double.  Every entry up to nmax = 262144 is below 2^63 (the 2^-44 table of the other kernels stops being

@@ -26,6 +26,7 @@ KERNEL_TUS += ["rpf_impl_d19_member.hip", "rpf_impl_d27_member.hip"]  # rpf_filt
 KERNEL_TUS += ["rpf_impl_%s_sched_%s.hip" % (lay, part) for lay in ("d19", "d27") for part in ("small", "mid", "large")]
 # ... their listed builds (RPF_IMPL_LISTED: stage 1b from the member pool; RPF_FLAG_SAMPLED_LISTED), and the listed scheduled ones
 KERNEL_TUS += ["rpf_impl_%s_listed_%s%s.hip" % (lay, sc, part) for lay in ("d19", "d27") for sc in ("", "sched_") for part in ("small", "mid", "large")]
+KERNEL_TUS += ["rpf_generic_quad.hip"]  # the four-wave layout-generic kernels for 832 < N <= 3136 (RPF_FLAG_GENERIC_QUAD)
 KERNEL_TUS += ["rpf_report.hip"]  # the per-pass activity report: per-pixel chains, per-row chains and counts (RPF_FLAG_PASS_REPORT)
 # the C ABI (host code only; rpf_api.h is what they share): context, validation and pass loops | pass router | film step | multi-GPU | spike pass | pass report
 # (the names start with rpf_api: the spill scan below skips them by that)
@@ -87,7 +88,7 @@ def _build(LIB, OBJ_DIR, defs, shipped, force, verbose):
         if force or _stale(obj, [src] + HEADERS):
             # -save-temps=obj keeps the device assembly next to the object: scripts/check_spills.py reads it below
             cmds.append([hipcc_path()] + flags + ["-save-temps=obj", "-c", src, "-o", obj])
-    # at most MAX_JOBS compilers at a time, 16 at the most (43 translation units: one hipcc each all at once oversubscribes a
+    # at most MAX_JOBS compilers at a time, 16 at the most (44 translation units: one hipcc each all at once oversubscribes a
     # machine that gives the build a share of its cores).  The largest units (the rpf_impl_* parts) start first
     jobs = max(1, min(16, int(os.environ.get("MAX_JOBS", 16))))
     cmds.sort(key=lambda c: not os.path.basename(c[-3]).startswith("rpf_impl_"))

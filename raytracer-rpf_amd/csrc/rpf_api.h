@@ -63,6 +63,7 @@ enum Route : int {
     kRouteMemberFused = 10,  // ... with RPF_FLAG_MEMBER_FUSED, on a compiled layout: route 2's structure behind the configured test
     kRouteSampledFused = 11, // a sampled pass under RPF_FLAG_SAMPLED_FUSED on a compiled layout: route 2's class kernels behind the draws' mask kernel
     kRouteSampledListed = 12, // ... under RPF_FLAG_SAMPLED_LISTED: the listed builds of route 2's class kernels behind a count kernel that lists into the member pool
+    kRouteGenericQuad = 13,  // route 5 with 832 < N <= 3136 on the four-wave layout-generic kernels (RPF_FLAG_GENERIC_QUAD)
 };
 
 static_assert(sizeof(rpf_sampling) == 48 && offsetof(rpf_sampling, draws) == 16, "rpf_sampling is ABI");

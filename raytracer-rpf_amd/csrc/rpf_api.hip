@@ -45,7 +45,12 @@ struct FlagRule {
     const char *msg;
 };
 constexpr uint32_t kPackedRoute = RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED;
+constexpr uint32_t kWaveRoute = kPackedRoute | RPF_FLAG_GENERIC_WAVE;
 constexpr FlagRule kFlagRules[] = {
+    {RPF_FLAG_GENERIC_QUAD, kWaveRoute, 0, 0, "RPF_FLAG_GENERIC_QUAD without RPF_FLAG_GENERIC | RPF_FLAG_GENERIC_PACKED | RPF_FLAG_GENERIC_WAVE: the flag modifies the one-wave layout-generic route"},
+    {RPF_FLAG_GENERIC_QUAD, 0, 0, RPF_FLAG_FAST_WEIGHTS, "RPF_FLAG_FAST_WEIGHTS with RPF_FLAG_GENERIC_QUAD: the layout-generic kernels are fp64 throughout"},
+    {RPF_FLAG_GENERIC_QUAD, 0, 0, RPF_FLAG_GENERIC_FAST, "RPF_FLAG_GENERIC_QUAD with RPF_FLAG_GENERIC_FAST: the four-wave layout-generic kernels are fp64 only, and a pixel would move from an fp32 launch to an fp64 class kernel"},
+    {RPF_FLAG_GENERIC_QUAD, 0, 0, RPF_FLAG_STREAM_FAST, "RPF_FLAG_GENERIC_QUAD with RPF_FLAG_STREAM_FAST: the four-wave layout-generic kernels are fp64 only, and a pixel would move from an fp32 streaming launch to an fp64 class kernel"},
     {RPF_FLAG_SAMPLED_LISTED, RPF_FLAG_SAMPLED_NBHD, 0, 0, "RPF_FLAG_SAMPLED_LISTED without RPF_FLAG_SAMPLED_NBHD: the flag modifies the sampled route"},
     {RPF_FLAG_SAMPLED_FUSED, RPF_FLAG_SAMPLED_NBHD, 0, 0, "RPF_FLAG_SAMPLED_FUSED without RPF_FLAG_SAMPLED_NBHD: the flag modifies the sampled route"},
     {RPF_FLAG_SCHEDULE_FUSED, RPF_FLAG_SCHEDULE, 0, 0, "RPF_FLAG_SCHEDULE_FUSED without RPF_FLAG_SCHEDULE: the flag modifies the per-pass schedule"},
@@ -161,6 +166,7 @@ int32_t pass_generic_bits(const rpf_ctx *ctx, const rpf_desc *d, int box, int pa
         g = kGenericOn;
         if (d->flags & RPF_FLAG_GENERIC_PACKED) g |= kGenericPacked;
         if (d->flags & RPF_FLAG_GENERIC_WAVE) g |= kGenericWave;
+        if (d->flags & RPF_FLAG_GENERIC_QUAD) g |= kGenericQuad; // (validate: only with all three above, never with an fp32 flag)
     }
     if (d->flags & RPF_FLAG_GENERIC_FAST) g |= kGenericClassFast; // (validate: only with G | P; read by routes 4 and 5, never by the fused code)
     // a wide pass: every pixel on generic::filter_wide_kernel (option "wide" = 1: every pass of a call with the flag)
@@ -891,6 +897,17 @@ int32_t rpf_max_draws(const rpf_desc *d, int32_t *dmax_out) {
     if (!d || !dmax_out || d->S <= 0) return RPF_E_BADARG;
     const int32_t cap = (d->flags & RPF_FLAG_SAMPLED_REST) ? RPF_SAMPLED_MAX : 832;
     *dmax_out = std::max(0, cap - d->S);
+    return RPF_OK;
+}
+
+int32_t rpf_generic_quad_carve(const rpf_desc *d, int32_t capacity, int32_t *workgroups_per_cu_out, int64_t *lds_bytes_out) {
+    if (!d || (capacity != class_capacity(kNumClasses - 3) && capacity != class_capacity(kNumClasses - 2))) return RPF_E_BADARG;
+    const SampleLayout lay = layout_of(d);
+    if (!lay.generic_ok()) return RPF_E_UNSUPPORTED;
+    const GenericQuadCarve cv = generic_quad_carve(lay, capacity);
+    if (cv.hists == 0) return RPF_E_UNSUPPORTED;
+    if (workgroups_per_cu_out) *workgroups_per_cu_out = (int32_t)cv.workgroups_per_cu;
+    if (lds_bytes_out) *lds_bytes_out = (int64_t)cv.total;
     return RPF_OK;
 }
 

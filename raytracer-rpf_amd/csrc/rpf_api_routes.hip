@@ -348,19 +348,22 @@ int32_t route_wide(rpf_ctx *ctx, const PassParams &p, hipStream_t s, int *launch
 }
 
 constexpr int kNumWave = 8;                   // classes 0 .. 3 packed, 4 .. 7 one wave per pixel (capacities 128, 256, 448, 832)
+constexpr int kNumQuad = 10;                  // ... 8 and 9 four waves per pixel (capacities 1600, 3136; route 13 only)
 constexpr int kRestClass = kNumClasses - 1;   // the list of the pixels no class kernel of a generic route takes
 
 // One launch per non-empty list of the classes 0 .. n_classes - 1 of p's pass: generic::filter_packed_kernel below kNumPacked,
-// else generic::filter_wave_kernel.  fast: their fp32 stage 4 -- class_fast on routes 4 / 5, stream_fast on route 7
+// generic::filter_wave_kernel below kNumWave, else (route 13) generic::filter_quad_kernel, which is fp64 only.  fast: the fp32
+// stage 4 of the first two -- class_fast on routes 4 / 5, stream_fast on route 7
 int32_t launch_classes(rpf_ctx *ctx, const PassParams &p, const uint32_t *counts, int n_classes, bool fast, const char *packed_label,
                        const char *wave_label, hipStream_t s, int *launches) {
     for (int c = 0; c < n_classes; ++c) {
         if (counts[c] == 0) continue;
-        Range rg(c < kNumPacked ? packed_label : wave_label);
+        Range rg(c < kNumPacked ? packed_label : (c < kNumWave ? wave_label : "rpf:generic quad class"));
         PassParams q = p;
         q.pix_list = ctx->d_lists + (size_t)c * p.W * p.H;
         q.list_count = counts[c];
         if (c < kNumPacked) { HIP_TRY(generic::launch_filter_packed(q, class_capacity(c), s, fast)); }
+        else if (c >= kNumWave) { HIP_TRY(generic::launch_filter_quad(q, class_capacity(c), s)); }
         else { HIP_TRY(generic::launch_filter_wave(q, class_capacity(c), s, fast)); }
         if (launches) ++*launches;
     }
@@ -615,13 +618,17 @@ int32_t route_sampled_listed(rpf_ctx *ctx, const PassParams &p_in, bool packed, 
 // generic::filter_pixel_kernel walks (it runs its own 3-sigma test); then one launch per non-empty list.  One read-back per pass
 // (the list sizes).  REF_ABORT: the class kernels put the pixels with an in-band table on the redo list, which launch_redo
 // filters again.  None of the rpf_set_option names applies here.
+// Route 13 (... | RPF_FLAG_GENERIC_QUAD on a pass with S <= 3136) is route 5 with up to two classes more,
+// N <= 1600 and N <= 3136 on generic::filter_quad_kernel: n_classes is kNumQuad cut back to the last capacity whose carve-up the
+// layout fits (generic_quad_carve), and the rest list is what lies above it.
 int32_t route_generic_classes(rpf_ctx *ctx, const PassParams &p_in, int n_classes, Route route, hipStream_t s, int *launches) {
     const size_t HW = (size_t)p_in.W * p_in.H;
-    const bool wave = route == kRouteGenericWave;
+    const bool wave = route == kRouteGenericWave || route == kRouteGenericQuad;
     int32_t st;
     ctx->last_route = route;
     PassParams p = p_in;
     if (p.row_end <= p.row_begin) return RPF_OK;
+    while (n_classes > kNumWave && generic_quad_carve(p.lay, class_capacity(n_classes - 1)).hists == 0) --n_classes; // (route 13)
     if ((st = ctx->d_lists.ensure(ctx, (size_t)kNumClasses * HW * sizeof(uint32_t)))) return st;
     p.mask_stride = mask_stride(p);
     if ((st = ctx->d_masks.ensure(ctx, HW * p.mask_stride * sizeof(uint64_t)))) return st;
@@ -638,7 +645,8 @@ int32_t route_generic_classes(rpf_ctx *ctx, const PassParams &p_in, int n_classe
     }
     if ((st = launch_classes(ctx, p, counts, n_classes, class_fast(p), "rpf:generic packed class", "rpf:generic wave class", s, launches))) return st;
     if (counts[kRestClass] != 0) {
-        Range rg(wave ? "rpf:generic filter kernel (N > 832)" : "rpf:generic filter kernel (N > 64)");
+        Range rg(n_classes > kNumWave ? "rpf:generic filter kernel (N above the four-wave classes)"
+                                      : (wave ? "rpf:generic filter kernel (N > 832)" : "rpf:generic filter kernel (N > 64)"));
         PassParams q = p;
         q.pix_list = ctx->d_lists + (size_t)kRestClass * HW;
         q.list_count = counts[kRestClass];
@@ -648,7 +656,7 @@ int32_t route_generic_classes(rpf_ctx *ctx, const PassParams &p_in, int n_classe
 }
 
 // Which layout-generic route a pass takes (kRouteNone: none, a pass on the compiled kernels).  Above 64 spp N >= S fits no
-// packed class, above 832 spp no one-wave class: such a pass runs as route 3 does.
+// packed class, above 832 spp no one-wave class, above 3136 spp no four-wave class: such a pass runs as route 3 does.
 Route generic_route(const PassParams &p) {
     if (p.generic & kGenericSampledListed) return kRouteSampledListed; // (... a sampled pass the listed builds take under RPF_FLAG_SAMPLED_LISTED)
     if (p.generic & kGenericSampledFused) return kRouteSampledFused; // (... a sampled pass the compiled kernels take under RPF_FLAG_SAMPLED_FUSED)
@@ -657,6 +665,7 @@ Route generic_route(const PassParams &p) {
     if (p.generic & kGenericMemberTest) return kRouteMemberTest; // (... a full-box pass of a call under RPF_FLAG_MEMBER_TEST)
     if (p.generic & kGenericWide) return (p.generic & kGenericWideClasses) ? kRouteWideClasses : kRouteWide; // (setup_pass marked it)
     if (!route_bits(p.generic)) return kRouteNone; // (kGenericScheduleFused picks the build of the compiled kernels, not a route)
+    if ((p.generic & kGenericQuad) && p.S <= class_capacity(kNumQuad - 1)) return kRouteGenericQuad; // (validate: the three bits below are set)
     if ((p.generic & kGenericWave) && p.S <= class_capacity(kNumWave - 1)) return kRouteGenericWave;
     if ((p.generic & kGenericPacked) && p.S <= class_capacity(kNumPacked - 1)) return kRouteGenericPacked;
     return kRouteGeneric;
@@ -673,7 +682,7 @@ int32_t route_pass(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *lau
     const Route route = generic_route(p_in);
     PassParams p = p_in;
     int32_t st;
-    // Who keeps a redo list: routes 4, 5 and 7; routes 3 and 6 never (their kernels evaluate the reference's expression in
+    // Who keeps a redo list: routes 4, 5, 7 and 13; routes 3 and 6 never (their kernels evaluate the reference's expression in
     // place); a fused pass unless stages are skipped.  RPF_FLAG_FAST_WEIGHTS keeps the list too: MI, alpha, beta and W_r_c are the
     // reference's under the flag as well, and a redone pixel is filtered whole, in fp64, by the reference-expression kernel (the
     // FAST instantiations test p.redo_list at run time like the others, stage 3b)
@@ -699,6 +708,7 @@ int32_t route_pass(rpf_ctx *ctx, const PassParams &p_in, hipStream_t s, int *lau
     case kRouteMemberTest: return route_member_test(ctx, p, s, launches);
     case kRouteWideClasses: return route_wide_classes(ctx, p, nullptr, s, launches);
     case kRouteWide: return route_wide(ctx, p, s, launches);
+    case kRouteGenericQuad: return route_generic_classes(ctx, p, kNumQuad, route, s, launches);
     case kRouteGenericWave: return route_generic_classes(ctx, p, kNumWave, route, s, launches);
     case kRouteGenericPacked: return route_generic_classes(ctx, p, kNumPacked, route, s, launches);
     case kRouteGeneric: return route_generic(ctx, p, s, launches);

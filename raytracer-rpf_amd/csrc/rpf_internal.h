@@ -73,6 +73,9 @@ enum GenericBits : int32_t {
                               //   in their listed builds (rpf_impl_*_listed_*.hip: launch_filter_pass and launch_filter_packed dispatch on
                               //   it) behind a count kernel that lists into the member pool.  Never together with kGenericSampledFused or
                               //   kGenericWide; generic_route looks at it before kGenericSampled.  Host-side only: no kernel reads it
+    kGenericQuad = 16384,     // RPF_FLAG_GENERIC_QUAD (validate: only with kGenericOn | kGenericPacked | kGenericWave): 832 < N <= 3136 on
+                              //   the four-wave generic kernels (rpf_generic_quad.hip): route 13 for a pass with S <= 3136 that is
+                              //   neither sampled, member-test nor wide (generic_route looks at those first).  Host-side only
 };
 // what routes a pass: its bits without the one that only picks the build of the compiled kernels
 inline int32_t route_bits(int32_t generic) { return generic & ~kGenericScheduleFused; }
@@ -313,6 +316,27 @@ namespace generic {
 // REF_ABORT p.redo_list / p.redo_count take the pixels that generic::filter_pixel_kernel must filter again.  fast: as for
 // launch_filter_packed
 hipError_t launch_filter_wave(const PassParams &p, int capacity, hipStream_t s, bool fast = false);
+} // namespace generic
+
+// ---- the four-wave layout-generic kernels (rpf_generic_quad.hip, RPF_FLAG_GENERIC_QUAD): 832 < N <= 3136, four waves per pixel --
+// LDS carve-up of generic::filter_quad_kernel, a host-side function of the layout and the class capacity (1600 or 3136); byte
+// offsets into the workgroup's one block:
+//   T[0 .. capacity] u64 at 0, the columns of every MI pair (off_pairtab), the member list [capacity] u32 (off_list); one block
+//   (off_shared) shared by the word prefix of stage 1b, the staging chunk [ndim][129] fp64 of the in-order sums (stage 2), the bin
+//   ids [ndim][capacity] bytes (stages 3a, 3b) and the own rows of a sweep of stage 4 (never live together); hist: per wave
+//   `hists` histograms of hist_words 32-bit words each (floor(sqrt(capacity))^2 16-bit cells); stat (the fp64 block of
+//   generic_f64_doubles); red: [4 waves][own samples of a sweep][4] fp64 partial sums of stage 4; flag (redo)
+// hists: of 4, 2 and 1 the count that lets a CU hold the most workgroups within 160 KiB (at most what its registers allow: two
+// at the four own samples per sweep of the class 1600, one at the eight of the class 3136), the larger on a tie; 0: the layout does not fit the capacity and route 13 does not offer it that class.
+struct GenericQuadCarve {
+    uint32_t off_pairtab, off_list, off_shared, off_hist, off_stat, off_red, off_flag;
+    uint32_t hist_words, hists, total, capacity, workgroups_per_cu;
+};
+GenericQuadCarve generic_quad_carve(const SampleLayout &lay, int capacity);
+namespace generic {
+// the pixels of p.pix_list (p.list_count of them, N <= capacity = 1600 or 3136) from p.nbhd and p.masks; under REF_ABORT
+// p.redo_list / p.redo_count take the pixels that generic::filter_pixel_kernel must filter again.  fp64 only
+hipError_t launch_filter_quad(const PassParams &p, int capacity, hipStream_t s);
 } // namespace generic
 
 // ---- the wide layout-generic kernel (rpf_generic_wide.hip, RPF_FLAG_WIDE_NBHD): 65535 < box*box*S <= 262144 ----------------

@@ -97,7 +97,13 @@ SAMPLED_MAX = 8192  # RPF_SAMPLED_MAX
 # route 12.  Wide windows (box*box*S > 65535 with FLAG_WIDE_NBHD) included; no mask buffer.  With SAMPLED_FUSED_FLAG as well, option
 # "sampled_listed_stride" picks between routes 11 and 12 where both apply.  Every other pass runs as without it.  Refused without
 # SAMPLED_NBHD_FLAG.  Its table: tests/test_sampled_listed_cpu.py
-_LATER_BITS = {"SAMPLED_FUSED_FLAG": 262144, "SAMPLED_LISTED_FLAG": 524288}
+#
+# GENERIC_QUAD_FLAG (RPF_FLAG_GENERIC_QUAD of the header) modifies FLAG_GENERIC | FLAG_GENERIC_PACKED |
+# FLAG_GENERIC_WAVE: the pixels with 832 < N <= 3136 run on the four-wave layout-generic kernels (size classes 1600 and 3136, where
+# generic_quad_carve says the layout fits them) and only what lies above stays on the generic filter kernel: route 13 for a pass with
+# S <= 3136.  A wide, sampled or member-test pass runs as without it.  fp64 only: refused without all three of those flags and with
+# FLAG_FAST_WEIGHTS, FLAG_GENERIC_FAST or FLAG_STREAM_FAST.  Its table: tests/test_generic_quad_cpu.py
+_LATER_BITS = {"SAMPLED_FUSED_FLAG": 262144, "SAMPLED_LISTED_FLAG": 524288, "GENERIC_QUAD_FLAG": 1048576}
 
 
 def __getattr__(name):
@@ -132,7 +138,7 @@ EXPORTS = ["rpf_version", "rpf_status_string", "rpf_create", "rpf_destroy", "rpf
            "rpf_max_nbhd", "rpf_wide_table", "rpf_set_spike", "rpf_multi_set_spike", "rpf_query_spike", "rpf_multi_query_spike",
            "rpf_spike_clamp_device", "rpf_colour_add_device", "rpf_spike_delta", "rpf_set_sampling", "rpf_multi_set_sampling",
            "rpf_sampling_table", "rpf_sampling_draws", "rpf_set_membership", "rpf_multi_set_membership", "rpf_membership_preset",
-           "rpf_set_schedule", "rpf_multi_set_schedule", "rpf_schedule_preset", "rpf_max_draws", "rpf_query_pass_report",
+           "rpf_set_schedule", "rpf_multi_set_schedule", "rpf_schedule_preset", "rpf_max_draws", "rpf_generic_quad_carve", "rpf_query_pass_report",
            "rpf_query_pass_report_rows", "rpf_multi_query_pass_report", "rpf_pass_report_rows_device", "rpf_pass_report_fold"]
 
 # the film step: pbrt's PixelFilters (include/rpf_hip.h, rpf_film)
@@ -393,6 +399,15 @@ def max_draws(desc):
     return st, (n.value if st == OK else None)
 
 
+def generic_quad_carve(desc, capacity):
+    """rpf_generic_quad_carve (no GPU needed): (status, workgroups_per_cu, lds_bytes) -- what the layout of `desc` gets from
+    GENERIC_QUAD_FLAG at the size class `capacity` (1600 or 3136): OK when the four-wave kernel's LDS carve-up fits, E_UNSUPPORTED
+    when it does not (route 13 leaves that class to the generic filter kernel), E_BADARG for any other capacity or desc None"""
+    wg, lds = C.c_int32(-1), C.c_int64(-1)
+    st = load().rpf_generic_quad_carve(None if desc is None else C.byref(desc), int(capacity), C.byref(wg), C.byref(lds))
+    return st, (wg.value if st == OK else None), (lds.value if st == OK else None)
+
+
 def wide_table(nmax):
     """rpf_wide_table (no GPU needed): uint64 [nmax + 1], round(k ln k * 2^41) -- the table the wide kernel forms MI from"""
     out = np.empty(nmax + 1, np.uint64)
@@ -529,6 +544,8 @@ def load():
             L.rpf_schedule_preset.argtypes = [C.c_int32, C.c_int32, C.POINTER(Schedule)]
         if hasattr(L, "rpf_max_draws"):  # (absent from a build of before the listed rest launch, loaded through RPF_HIP_LIB)
             L.rpf_max_draws.argtypes = [C.POINTER(Desc), C.POINTER(C.c_int32)]
+        if hasattr(L, "rpf_generic_quad_carve"):  # (absent from a build of before the four-wave generic kernels, loaded through RPF_HIP_LIB)
+            L.rpf_generic_quad_carve.argtypes = [C.POINTER(Desc), C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
         if hasattr(L, "rpf_query_pass_report"):  # (absent from a build of before the pass report, loaded through RPF_HIP_LIB)
             L.rpf_query_pass_report.argtypes = [C.c_void_p, C.c_int32, C.POINTER(PassReport)]
             L.rpf_query_pass_report_rows.argtypes = [C.c_void_p, C.c_int32, C.POINTER(ReportRow), C.c_int64]
@@ -616,7 +633,7 @@ class Context:
         (FLAG_GENERIC), 4 the same with small neighbourhoods packed (FLAG_GENERIC_PACKED), 5 the same with
         64 < N <= 832 on the one-wave generic kernels (FLAG_GENERIC_WAVE; 3 for a pass with S > 832), 6 the wide kernel
         (FLAG_WIDE_NBHD on a pass with box*box*S > 65535), 7 such a pass dealt by size class (FLAG_WIDE_CLASSES), 8 a sampled
-        pass (SAMPLED_NBHD_FLAG with draws > 0), 9 a full-box pass under MEMBER_TEST_FLAG, 10 such a pass on the compiled kernels (MEMBER_FUSED_FLAG), 11 a sampled pass on the compiled kernels (SAMPLED_FUSED_FLAG), 12 a sampled pass on their listed builds (SAMPLED_LISTED_FLAG); -1 before any pass.  FLAG_GENERIC_FAST and FLAG_STREAM_FAST change no route
+        pass (SAMPLED_NBHD_FLAG with draws > 0), 9 a full-box pass under MEMBER_TEST_FLAG, 10 such a pass on the compiled kernels (MEMBER_FUSED_FLAG), 11 a sampled pass on the compiled kernels (SAMPLED_FUSED_FLAG), 12 a sampled pass on their listed builds (SAMPLED_LISTED_FLAG), 13 route 5 with 832 < N <= 3136 on the four-wave generic kernels (GENERIC_QUAD_FLAG; a pass with S <= 3136); -1 before any pass.  FLAG_GENERIC_FAST and FLAG_STREAM_FAST change no route
         (rpf_query_route)"""
         r = C.c_int32(-1)
         self._check(self._L.rpf_query_route(self._h, C.byref(r)))

@@ -218,6 +218,9 @@ def demangle_short(name):
     t = re.search(r"3rpf7generic.*packed_kernelI(f|6__half)Li(\d+)E(?:Lb([01])E)?", name)  # ... and of their packed kernels the lanes per pixel
     if t:
         s += "<%s,G=%s%s>" % ("float" if t.group(1) == "f" else "__half", t.group(2), ",FAST" if t.group(3) == "1" else "")
+    t = re.search(r"3rpf7generic.*filter_quad_kernelI(f|6__half)Li(\d+)E", name)  # ... of the four-wave kernels the own samples per sweep
+    if t:
+        s += "<%s,OWN=%s>" % ("float" if t.group(1) == "f" else "__half", t.group(2))
     return s
 
 

@@ -19,6 +19,14 @@ the launches and the mean neighbourhood size.  Cases (--case to pick by name):
   flat55       a 1920x64 slab at 32 spp, box 55 (96800: the reference's first box), flat_frac = 0.94, routes 6 and 7: many
                rounds of the wide kernel's slots (seconds per step; not in the default case list's spirit: pick it by name)
   lay4_18_f16  the smooth slab as (4, 18) stored as fp16 halves: routes 3, 4, 5 and the fp32-weight legs of 4 and 5
+  smooth32     1920x68x32 smooth, box 7 (N up to 1568), layouts (2, 12) and (3, 12): route 3, route 5 and route 13
+               (RPF_FLAG_GENERIC_QUAD on top of route 5's flags, `generic` = 4: 832 < N <= 3136 on the four-wave kernels)
+  smooth64     960x34x64 smooth, box 7 (N up to 3136): routes 3, 5 and 13
+  box17_8      256x64x8 smooth, box 17 (N up to 2312): routes 3, 5 and 13
+  smooth8_quad, flat8_quad   the slabs of smooth8 and flat8 (no pixel above 832) under route 5 and route 13: what the flag
+               costs where it has nothing to do
+A record of these five cases carries census4, the pixels with N <= 832, <= 1600, <= 3136 and above; a route-13 record carries
+ratio_to_route5 and below_route5 (its slowest call against route 5's fastest).
 smooth8, flat8, lay3_12, lay4_18 and lay4_18_f16 end with the legs of RPF_FLAG_GENERIC_FAST (`generic` = 12: route 4 with the
 flag, 13: route 5 with it; skipped on a library from before the flag): such a record carries ratio_to_fp64, its time over the
 same route's without the flag.
@@ -57,7 +65,13 @@ CASES = {
     "wide57": (256, 57, 21, 57, 0.0, [(2, 12, 1, 14), (2, 12, 6, 21), (2, 12, 7, 21), (2, 12, 21, 14), (2, 12, 26, 21), (2, 12, 27, 21)]),
     "flat57": (256, 57, 21, 57, 0.94, [(2, 12, 6, 21), (2, 12, 7, 21), (2, 12, 26, 21), (2, 12, 27, 21)]),
     "flat55": (1920, 64, 32, 55, 0.94, [(2, 12, 6, 32), (2, 12, 7, 32)]),
+    "smooth32": (1920, 68, 32, 7, 0.0, [(2, 12, 1), (2, 12, 3), (2, 12, 4), (3, 12, 1), (3, 12, 3), (3, 12, 4)]),
+    "smooth64": (960, 34, 64, 7, 0.0, [(2, 12, 1), (2, 12, 3), (2, 12, 4)]),
+    "box17_8": (256, 64, 8, 17, 0.0, [(2, 12, 1), (2, 12, 3), (2, 12, 4)]),
+    "smooth8_quad": (1920, 270, 8, 7, 0.0, [(2, 12, 3), (2, 12, 4)]),
+    "flat8_quad": (1920, 270, 8, 7, 0.94, [(2, 12, 3), (2, 12, 4)]),
 }
+QUAD_CASES = ("smooth32", "smooth64", "box17_8", "smooth8_quad", "flat8_quad")  # the cases of RPF_FLAG_GENERIC_QUAD (`generic` = 4)
 F16_CASES = ("lay4_18_f16",)  # planes stored as fp16 halves
 CLASS_CAPS = (8, 16, 32, 64, 128, 256, 448, 832)
 
@@ -95,8 +109,9 @@ def run(ctx, name, steps):
             made = (nr, nf)
         planes = whole if S == S_buf else whole[..., :S].contiguous()
         colour = torch.empty((3, H, W, S), dtype=torch.float64, device=dev)
-        flags = hip.FLAG_TIMING | (hip.FLAG_GENERIC if generic else 0) | (hip.FLAG_GENERIC_PACKED if generic in (2, 3) else 0)
-        flags |= hip.FLAG_GENERIC_WAVE if generic == 3 else 0
+        flags = hip.FLAG_TIMING | (hip.FLAG_GENERIC if generic else 0) | (hip.FLAG_GENERIC_PACKED if generic in (2, 3, 4) else 0)
+        flags |= hip.FLAG_GENERIC_WAVE if generic in (3, 4) else 0
+        flags |= hip.GENERIC_QUAD_FLAG if generic == 4 else 0
         flags |= hip.FLAG_WIDE_NBHD if generic in (6, 7) else 0
         flags |= hip.FLAG_WIDE_CLASSES if generic == 7 else 0
         flags |= hip.FLAG_GENERIC_FAST if fast else 0
@@ -119,6 +134,13 @@ def run(ctx, name, steps):
             n = ctx.nbhd(W, H).ravel()
             lo = (0,) + CLASS_CAPS[:-1]
             rec["census"] = [int(((n > a) & (n <= b)).sum()) for a, b in zip(lo, CLASS_CAPS)] + [int((n > CLASS_CAPS[-1]).sum())]
+        if name in QUAD_CASES:
+            n = ctx.nbhd(W, H).ravel()
+            rec["census4"] = [int((n <= 832).sum()), int(((n > 832) & (n <= 1600)).sum()), int(((n > 1600) & (n <= 3136)).sum()), int((n > 3136).sum())]
+        r5 = out.get((nr, nf, 3))
+        if generic == 4 and r5:
+            rec["ratio_to_route5"] = round(rec["filter_ms_min"] / r5["filter_ms_min"], 3)
+            rec["below_route5"] = bool(rec["filter_ms_max"] < r5["filter_ms_min"])
         r6 = out.get((nr, nf, 6))
         if generic == 7 and r6:
             rec["ratio_to_route6"] = round(rec["filter_ms_min"] / r6["filter_ms_min"], 4)
@@ -134,7 +156,7 @@ def run(ctx, name, steps):
         if generic and base:
             rec["ratio_to_fused"] = round(rec["filter_ms_min"] / base["filter_ms_min"], 2)
         r3 = out.get((nr, nf, 1))
-        if generic in (2, 3) and r3:
+        if generic in (2, 3, 4) and r3:
             rec["ratio_to_route3"] = round(rec["filter_ms_min"] / r3["filter_ms_min"], 3)
         r4 = out.get((nr, nf, 2))
         if generic == 3 and r4:
@@ -146,7 +168,7 @@ def run(ctx, name, steps):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--case", nargs="*", default=[c for c in CASES if c != "flat55"])
+    ap.add_argument("--case", nargs="*", default=[c for c in CASES if c != "flat55" and c not in QUAD_CASES])
     a = ap.parse_args()
     print(json.dumps({"library": hip.LIB_PATH, "version": hip.load().rpf_version().decode()}), flush=True)
     with hip.Context(0) as ctx:
