@@ -14,6 +14,15 @@ own samples are never touched, so its statistics stay and it keeps exactly the N
 the window and interleave with rejected candidates in the reference's visiting order.  The window's other pixels, some of
 whose own samples were pushed, get wide sigmas on some features and assorted N: they are compared like every pixel.
 
+Targets off the centre (plant(at=(ty, dx)); tests/test_generic_wide_windows_cpu.py, tests/test_generic_wide_windows_gpu.py).  Every
+target sits at row ty of the frame and column t * box + dx of its block, so the frame clips its window: the kernels see a window
+whose candidate count, and so whose number of acceptance words, is well below what the box alone allows.  The candidates are the
+block's pixels inside the clipped window, and N is planted among them as above.  A placement whose clipped window would reach
+into another block is refused (ValueError): dx != b is possible only where the frame's edge does the clipping -- dx <= b on the
+first block, dx >= b on the last -- and as every target shares dx, only on a frame of one target; any row 0 <= ty < box is
+allowed, the frame being one block high.  at=None is the centre placement, unchanged to the byte: the calls on the random
+generator come in the same order (tests/test_generic_wide_windows_cpu.py holds U8, B17 and H16 to recorded hashes).
+
 Sampled passes (routes 8, 11 and 12: tests/test_planted_routes_cpu.py, tests/test_class_edges_routes_gpu.py).  plant_sampled()
 plants the same way among the DRAWS of a target: its candidates are the distinct surviving draws of sampled_ref.draws, of which
 as many as must go are pushed, so the target keeps S + (draws not pushed) members.  Two edges meet on such a pass: the class
@@ -48,13 +57,26 @@ FRAMES = {
 }
 
 
-def plant(S, box, targets, n_random=2, n_feat=12, seed=0):
+def plant(S, box, targets, n_random=2, n_feat=12, seed=0, at=None):
     """float32 planes [5 + n_random + n_feat, box, box * len(targets), S] and the target pixels [(y, x), ...]: pixel
-    targets[t]'s neighbourhood under a box x box window holds exactly targets[t] samples (S <= targets[t] <= box * box * S)."""
+    targets[t]'s neighbourhood under a box x box window holds exactly targets[t] samples (S <= targets[t] <= the samples of
+    its window: box * box * S at the centre, fewer where the frame clips the window).
+
+    at: None -- every target at the centre of its block -- or (ty, dx): every target at row ty of the frame and column
+    t * box + dx of its block; see the module docstring for what is refused."""
     if S < 2:
         raise ValueError("S >= 2: one sample per pixel has sigma = 0 and accepts nobody")
     nt, b = len(targets), (box - 1) // 2
     H, W, ndim, f0 = box, box * nt, 5 + n_random + n_feat, 5 + n_random
+    if at is not None:
+        aty, adx = at
+        if not (0 <= aty < box and 0 <= adx < box):
+            raise ValueError("at = (%d, %d) outside the block [0, %d) x [0, %d)" % (aty, adx, box, box))
+        # the window of a target off its block's centre column reaches into the next block unless the frame's edge clips it
+        if adx < b and nt != 1:
+            raise ValueError("at: dx = %d < b = %d reaches into the block to the left of every target but the first" % (adx, b))
+        if adx > b and nt != 1:
+            raise ValueError("at: dx = %d > b = %d reaches into the block to the right of every target but the last" % (adx, b))
     rng = np.random.default_rng(seed)
     planes = rng.permuted(np.broadcast_to(np.linspace(0.4, 0.6, S), (ndim, H, W, S)), axis=3).astype(np.float32)
     planes[0] = (np.arange(W)[None, :, None] + rng.random((H, W, S))).astype(np.float32)
@@ -62,12 +84,15 @@ def plant(S, box, targets, n_random=2, n_feat=12, seed=0):
     planes[2:5] = rng.random((3, H, W, S)).astype(np.float32)
     pixels = []
     for t, n in enumerate(targets):
-        ty, tx = b, t * box + b
+        ty, tx = (b, t * box + b) if at is None else (at[0], t * box + at[1])
         pixels.append((ty, tx))
-        cand = [(y, x, s) for y in range(box) for x in range(t * box, (t + 1) * box) for s in range(S) if (y, x) != (ty, tx)]
+        # the block's pixels inside the window clipped to the frame (at the centre: the whole block)
+        ys = range(max(ty - b, 0), min(ty + b, H - 1) + 1)
+        xs = range(max(tx - b, t * box), min(tx + b, (t + 1) * box - 1) + 1)
+        cand = [(y, x, s) for y in ys for x in xs for s in range(S) if (y, x) != (ty, tx)]
         n_reject = len(cand) - (n - S)
         if not 0 <= n_reject <= len(cand):
-            raise ValueError("target %d: N = %d outside [S, box * box * S] = [%d, %d]" % (t, n, S, box * box * S))
+            raise ValueError("target %d: N = %d outside [S, S + candidates] = [%d, %d]" % (t, n, S, S + len(cand)))
         chosen = rng.permutation(len(cand))[:n_reject]
         feats = rng.integers(0, n_feat, n_reject)
         for i, (ci, k) in enumerate(zip(chosen, feats)):
