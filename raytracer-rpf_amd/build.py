@@ -9,9 +9,13 @@ import sys
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB = os.path.join(_HERE, "lib", "librpf_hip.so")
-# the fused per-pixel kernels compile as one translation unit per sample layout and size-class part (rpf_filter_impl.inc
-# with RPF_IMPL_PART = 1 / 2 / 3; part 4, the *_member TUs below; the *_sched_* TUs, their scheduled builds), in parallel: the single kernel TU of rounds 1-2 took 3.2 minutes
-KERNEL_TUS = ["rpf_impl_%s_%s.hip" % (lay, part) for lay in ("d19", "d27") for part in ("small", "mid", "large")] + ["rpf_kernels.hip"]
+# the fused per-pixel kernels compile as one translation unit per sample layout, build and size-class part, in parallel (the single
+# kernel TU of rounds 1-2 took 3.2 minutes).  Each unit is rpf_filter_impl.inc through rpf_impl_unit.inc: the listed builds read stage 1b
+# from the member pool (RPF_FLAG_SAMPLED_LISTED), the scheduled ones form stage 3c from the entry's gains
+# (RPF_FLAG_SCHEDULE_FUSED, section 15e); part 4, the *_member TUs, is the count pass under the membership test (RPF_FLAG_MEMBER_FUSED)
+IMPL_TUS = ["rpf_impl_%s_%s%s%s.hip" % (lay, li, sc, part) for lay in ("d19", "d27") for li in ("", "listed_") for sc in ("", "sched_")
+            for part in ("small", "mid", "large")] + ["rpf_impl_d19_member.hip", "rpf_impl_d27_member.hip"]
+KERNEL_TUS = IMPL_TUS + ["rpf_kernels.hip"]
 KERNEL_TUS += ["rpf_film.hip"]  # the film step (pbrt's reconstruction filter): rpf_filter_film / rpf_film_splat_device
 KERNEL_TUS += ["rpf_generic.hip"]  # the layout-generic kernel pair (RPF_FLAG_GENERIC): n_random / n_feat at run time
 KERNEL_TUS += ["rpf_generic_packed.hip"]  # ... its count pass and packed kernels for N <= 64 (RPF_FLAG_GENERIC_PACKED)
@@ -21,11 +25,6 @@ KERNEL_TUS += ["rpf_spike.hip"]  # the spike pass after the last filter pass: cl
 KERNEL_TUS += ["rpf_generic_wide_count.hip"]  # ... and the count pass that deals a wide pass by size class (RPF_FLAG_WIDE_CLASSES)
 KERNEL_TUS += ["rpf_generic_sampled_count.hip"]  # the count pass of a sampled pass: the draws of a pixel's key (RPF_FLAG_SAMPLED_NBHD)
 KERNEL_TUS += ["rpf_generic_sampled_mask.hip"]  # ... and the count pass that leaves the draws as acceptance masks for the compiled kernels (RPF_FLAG_SAMPLED_FUSED)
-KERNEL_TUS += ["rpf_impl_d19_member.hip", "rpf_impl_d27_member.hip"]  # rpf_filter_impl.inc part 4: the count pass under the membership test (RPF_FLAG_MEMBER_FUSED)
-# ... and the scheduled builds of parts 1 to 3 (RPF_IMPL_SCHED: stage 3c from the entry's gains; RPF_FLAG_SCHEDULE_FUSED)
-KERNEL_TUS += ["rpf_impl_%s_sched_%s.hip" % (lay, part) for lay in ("d19", "d27") for part in ("small", "mid", "large")]
-# ... their listed builds (RPF_IMPL_LISTED: stage 1b from the member pool; RPF_FLAG_SAMPLED_LISTED), and the listed scheduled ones
-KERNEL_TUS += ["rpf_impl_%s_listed_%s%s.hip" % (lay, sc, part) for lay in ("d19", "d27") for sc in ("", "sched_") for part in ("small", "mid", "large")]
 KERNEL_TUS += ["rpf_generic_quad.hip"]  # the four-wave layout-generic kernels for 832 < N <= 3136 (RPF_FLAG_GENERIC_QUAD)
 KERNEL_TUS += ["rpf_report.hip"]  # the per-pass activity report: per-pixel chains, per-row chains and counts (RPF_FLAG_PASS_REPORT)
 # the C ABI (host code only; rpf_api.h is what they share): context, validation and pass loops | pass router | film step | multi-GPU | spike pass | pass report
@@ -33,7 +32,7 @@ KERNEL_TUS += ["rpf_report.hip"]  # the per-pass activity report: per-pixel chai
 API_TUS = ["rpf_api.hip", "rpf_api_routes.hip", "rpf_api_film.hip", "rpf_api_multi.hip", "rpf_api_spike.hip", "rpf_api_report.hip"]
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in KERNEL_TUS + API_TUS]
 HEADERS = [os.path.join(_HERE, "csrc", "rpf_internal.h"), os.path.join(_HERE, "csrc", "rpf_api.h"), os.path.join(_HERE, "csrc", "rpf_xlane.h"),
-           os.path.join(_HERE, "csrc", "rpf_filter_impl.inc"), os.path.join(_HERE, "csrc", "rpf_packed_impl.inc"),
+           os.path.join(_HERE, "csrc", "rpf_impl_unit.inc"), os.path.join(_HERE, "csrc", "rpf_filter_impl.inc"), os.path.join(_HERE, "csrc", "rpf_packed_impl.inc"),
            os.path.join(_HERE, "csrc", "rpf_device_common.h"), os.path.join(_HERE, "csrc", "rpf_reflog.h"),
            os.path.join(_HERE, "csrc", "rpf_generic_common.h"),  # what the rpf_generic*.hip share
            os.path.join(_HERE, "csrc", "rpf_generic_sampled_draws.h"),  # ... the draws of a sampled pass, which its two count TUs share
@@ -88,8 +87,8 @@ def _build(LIB, OBJ_DIR, defs, shipped, force, verbose):
         if force or _stale(obj, [src] + HEADERS):
             # -save-temps=obj keeps the device assembly next to the object: scripts/check_spills.py reads it below
             cmds.append([hipcc_path()] + flags + ["-save-temps=obj", "-c", src, "-o", obj])
-    # at most MAX_JOBS compilers at a time, 16 at the most (44 translation units: one hipcc each all at once oversubscribes a
-    # machine that gives the build a share of its cores).  The largest units (the rpf_impl_* parts) start first
+    # at most MAX_JOBS compilers at a time, 16 at the most (one hipcc per translation unit all at once oversubscribes a machine
+    # that gives the build a share of its cores).  The largest units (the rpf_impl_* parts) start first
     jobs = max(1, min(16, int(os.environ.get("MAX_JOBS", 16))))
     cmds.sort(key=lambda c: not os.path.basename(c[-3]).startswith("rpf_impl_"))
     running, failed = [], None

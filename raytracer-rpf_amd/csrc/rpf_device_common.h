@@ -1,5 +1,5 @@
 // rpf_device_common.h -- device-side helpers shared by every kernel translation unit (the misc kernels in
-// rpf_kernels.hip, the per-layout / per-size-class parts rpf_impl_*.hip, which each include rpf_filter_impl.inc, and --
+// rpf_kernels.hip, the per-layout / per-build / per-size-class parts rpf_impl_*.hip, which each include rpf_filter_impl.inc (through rpf_impl_unit.inc), and --
 // through rpf_generic_common.h, which holds what only they share -- the layout-generic rpf_generic*.hip).
 // Everything here has internal linkage: each TU carries its own copy.
 #pragma once

@@ -1,7 +1,8 @@
 // rpf_filter_impl.inc -- the dimension-dependent kernels: included by the rpf_impl_*.hip translation units once per supported
 // sample-vector layout and size-class part (RPF_IMPL_PART: 1 = K <= 8 kernels + stage 1a + count pass + streaming kernel,
 // 2 = K 13 / 25, 3 = K 49, 4 = the count pass under the membership test alone, so that the code objects of parts 1 to 3 are
-// what they were before it existed; the parts compile in parallel), inside the layout's namespace, with
+// what they were before it existed; the parts compile in parallel) through rpf_impl_unit.inc, which opens the namespace of the
+// layout and build and sets
 //     RPF_IMPL_NR   number of random-parameter columns  (reference: 2, sd.h:42 SD_N_RANDOM)
 //     RPF_IMPL_NF   number of scene-feature columns     (reference: 12, sd.h:40 SD_N_FEATURES)
 //     RPF_IMPL_PLANE_T  storage type of the feature planes (float, or __half for fp16 feature storage)
@@ -2466,6 +2467,12 @@ __global__ __launch_bounds__(256) void nbhd_count_member_kernel(PassParams p, co
 
 #endif // RPF_IMPL_PART == 4
 
+// what every entry point asks first: is p a pass of this unit's layout and list source (pass_fits_unit), and of its schedule too (pass_fits_build)?  The
+// table in rpf_kernels.hip picks a build by the same three facts, so a wrong cell is refused here, on the host, before a listed
+// kernel is handed a mask pass or the reverse (either would follow a null pointer on the device)
+inline bool pass_fits_unit(const PassParams &p) { return p.lay.is_ref19() == kRef19 && ((p.generic & kGenericSampledListed) != 0) == kListed; }
+inline bool pass_fits_build(const PassParams &p) { return pass_fits_unit(p) && ((p.generic & kGenericScheduleFused) != 0) == kSched; }
+
 #if RPF_IMPL_PART == 1
 #include "rpf_packed_impl.inc"
 #endif
@@ -2493,18 +2500,11 @@ hipError_t launch_filter_w(const PassParams &p, const LdsLayout &L, unsigned gri
 }
 #if RPF_IMPL_SCHED
 // PHASE 3 (chains) or PHASE 2 (weights) of the split route on the unscheduled part that holds class K's kernels: the entry points
-// of parts 2 and 3 below, declared by the scheduled translation unit in the layout's namespace
-// (a listed scheduled build, namespace listed::sched: the entry points of the listed parts, which its translation unit declares in
-// namespace listed)
+// of parts 2 and 3 below in the enclosing namespace (the layout's, or its `listed`), where rpf_impl_unit.inc declares them
 template <int K>
 hipError_t unscheduled_phase(const PassParams &p, const LdsLayout &L, int phase, unsigned grid, hipStream_t s) {
-#if RPF_IMPL_LISTED
-    if constexpr (K == 25) return impl_filter_mid_phase_listed(p, L, phase, grid, s);
-    else return impl_filter_large_phase_listed(p, L, phase, grid, s);
-#else
     if constexpr (K == 25) return impl_filter_mid_phase(p, L, phase, grid, s);
     else return impl_filter_large_phase(p, L, phase, grid, s);
-#endif
 }
 #endif
 template <int K>
@@ -2539,27 +2539,11 @@ hipError_t launch_filter_k(const PassParams &p, const LdsLayout &L, const LdsLay
     return t_in_lds ? launch_filter_w<K, true, 1>(p, L, grid, s) : launch_filter_w<K, false, 1>(p, L, grid, s);
 }
 
-// entry points of this layout and part (called from the dispatchers at the end of rpf_kernels.hip); a scheduled build (namespace
-// sched) names its own impl_filter_*_sched, and of part 1 emits the filter entry alone
-// (a listed build, namespace listed: impl_filter_*_listed and impl_filter_*_phase_listed; namespace listed::sched:
-// impl_filter_*_listed_sched)
-#if RPF_IMPL_SCHED && RPF_IMPL_LISTED
-#define impl_filter_small impl_filter_small_listed_sched
-#define impl_filter_mid impl_filter_mid_listed_sched
-#define impl_filter_large impl_filter_large_listed_sched
-#elif RPF_IMPL_SCHED
-#define impl_filter_small impl_filter_small_sched
-#define impl_filter_mid impl_filter_mid_sched
-#define impl_filter_large impl_filter_large_sched
-#elif RPF_IMPL_LISTED
-#define impl_filter_small impl_filter_small_listed
-#define impl_filter_mid impl_filter_mid_listed
-#define impl_filter_large impl_filter_large_listed
-#define impl_filter_mid_phase impl_filter_mid_phase_listed
-#define impl_filter_large_phase impl_filter_large_phase_listed
-#endif
+// entry points of this layout, build and part (rpf_kernels.hip calls them through its table of builds); they carry the same
+// names in every build's namespace.  A scheduled or listed build of part 1 emits the filter entries alone
 #if RPF_IMPL_PART == 1
 hipError_t impl_filter_small(const PassParams &p, const LdsLayout &L, bool t_in_lds, unsigned grid, hipStream_t s) {
+    if (!pass_fits_build(p)) return hipErrorInvalidValue;
     const LdsLayout none{};
     switch (samples_per_lane(p.nmax)) {
     case 1: return launch_filter_k<1>(p, L, none, none, t_in_lds, grid, s);
@@ -2594,6 +2578,7 @@ hipError_t impl_nbhd_count(const PassParams &p, int step, uint32_t *probe, const
 #endif // !RPF_IMPL_SCHED && !RPF_IMPL_LISTED
 #elif RPF_IMPL_PART == 2
 hipError_t impl_filter_mid(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s) {
+    if (!pass_fits_build(p)) return hipErrorInvalidValue;
     switch (samples_per_lane(p.nmax)) {
     case 13: return launch_filter_k<13>(p, L, L2, L3, t_in_lds, grid, s);
     case 25: return launch_filter_k<25>(p, L, L2, L3, t_in_lds, grid, s);
@@ -2604,6 +2589,7 @@ hipError_t impl_filter_mid(const PassParams &p, const LdsLayout &L, const LdsLay
 // one kernel of the split route alone, for the scheduled build of this part (RPF_IMPL_SCHED, which compiles PHASE 4 only): PHASE 3,
 // the chains, on L = lds_layout_chains, or PHASE 2, the weights, on L = lds_layout_weights (two or four waves: L.nw)
 hipError_t impl_filter_mid_phase(const PassParams &p, const LdsLayout &L, int phase, unsigned grid, hipStream_t s) {
+    if (!pass_fits_unit(p)) return hipErrorInvalidValue; // (called from the scheduled units too)
     if (samples_per_lane(p.nmax) != 25 || (phase != 2 && phase != 3)) return hipErrorInvalidValue;
     if (phase == 3) return launch_filter_inst<25, false, false, 4, 3>(p, L, grid, s);
     return L.nw == 2 ? launch_filter_inst<25, false, false, 2, 2>(p, L, grid, s) : launch_filter_inst<25, false, false, 4, 2>(p, L, grid, s);
@@ -2611,12 +2597,14 @@ hipError_t impl_filter_mid_phase(const PassParams &p, const LdsLayout &L, int ph
 #endif
 #elif RPF_IMPL_PART == 3
 hipError_t impl_filter_large(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s) {
+    if (!pass_fits_build(p)) return hipErrorInvalidValue;
     if (samples_per_lane(p.nmax) != 49) return hipErrorInvalidValue;
     return launch_filter_k<49>(p, L, L2, L3, t_in_lds, grid, s);
 }
 #if !RPF_IMPL_SCHED
 // (as impl_filter_mid_phase, for the K = 49 class)
 hipError_t impl_filter_large_phase(const PassParams &p, const LdsLayout &L, int phase, unsigned grid, hipStream_t s) {
+    if (!pass_fits_unit(p)) return hipErrorInvalidValue; // (called from the scheduled units too)
     if (samples_per_lane(p.nmax) != 49 || (phase != 2 && phase != 3)) return hipErrorInvalidValue;
     if (phase == 3) return launch_filter_inst<49, false, false, 4, 3>(p, L, grid, s);
     return L.nw == 2 ? launch_filter_inst<49, false, false, 2, 2>(p, L, grid, s) : launch_filter_inst<49, false, false, 4, 2>(p, L, grid, s);
@@ -2632,15 +2620,6 @@ hipError_t impl_nbhd_count_member(const PassParams &p, const double *mt, hipStre
 #else
 #error "RPF_IMPL_PART must be 1, 2, 3 or 4"
 #endif
-#if RPF_IMPL_SCHED || RPF_IMPL_LISTED
-#undef impl_filter_small
-#undef impl_filter_mid
-#undef impl_filter_large
-#if RPF_IMPL_LISTED && !RPF_IMPL_SCHED
-#undef impl_filter_mid_phase
-#undef impl_filter_large_phase
-#endif
-#if RPF_IMPL_PART == 4
+#if (RPF_IMPL_SCHED || RPF_IMPL_LISTED) && RPF_IMPL_PART == 4
 #error "part 4 has no scheduled and no listed build: the count pass has no stage 3c and lists nothing"
-#endif
 #endif

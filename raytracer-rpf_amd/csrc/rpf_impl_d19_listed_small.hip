@@ -1,19 +1,6 @@
-// rpf_impl_d19_listed_small.hip -- one translation unit of the fused per-pixel kernels: layout d19 (2 random parameters, 12 features, float planes),
-// size-class part 1 (K <= 8 and the packed kernels) in its listed build: stage 1b from the member pool (RPF_FLAG_SAMPLED_LISTED; RPF_IMPL_LISTED in
-// rpf_filter_impl.inc).  Compiled with -ffp-contract=off like every kernel TU.
-#include "rpf_device_common.h"
-
-namespace rpf {
-namespace d19 {
-namespace listed {
-namespace {
-#define RPF_IMPL_NR 2
-#define RPF_IMPL_NF 12
-#define RPF_IMPL_PLANE_T float
+// rpf_impl_d19_listed_small.hip -- the fused per-pixel kernels: layout d19, part 1 (small: K <= 8 and the packed kernels), listed build (rpf_impl_unit.inc)
+#define RPF_IMPL_DIMS 19
 #define RPF_IMPL_PART 1
+#define RPF_IMPL_SCHED 0
 #define RPF_IMPL_LISTED 1
-} // namespace
-#include "rpf_filter_impl.inc"
-} // namespace listed
-} // namespace d19
-} // namespace rpf
+#include "rpf_impl_unit.inc"

@@ -1,15 +1,6 @@
-// rpf_impl_d19_member.hip -- one translation unit of the fused per-pixel kernels: layout d19 (2 random parameters, 12 features,
-// float planes), part 4, the count pass of route 10 under the membership test (see rpf_filter_impl.inc).  Compiled with -ffp-contract=off like every kernel TU.
-#include "rpf_device_common.h"
-
-namespace rpf {
-namespace d19 {
-namespace {
-#define RPF_IMPL_NR 2
-#define RPF_IMPL_NF 12
-#define RPF_IMPL_PLANE_T float
+// rpf_impl_d19_member.hip -- the fused per-pixel kernels: layout d19, part 4 (member: the count pass of route 10), plain build (rpf_impl_unit.inc)
+#define RPF_IMPL_DIMS 19
 #define RPF_IMPL_PART 4
-} // namespace
-#include "rpf_filter_impl.inc"
-} // namespace d19
-} // namespace rpf
+#define RPF_IMPL_SCHED 0
+#define RPF_IMPL_LISTED 0
+#include "rpf_impl_unit.inc"

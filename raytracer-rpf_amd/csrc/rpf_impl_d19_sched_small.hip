@@ -1,22 +1,6 @@
-// rpf_impl_d19_sched_small.hip -- one translation unit of the fused per-pixel kernels: layout d19 (2 random parameters, 12 features, float planes),
-// size-class part 1 (K <= 8 and the packed kernels) in its scheduled build: stage 3c from the entry's gains (RPF_FLAG_SCHEDULE_FUSED; RPF_IMPL_SCHED in
-// rpf_filter_impl.inc).  Compiled with -ffp-contract=off like every kernel TU.
-#include "rpf_device_common.h"
-
-namespace rpf {
-namespace d19 {
-// PHASE 3 / PHASE 2 of the split route: the unscheduled parts 2 and 3 hold them (rpf_impl_d19_mid.hip, rpf_impl_d19_large.hip)
-hipError_t impl_filter_mid_phase(const PassParams &p, const LdsLayout &L, int phase, unsigned grid, hipStream_t s);
-hipError_t impl_filter_large_phase(const PassParams &p, const LdsLayout &L, int phase, unsigned grid, hipStream_t s);
-namespace sched {
-namespace {
-#define RPF_IMPL_NR 2
-#define RPF_IMPL_NF 12
-#define RPF_IMPL_PLANE_T float
+// rpf_impl_d19_sched_small.hip -- the fused per-pixel kernels: layout d19, part 1 (small: K <= 8 and the packed kernels), scheduled build (rpf_impl_unit.inc)
+#define RPF_IMPL_DIMS 19
 #define RPF_IMPL_PART 1
 #define RPF_IMPL_SCHED 1
-} // namespace
-#include "rpf_filter_impl.inc"
-} // namespace sched
-} // namespace d19
-} // namespace rpf
+#define RPF_IMPL_LISTED 0
+#include "rpf_impl_unit.inc"

@@ -1,15 +1,6 @@
-// rpf_impl_d19_small.hip -- one translation unit of the fused per-pixel kernels: layout d19 (2 random parameters, 12 features,
-// float planes), size-class part 1 (see rpf_filter_impl.inc).  Compiled with -ffp-contract=off like every kernel TU.
-#include "rpf_device_common.h"
-
-namespace rpf {
-namespace d19 {
-namespace {
-#define RPF_IMPL_NR 2
-#define RPF_IMPL_NF 12
-#define RPF_IMPL_PLANE_T float
+// rpf_impl_d19_small.hip -- the fused per-pixel kernels: layout d19, part 1 (small: K <= 8 and the packed kernels), plain build (rpf_impl_unit.inc)
+#define RPF_IMPL_DIMS 19
 #define RPF_IMPL_PART 1
-} // namespace
-#include "rpf_filter_impl.inc"
-} // namespace d19
-} // namespace rpf
+#define RPF_IMPL_SCHED 0
+#define RPF_IMPL_LISTED 0
+#include "rpf_impl_unit.inc"

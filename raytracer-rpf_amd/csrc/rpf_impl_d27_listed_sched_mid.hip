@@ -1,26 +1,6 @@
-// rpf_impl_d27_listed_sched_mid.hip -- one translation unit of the fused per-pixel kernels: layout d27 (4 random parameters, 18 features, fp16 planes),
-// size-class part 2 (K 13 / 25) in its listed, scheduled build: stage 1b from the member pool, stage 3c from the entry's gains
-// (RPF_FLAG_SAMPLED_LISTED with RPF_FLAG_SCHEDULE_FUSED; RPF_IMPL_LISTED and RPF_IMPL_SCHED in rpf_filter_impl.inc, DESIGN.md sections 13g and
-// 15e).  Compiled with -ffp-contract=off like every kernel TU.
-#include "rpf_device_common.h"
-
-namespace rpf {
-namespace d27 {
-namespace listed {
-// PHASE 3 / PHASE 2 of the split route: the listed parts 2 and 3 hold them (rpf_impl_d27_listed_mid.hip, rpf_impl_d27_listed_large.hip)
-hipError_t impl_filter_mid_phase_listed(const PassParams &p, const LdsLayout &L, int phase, unsigned grid, hipStream_t s);
-hipError_t impl_filter_large_phase_listed(const PassParams &p, const LdsLayout &L, int phase, unsigned grid, hipStream_t s);
-namespace sched {
-namespace {
-#define RPF_IMPL_NR 4
-#define RPF_IMPL_NF 18
-#define RPF_IMPL_PLANE_T __half
+// rpf_impl_d27_listed_sched_mid.hip -- the fused per-pixel kernels: layout d27, part 2 (mid: K 13 / 25), listed scheduled build (rpf_impl_unit.inc)
+#define RPF_IMPL_DIMS 27
 #define RPF_IMPL_PART 2
 #define RPF_IMPL_SCHED 1
 #define RPF_IMPL_LISTED 1
-} // namespace
-#include "rpf_filter_impl.inc"
-} // namespace sched
-} // namespace listed
-} // namespace d27
-} // namespace rpf
+#include "rpf_impl_unit.inc"

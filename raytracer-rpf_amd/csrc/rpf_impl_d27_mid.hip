@@ -1,15 +1,6 @@
-// rpf_impl_d27_mid.hip -- one translation unit of the fused per-pixel kernels: layout d27 (4 random parameters, 18 features,
-// __half planes), size-class part 2 (see rpf_filter_impl.inc).  Compiled with -ffp-contract=off like every kernel TU.
-#include "rpf_device_common.h"
-
-namespace rpf {
-namespace d27 {
-namespace {
-#define RPF_IMPL_NR 4
-#define RPF_IMPL_NF 18
-#define RPF_IMPL_PLANE_T __half
+// rpf_impl_d27_mid.hip -- the fused per-pixel kernels: layout d27, part 2 (mid: K 13 / 25), plain build (rpf_impl_unit.inc)
+#define RPF_IMPL_DIMS 27
 #define RPF_IMPL_PART 2
-} // namespace
-#include "rpf_filter_impl.inc"
-} // namespace d27
-} // namespace rpf
+#define RPF_IMPL_SCHED 0
+#define RPF_IMPL_LISTED 0
+#include "rpf_impl_unit.inc"

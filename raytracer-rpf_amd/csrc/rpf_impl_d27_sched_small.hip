@@ -1,22 +1,6 @@
-// rpf_impl_d27_sched_small.hip -- one translation unit of the fused per-pixel kernels: layout d27 (4 random parameters, 18 features, fp16 planes),
-// size-class part 1 (K <= 8 and the packed kernels) in its scheduled build: stage 3c from the entry's gains (RPF_FLAG_SCHEDULE_FUSED; RPF_IMPL_SCHED in
-// rpf_filter_impl.inc).  Compiled with -ffp-contract=off like every kernel TU.
-#include "rpf_device_common.h"
-
-namespace rpf {
-namespace d27 {
-// PHASE 3 / PHASE 2 of the split route: the unscheduled parts 2 and 3 hold them (rpf_impl_d27_mid.hip, rpf_impl_d27_large.hip)
-hipError_t impl_filter_mid_phase(const PassParams &p, const LdsLayout &L, int phase, unsigned grid, hipStream_t s);
-hipError_t impl_filter_large_phase(const PassParams &p, const LdsLayout &L, int phase, unsigned grid, hipStream_t s);
-namespace sched {
-namespace {
-#define RPF_IMPL_NR 4
-#define RPF_IMPL_NF 18
-#define RPF_IMPL_PLANE_T __half
+// rpf_impl_d27_sched_small.hip -- the fused per-pixel kernels: layout d27, part 1 (small: K <= 8 and the packed kernels), scheduled build (rpf_impl_unit.inc)
+#define RPF_IMPL_DIMS 27
 #define RPF_IMPL_PART 1
 #define RPF_IMPL_SCHED 1
-} // namespace
-#include "rpf_filter_impl.inc"
-} // namespace sched
-} // namespace d27
-} // namespace rpf
+#define RPF_IMPL_LISTED 0
+#include "rpf_impl_unit.inc"

@@ -58,7 +58,7 @@ enum GenericBits : int32_t {
                               //   Host-side only: no kernel reads it, and the compiled kernels read no bit of `generic`
     kGenericScheduleFused = 2048, // RPF_FLAG_SCHEDULE_FUSED on a pass of the compiled kernels whose entry has a gain other than 1 (setup_pass:
                               //   no layout-generic bit, or route 10): the pass runs the scheduled builds of those kernels
-                              //   (rpf_impl_*_sched_*.hip: launch_filter_pass and launch_filter_packed dispatch on it), which form alpha
+                              //   (rpf_impl_*_sched_*.hip: launch_filter_pass and launch_filter_packed pick their table row by it), which form alpha
                               //   and beta from PassParams::gain_c / gain_f; its streaming class gets a copy of the params with
                               //   kGenericSchedule in its place (scheduled_stream).  Host-side only, selects no route
     kGenericSampledFused = 4096, // RPF_FLAG_SAMPLED_FUSED on a pass that carries kGenericSampled and that the compiled kernels can take
@@ -70,7 +70,7 @@ enum GenericBits : int32_t {
                               //   kernels can take (setup_pass: a compiled layout without RPF_FLAG_GENERIC, S + draws <= kMaxResident, not
                               //   forced wide, no kGenericSchedule; with kGenericSampledFused possible too, option "sampled_listed_stride"
                               //   picks one): route 12 (route_sampled_listed), the size-binned route's class kernels
-                              //   in their listed builds (rpf_impl_*_listed_*.hip: launch_filter_pass and launch_filter_packed dispatch on
+                              //   in their listed builds (rpf_impl_*_listed_*.hip: launch_filter_pass and launch_filter_packed pick their table row by
                               //   it) behind a count kernel that lists into the member pool.  Never together with kGenericSampledFused or
                               //   kGenericWide; generic_route looks at it before kGenericSampled.  Host-side only: no kernel reads it
     kGenericQuad = 16384,     // RPF_FLAG_GENERIC_QUAD (validate: only with kGenericOn | kGenericPacked | kGenericWave): 832 < N <= 3136 on

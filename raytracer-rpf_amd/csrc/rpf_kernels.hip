@@ -231,39 +231,52 @@ __global__ __launch_bounds__(256) void nbhd_reduce_kernel(const int32_t *nbhd, u
 }
 
 // ---- the layout-dependent kernels live in their own translation units (rpf_impl_*.hip: rpf_filter_impl.inc once per
-// sample-vector layout and size-class part, compiled in parallel); their entry points:
+// sample-vector layout, build and size-class part, compiled in parallel); their entry points:
 } // namespace
-#define RPF_DECLARE_IMPL(NS)                                                                                              \
+// the entries of one build of one layout (namespace rpf::d19 | d27 [::listed] [::sched], rpf_impl_unit.inc): parts 1, 2, 3 and
+// part 1's packed kernels.  Each refuses a pass that is not its build's (pass_fits_build in rpf_filter_impl.inc)
+struct ImplBuild {
+    hipError_t (*small)(const PassParams &p, const LdsLayout &L, bool t_in_lds, unsigned grid, hipStream_t s);
+    hipError_t (*mid)(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s);
+    hipError_t (*large)(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s);
+    hipError_t (*packed)(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s);
+};
+#define RPF_DECLARE_BUILD(NS)                                                                                              \
     namespace NS {                                                                                                        \
     hipError_t impl_filter_small(const PassParams &p, const LdsLayout &L, bool t_in_lds, unsigned grid, hipStream_t s);   \
     hipError_t impl_filter_mid(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
     hipError_t impl_filter_large(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
+    hipError_t impl_filter_packed(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s);    \
+    constexpr ImplBuild kBuild = {impl_filter_small, impl_filter_mid, impl_filter_large, impl_filter_packed};            \
+    }
+// stage 1a and the count passes exist in the plain build only
+#define RPF_DECLARE_PLAIN(NS)                                                                                              \
+    namespace NS {                                                                                                        \
     hipError_t impl_pixel_stats(const PassParams &p, uint64_t pix0, uint64_t pix1, hipStream_t s);                        \
     hipError_t impl_nbhd_count(const PassParams &p, int step, uint32_t *probe, const uint32_t *list, const uint32_t *list_count, uint32_t list_max, hipStream_t s); \
-    hipError_t impl_nbhd_count_member(const PassParams &p, const double *mt, hipStream_t s); \
-    hipError_t impl_filter_packed(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s);    \
-    namespace sched { /* the scheduled builds (rpf_impl_*_sched_*.hip): a pass that carries kGenericScheduleFused */        \
-    hipError_t impl_filter_small_sched(const PassParams &p, const LdsLayout &L, bool t_in_lds, unsigned grid, hipStream_t s); \
-    hipError_t impl_filter_mid_sched(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
-    hipError_t impl_filter_large_sched(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
-    hipError_t impl_filter_packed_sched(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s); \
-    }                                                                                                                     \
-    namespace listed { /* the listed builds (rpf_impl_*_listed_*.hip): a pass that carries kGenericSampledListed */         \
-    hipError_t impl_filter_small_listed(const PassParams &p, const LdsLayout &L, bool t_in_lds, unsigned grid, hipStream_t s); \
-    hipError_t impl_filter_mid_listed(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
-    hipError_t impl_filter_large_listed(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
-    hipError_t impl_filter_packed_listed(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s); \
-    namespace sched { /* ... and kGenericScheduleFused with it (rpf_impl_*_listed_sched_*.hip) */                           \
-    hipError_t impl_filter_small_listed_sched(const PassParams &p, const LdsLayout &L, bool t_in_lds, unsigned grid, hipStream_t s); \
-    hipError_t impl_filter_mid_listed_sched(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
-    hipError_t impl_filter_large_listed_sched(const PassParams &p, const LdsLayout &L, const LdsLayout &L2, const LdsLayout &L3, bool t_in_lds, unsigned grid, hipStream_t s); \
-    hipError_t impl_filter_packed_listed_sched(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s); \
-    }                                                                                                                     \
-    }                                                                                                                     \
+    hipError_t impl_nbhd_count_member(const PassParams &p, const double *mt, hipStream_t s);                              \
     }
-RPF_DECLARE_IMPL(d19) // the reference's 19 dims (2 random parameters, 12 features), fp32 planes
-RPF_DECLARE_IMPL(d27) // BASELINE configs[4]: 27 dims (4 random parameters, 18 features), fp16 feature storage
-#undef RPF_DECLARE_IMPL
+RPF_DECLARE_PLAIN(d19) // the reference's 19 dims (2 random parameters, 12 features), fp32 planes
+RPF_DECLARE_PLAIN(d27) // BASELINE configs[4]: 27 dims (4 random parameters, 18 features), fp16 feature storage
+RPF_DECLARE_BUILD(d19)
+RPF_DECLARE_BUILD(d19::sched) // the scheduled builds (rpf_impl_*_sched_*.hip): a pass that carries kGenericScheduleFused
+RPF_DECLARE_BUILD(d19::listed) // the listed builds (rpf_impl_*_listed_*.hip): a pass that carries kGenericSampledListed
+RPF_DECLARE_BUILD(d19::listed::sched) // ... and kGenericScheduleFused with it (rpf_impl_*_listed_sched_*.hip)
+RPF_DECLARE_BUILD(d27)
+RPF_DECLARE_BUILD(d27::sched)
+RPF_DECLARE_BUILD(d27::listed)
+RPF_DECLARE_BUILD(d27::listed::sched)
+#undef RPF_DECLARE_BUILD
+#undef RPF_DECLARE_PLAIN
+// [layout: d19, d27][listed][scheduled]
+static constexpr ImplBuild kBuilds[2][2][2] = {{{d19::kBuild, d19::sched::kBuild}, {d19::listed::kBuild, d19::listed::sched::kBuild}},
+                                               {{d27::kBuild, d27::sched::kBuild}, {d27::listed::kBuild, d27::listed::sched::kBuild}}};
+// the build of pass p (p.lay.supported() holds): a scheduled pass (kGenericScheduleFused: RPF_FLAG_SCHEDULE_FUSED, a gain other
+// than 1) runs the scheduled builds of the same parts, a listed pass (kGenericSampledListed: RPF_FLAG_SAMPLED_LISTED, route 12) the
+// listed builds, which copy their member lists from the pool
+static const ImplBuild &build_of(const PassParams &p) {
+    return kBuilds[p.lay.is_ref19() ? 0 : 1][(p.generic & kGenericSampledListed) != 0][(p.generic & kGenericScheduleFused) != 0];
+}
 
 int max_lds_per_block() { return 160 * 1024; }
 
@@ -427,31 +440,9 @@ hipError_t launch_filter_pass(const PassParams &p, const Tuning &tun, hipStream_
         L3 = lds_layout_chains(p.S, p.nmax, p.lay, 4);
     }
     const int K = samples_per_lane(p.nmax);
-    const bool r19 = p.lay.is_ref19();
     if (K == 0) return hipErrorInvalidValue;
-    // a scheduled pass (kGenericScheduleFused: RPF_FLAG_SCHEDULE_FUSED, a gain other than 1) runs the scheduled builds of the same parts
-    const bool sc = (p.generic & kGenericScheduleFused) != 0;
-    // a listed pass (kGenericSampledListed: RPF_FLAG_SAMPLED_LISTED, route 12) runs the listed builds, which copy their member lists from the pool
-    const bool li = (p.generic & kGenericSampledListed) != 0;
-    if (li && (p.members == nullptr || p.member_base == nullptr || p.pix_list == nullptr || p.fast_weights)) return hipErrorInvalidValue;
-    const auto small = [&](const PassParams &q, unsigned g) {
-        if (li && sc) return r19 ? d19::listed::sched::impl_filter_small_listed_sched(q, L, t_in_lds, g, s) : d27::listed::sched::impl_filter_small_listed_sched(q, L, t_in_lds, g, s);
-        if (li) return r19 ? d19::listed::impl_filter_small_listed(q, L, t_in_lds, g, s) : d27::listed::impl_filter_small_listed(q, L, t_in_lds, g, s);
-        if (sc) return r19 ? d19::sched::impl_filter_small_sched(q, L, t_in_lds, g, s) : d27::sched::impl_filter_small_sched(q, L, t_in_lds, g, s);
-        return r19 ? d19::impl_filter_small(q, L, t_in_lds, g, s) : d27::impl_filter_small(q, L, t_in_lds, g, s);
-    };
-    const auto mid = [&](const PassParams &q, unsigned g) {
-        if (li && sc) return r19 ? d19::listed::sched::impl_filter_mid_listed_sched(q, L, L2, L3, t_in_lds, g, s) : d27::listed::sched::impl_filter_mid_listed_sched(q, L, L2, L3, t_in_lds, g, s);
-        if (li) return r19 ? d19::listed::impl_filter_mid_listed(q, L, L2, L3, t_in_lds, g, s) : d27::listed::impl_filter_mid_listed(q, L, L2, L3, t_in_lds, g, s);
-        if (sc) return r19 ? d19::sched::impl_filter_mid_sched(q, L, L2, L3, t_in_lds, g, s) : d27::sched::impl_filter_mid_sched(q, L, L2, L3, t_in_lds, g, s);
-        return r19 ? d19::impl_filter_mid(q, L, L2, L3, t_in_lds, g, s) : d27::impl_filter_mid(q, L, L2, L3, t_in_lds, g, s);
-    };
-    const auto large = [&](const PassParams &q, unsigned g) {
-        if (li && sc) return r19 ? d19::listed::sched::impl_filter_large_listed_sched(q, L, L2, L3, t_in_lds, g, s) : d27::listed::sched::impl_filter_large_listed_sched(q, L, L2, L3, t_in_lds, g, s);
-        if (li) return r19 ? d19::listed::impl_filter_large_listed(q, L, L2, L3, t_in_lds, g, s) : d27::listed::impl_filter_large_listed(q, L, L2, L3, t_in_lds, g, s);
-        if (sc) return r19 ? d19::sched::impl_filter_large_sched(q, L, L2, L3, t_in_lds, g, s) : d27::sched::impl_filter_large_sched(q, L, L2, L3, t_in_lds, g, s);
-        return r19 ? d19::impl_filter_large(q, L, L2, L3, t_in_lds, g, s) : d27::impl_filter_large(q, L, L2, L3, t_in_lds, g, s);
-    };
+    const ImplBuild &B = build_of(p);
+    if ((p.generic & kGenericSampledListed) && (p.members == nullptr || p.member_base == nullptr || p.pix_list == nullptr || p.fast_weights)) return hipErrorInvalidValue;
     if (L2.total != 0 && tun.split_chunk > 0 && p.pix_list != nullptr && p.list_count > (uint32_t)tun.split_chunk) {
         // experiment (option "split_chunk"): the three launches of the split route over one chunk of the pixel list after the
         // other, so that a chunk's samples, masks and hand-over records are still in the 256 MiB Infinity Cache when the next
@@ -461,14 +452,14 @@ hipError_t launch_filter_pass(const PassParams &p, const Tuning &tun, hipStream_
             q.pix_list = p.pix_list + off;
             q.list_count = (p.list_count - off < (uint32_t)tun.split_chunk) ? p.list_count - off : (uint32_t)tun.split_chunk;
             const unsigned g = (unsigned)(((q.list_count + 7u) / 8u) * 8u);
-            const hipError_t e = K <= 25 ? mid(q, g) : large(q, g);
+            const hipError_t e = (K <= 25 ? B.mid : B.large)(q, L, L2, L3, t_in_lds, g, s);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
     }
-    if (K <= 8) return small(p, grid);
-    if (K <= 25) return mid(p, grid);
-    return large(p, grid);
+    if (K <= 8) return B.small(p, L, t_in_lds, grid, s);
+    if (K <= 25) return B.mid(p, L, L2, L3, t_in_lds, grid, s);
+    return B.large(p, L, L2, L3, t_in_lds, grid, s);
 }
 
 int class_capacity(int c) {
@@ -489,17 +480,7 @@ hipError_t launch_nbhd_count_member(const PassParams &p, const double *member, h
 
 hipError_t launch_filter_packed(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s) {
     if (!p.lay.supported()) return hipErrorNotSupported;
-    if (p.generic & kGenericSampledListed) { // a listed pass: the listed build of the packed kernels (rpf_impl_*_listed_small.hip), scheduled or not
-        if (p.generic & kGenericScheduleFused)
-            return p.lay.is_ref19() ? d19::listed::sched::impl_filter_packed_listed_sched(p, lanes_per_pixel, count_dev, s)
-                                    : d27::listed::sched::impl_filter_packed_listed_sched(p, lanes_per_pixel, count_dev, s);
-        return p.lay.is_ref19() ? d19::listed::impl_filter_packed_listed(p, lanes_per_pixel, count_dev, s)
-                                : d27::listed::impl_filter_packed_listed(p, lanes_per_pixel, count_dev, s);
-    }
-    if (p.generic & kGenericScheduleFused) // a scheduled pass: the scheduled build of the packed kernels (rpf_impl_*_sched_small.hip)
-        return p.lay.is_ref19() ? d19::sched::impl_filter_packed_sched(p, lanes_per_pixel, count_dev, s)
-                                : d27::sched::impl_filter_packed_sched(p, lanes_per_pixel, count_dev, s);
-    return p.lay.is_ref19() ? d19::impl_filter_packed(p, lanes_per_pixel, count_dev, s) : d27::impl_filter_packed(p, lanes_per_pixel, count_dev, s);
+    return build_of(p).packed(p, lanes_per_pixel, count_dev, s);
 }
 
 hipError_t launch_classify(const PassParams &p, uint32_t *lists, uint32_t *counts, int max_class, int rest_class, hipStream_t s) {

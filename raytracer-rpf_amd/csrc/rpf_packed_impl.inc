@@ -653,18 +653,9 @@ hipError_t launch_packed_inst(const PassParams &p, const uint32_t *count_dev, ui
 
 // entry point: pixels of p.pix_list with N <= lanes_per_pixel (8, 16, 32, 64); needs the acceptance masks and the N plane
 // (count pass, or filter_pixel_kernel's re-route).  count_dev != null: the list size is read on the device and
-// p.list_count is only its upper bound (sizes the grid).  (A scheduled build, RPF_IMPL_SCHED: impl_filter_packed_sched)
-// (A listed build, RPF_IMPL_LISTED: impl_filter_packed_listed / impl_filter_packed_listed_sched; it needs the member pool for the masks)
-#if RPF_IMPL_SCHED && RPF_IMPL_LISTED
-hipError_t impl_filter_packed_listed_sched(
-#elif RPF_IMPL_LISTED
-hipError_t impl_filter_packed_listed(
-#elif RPF_IMPL_SCHED
-hipError_t impl_filter_packed_sched(
-#else
-hipError_t impl_filter_packed(
-#endif
-const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s) {
+// p.list_count is only its upper bound (sizes the grid).  (A listed build needs the member pool for the masks)
+hipError_t impl_filter_packed(const PassParams &p, int lanes_per_pixel, const uint32_t *count_dev, hipStream_t s) {
+    if (!pass_fits_build(p)) return hipErrorInvalidValue;
     if (kListed ? (p.members == nullptr || p.member_base == nullptr) : p.masks == nullptr) return hipErrorInvalidValue;
     if (p.pix_list == nullptr || p.S > lanes_per_pixel) return hipErrorInvalidValue;
     switch (lanes_per_pixel) {

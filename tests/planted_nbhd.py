@@ -102,7 +102,7 @@ def plant(S, box, targets, n_random=2, n_feat=12, seed=0, at=None):
 
 
 # id: layout, S, box, draws D, sampling seed, planted N per target, planting seed.  Distinct surviving draws at the targets (what a
-# planted N cannot exceed, S added): SP8 156 .. 177, SP16 1233 .. 1270, SP32 2451 .. 2474, SPH16 191 .. 210; tests/
+# planted N cannot exceed, S added): SP8 156 .. 177, SP16 1233 .. 1270, SP32 and SPH32 2451 .. 2474, SPH16 191 .. 210; tests/
 # test_planted_routes_cpu.py holds the planted sizes.  SP32: (17 * 17 - 1) * 32 > 4096 candidates, the one-wave instantiations on
 # route 11.  NM*: N = S + D = nmax at the targets whose D draws are all distinct, S + D - 1 beside them.
 SAMPLING_SEED = 0x5EED5EED
@@ -111,6 +111,7 @@ SAMPLED_FRAMES = {
     "SP16": ((2, 12, "f32"), 16, 17, 1584, SAMPLING_SEED, (256, 257, 448, 449, 832, 833), 0),
     "SP32": ((2, 12, "f32"), 32, 17, 3104, SAMPLING_SEED, (1600, 1601, 833, 2400), 0),          # S + D = 3136, the cap
     "SPH16": ((4, 18, "f16"), 16, 7, 240, SAMPLING_SEED, (16, 17, 64, 65, 128, 129), 0),        # the d27 builds
+    "SPH32": ((4, 18, "f16"), 32, 17, 3104, SAMPLING_SEED, (833, 1600, 1601, 2400), 0),         # ... their K = 25 and K = 49 parts
     "NM16": ((2, 12, "f32"), 8, 7, 8, SAMPLING_SEED, (16, 15, 16, 8, 9, 16, 13, 15, 14, 16, 16, 15), 0),   # nmax = capacity 16
     "NM64": ((2, 12, "f32"), 8, 17, 56, SAMPLING_SEED, (33, 32, 63, 33, 63, 64, 63, 62, 64), 0),           # nmax = capacity 64
     "NM100": ((2, 12, "f32"), 8, 17, 92, SAMPLING_SEED + 1, (65, 64, 99, 98, 96, 100), 0),                 # nmax = 100 inside class 128
@@ -119,14 +120,14 @@ NMAX_FRAMES = ("NM16", "NM64", "NM100")
 
 
 # ---- what tests/test_planted_routes_cpu.py proves and tests/test_class_edges_routes_gpu.py runs -----------------------------------------
-ROUTE10_FRAMES = ("U8", "B16", "B32", "B64", "B40", "B17", "H8", "H16")
+ROUTE10_FRAMES = ("U8", "B16", "B32", "B64", "B40", "B17", "H8", "H16", "H64")
 # (gain_c, gain_f) of the scheduled cases, per frame: chosen on the oracle's MI of the target row so that clamped and open entries
 # of alpha, and of beta's factor, each hold tests/test_schedule_fused_cpu.py's SHARE (asserted in tests/test_planted_routes_cpu.py).  On a planted frame W_r_c and W_r_f of a row lie in a narrow band (the colours are white noise, every pixel has the
 # same law), so one pair of gains cannot serve every frame: each gain is near 1 / (the row's median ratio)
 GAINS = {"U8": (2.4, 2.2), "B16": (2.1, 2.0), "B32": (2.0, 1.9), "B64": (2.0, 1.93), "B40": (2.3, 2.2), "B17": (4.0, 3.0),
-         "H8": (1.65, 1.6), "H16": (1.68, 1.58)}
+         "H8": (1.65, 1.6), "H16": (1.68, 1.58), "H64": (1.505, 1.473)}
 SAMPLED_GAINS = {"SP8": (2.25, 2.05), "SP16": (2.9, 2.5), "SP32": (2.35, 2.2), "NM16": (1.9, 1.75), "NM64": (2.1, 2.0),
-                 "NM100": (2.05, 2.0), "SPH16": (1.49, 1.43)}
+                 "NM100": (2.05, 2.0), "SPH16": (1.49, 1.43), "SPH32": (1.69, 1.65)}
 
 
 def nonref(n_feat=12):

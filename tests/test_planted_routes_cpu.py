@@ -130,10 +130,28 @@ def test_every_class_edge_a_sampled_pass_reaches_is_planted():
     planted = set(n for v in P.SAMPLED_FRAMES.values() for n in v[5])
     for cap in CAPS[:-1]:                      # N = 3136 cannot be reached on a sampled pass: the module docstring of planted_nbhd
         assert cap in planted and cap + 1 in planted, cap
-    d27 = set(P.SAMPLED_FRAMES["SPH16"][5])
-    assert {16, 17, 64, 65, 128, 129} <= d27
+    d27 = set(n for v in P.SAMPLED_FRAMES.values() if v[0][:2] == (4, 18) for n in v[5])
+    assert {16, 17, 64, 65, 128, 129} <= d27 and {833, 1600, 1601} <= d27
     _, S, box, D, _, _, _ = P.SAMPLED_FRAMES["SP32"]
     assert S + D == CAPS[-1] and (box * box - 1) * S > 4096
+
+
+# the translation units of the compiled kernels: per layout and build, part 1's packed kernels (N <= 64) and its K <= 7 kernels
+# (N <= 448), part 2 (K 13 / 25: N <= 1600) and part 3 (K 49: N <= 3136)
+PART_BANDS = ((1, 64), (65, 448), (449, 1600), (1601, 3136))
+
+
+@pytest.mark.parametrize("build", ["plain", "scheduled", "listed", "listed_scheduled"])
+@pytest.mark.parametrize("lay", [(2, 12, "f32"), (4, 18, "f16")], ids=["d19", "d27"])
+def test_every_part_of_every_compiled_build_has_a_planted_size(lay, build):
+    """a property of the frame tables: the parametrised GPU tests iterate them, so each layout x build x part -- each entry of the
+    dispatch table in csrc/rpf_kernels.hip -- runs at a planted N only if the tables hold one in its band"""
+    table = P.SAMPLED_FRAMES if build.startswith("listed") else P.FRAMES
+    fids = {"plain": P.FRAMES, "scheduled": GAINS, "listed": P.SAMPLED_FRAMES, "listed_scheduled": SAMPLED_GAINS}[build]
+    assert set(fids) <= set(table)
+    planted = sorted(set(n for fid in fids if table[fid][0] == lay for n in table[fid][5 if table is P.SAMPLED_FRAMES else 3]))
+    for lo, hi in PART_BANDS:
+        assert any(lo <= n <= hi for n in planted), (lay, build, (lo, hi), planted)
 
 
 @pytest.mark.parametrize("fid", P.NMAX_FRAMES)
