@@ -411,7 +411,9 @@ typedef struct rpf_desc {
     int32_t beta_map;                  /* rpf_beta_map                                              */
     int32_t degenerate_policy;         /* rpf_degenerate_policy                                     */
     int32_t flags;
-    double eps;                        /* RPF_DEGEN_EPS epsilon (1e-10)                             */
+    double eps;                        /* RPF_DEGEN_EPS epsilon (1e-10).  Under RPF_DEGEN_EPS a NaN or negative value is
+                                          RPF_E_BADARG before any device work; a zero of either sign (IEEE: 0 / 0 is a NaN and the
+                                          colour falls back), +inf and every positive value are accepted.  RPF_DEGEN_REF_ABORT never reads it */
     double sigma_seed;                 /* rpf.cpp:533: 0.002                                        */
     /* Sample-vector layout.  All three 0 = the reference's: 2 random parameters (pLens), 12 features, fp32 planes.
      * Compiled kernels also exist for n_random = 4, n_feat = 18 with RPF_PLANES_F16 (27 dims, fp16 feature storage: BASELINE

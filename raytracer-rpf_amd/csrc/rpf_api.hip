@@ -233,6 +233,10 @@ int32_t validate(rpf_ctx *ctx, const rpf_desc *d, bool need_boxes) {
     }
     if (d->degenerate_policy < 0 || d->degenerate_policy > RPF_DEGEN_EPS)
         return fail(ctx, RPF_E_BADARG, "unknown degenerate_policy");
+    // RPF_DEGEN_EPS adds eps to the three denominators of stage 3c: a zero (-0 adds what +0 adds), +inf and every positive value are IEEE arithmetic there, a
+    // NaN or a negative one is a mistake.  RPF_DEGEN_REF_ABORT never reads the field
+    if (d->degenerate_policy == RPF_DEGEN_EPS && (std::isnan(d->eps) || d->eps < 0.0))
+        return fail(ctx, RPF_E_BADARG, "eps must be zero, positive or +inf under RPF_DEGEN_EPS (NaN or negative)");
     if (need_boxes) {
         int32_t st = check_sampled(ctx, d, d->n_box);
         if (st) return st;

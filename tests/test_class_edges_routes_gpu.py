@@ -93,9 +93,11 @@ def assert_same_pass(a, b, keys=ALL):
     assert (a["sum_nbhd"], a["max_nbhd"], a["launches"], a["redo_pixels"]) == (b["sum_nbhd"], b["max_nbhd"], b["launches"], b["redo_pixels"])
 
 
-def assert_row_stage4(got, ref, colour_in, row, box, label, nmax=None, n_feat=12):
+def assert_row_stage4(got, ref, colour_in, row, box, label, nmax=None, n_feat=12, form="expanded"):
     """every sample of the target row within the per-sample bar of the form its pixel's kernel uses (nmax: one bar for the row, from
-    the pass's bound, on the sampled routes); ref: the restatement's stage 4 on the device's own stage outputs"""
+    the pass's bound, on the sampled routes); ref: the restatement's stage 4 on the device's own stage outputs.  form: the form of
+    the kernels of the resident classes (the compiled kernels, which this module runs: expanded; a layout-generic route: direct,
+    the tighter bar).  Returns (worst distance, its bar), relative to cmax"""
     g, r, n = got["colour"][:, row], ref[:, row], got["nbhd_size"][row]
     assert np.array_equal(np.isnan(g), np.isnan(r))
     both = np.isfinite(g) & np.isfinite(r)
@@ -103,16 +105,17 @@ def assert_row_stage4(got, ref, colour_in, row, box, label, nmax=None, n_feat=12
     bars = np.empty(n.shape)
     if nmax is not None:
         assert n.max() <= nmax <= B.RESIDENT
-        bars[:] = B.sample_bar("expanded", n_feat, nmax, SIGMA, box)
+        bars[:] = B.sample_bar(form, n_feat, nmax, SIGMA, box)
     else:
-        for form, sel in (("expanded", n <= B.RESIDENT), ("direct", n > B.RESIDENT)):
+        for fm, sel in ((form, n <= B.RESIDENT), ("direct", n > B.RESIDENT)):
             if sel.any():
-                bars[sel] = B.sample_bar(form, n_feat, int(n[sel].max()), SIGMA, box)
+                bars[sel] = B.sample_bar(fm, n_feat, int(n[sel].max()), SIGMA, box)
     worst = int(np.argmax(dist / bars))
     print("%s stage 4 on the target row: worst %.3e (bar %.3e) at x %d, N %d" % (label, dist[worst], bars[worst], worst, n[worst]))
     assert both.any() and (dist <= bars).all(), (float(dist[worst]), float(bars[worst]))
     moved = rel_l2(g, colour_in[:, row].astype(np.float64))            # the `moved` condition on the device's own row: the bar is not vacuous
     assert moved > 0.05, moved
+    return float(dist[worst]), float(bars[worst])
 
 
 # ---- (a) route 10 on the planted full-box frames -------------------------------------------------------------------------------------
